@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Headline benchmark: Flow.log_prob throughput of the 32-layer RQ-NSF coupling flow
 (dim=64, K=8) on MI355X, with the layer kernel's roofline fraction and the reference-CPU-path
-baseline (the reference classes where /root/reference exists, else their bit-identical port).
+baseline (oracle/eager.py, the bit-identical port of the reference's CPU path).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 The workload is BASELINE configs[3] as named, at every N: a global batch of 262 144 rows, all of them on
 the one GPU at N = 1, sharded over the N ranks otherwise (one process per GPU, launched by
@@ -184,57 +184,42 @@ def usable_cores():
     return n
 
 
-def _reference_flow(flow_cpu):
-    """The unmodified reference classes (bayesiains/nflows imported from /root/reference, present in
-    the build container only) carrying the same weights, or None where the reference is absent."""
-    ref_root = "/root/reference"
-    if not os.path.isdir(os.path.join(ref_root, "nflows")):
-        return None
-    try:
-        shim = os.path.join(ROOT, "tests", "_refshim")
-        for p_ in (shim, ref_root):
-            if p_ not in sys.path:
-                sys.path.insert(0, p_)
-        from nflows.distributions.normal import StandardNormal
-        from nflows.flows.base import Flow
-        from nflows.nn.nets import ResidualNet
-        from nflows.transforms.base import CompositeTransform
-        from nflows.transforms.coupling import PiecewiseRationalQuadraticCouplingTransform
-        from nflows.transforms.permutations import RandomPermutation
-        from nflows.utils.torchutils import create_alternating_binary_mask
-        layers = []
-        ours = list(flow_cpu._transform._transforms)
-        for i in range(len(ours) // 2):
-            c = ours[2 * i + 1]
-            layers.append(RandomPermutation(c.features))
-            layers.append(PiecewiseRationalQuadraticCouplingTransform(
-                mask=create_alternating_binary_mask(c.features, even=(i % 2 == 0)),
-                transform_net_create_fn=lambda i_, o_: ResidualNet(i_, o_, hidden_features=128, num_blocks=2),
-                num_bins=c.num_bins, tails="linear", tail_bound=c.tail_bound))
-        ref = Flow(CompositeTransform(layers), StandardNormal([ours[1].features]))
-        ref.load_state_dict(flow_cpu.state_dict(), strict=True)
-        return ref.eval()
-    except Exception as e:  # the port below is bit-identical to it
-        log("reference import failed (%r): timing the port" % (e,))
-        return None
+def dump_outputs(out_dir, log_prob, acc, rank, world, limit_bytes=64 << 20):
+    """--dump-outputs: what the timed step handed its caller in the LAST timed step -- the per-row log-densities of this
+    rank's rows (log_prob.npy, float32) and the (sum, count) the log-likelihood reduction returned (log_likelihood_sum_count.npy,
+    float64) -- so that two builds can be compared output for output on the same seeded inputs.  At most `limit_bytes` in
+    all: log-densities beyond that are cut to a fixed, seeded sample of rows, whose indices go to log_prob_rows.npy
+    (float64).  Ranks other than 0 add _rank<r> to the names and share the limit."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "" if world == 1 else "_rank%d" % rank
+    lp = log_prob.detach().float().cpu().numpy().reshape(-1)
+    budget = limit_bytes // world - 4096
+    written = {}
+    if lp.nbytes > budget:
+        n = budget // (4 + 8)
+        rows = np.sort(np.random.RandomState(0).choice(lp.size, n, replace=False))
+        lp = lp[rows]
+        written["log_prob_rows"] = rows.astype(np.float64)
+    written["log_prob"] = np.ascontiguousarray(lp, dtype=np.float32)
+    written["log_likelihood_sum_count"] = acc.detach().double().cpu().numpy().reshape(-1)
+    for name, arr in written.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), arr)
+    log("outputs of the last timed step written to %s: %s" % (out_dir, ", ".join(
+        "%s%s.npy %s" % (k, suffix, list(v.shape)) for k, v in written.items())))
 
 
 def cpu_baseline(flow_cpu, features, sample_rows, x_consistency=None, budget_s=20.0, full_rows=0):
-    """The reference's CPU path on the host cores this process may use: the unmodified reference
-    classes when /root/reference is importable (build container), else their bit-identical
-    PyTorch-eager port (oracle/eager.py; tests/test_oracle_golden.py pins it bit for bit).  Bounded:
+    """The reference's CPU path on the host cores this process may use: its bit-identical PyTorch-eager
+    port (oracle/eager.py; tests/test_oracle_golden.py pins it bit for bit).  Bounded:
     rows are reduced until one pass fits the time budget.  Also reports a one-thread figure and the
     reference's own forward/inverse consistency error on the rows bench.py uses for the HIP path."""
     from oracle import eager
     threads = usable_cores()
-    ref = _reference_flow(flow_cpu)
-    kind = "reference" if ref is not None else "port"
-    if ref is not None:
-        def run(x):
-            return ref.log_prob(x)
-    else:
-        def run(x):
-            return eager.flow_log_prob(flow_cpu, x)
+    kind = "port"
+
+    def run(x):
+        return eager.flow_log_prob(flow_cpu, x)
 
     def timed(rows, nthreads, budget):
         torch.set_num_threads(nthreads)
@@ -280,8 +265,7 @@ def cpu_baseline(flow_cpu, features, sample_rows, x_consistency=None, budget_s=2
         log("cpu baseline at %d rows: one pass %.1f s" % (full_rows, dtf))
     out = {"value": rows / dt, "unit": "samples/s", "cores": threads, "kind": kind,
            "sample": "same 32-layer flow and weights, %d rows x %d timed passes of %s, %.2f s/pass"
-                     % (rows, reps, "the reference classes imported from /root/reference" if ref is not None
-                        else "oracle/eager.py (bit-identical port of the reference CPU path)", dt),
+                     % (rows, reps, "oracle/eager.py (bit-identical port of the reference CPU path)", dt),
            "one_thread": {"value": rows1 / dt1, "unit": "samples/s", "rows": rows1, "passes": reps1}}
     if full is not None:
         out["at_baseline_batch"] = full
@@ -431,7 +415,12 @@ def main():
                     help="skip the extra measurement at 65 536 rows per GPU (profiling runs: one launch size in the trace)")
     ap.add_argument("--skip-consistency", action="store_true",
                     help="skip the fwd/inv check (profiling runs: only full-batch launches in the trace)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (per-row log-densities, log-likelihood sum and count) "
+                         "as DIR/<name>.npy, at most 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -492,10 +481,10 @@ def main():
     def step():
         with torch.no_grad():
             lp = flow.log_prob(x)
-        return parallel.reduce_log_likelihood(lp)
+        return lp, parallel.reduce_log_likelihood(lp)
 
     for _ in range(args.warmup):
-        acc = step()
+        lp, acc = step()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -506,7 +495,7 @@ def main():
     _native.check(_native.load().nfa_profile_enable(max_launches))
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        acc = step()
+        lp, acc = step()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -516,6 +505,9 @@ def main():
     _native.check(_native.load().nfa_profile_enable(0))
     log("timed region done: %.1f ms/step" % (elapsed / args.steps * 1e3))
     nflows_amd.check_status()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, lp, acc, rank, world)
+    del lp
     # 128-row blocks of the last timed step that left the f16 range and were redone by the exact kernel
     # (K8h only; 0 = the whole batch ran on the measured kernel)
     redo_blocks = ops.last_redo_blocks() if args.path == "k8" else None
