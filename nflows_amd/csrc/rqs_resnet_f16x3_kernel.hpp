@@ -31,6 +31,46 @@ struct Args {
     float* dbg_logits;       // DBG: [batch][dt * 24], packed row order (tile, lane-half, register)
 };
 
+// LDS addresses as 32-bit LDS pointers: a generic pointer into the row tile is a 64-bit register pair and its arithmetic
+// 64-bit VALU (the group loop spent 23 v_lshl_add_u64 / v_mad_*64 per iteration on five of them, and they were among the
+// values the layer loop kept in scratch)
+typedef __attribute__((address_space(3))) float lds_f32;
+
+using nfa::load_bias_tile;   // (global biases; the overload below reads the final layer's from LDS)
+
+__device__ __forceinline__ void load_bias_tile(f32x16& acc, const lds_f32* bias_tile_half) {
+    typedef __attribute__((address_space(3))) const vec4f lds_vec4f;
+    lds_vec4f* bp = reinterpret_cast<lds_vec4f*>(bias_tile_half);
+#pragma unroll
+    for (int q4 = 0; q4 < 4; ++q4) {
+        const vec4f b = bp[q4];
+        acc[q4 * 4 + 0] = b.x;
+        acc[q4 * 4 + 1] = b.y;
+        acc[q4 * 4 + 2] = b.z;
+        acc[q4 * 4 + 3] = b.w;
+    }
+}
+
+// Two or four wave-uniform floats through the scalar cache.  The kernel stores to global memory, so the compiler cannot prove the
+// per-layer scales unchanged and reads them with a VECTOR load -- whose wait, vmcnt(0), also drains the weight stream's
+// LDS-DMA requests in flight.  The wait of a scalar load is lgkmcnt(0).
+template <int N>
+__device__ __forceinline__ void uniform_load(const float* p, float (&v)[N]) {
+    static_assert(N == 2 || N == 4, "one or two pairs");
+    uint64_t v01, v23 = 0;
+    if constexpr (N == 2)
+        asm volatile("s_load_dwordx2 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(v01) : "s"(p) : "memory");
+    else
+        asm volatile("s_load_dwordx2 %0, %2, 0x0\n\ts_load_dwordx2 %1, %2, 0x8\n\ts_waitcnt lgkmcnt(0)"
+                     : "=&s"(v01), "=&s"(v23) : "s"(p) : "memory");
+    v[0] = __builtin_bit_cast(float, (unsigned)v01);
+    v[1] = __builtin_bit_cast(float, (unsigned)(v01 >> 32));
+    if constexpr (N == 4) {
+        v[2] = __builtin_bit_cast(float, (unsigned)v23);
+        v[3] = __builtin_bit_cast(float, (unsigned)(v23 >> 32));
+    }
+}
+
 // What runs behind the MFMAs of a final-layer tile: a tile's 24 f16 MFMAs count one time unit each, its four bf8 MFMAs two
 // (64 against 32 cycles): 32 units per tile, a weave's slices spread evenly over them.
 struct NoWeave {
@@ -137,8 +177,8 @@ __device__ __forceinline__ void gemm_tile_pumped(f32x16& acc, const Pieces (&p)[
 
 // tiles TI .. T - 1 of a group of the general final layer (K8h's any_group_tiles on this kernel's GEMM): biases, the tile's
 // MFMAs with their share of the evaluation, the tile's sixteen logits into the evaluation's arrays
-template <int TI, int T, int KB, class Steps>
-__device__ __forceinline__ void any_group_tiles(f32x16& acc, Steps& f, const float* gb, const Pieces (&p)[8], const i32x8 (&bx)[4],
+template <int TI, int T, int KB, class Steps, class BiasPtr>
+__device__ __forceinline__ void any_group_tiles(f32x16& acc, Steps& f, BiasPtr gb, const Pieces (&p)[8], const i32x8 (&bx)[4],
                                                 WeightStream& sm, int lane, Lead& lead, const RqsDev& sp) {
     if constexpr (TI < T) {
         constexpr int kMask = k8h::any_tile_mask(KB, TI);
@@ -146,7 +186,7 @@ __device__ __forceinline__ void any_group_tiles(f32x16& acc, Steps& f, const flo
         if constexpr (kMask != 0) gemm_tile_pumped(acc, p, bx, sm, lane, lead, SeqWeave<kMask, Steps>{f, sp});
         else gemm_tile_pumped(acc, p, bx, sm, lane, lead, NoWeave{});
         k8h::take_chunk<TI, KB>(f, acc);
-        any_group_tiles<TI + 1, T, KB, Steps>(acc, f, gb, p, bx, sm, lane, lead, sp);
+        any_group_tiles<TI + 1, T, KB, Steps, BiasPtr>(acc, f, gb, p, bx, sm, lane, lead, sp);
     }
 }
 
@@ -164,7 +204,7 @@ __global__ void __launch_bounds__(kBlock, 2) rqs_resnet_f16x3_kernel(const Args 
     __shared__ int s_tab[2][kTabLayer];   // tables of the current and the next layer
     __shared__ int s_final[128];
     __shared__ int s_bad[NW];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int D = a.D, dt = a.dt;
     int my_status = 0;
     auto checked = [&](int v, bool used) {
@@ -193,8 +233,8 @@ __global__ void __launch_bounds__(kBlock, 2) rqs_resnet_f16x3_kernel(const Args 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
-    float* s_row = lds_dyn + kRing * kStageVec4 * 4 + wave * D * kRowPad;
-    float* s_fbias = lds_dyn + kRing * kStageVec4 * 4 + NW * D * kRowPad;
+    lds_f32* s_row = (lds_f32*)lds_dyn + kRing * kStageVec4 * 4 + wave * D * kRowPad;
+    lds_f32* s_fbias = (lds_f32*)lds_dyn + kRing * kStageVec4 * 4 + NW * D * kRowPad;
     const int groups = dt >> 2;
     const int64_t num_quads = a.batch >> 7;
     const int gemms = 2 + 2 * a.num_blocks;   // per layer
@@ -245,11 +285,16 @@ __global__ void __launch_bounds__(kBlock, 2) rqs_resnet_f16x3_kernel(const Args 
             // the next layer's table (the first one again after the last: next row block) goes to the other half
             // now; it is read only after this layer's many stage barriers
             {
+                // (te made afresh from the lane count: carried from the kernel's entry it held a register through the
+                //  whole layer, one of the values the layer loop kept in scratch)
+                unsigned all = ~0u;
+                asm volatile("" : "+s"(all));
+                const int te_l = (int)__builtin_amdgcn_mbcnt_hi(all, __builtin_amdgcn_mbcnt_lo(all, 0u)) + ((wave & 1) << 6);
                 const int nl = layer + 1 < a.num_layers ? layer + 1 : 0;
-                s_tab[tb ^ 1][te] = checked(a.tables[nl * kTabLayer + te], te < kTabTr ? te < a.di : te - kTabTr < dt);
+                s_tab[tb ^ 1][te_l] = checked(a.tables[nl * kTabLayer + te_l], te_l < kTabTr ? te_l < a.di : te_l - kTabTr < dt);
             }
             const float* bias = a.bias + (size_t)layer * a.bias_per_layer + half * 16;  // + 32 per tile
-            const float* sc = a.scales + (size_t)layer * gemms * 2;                      // {1 / T, T} per GEMM (uniform)
+            const float* sc = a.scales + (size_t)layer * gemms * 2;   // {1 / T, T} per GEMM (uniform)
             Pieces p[8];   // the current activations (128 k per sample) as f16 pieces at scale S
 
             // ---- identity features: k = ks*16 + half*8 + j
@@ -275,7 +320,9 @@ __global__ void __launch_bounds__(kBlock, 2) rqs_resnet_f16x3_kernel(const Args 
 #pragma unroll
                 for (int t = 0; t < 4; ++t) load_bias_tile(h[t], bias + t * 32);
                 gemm_kmajor<false, INIT_KS>(h, p, sm, lane);
-                const float inv_t = sc[0];
+                float s0[2];
+                uniform_load(sc, s0);
+                const float inv_t = s0[0];
 #pragma unroll
                 for (int t = 0; t < 4; ++t) tile_to_pieces<false>(h[t], inv_t, p[2 * t], p[2 * t + 1]);
             }
@@ -302,23 +349,25 @@ __global__ void __launch_bounds__(kBlock, 2) rqs_resnet_f16x3_kernel(const Args 
                 //   second Linear   v (64) + q (96)
                 f32x16 v[4];
                 Pieces q[8];
+                float sb[4];
                 {
                     f32x16 u[4];
 #pragma unroll
                     for (int t = 0; t < 4; ++t) load_bias_tile(u[t], bias + t * 32);
                     gemm_kmajor<true, 8>(u, p, sm, lane);
-                    const float t1 = sc[3];
+                    uniform_load(sc, sb);
+                    const float t1 = sb[3];
 #pragma unroll
                     for (int t = 0; t < 4; ++t) {
                         load_bias_tile(v[t], bias + 128 + t * 32);
                         add_pieces(v[t], 0, p[2 * t], t1);
                         add_pieces(v[t], 8, p[2 * t + 1], t1);
                     }
-                    const float inv_t = sc[0];
+                    const float inv_t = sb[0];
 #pragma unroll
                     for (int t = 0; t < 4; ++t) tile_to_pieces<true>(u[t], inv_t, q[2 * t], q[2 * t + 1]);
                 }
-                const float inv_t1 = sc[2];
+                const float inv_t1 = sb[2];
                 gemm_kmajor<false, 8>(v, q, sm, lane);
 #pragma unroll
                 for (int t = 0; t < 4; ++t) tile_to_pieces<false>(v[t], inv_t1, p[2 * t], p[2 * t + 1]);
@@ -330,13 +379,18 @@ __global__ void __launch_bounds__(kBlock, 2) rqs_resnet_f16x3_kernel(const Args 
             //      logits of this lane's two features A, B (A = T0 + T1[0:8], B = T1[8:16] + T2), at scale 1 / kappa
             if constexpr (KB == 8) {
                 using Steps = FusedSteps<INVERSE, 8>;
-                Steps fa, fb;
-                const float kappa = sc[0];
+                // (value-initialised although the first group reads nothing of them: the fields the group loop carries
+                //  from one group to the next were undefined on entry, and hipcc merged them with the PREVIOUS layer's
+                //  values -- a dozen registers kept across the whole layer, through scratch)
+                Steps fa{}, fb{};
+                float sf[2];
+                uniform_load(sc, sf);
+                const float kappa = sf[0];
                 fa.kappa = fb.kappa = kappa;
                 fa.kl2e = fb.kl2e = 1.44269502162933349609375f * kappa;
-                fa.tail_s = fb.tail_s = a.sp.tail_logit * sc[1];
-                float* slot_b = nullptr;
-                const float* fbias = s_fbias + half * 16;
+                fa.tail_s = fb.tail_s = a.sp.tail_logit * sf[1];
+                lds_f32* slot_b = s_row;   // (written from the second group on)
+                const lds_f32* fbias = s_fbias + half * 16;
                 // the bf8 B operands of the four k-step pairs, made once for the layer's 24 tiles (the r' pieces are read by
                 // nothing else from here on: their registers are these)
                 i32x8 bx[4];
@@ -346,7 +400,7 @@ __global__ void __launch_bounds__(kBlock, 2) rqs_resnet_f16x3_kernel(const Args 
                 //  last one reads the next layer's first stage, which nobody uses -- the next GEMM reads its own)
                 Lead lead = read_lead(sm.ring + sm.slot * kStageVec4 + lane);
                 f32x16 acc[3];
-                auto commit = [&](Steps& f, float* slot) {
+                auto commit = [&](Steps& f, lds_f32* slot) {
                     *slot = f.y;
                     lad_acc += f.lad;
                     quad_status |= f.status;
@@ -367,8 +421,8 @@ __global__ void __launch_bounds__(kBlock, 2) rqs_resnet_f16x3_kernel(const Args 
                 UnitWeave<k8h::kUnitFinishA, Steps> w1{fa, fb, a.sp};
                 UnitWeave<k8h::kUnitFinishB, Steps> w2{fa, fb, a.sp};
                 for (int g = 0; g < groups; ++g) {
-                    float* slot0 = s_row + tab[kTabTr + g * 4 + half * 2] * kRowPad + r;
-                    float* slot1 = s_row + tab[kTabTr + g * 4 + half * 2 + 1] * kRowPad + r;
+                    lds_f32* slot0 = s_row + tab[kTabTr + g * 4 + half * 2] * kRowPad + r;
+                    lds_f32* slot1 = s_row + tab[kTabTr + g * 4 + half * 2 + 1] * kRowPad + r;
                     load_bias_tile(acc[0], fbias + (g * 3 + 0) * 32);
                     if (g > 0) {
                         gemm_tile_pumped(acc[0], p, bx, sm, lane, lead, w2);
@@ -413,28 +467,30 @@ __global__ void __launch_bounds__(kBlock, 2) rqs_resnet_f16x3_kernel(const Args 
                 static_assert(T >= 1 && T <= 6, "2 .. 32 bins");
                 using Steps = FusedSteps<INVERSE, KB>;
                 constexpr int kRest = k8h::any_rest_mask(KB);   // what is left for the next group's first tile
-                Steps f;
-                const float kappa = sc[0];
+                Steps f{};   // (value-initialised: see the 8-bin branch)
+                float sf[2];
+                uniform_load(sc, sf);
+                const float kappa = sf[0];
                 f.kappa = kappa;
                 f.kl2e = 1.44269502162933349609375f * kappa;
-                f.tail_s = a.sp.tail_logit * sc[1];
-                const float* fbias = s_fbias + half * 16;
+                f.tail_s = a.sp.tail_logit * sf[1];
+                const lds_f32* fbias = s_fbias + half * 16;
                 i32x8 bx[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) bx[j] = bf8_operand(p[2 * j], p[2 * j + 1]);
                 Lead lead = read_lead(sm.ring + sm.slot * kStageVec4 + lane);
                 const int groups_any = dt >> 1;
                 f32x16 acc;
-                float* slot = s_row + tab[kTabTr + half] * kRowPad + r;
+                lds_f32* slot = s_row + tab[kTabTr + half] * kRowPad + r;
                 load_bias_tile(acc, fbias);
                 gemm_tile_pumped(acc, p, bx, sm, lane, lead, NoWeave{});
                 for (int g = 0; g < groups_any; ++g) {
-                    const float* gb = fbias + g * T * 32;
+                    const lds_f32* gb = fbias + g * T * 32;
                     f.x = *slot;
                     k8h::take_chunk<0, KB>(f, acc);
                     any_group_tiles<1, T, KB, Steps>(acc, f, gb, p, bx, sm, lane, lead, a.sp);
                     if (g + 1 < groups_any) {
-                        float* next_slot = s_row + tab[kTabTr + (g + 1) * 2 + half] * kRowPad + r;
+                        lds_f32* next_slot = s_row + tab[kTabTr + (g + 1) * 2 + half] * kRowPad + r;
                         load_bias_tile(acc, gb + T * 32);
                         gemm_tile_pumped(acc, p, bx, sm, lane, lead, SeqWeave<kRest, Steps>{f, a.sp});
                         *slot = f.y;
@@ -456,7 +512,7 @@ __global__ void __launch_bounds__(kBlock, 2) rqs_resnet_f16x3_kernel(const Args 
         // ---- results: position p of a row comes from slot final[p].  A block with any non-finite value (f16 range
         //      exceeded somewhere, or non-finite inputs) is not written at all: the exact kernel redoes it.
         lad_acc += __shfl_xor(lad_acc, 32, kWave);
-        const float sumsq = tile_row_sumsq(s_row, a.Ds, half, r);
+        const float sumsq = tile_row_sumsq((const float*)s_row, a.Ds, half, r);
         const bool bad = not_finite(lad_acc) || not_finite(sumsq);
         const bool wave_bad = __builtin_amdgcn_ballot_w64(bad) != 0;
         if (lane == 0) s_bad[wave] = wave_bad ? 1 : 0;
