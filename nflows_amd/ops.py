@@ -1859,8 +1859,11 @@ def use_tile16(batch, num_bins, context, device, activation=0):
     """K8s (16-sample tiles, csrc/rqs_resnet_f16s.hip) serves the batches that give a CU at most ONE 128-row block
     -- K8h would run them one wave per SIMD (or leave CUs idle): 8 bins, no context.  `NFA_K8S=0` switches it off.
     Returns 0 (K8h), 1 (K8s) or 2 (round 6: K8c, csrc/rqs_resnet_f16c.hip, the column-split form: batches of at most 96
-    rows per CU -- measured: 24 576 rows 0.875 ms against K8s's 0.936, 32 768 rows 1.15 against 1.01 --; `NFA_K8C=0` switches it off, the diagnostic bin capture has no twin of it)."""
+    rows per CU -- measured: 24 576 rows 0.875 ms against K8s's 0.936, 32 768 rows 1.15 against 1.01 --; `NFA_K8C=0` switches it off, the diagnostic bin capture has no twin of it).
+    0 while `capture_last_layer_logits` is active: neither has a logits twin, and the capture would otherwise be ignored."""
     if not K8S_ENABLED or num_bins != 8 or context is not None or activation != N.ACTIVATION_RELU:
+        return 0
+    if capture_last_layer_logits.active is not None:   # (K8s / K8c have no logits twin: the capture runs K8h's)
         return 0
     key = device.index if device.index is not None else torch.cuda.current_device()
     cus = _cu_counts.get(key)

