@@ -46,6 +46,25 @@ constexpr int kScaleA = 119, kScaleB = 127;   // e8m0 block scales of the bf8 in
 #define NFA_K8X_BF8(a, b, c) __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 1, 1, 0, kScaleA, 0, kScaleB)
 #endif
 
+// stream_request (bf16x3_gemm.hpp) on buffer loads: the three LDS-DMA requests of a stage from a buffer resource over the
+// stage (SGPRs: base and size are wave-uniform), the lane's byte offset as voffset, the request's as soffset -- the
+// global_load_lds form took a 64-bit per-lane address for each request, two or three 64-bit VALU instructions apiece.
+// Same requests, same slots, same vmcnt count: stream_advance's counted wait is unchanged.
+__device__ __forceinline__ void request_stage(WeightStream& sm) {
+    const int dst_slot = sm.slot >= 1 ? sm.slot - 1 : kRing - 1;  // (slot + 2) % 3
+    const char* stage = reinterpret_cast<const char*>(sm.w) + (size_t)sm.fetch * (kStageVec4 * 16);
+    const __amdgpu_buffer_rsrc_t rsrc =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(stage), (short)0, kStageVec4 * 16, 0x00020000);
+    const int wave = __builtin_amdgcn_readfirstlane(sm.tid >> 6);
+    char* slot = reinterpret_cast<char*>(sm.ring) + dst_slot * (kStageVec4 * 16) + wave * (kWave * 16);
+    const unsigned lane_off = (unsigned)sm.tid * 16u;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)(slot + i * kBlock * 16), 16,
+                                                 lane_off, i * kBlock * 16, 0, 0);
+    sm.fetch = (sm.fetch + 1 == sm.num_stages) ? 0 : sm.fetch + 1;
+}
+
 // the pieces of a k-step: 8 values per lane and piece = one register quad each (r: the last piece x 2^8)
 struct Pieces {
     uvec4 h, l, r;
@@ -60,7 +79,9 @@ struct Pieces {
 // in front of the first block that reads a tile.  NFA_K8X_NO_ASM (measurement builds): the same arithmetic in C++.
 #define NFA_K8X_ASM asm volatile
 
-// two fp32 values x `scale` (a power of two) -> packed f16 pairs of the three pieces.
+// two fp32 values x `scale` (a power of two) -> packed f16 pairs of the three pieces.  RELU: of max(v, 0) instead.
+//   v  = max(v, 0)                         v_maximum3_f32 v, 0, 0 (RELU only): NaN stays NaN -- overflow poison keeps
+//                                          propagating like torch.relu's --, -0 and -inf become +0
 //   hi = RN16(v s)                         v_fma_mixlo / mixhi_f16: fp32 fma, result rounded to f16
 //   t  = v s - hi                          v_fma_mix_f32 with the f16 `hi` as negated addend: exact (<= 13 bits)
 //   lo = RN16(t)
@@ -69,9 +90,23 @@ struct Pieces {
 // |v s| >= 65520 gives hi = inf, t = -inf, lo = -inf, d = NaN: the overflow poisons every sum it enters, the row block is
 // flagged and redone by the exact kernel.  (One asm block: hipcc puts an `s_nop 0` between two adjacent asm statements;
 // early-clobber everywhere: every output is written before the last input is read.)
+// ReLU before the split gives the pieces the sign mask on the pieces gave (K8x up to round 6): a negative v, -0 included,
+// has a negative or -0 `hi`, and all three pieces were cleared; NaN and +inf pass both ways.
+#define NFA_K8X_SPLIT_REST                                                  \
+    "v_fma_mixlo_f16 %1, %3, 1.0, 0 op_sel_hi:[0,0,0]\n\t"                  \
+    "v_fma_mixhi_f16 %1, %4, 1.0, 0 op_sel_hi:[0,0,0]\n\t"                  \
+    "v_fma_mix_f32 %3, %3, 1.0, -%1 op_sel_hi:[0,0,1]\n\t"                  \
+    "v_fma_mix_f32 %4, %4, 1.0, -%1 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"   \
+    "v_fma_mixlo_f16 %2, %3, %8, 0 op_sel_hi:[0,0,0]\n\t"                   \
+    "v_fma_mixhi_f16 %2, %4, %8, 0 op_sel_hi:[0,0,0]"
+template <bool RELU = false>
 __device__ __forceinline__ void split3_scaled(float v0, float v1, float scale, unsigned& hi, unsigned& lo, unsigned& rr) {
 #if defined(NFA_K8X_NO_ASM)
     typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+    if (RELU) {
+        v0 = __builtin_isnan(v0) ? v0 : (v0 > 0.0f ? v0 : 0.0f);
+        v1 = __builtin_isnan(v1) ? v1 : (v1 > 0.0f ? v1 : 0.0f);
+    }
     const float x0 = v0 * scale, x1 = v1 * scale;
     const h2 h = {(_Float16)x0, (_Float16)x1};
     const float t0 = x0 - (float)h[0], t1 = x1 - (float)h[1];
@@ -83,67 +118,32 @@ __device__ __forceinline__ void split3_scaled(float v0, float v1, float scale, u
 #else
     unsigned h, l, r;
     float t0, t1;
-    NFA_K8X_ASM(
-        "v_fma_mixlo_f16 %0, %5, %7, 0 op_sel_hi:[0,0,0]\n\t"
-        "v_fma_mixhi_f16 %0, %6, %7, 0 op_sel_hi:[0,0,0]\n\t"
-        "v_fma_mix_f32 %3, %5, %7, -%0 op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mix_f32 %4, %6, %7, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixlo_f16 %1, %3, 1.0, 0 op_sel_hi:[0,0,0]\n\t"
-        "v_fma_mixhi_f16 %1, %4, 1.0, 0 op_sel_hi:[0,0,0]\n\t"
-        "v_fma_mix_f32 %3, %3, 1.0, -%1 op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mix_f32 %4, %4, 1.0, -%1 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixlo_f16 %2, %3, %8, 0 op_sel_hi:[0,0,0]\n\t"
-        "v_fma_mixhi_f16 %2, %4, %8, 0 op_sel_hi:[0,0,0]"
-        : "=&v"(h), "=&v"(l), "=&v"(r), "=&v"(t0), "=&v"(t1)
-        : "v"(v0), "v"(v1), "v"(scale), "s"(256.0f));
+    if constexpr (RELU)
+        NFA_K8X_ASM(
+            "v_maximum3_f32 %3, %5, 0, 0\n\t"
+            "v_maximum3_f32 %4, %6, 0, 0\n\t"
+            "v_fma_mixlo_f16 %0, %3, %7, 0 op_sel_hi:[0,0,0]\n\t"
+            "v_fma_mixhi_f16 %0, %4, %7, 0 op_sel_hi:[0,0,0]\n\t"
+            "v_fma_mix_f32 %3, %3, %7, -%0 op_sel_hi:[0,0,1]\n\t"
+            "v_fma_mix_f32 %4, %4, %7, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
+            NFA_K8X_SPLIT_REST
+            : "=&v"(h), "=&v"(l), "=&v"(r), "=&v"(t0), "=&v"(t1)
+            : "v"(v0), "v"(v1), "v"(scale), "s"(256.0f));
+    else
+        NFA_K8X_ASM(
+            "v_fma_mixlo_f16 %0, %5, %7, 0 op_sel_hi:[0,0,0]\n\t"
+            "v_fma_mixhi_f16 %0, %6, %7, 0 op_sel_hi:[0,0,0]\n\t"
+            "v_fma_mix_f32 %3, %5, %7, -%0 op_sel_hi:[0,0,1]\n\t"
+            "v_fma_mix_f32 %4, %6, %7, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
+            NFA_K8X_SPLIT_REST
+            : "=&v"(h), "=&v"(l), "=&v"(r), "=&v"(t0), "=&v"(t1)
+            : "v"(v0), "v"(v1), "v"(scale), "s"(256.0f));
     hi = h;
     lo = l;
     rr = r;
 #endif
 }
-
-// the fp32 value of a piece triple (exact: hi + lo has at most 23 bits, + r' 2^-8 at most 24) times `mul`, plus what the
-// accumulators hold: the skip connection, acc = bias + T x h
-__device__ __forceinline__ void pieces_fma2(unsigned h, unsigned l, unsigned r, float mul, float& acc0, float& acc1) {
-    float t0, t1;
-#if defined(NFA_K8X_NO_ASM)
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    const h2 hh = __builtin_bit_cast(h2, h), ll = __builtin_bit_cast(h2, l), rr = __builtin_bit_cast(h2, r);
-    t0 = ((float)hh[0] + (float)ll[0]) + (float)rr[0] * 0.00390625f;
-    t1 = ((float)hh[1] + (float)ll[1]) + (float)rr[1] * 0.00390625f;
-#else
-    NFA_K8X_ASM(
-        "v_fma_mix_f32 %0, %2, 1.0, %3 op_sel_hi:[1,0,1]\n\t"
-        "v_fma_mix_f32 %1, %2, 1.0, %3 op_sel:[1,0,1] op_sel_hi:[1,0,1]\n\t"
-        "v_fma_mix_f32 %0, %4, %5, %0 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mix_f32 %1, %4, %5, %1 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
-        : "=&v"(t0), "=&v"(t1)
-        : "v"(h), "v"(l), "v"(r), "s"(0.00390625f));
-#endif
-    acc0 = __builtin_fmaf(t0, mul, acc0);
-    acc1 = __builtin_fmaf(t1, mul, acc1);
-}
-
-// ReLU applied to a value given as f16 pieces: all three are cleared where the leading piece is negative and not a
-// NaN (f16 bit patterns 0x8000 .. 0xFC00 = int16 <= -1024), so that NaNs -- overflow poison included -- keep
-// propagating like torch.relu's; -inf (a large negative pre-activation) becomes the zero it should.
-__device__ __forceinline__ void relu_pieces(Pieces& p) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        unsigned keep;
-        // (volatile: a pure statement may be hoisted or merged by the compiler, and ReLU'd copies kept alive beside the
-        //  originals would not fit the register file)
-        asm volatile("v_pk_min_i16 %0, %1, 0\n\t"
-            "v_pk_add_i16 %0, %0, %2\n\t"
-            "v_pk_ashrrev_i16 %0, %3, %0\n\t"
-            "v_not_b32 %0, %0"
-            : "=&v"(keep)
-            : "v"(p.h[i]), "s"(0x03FF03FFu), "s"(0x000F000Fu));  // (packed inline constants fill one half only)
-        p.h[i] &= keep;
-        p.l[i] &= keep;
-        p.r[i] &= keep;
-    }
-}
+#undef NFA_K8X_SPLIT_REST
 
 // the bf8 B operand of two k-steps: the high bytes of the r' and hi pieces (an f16's high byte IS its bf8 truncation: same
 // sign, same five exponent bits, the two leading fraction bits; infinities and NaNs stay what they are)
@@ -161,20 +161,15 @@ __device__ __forceinline__ i32x8 bf8_operand(const Pieces& p0, const Pieces& p1)
     return b;
 }
 
-// accumulator tile (x `scale`), registers 8 hk .. 8 hk + 7  ->  pieces of k-step 2 t + hk.  RELU: `v < 0 ? 0 : v`
-// (compare + select: NaN stays NaN, v_max_f32 would return the zero)
-template <bool RELU>
+// accumulator tile (x `scale`), registers 8 hk .. 8 hk + 7  ->  pieces of k-step 2 t + hk (RELU: of max(v, 0)).
+// WB: the matrix pipe's write-back distance in front (see NFA_K8X_ASM) -- needed where the tile's last MFMA may be close
+template <bool RELU, bool WB = true>
 __device__ __forceinline__ void tile_to_pieces(const f32x16& a, float scale, Pieces& p0, Pieces& p1) {
-    asm volatile("s_nop 7\n\ts_nop 3" : : "v"(a));   // (see NFA_K8X_ASM: the tile's last MFMA has written back)
+    if constexpr (WB) asm volatile("s_nop 7\n\ts_nop 3" : : "v"(a));   // (the tile's last MFMA has written back)
 #pragma unroll
     for (int q2 = 0; q2 < 8; ++q2) {
-        float v0 = a[q2 * 2], v1 = a[q2 * 2 + 1];
-        if (RELU) {
-            v0 = v0 < 0.0f ? 0.0f : v0;
-            v1 = v1 < 0.0f ? 0.0f : v1;
-        }
         unsigned h, l, r;
-        split3_scaled(v0, v1, scale, h, l, r);
+        split3_scaled<RELU>(a[q2 * 2], a[q2 * 2 + 1], scale, h, l, r);
         if (q2 < 4) {
             p0.h[q2] = h;
             p0.l[q2] = l;
@@ -184,17 +179,6 @@ __device__ __forceinline__ void tile_to_pieces(const f32x16& a, float scale, Pie
             p1.l[q2 - 4] = l;
             p1.r[q2 - 4] = r;
         }
-    }
-}
-
-// value of the pieces of one k-step x `mul`, added to 8 accumulator registers (the skip connection)
-__device__ __forceinline__ void add_pieces(f32x16& a, int q0, const Pieces& p, float mul) {
-#pragma unroll
-    for (int j2 = 0; j2 < 4; ++j2) {
-        float a0 = a[q0 + 2 * j2], a1 = a[q0 + 2 * j2 + 1];   // (no references to vector elements)
-        pieces_fma2(p.h[j2], p.l[j2], p.r[j2], mul, a0, a1);
-        a[q0 + 2 * j2] = a0;
-        a[q0 + 2 * j2 + 1] = a1;
     }
 }
 
@@ -226,7 +210,7 @@ __device__ __forceinline__ Lead read_lead(const vec4f* stage) {
 template <bool LAST>
 __device__ __forceinline__ void stage_kmajor(f32x16& acc0, f32x16& acc1, const Pieces& b0, const Pieces& b1, const i32x8& bx,
                                              WeightStream& sm, int lane, Lead& lead) {
-    stream_request(sm);
+    request_stage(sm);
     const vec4f* cur = sm.ring + sm.slot * kStageVec4 + lane;
     const f16x8 bh0 = __builtin_bit_cast(f16x8, b0.h), bl0 = __builtin_bit_cast(f16x8, b0.l);
     const f16x8 bh1 = __builtin_bit_cast(f16x8, b1.h), bl1 = __builtin_bit_cast(f16x8, b1.l);
@@ -262,24 +246,40 @@ __device__ __forceinline__ void stage_kmajor(f32x16& acc0, f32x16& acc1, const P
 }
 
 // k-major GEMM (all four output tiles accumulate together): out^T[128 x 32 samples] += W[128 x 16 NKS] x act^T; two
-// stages per pair of k-steps (tiles 0, 1 and tiles 2, 3).  RELU: applied to the input pieces on the fly (the pieces
-// themselves stay: they are the residual stream)
-template <bool RELU, int NKS>
-__device__ __forceinline__ void gemm_kmajor(f32x16 (&acc)[4], const Pieces (&p)[8], WeightStream& sm, int lane) {
+// stages per pair of k-steps (tiles 0, 1 and tiles 2, 3).  pair(pr, b0, b1) makes the pieces of k-steps 2 pr, 2 pr + 1.
+template <int NKS, class PairFn>
+__device__ __forceinline__ void gemm_kmajor_pairs(f32x16 (&acc)[4], WeightStream& sm, int lane, PairFn&& pair) {
     static_assert(NKS % 2 == 0, "pairs of k-steps");
     Lead lead = read_lead(sm.ring + sm.slot * kStageVec4 + lane);
 #pragma unroll
     for (int pr = 0; pr < NKS / 2; ++pr) {
-        Pieces b0 = p[2 * pr], b1 = p[2 * pr + 1];
-        if (RELU) {
-            relu_pieces(b0);
-            relu_pieces(b1);
-        }
+        Pieces b0, b1;
+        pair(pr, b0, b1);
         const i32x8 bx = bf8_operand(b0, b1);
         stage_kmajor<false>(acc[0], acc[1], b0, b1, bx, sm, lane, lead);
         if (pr + 1 < NKS / 2) stage_kmajor<false>(acc[2], acc[3], b0, b1, bx, sm, lane, lead);
         else stage_kmajor<true>(acc[2], acc[3], b0, b1, bx, sm, lane, lead);
     }
+}
+
+// ... on activations given as pieces
+template <int NKS>
+__device__ __forceinline__ void gemm_kmajor(f32x16 (&acc)[4], const Pieces (&p)[8], WeightStream& sm, int lane) {
+    gemm_kmajor_pairs<NKS>(acc, sm, lane, [&](int pr, Pieces& b0, Pieces& b1) {
+        b0 = p[2 * pr];
+        b1 = p[2 * pr + 1];
+    });
+}
+
+// ... on the previous GEMM's accumulator tiles: relu(src) x scale split into pieces on the fly, one pair of k-steps (= one
+// source tile: the accumulator layout is the B layout) at a time; src itself stays.  Only the first tile can have an MFMA
+// close in front (the previous GEMM's); the others are read behind at least one stage of this GEMM.
+__device__ __forceinline__ void gemm_kmajor_relu(f32x16 (&acc)[4], const f32x16 (&src)[4], float scale, WeightStream& sm,
+                                                 int lane) {
+    gemm_kmajor_pairs<8>(acc, sm, lane, [&](int pr, Pieces& b0, Pieces& b1) {
+        if (pr == 0) tile_to_pieces<true, true>(src[pr], scale, b0, b1);
+        else tile_to_pieces<true, false>(src[pr], scale, b0, b1);
+    });
 }
 
 }  // namespace k8x

@@ -12,12 +12,14 @@
 //   * a wave owns 32 rows for the whole run; the rows live in an LDS tile by slot, every GEMM is computed transposed
 //     and chained through the register file (the accumulator tiles of one GEMM are the B operand of the next, up to
 //     a column permutation the host applies to the weights);
-//   * the residual stream is NOT kept in fp32: its three pieces are exact, the skip connection rebuilds the value
-//     from them (two v_fma_mix_f32 per value), the first ReLU of a block is a sign mask on the pieces; block order:
-//     skip first (v = bias + T p), then u's pieces, then the second Linear (K8's order spilled 12 GB per launch here);
+//   * the residual stream stays in fp32, in the accumulators of the GEMM that made it (64 registers, at that GEMM's
+//     power-of-two scale): each Linear splits the ReLU of its input accumulators into pieces one pair of k-steps at a
+//     time (v_maximum3_f32 + the split), the skip connection is the second Linear's accumulator init, one fma per
+//     value (v = bias + T h), and h is split once more only for the final layer;
 //   * weights: 12 KB stages of twelve 1 KB fragments ([64 lanes] x 16 B) -- k-major: two k-steps of two output tiles,
 //     [H0, L0, H1, L1, X lo, X hi] per tile; tile-major final layer: four k-steps of a tile, [H0, L0, H1, L1][H2, L2,
-//     H3, L3][X01 lo, X01 hi, X23 lo, X23 hi] -- through the three-slot LDS-DMA ring of bf16x3_gemm.hpp, four waves per
+//     H3, L3][X01 lo, X01 hi, X23 lo, X23 hi] -- through the three-slot LDS-DMA ring of bf16x3_gemm.hpp (requested with buffer
+//     loads: f16x3_gemm.hpp, request_stage), four waves per
 //     workgroup, two workgroups per CU; fragments 0 .. 3 of every stage are read right behind the PREVIOUS stage's
 //     barrier (f16x3_gemm.hpp: Lead), the barrier stands in front of a stage's last MFMAs;
 //   * the final layer is tile-major with the spline evaluation (rqs_fused8.hpp: one walk over fp32 running knot
@@ -29,9 +31,9 @@
 // split at scale S (a power of two, host: 16): a value keeps all its 24 bits while |v S| >= 2^-9 (the last piece,
 // kept x 2^8, then is >= 2^-24, f16's smallest subnormal), below that the absolute error is <= 2^-33 / S; |v S| >=
 // 65520 overflows.  Accumulators hold S T x (the reference's pre-activation); `scales` = per GEMM {1 / T, T}: 1 / T
-// takes an accumulator to the next pieces' scale (exact), T takes the residual stream's pieces to the second Linear's
-// accumulator scale; the final layer's pair is {kappa = 1 / (S T), S T} for the spline evaluation.  Overflow poisons
-// (hi = inf, lo = -inf, r = NaN, and ReLU's sign mask keeps NaN): a row block with any non-finite result writes
+// takes an accumulator to the next pieces' scale (exact), T / T' takes the residual stream (at the scale S T' of the GEMM
+// that made it) to the second Linear's accumulator scale; the final layer's pair is {kappa = 1 / (S T), S T} for the spline evaluation.  Overflow poisons
+// (hi = inf, lo = -inf, r = NaN, and ReLU's v_maximum3_f32 keeps NaN): a row block with any non-finite result writes
 // nothing and raises its entry of `redo`, the caller runs K8 (three bf16 pieces: full fp32 range) on the flagged
 // blocks right behind (nfa_rqs_flow_resnet_redo_f32), as for K8h.
 //

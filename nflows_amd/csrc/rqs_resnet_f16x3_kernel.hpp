@@ -119,7 +119,7 @@ struct SeqWeave {
 template <int HS, class W>
 __device__ __forceinline__ void stage_pumped(f32x16& acc, const Pieces (&p)[8], const i32x8 (&bx)[4], WeightStream& sm, int lane,
                                              Lead& lead, W& w) {
-    stream_request(sm);
+    request_stage(sm);
     const vec4f* cur = sm.ring + sm.slot * kStageVec4 + lane;
     vec4f xa = cur[8 * 64], xb = cur[9 * 64];
     vec4f fh0 = lead.h0, fl0 = lead.l0, fh1 = lead.h1, fl1 = lead.l1;
@@ -226,9 +226,9 @@ __global__ void __launch_bounds__(kBlock, 2) rqs_resnet_f16x3_kernel(const Args 
     sm.fetch = 0;
     sm.num_stages = a.num_stages * a.num_layers;
     sm.tid = tid;
-    stream_request(sm);  // stage 0 -> slot 0
+    request_stage(sm);  // stage 0 -> slot 0
     sm.slot = 2;
-    stream_request(sm);  // stage 1 -> slot 1
+    request_stage(sm);  // stage 1 -> slot 1
     sm.slot = 0;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -295,7 +295,7 @@ __global__ void __launch_bounds__(kBlock, 2) rqs_resnet_f16x3_kernel(const Args 
             }
             const float* bias = a.bias + (size_t)layer * a.bias_per_layer + half * 16;  // + 32 per tile
             const float* sc = a.scales + (size_t)layer * gemms * 2;   // {1 / T, T} per GEMM (uniform)
-            Pieces p[8];   // the current activations (128 k per sample) as f16 pieces at scale S
+            Pieces p[8];   // f16 pieces at scale S: the identity features, then the final layer's input
 
             // ---- identity features: k = ks*16 + half*8 + j
 #pragma unroll
@@ -314,17 +314,17 @@ __global__ void __launch_bounds__(kBlock, 2) rqs_resnet_f16x3_kernel(const Args 
                 }
             }
 
-            // ---- initial layer: h = W_i x + b_i   (accumulators: S T_0 h)
+            // ---- initial layer: h = W_i x + b_i   (accumulators: S T_0 h).  The residual stream stays in these 64 fp32
+            //      accumulators, at the scale of the GEMM that made it: h * hs = S h (hs = 1 / T, a power of two)
+            f32x16 h[4];
+            float hs;
             {
-                f32x16 h[4];
 #pragma unroll
                 for (int t = 0; t < 4; ++t) load_bias_tile(h[t], bias + t * 32);
-                gemm_kmajor<false, INIT_KS>(h, p, sm, lane);
+                gemm_kmajor<INIT_KS>(h, p, sm, lane);
                 float s0[2];
                 uniform_load(sc, s0);
-                const float inv_t = s0[0];
-#pragma unroll
-                for (int t = 0; t < 4; ++t) tile_to_pieces<false>(h[t], inv_t, p[2 * t], p[2 * t + 1]);
+                hs = s0[0];
             }
             bias += 128;
             sc += 2;
@@ -336,44 +336,36 @@ __global__ void __launch_bounds__(kBlock, 2) rqs_resnet_f16x3_kernel(const Args 
                 if (a.num_blocks == 0) __syncthreads();   // without blocks the final layer follows at once
             }
 
-            // ---- residual blocks: h += W_1 relu(W_0 relu(h) + b_0) + b_1, both Linears k-major.  The h pieces (96
-            //      registers) survive the first Linear for the skip connection; u (64 accumulators) turns into the
-            //      relu(u) pieces tile by tile; the skip is added into the second Linear's accumulators tile by tile.
+            // ---- residual blocks: h += W_1 relu(W_0 relu(h) + b_0) + b_1, both Linears k-major, each splitting the ReLU of
+            //      its input accumulators into pieces one pair of k-steps at a time (gemm_kmajor_relu).  Registers: h (64),
+            //      u (64) and one pair's pieces (24) -- the pieces of h (96) and of relu(u) (96) are never all live.
+            //   first Linear    u = b_0 + W_0 relu(h)
+            //   skip            v = b_1 + T_1 h = fma(h, hs T_1, b_1): one rounding, as from exact pieces; in place of h
+            //   second Linear   v += W_1 relu(u); v is the next h, at hs = 1 / T_1
             for (int blk = 0; blk < a.num_blocks; ++blk) {
-                // Register budget (what keeps this kernel out of scratch: K8's order -- u into pieces FIRST, then the skip
-                // connection -- holds the pieces of h, the pieces of relu(u) and the second Linear's accumulators at the same
-                // time, 96 + 96 + 64 registers, and spilled 74 x the kernel's algorithmic bytes through HBM, profiles/r6):
-                //   first Linear    pieces of h (96) + u (64)
-                //   skip            v = b_1 + T h from the pieces, which die tile by tile: u (64) + v (64) + at most 96
-                //   u -> pieces     relu(u) / T into q (96), u dies tile by tile: v (64) + q + what is left of u
-                //   second Linear   v (64) + q (96)
-                f32x16 v[4];
-                Pieces q[8];
                 float sb[4];
-                {
-                    f32x16 u[4];
+                f32x16 u[4];
 #pragma unroll
-                    for (int t = 0; t < 4; ++t) load_bias_tile(u[t], bias + t * 32);
-                    gemm_kmajor<true, 8>(u, p, sm, lane);
-                    uniform_load(sc, sb);
-                    const float t1 = sb[3];
+                for (int t = 0; t < 4; ++t) load_bias_tile(u[t], bias + t * 32);
+                gemm_kmajor_relu(u, h, hs, sm, lane);
+                uniform_load(sc, sb);
+                const float skip = hs * sb[3];   // (powers of two: exact)
 #pragma unroll
-                    for (int t = 0; t < 4; ++t) {
-                        load_bias_tile(v[t], bias + 128 + t * 32);
-                        add_pieces(v[t], 0, p[2 * t], t1);
-                        add_pieces(v[t], 8, p[2 * t + 1], t1);
-                    }
-                    const float inv_t = sb[0];
+                for (int t = 0; t < 4; ++t) {
+                    f32x16 b1;
+                    load_bias_tile(b1, bias + 128 + t * 32);
 #pragma unroll
-                    for (int t = 0; t < 4; ++t) tile_to_pieces<true>(u[t], inv_t, q[2 * t], q[2 * t + 1]);
+                    for (int q_ = 0; q_ < 16; ++q_) h[t][q_] = __builtin_fmaf(h[t][q_], skip, b1[q_]);
                 }
-                const float inv_t1 = sb[2];
-                gemm_kmajor<false, 8>(v, q, sm, lane);
-#pragma unroll
-                for (int t = 0; t < 4; ++t) tile_to_pieces<false>(v[t], inv_t1, p[2 * t], p[2 * t + 1]);
+                gemm_kmajor_relu(h, u, sb[0], sm, lane);
+                hs = sb[2];
                 bias += 256;
                 sc += 4;
             }
+
+            // the residual stream's pieces for the final layer's 24 tiles
+#pragma unroll
+            for (int t = 0; t < 4; ++t) tile_to_pieces<false>(h[t], hs, p[2 * t], p[2 * t + 1]);
 
             // ---- final layer with the spline evaluation woven into the MFMAs: the three tiles of a group hold the
             //      logits of this lane's two features A, B (A = T0 + T1[0:8], B = T1[8:16] + T2), at scale 1 / kappa
