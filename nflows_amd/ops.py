@@ -1197,9 +1197,6 @@ def pack_resnet_conditioner(net, num_transform, params_per_feature, log2e=False,
     return torch.cat(stages, dim=0).contiguous(), torch.cat(biases).contiguous()
 
 
-_TRAIN_ORDER_K = {}
-
-
 def pack_resnet_hidden_train(w_in, b_in, block_params, final=None):
     """K14's packer as ONE launch (nfa_pack_resnet_hidden_train_f32): fp32 parameters on the device -> (forward stages,
     forward biases, backward stages, final-layer bias or None), the bytes of `pack_resnet_hidden_train_reference`.
@@ -1451,40 +1448,19 @@ def pack_mlp_conditioner(net, num_transform, additive=False):
 
 def affine_flow_mlp(inputs, weights_packed, bias_packed, tables, num_transform, num_identity, num_hidden_layers,
                     scale_activation, inverse=False, accumulate_into=None, num_layers=1,
-                    standard_normal_log_prob=False, pad=None, _pad_columns_count=0, residual_blocks=False):
+                    standard_normal_log_prob=False, pad=None, residual_blocks=False):
     """K11 -- a run of affine / additive coupling layers with their MLP conditioners in one launch
     (weights / biases of the layers concatenated in execution order, tables from
-    `flow_layer_tables`).  `residual_blocks` (round 5): the conditioners are ResidualNets, `num_hidden_layers` = twice
-    their number of blocks.  Returns (outputs, logabsdet), or (None, log_prob) with
-    `standard_normal_log_prob`; None when the shape is outside the fast path."""
-    N.require_device_f32("inputs", inputs, 2)
-    if pad is not None and inputs.shape[1] != pad[0]:   # rows padded to a multiple of four columns (tables too)
-        out = affine_flow_mlp(_pad_columns(inputs, pad[0], pad[1]), weights_packed, bias_packed, tables, num_transform,
-                              num_identity, num_hidden_layers, scale_activation, inverse, accumulate_into, num_layers,
-                              standard_normal_log_prob, None, pad[0] - inputs.shape[1], residual_blocks)
-        return _without_pad_columns(out, inputs.shape[1])
-    if inputs.shape[0] % 128:
-        return _on_full_blocks(
-            lambda x_, acc_, ctx_: affine_flow_mlp(x_, weights_packed, bias_packed, tables, num_transform, num_identity,
-                                                   num_hidden_layers, scale_activation, inverse, acc_, num_layers,
-                                                   standard_normal_log_prob, None, _pad_columns_count, residual_blocks),
-            inputs, accumulate_into)
-    dev = inputs.device
-    B, D = inputs.shape
-    x = inputs.detach().contiguous()
-    lad, flags = _lad_buffer(accumulate_into, B, dev, inverse)
-    flags, out = _density_epilogue(flags, standard_normal_log_prob, inverse, x, _pad_columns_count)
-    if residual_blocks:
-        flags |= N.FLAG_RESIDUAL_BLOCKS
-    with torch.cuda.device(dev):
-        rc = N.load().nfa_affine_flow_mlp_f32(
-            N.ptr(x), N.ptr(weights_packed), N.ptr(bias_packed), N.ptr(tables), num_layers, N.ptr(out),
-            N.ptr(lad), N.ptr(_status_word(dev)), B, D, num_transform, num_identity, 128, num_hidden_layers,
-            scale_activation, flags, N.stream_handle(dev))
-    if rc == N.ERR_UNSUPPORTED:
-        return None
-    N.check(rc)
-    return out, lad
+    `flow_layer_tables`; rows padded to a multiple of four columns by `pad`).  `residual_blocks` (round 5): the
+    conditioners are ResidualNets, `num_hidden_layers` = twice their number of blocks.  Returns (outputs, logabsdet),
+    or (None, log_prob) with `standard_normal_log_prob`; None when the shape is outside the fast path."""
+    def launch(x, ctx, out, lad, redo, flags, status, stream):
+        return N.load().nfa_affine_flow_mlp_f32(
+            N.ptr(x), N.ptr(weights_packed), N.ptr(bias_packed), N.ptr(tables), num_layers, N.ptr(out), N.ptr(lad),
+            status, x.shape[0], x.shape[1], num_transform, num_identity, 128, num_hidden_layers, scale_activation, flags,
+            stream)
+    return _whole_layer_launch(launch, inputs, inverse, accumulate_into, standard_normal_log_prob, pad,
+                               flags=N.FLAG_RESIDUAL_BLOCKS if residual_blocks else 0)
 
 
 def split_f16x2(w):
@@ -1732,25 +1708,71 @@ def _pad_columns(inputs, padded_features, value):
     return torch.cat((inputs, fill), dim=1)
 
 
-def _on_full_blocks(run, inputs, accumulate_into, context=None):
-    """The whole-layer kernels work on full 128-row blocks.  A ragged batch is padded with zero rows whose
-    results are dropped (rows are independent: a row's result does not depend on the others in its block);
-    `run(inputs, accumulate_into, context)` is the launch on a batch of full blocks."""
-    B = inputs.shape[0]
-    pad = (-B) % 128
-    if pad == 0:
-        return run(inputs, accumulate_into, context)
-    padded = torch.cat((inputs, inputs.new_zeros(pad, inputs.shape[1])), dim=0)
-    padded_context = None if context is None else torch.cat((context, context.new_zeros(pad, context.shape[1])), dim=0)
-    result = run(padded, None, padded_context)
-    if result is None:
-        return None
-    out, lad = result
-    out = None if out is None else out[:B]
-    lad = lad[:B]
-    if accumulate_into is not None:
-        accumulate_into += lad
-        lad = accumulate_into
+def _whole_layer_launch(launch, inputs, inverse, accumulate_into, standard_normal_log_prob, pad, context=None,
+                        flags=0, spec=None, redo=None):
+    """The steps around every whole-layer launch (K8, K8h / K8s / K8c, K8x, K11).  `launch(x, ctx, out, lad, redo, flags,
+    status, stream)` enqueues the engine's entry point on the prepared rows and returns its status code; `flags` are the
+    engine's own bits.
+
+    `pad` = (padded features, pad value) of `fused_geometry`: the launcher's `num_transform`, blobs and tables are the
+    padded layer's, and the density epilogue is told how many trailing columns are padding.  The kernels work on full
+    128-row blocks: a ragged batch is padded with zero rows whose results are dropped (rows are independent: a row's
+    result does not depend on the others in its block); `accumulate_into` then gets the result added on the host.
+    `redo` = (weights, biases, tables, num_layers, num_transform, num_identity, num_blocks) of the exact kernel (K8h,
+    K8x): the launch flags the 128-row blocks it gave up on (`last_redo_blocks`), and K8 redoes them (`NFA_K8H_NOREDO`:
+    not).  `spec`: a spline engine (`_after_spline`).  Returns (outputs, logabsdet), (None, log_prob) with
+    `standard_normal_log_prob`, or None when the entry point declines the shape."""
+    N.require_device_f32("inputs", inputs, 2)
+    B, D = inputs.shape
+    x, pad_columns, acc = inputs, 0, accumulate_into
+    if pad is not None and D != pad[0]:
+        x, pad_columns = _pad_columns(inputs, pad[0], pad[1]), pad[0] - D
+    pad_rows = (-B) % 128
+    if pad_rows:
+        x = torch.cat((x, x.new_zeros(pad_rows, x.shape[1])), dim=0)
+        if context is not None:
+            context = torch.cat((context, context.new_zeros(pad_rows, context.shape[1])), dim=0)
+        acc = None
+    x = x.detach().contiguous()
+    dev = x.device
+    rows = x.shape[0]
+    lad, lad_flags = _lad_buffer(acc, rows, dev, inverse)
+    flags, out = _density_epilogue(lad_flags | flags, standard_normal_log_prob, inverse, x, pad_columns)
+    ctx = None
+    if context is not None:   # conditioners with a context: [B, context_features] rows
+        N.require_device_f32("context", context, 2)
+        ctx = context.detach().contiguous()
+        if ctx.shape[0] != rows:
+            raise ValueError("context must have one row per input row")
+    redo_flags = None
+    if redo is not None:
+        global _last_redo
+        redo_flags = _last_redo = torch.empty(max(1, rows // 128), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        status, stream = N.ptr(_status_word(dev)), N.stream_handle(dev)
+        rc = launch(x, ctx, out, lad, redo_flags, flags, status, stream)
+        if rc == N.ERR_UNSUPPORTED:
+            return None
+        N.check(rc)
+        if redo is not None and os.environ.get("NFA_K8H_NOREDO"):
+            spec = None   # (the measurement switch skips the status check with the redo pass)
+        elif redo is not None:
+            weights, biases, tables, num_layers, num_transform, num_identity, num_blocks = redo
+            lib = N.load()
+            entry, head = ((lib.nfa_rqs_flow_resnet_redo_f32, (N.ptr(x),)) if ctx is None else
+                           (lib.nfa_rqs_flow_resnet_context_redo_f32, (N.ptr(x), N.ptr(ctx), ctx.shape[1])))
+            N.check(entry(*head, N.ptr(weights), N.ptr(biases), N.ptr(tables), num_layers, N.ptr(out), N.ptr(lad),
+                          N.ptr(redo_flags), status, rows, x.shape[1], num_transform, num_identity, 128, num_blocks,
+                          ctypes.byref(spec), flags, stream))
+    if spec is not None:
+        _after_spline(spec, inverse, dev)
+    if pad_rows:
+        out, lad = None if out is None else out[:B], lad[:B]
+        if accumulate_into is not None:
+            accumulate_into += lad
+            lad = accumulate_into
+    if pad_columns and out is not None:
+        out = out[:, :D]
     return out, lad
 
 
@@ -1767,73 +1789,31 @@ def _density_epilogue(flags, standard_normal_log_prob, inverse, like, pad_column
     return flags | N.FLAG_STANDARD_NORMAL_LOG_PROB | N.FLAG_SKIP_OUTPUTS | (pad_columns << N.FLAG_PAD_COLUMNS_SHIFT), None
 
 
-def _without_pad_columns(result, features):
-    """(outputs, logabsdet) of a launch on padded rows -> the caller's columns ((None, log_prob) stays)."""
-    if result is None or result[0] is None:
-        return result
-    return result[0][:, :features], result[1]
-
-
 def rqs_coupling_resnet(inputs, weights_packed, bias_packed, tables, num_transform, num_identity, num_blocks,
                         spec, inverse=False, accumulate_into=None, log2e=False, num_layers=1,
-                        standard_normal_log_prob=False, context=None, pad=None, _pad_columns_count=0, activation=0):
+                        standard_normal_log_prob=False, context=None, pad=None, activation=0):
     """K8 -- ResidualNet conditioner + spline coupling layer in one kernel; with num_layers > 1 a
     whole run of such layers (weights / biases concatenated in execution order, tables from
-    `flow_layer_tables`).  Returns (outputs, logabsdet), or (None, log_prob) with
+    `flow_layer_tables`).  `pad`: see `_whole_layer_launch`.  Returns (outputs, logabsdet), or (None, log_prob) with
     `standard_normal_log_prob` (Flow.log_prob with a StandardNormal base: flows/base.py:42-49);
     None when the shape is outside the fast path."""
-    N.require_device_f32("inputs", inputs, 2)
-    if pad is not None and inputs.shape[1] != pad[0]:
-        # `pad` = (padded features, pad value) of `fused_geometry`: `num_transform`, the blobs and the tables
-        # are the padded layer's; the pad columns come off the result again
-        # (the density epilogue is told how many trailing columns are padding)
-        out = rqs_coupling_resnet(_pad_columns(inputs, pad[0], pad[1]), weights_packed, bias_packed, tables,
-                                  num_transform, num_identity, num_blocks, spec, inverse, accumulate_into, log2e,
-                                  num_layers, standard_normal_log_prob, context, None, pad[0] - inputs.shape[1], activation)
-        return _without_pad_columns(out, inputs.shape[1])
-    if inputs.shape[0] % 128:
-        return _on_full_blocks(
-            lambda x_, acc_, ctx_: rqs_coupling_resnet(x_, weights_packed, bias_packed, tables, num_transform,
-                                                       num_identity, num_blocks, spec, inverse, acc_, log2e,
-                                                       num_layers, standard_normal_log_prob, ctx_, None,
-                                                       _pad_columns_count, activation),
-            inputs, accumulate_into, context)
-    dev = inputs.device
-    B, D = inputs.shape
-    x = inputs.detach().contiguous()
-    lad, flags = _lad_buffer(accumulate_into, B, dev, inverse)
-    flags, out = _density_epilogue(flags, standard_normal_log_prob, inverse, x, _pad_columns_count)
-    if log2e:
-        flags |= N.FLAG_LOGITS_LOG2E
-    flags |= int(activation) << N.FLAG_ACTIVATION_SHIFT
-    with torch.cuda.device(dev):
-        if context is not None:   # conditioners with a context: [B, context_features] rows
-            N.require_device_f32("context", context, 2)
-            ctx = context.detach().contiguous()
-            if ctx.shape[0] != B:
-                raise ValueError("context must have one row per input row")
-            rc = N.load().nfa_rqs_flow_resnet_context_f32(
-                N.ptr(x), N.ptr(ctx), ctx.shape[1], N.ptr(weights_packed), N.ptr(bias_packed), N.ptr(tables),
-                num_layers, N.ptr(out), N.ptr(lad), N.ptr(_status_word(dev)), B, D, num_transform, num_identity,
-                128, num_blocks, ctypes.byref(spec), flags, N.stream_handle(dev))
-        elif capture_last_layer_logits.active is not None:
-            capture = capture_last_layer_logits.active
-            rc = N.load().nfa_rqs_flow_resnet_logits_f32(
-                N.ptr(x), N.ptr(weights_packed), N.ptr(bias_packed), N.ptr(tables), num_layers, N.ptr(out),
-                N.ptr(lad), N.ptr(_status_word(dev)), B, D, num_transform, num_identity, 128, num_blocks,
-                ctypes.byref(spec), flags, N.stream_handle(dev), N.ptr(capture.buffer(B, num_transform, dev)))
-            if rc == N.OK:
-                capture.finish(None)
-        else:
-            rc = N.load().nfa_rqs_flow_resnet_f32(
-                N.ptr(x), N.ptr(weights_packed), N.ptr(bias_packed), N.ptr(tables), num_layers, N.ptr(out),
-                N.ptr(lad), N.ptr(_status_word(dev)), B, D, num_transform, num_identity, 128, num_blocks,
-                ctypes.byref(spec), flags, N.stream_handle(dev))
-    if rc == N.ERR_UNSUPPORTED:
-        return None
-    N.check(rc)
-    _after_spline(spec, inverse, dev)
-    return out, lad
+    def launch(x, ctx, out, lad, redo, flags, status, stream):
+        lib = N.load()
+        B, D = x.shape
+        args = (N.ptr(weights_packed), N.ptr(bias_packed), N.ptr(tables), num_layers, N.ptr(out), N.ptr(lad), status,
+                B, D, num_transform, num_identity, 128, num_blocks, ctypes.byref(spec), flags, stream)
+        if ctx is not None:
+            return lib.nfa_rqs_flow_resnet_context_f32(N.ptr(x), N.ptr(ctx), ctx.shape[1], *args)
+        capture = capture_last_layer_logits.active
+        if capture is None:
+            return lib.nfa_rqs_flow_resnet_f32(N.ptr(x), *args)
+        rc = lib.nfa_rqs_flow_resnet_logits_f32(N.ptr(x), *args, N.ptr(capture.buffer(B, num_transform, x.device)))
+        if rc == N.OK:
+            capture.finish(None)
+        return rc
+    flags = (N.FLAG_LOGITS_LOG2E if log2e else 0) | int(activation) << N.FLAG_ACTIVATION_SHIFT
+    return _whole_layer_launch(launch, inputs, inverse, accumulate_into, standard_normal_log_prob, pad, context,
+                               flags=flags, spec=spec)
 
 
 _ACTIVATION_CODES = {id(torch.nn.functional.relu): N.ACTIVATION_RELU, id(torch.relu): N.ACTIVATION_RELU,
@@ -1894,8 +1874,7 @@ class capture_last_layer_bins:
 
 def rqs_coupling_resnet_f16(inputs, stream_f16, packed_exact, tables, num_transform, num_identity, num_blocks,
                             spec, inverse=False, accumulate_into=None, num_layers=1,
-                            standard_normal_log_prob=False, pad=None, context=None, _pad_columns_count=0,
-                            tile16=False, activation=0):
+                            standard_normal_log_prob=False, pad=None, context=None, tile16=False, activation=0):
     """K8h -- the run of whole-layer kernels on the f16 matrix pipe (two f16 pieces per operand),
     followed by the exact kernel (three bf16 pieces, full fp32 range) on the row blocks the first
     pass gave up on: blocks with a non-finite result, i.e. an activation beyond the f16 range or
@@ -1905,88 +1884,35 @@ def rqs_coupling_resnet_f16(inputs, stream_f16, packed_exact, tables, num_transf
     (pack_resnet_conditioner_f16(tile16=True)) and the launch goes to the 16-sample-tile kernel; 2: packed for K8c
     (`colsplit=True`), the column-split form.
     Results as for `rqs_coupling_resnet`."""
-    N.require_device_f32("inputs", inputs, 2)
-    if pad is not None and inputs.shape[1] != pad[0]:   # (see rqs_coupling_resnet)
-        out = rqs_coupling_resnet_f16(_pad_columns(inputs, pad[0], pad[1]), stream_f16, packed_exact, tables,
-                                      num_transform, num_identity, num_blocks, spec, inverse, accumulate_into,
-                                      num_layers, standard_normal_log_prob, None, context,
-                                      pad[0] - inputs.shape[1], tile16, activation)
-        return _without_pad_columns(out, inputs.shape[1])
-    if inputs.shape[0] % 128:
-        return _on_full_blocks(
-            lambda x_, acc_, ctx_: rqs_coupling_resnet_f16(x_, stream_f16, packed_exact, tables, num_transform,
-                                                           num_identity, num_blocks, spec, inverse, acc_, num_layers,
-                                                           standard_normal_log_prob, None, ctx_, _pad_columns_count,
-                                                           tile16, activation),
-            inputs, accumulate_into, context)
-    dev = inputs.device
-    B, D = inputs.shape
-    x = inputs.detach().contiguous()
-    lad, flags = _lad_buffer(accumulate_into, B, dev, inverse)
-    flags, out = _density_epilogue(flags, standard_normal_log_prob, inverse, x, _pad_columns_count)
-    flags |= int(activation) << N.FLAG_ACTIVATION_SHIFT
-    global _last_redo
-    redo = torch.empty(max(1, B // 128), dtype=torch.int32, device=dev)
-    _last_redo = redo
-    lib = N.load()
-    stream, param_stages, final_table = stream_f16
-    ctx = None
-    if context is not None:   # conditioners with a context: [B, context_features] rows
-        N.require_device_f32("context", context, 2)
-        ctx = context.detach().contiguous()
-        if ctx.shape[0] != B:
-            raise ValueError("context must have one row per input row")
-    capture = capture_last_layer_bins.active
-    capture_logits = capture_last_layer_logits.active
-    with torch.cuda.device(dev):
-        if ctx is None and capture_logits is not None and not tile16:
-            bins = torch.full((B, num_transform), -2, dtype=torch.int32, device=dev)
-            rc = lib.nfa_rqs_flow_resnet_f16x2_logits_f32(
-                N.ptr(x), N.ptr(stream), param_stages, N.ptr(final_table), num_layers, N.ptr(out),
-                N.ptr(lad), N.ptr(redo), N.ptr(_status_word(dev)), B, D, num_transform, num_identity, 128,
-                num_blocks, ctypes.byref(spec), flags, N.stream_handle(dev), N.ptr(bins),
-                N.ptr(capture_logits.buffer(B, num_transform, dev)))
+    weights, param_stages, final_table = stream_f16
+
+    def launch(x, ctx, out, lad, redo, flags, status, stream):
+        lib = N.load()
+        B, D = x.shape
+        args = (N.ptr(weights), param_stages, N.ptr(final_table), num_layers, N.ptr(out), N.ptr(lad), N.ptr(redo),
+                status, B, D, num_transform, num_identity, 128, num_blocks, ctypes.byref(spec), flags, stream)
+        if ctx is not None:
+            return lib.nfa_rqs_flow_resnet_context_f16x2_f32(N.ptr(x), N.ptr(ctx), ctx.shape[1], *args)
+        capture_logits, capture = capture_last_layer_logits.active, capture_last_layer_bins.active
+        if capture_logits is not None and not tile16:
+            bins = torch.full((B, num_transform), -2, dtype=torch.int32, device=x.device)
+            rc = lib.nfa_rqs_flow_resnet_f16x2_logits_f32(N.ptr(x), *args, N.ptr(bins),
+                                                          N.ptr(capture_logits.buffer(B, num_transform, x.device)))
             if rc == N.OK:
                 capture_logits.finish(redo)
-        elif ctx is None and capture is not None:
+            return rc
+        if capture is not None:
             entry = lib.nfa_rqs_flow_resnet_f16x2_tile16_bins_f32 if tile16 else lib.nfa_rqs_flow_resnet_f16x2_bins_f32
-            capture.bins = torch.full((B, num_transform), -2, dtype=torch.int32, device=dev)
+            capture.bins = torch.full((B, num_transform), -2, dtype=torch.int32, device=x.device)
             capture.redo = redo
             capture.launches += 1
-            rc = entry(
-                N.ptr(x), N.ptr(stream), param_stages, N.ptr(final_table), num_layers, N.ptr(out),
-                N.ptr(lad), N.ptr(redo), N.ptr(_status_word(dev)), B, D, num_transform, num_identity, 128,
-                num_blocks, ctypes.byref(spec), flags, N.stream_handle(dev), N.ptr(capture.bins))
-        elif ctx is None:
-            entry = (lib.nfa_rqs_flow_resnet_f16x2_colsplit_f32 if tile16 == 2 else
-                     lib.nfa_rqs_flow_resnet_f16x2_tile16_f32 if tile16 else lib.nfa_rqs_flow_resnet_f16x2_f32)
-            rc = entry(
-                N.ptr(x), N.ptr(stream), param_stages, N.ptr(final_table), num_layers, N.ptr(out),
-                N.ptr(lad), N.ptr(redo), N.ptr(_status_word(dev)), B, D, num_transform, num_identity, 128,
-                num_blocks, ctypes.byref(spec), flags, N.stream_handle(dev))
-        else:
-            rc = lib.nfa_rqs_flow_resnet_context_f16x2_f32(
-                N.ptr(x), N.ptr(ctx), ctx.shape[1], N.ptr(stream), param_stages, N.ptr(final_table), num_layers,
-                N.ptr(out), N.ptr(lad), N.ptr(redo), N.ptr(_status_word(dev)), B, D, num_transform, num_identity,
-                128, num_blocks, ctypes.byref(spec), flags, N.stream_handle(dev))
-        if rc == N.ERR_UNSUPPORTED:
-            return None
-        N.check(rc)
-        if os.environ.get("NFA_K8H_NOREDO"):
-            return out, lad
-        if ctx is None:
-            rc = lib.nfa_rqs_flow_resnet_redo_f32(
-                N.ptr(x), N.ptr(packed_exact[0]), N.ptr(packed_exact[1]), N.ptr(tables), num_layers, N.ptr(out),
-                N.ptr(lad), N.ptr(redo), N.ptr(_status_word(dev)), B, D, num_transform, num_identity, 128,
-                num_blocks, ctypes.byref(spec), flags, N.stream_handle(dev))
-        else:
-            rc = lib.nfa_rqs_flow_resnet_context_redo_f32(
-                N.ptr(x), N.ptr(ctx), ctx.shape[1], N.ptr(packed_exact[0]), N.ptr(packed_exact[1]), N.ptr(tables),
-                num_layers, N.ptr(out), N.ptr(lad), N.ptr(redo), N.ptr(_status_word(dev)), B, D, num_transform,
-                num_identity, 128, num_blocks, ctypes.byref(spec), flags, N.stream_handle(dev))
-        N.check(rc)
-    _after_spline(spec, inverse, dev)
-    return out, lad
+            return entry(N.ptr(x), *args, N.ptr(capture.bins))
+        entry = (lib.nfa_rqs_flow_resnet_f16x2_colsplit_f32 if tile16 == 2 else
+                 lib.nfa_rqs_flow_resnet_f16x2_tile16_f32 if tile16 else lib.nfa_rqs_flow_resnet_f16x2_f32)
+        return entry(N.ptr(x), *args)
+    return _whole_layer_launch(launch, inputs, inverse, accumulate_into, standard_normal_log_prob, pad, context,
+                               flags=int(activation) << N.FLAG_ACTIVATION_SHIFT, spec=spec,
+                               redo=(*packed_exact, tables, num_layers, num_transform, num_identity, num_blocks))
 
 
 def split_f16x3(w):
@@ -2162,60 +2088,30 @@ class capture_last_layer_logits:
 
 def rqs_coupling_resnet_f16x3(inputs, packed_f16x3, packed_exact, tables, num_transform, num_identity, num_blocks,
                               spec, inverse=False, accumulate_into=None, num_layers=1,
-                              standard_normal_log_prob=False, pad=None, _pad_columns_count=0,
-                              act_scale=K8X_ACT_SCALE):
+                              standard_normal_log_prob=False, pad=None, act_scale=K8X_ACT_SCALE):
     """K8x -- the run of whole-layer kernels on the f16 matrix pipe with THREE f16 pieces per operand (five
     products: operands at the reference's fp32 width), followed by the exact kernel (K8: three bf16 pieces, full
     fp32 range) on the row blocks the first pass gave up on (a value beyond the f16 range at scale `act_scale`, or
     non-finite inputs).  Bin counts: whole_layer_bins.  `packed_f16x3`: (weights, biases, scales) of the run's layers concatenated, from
     pack_resnet_conditioner_f16x3; `packed_exact`: (weights, biases) from pack_resnet_conditioner; `tables`: the
     run's `flow_layer_tables`.  Results as for `rqs_coupling_resnet`; None when the shape is outside the kernel's."""
-    N.require_device_f32("inputs", inputs, 2)
-    if pad is not None and inputs.shape[1] != pad[0]:   # (see rqs_coupling_resnet)
-        out = rqs_coupling_resnet_f16x3(_pad_columns(inputs, pad[0], pad[1]), packed_f16x3, packed_exact, tables,
-                                        num_transform, num_identity, num_blocks, spec, inverse, accumulate_into,
-                                        num_layers, standard_normal_log_prob, None, pad[0] - inputs.shape[1], act_scale)
-        return _without_pad_columns(out, inputs.shape[1])
-    if inputs.shape[0] % 128:
-        return _on_full_blocks(
-            lambda x_, acc_, ctx_: rqs_coupling_resnet_f16x3(x_, packed_f16x3, packed_exact, tables, num_transform,
-                                                             num_identity, num_blocks, spec, inverse, acc_, num_layers,
-                                                             standard_normal_log_prob, None, _pad_columns_count,
-                                                             act_scale),
-            inputs, accumulate_into)
-    dev = inputs.device
-    B, D = inputs.shape
-    x = inputs.detach().contiguous()
-    lad, flags = _lad_buffer(accumulate_into, B, dev, inverse)
-    flags, out = _density_epilogue(flags, standard_normal_log_prob, inverse, x, _pad_columns_count)
-    global _last_redo
-    redo = torch.empty(max(1, B // 128), dtype=torch.int32, device=dev)
-    _last_redo = redo
-    lib = N.load()
     weights, biases, scales = packed_f16x3
-    capture = capture_last_layer_logits.active
-    with torch.cuda.device(dev):
+
+    def launch(x, ctx, out, lad, redo, flags, status, stream):
+        lib = N.load()
+        B, D = x.shape
         args = (N.ptr(x), N.ptr(weights), N.ptr(biases), N.ptr(scales), N.ptr(tables), num_layers, N.ptr(out),
-                N.ptr(lad), N.ptr(redo), N.ptr(_status_word(dev)), B, D, num_transform, num_identity, 128, num_blocks,
-                float(act_scale), ctypes.byref(spec), flags, N.stream_handle(dev))
-        if capture is not None:
-            rc = lib.nfa_rqs_flow_resnet_f16x3_logits_f32(*args, N.ptr(capture.buffer(B, num_transform, dev)))
-        else:
-            rc = lib.nfa_rqs_flow_resnet_f16x3_f32(*args)
-        if rc == N.ERR_UNSUPPORTED:
-            return None
-        N.check(rc)
-        if capture is not None:
+                N.ptr(lad), N.ptr(redo), status, B, D, num_transform, num_identity, 128, num_blocks,
+                float(act_scale), ctypes.byref(spec), flags, stream)
+        capture = capture_last_layer_logits.active
+        if capture is None:
+            return lib.nfa_rqs_flow_resnet_f16x3_f32(*args)
+        rc = lib.nfa_rqs_flow_resnet_f16x3_logits_f32(*args, N.ptr(capture.buffer(B, num_transform, x.device)))
+        if rc == N.OK:
             capture.finish(redo)
-        if os.environ.get("NFA_K8H_NOREDO"):
-            return out, lad
-        rc = lib.nfa_rqs_flow_resnet_redo_f32(
-            N.ptr(x), N.ptr(packed_exact[0]), N.ptr(packed_exact[1]), N.ptr(tables), num_layers, N.ptr(out),
-            N.ptr(lad), N.ptr(redo), N.ptr(_status_word(dev)), B, D, num_transform, num_identity, 128,
-            num_blocks, ctypes.byref(spec), flags, N.stream_handle(dev))
-        N.check(rc)
-    _after_spline(spec, inverse, dev)
-    return out, lad
+        return rc
+    return _whole_layer_launch(launch, inputs, inverse, accumulate_into, standard_normal_log_prob, pad, spec=spec,
+                               redo=(*packed_exact, tables, num_layers, num_transform, num_identity, num_blocks))
 
 
 def rqs_coupling_fused_linear(inputs, hidden, weight_packed, bias_padded, transform_idx, spec,

@@ -305,15 +305,16 @@ class CompositeTransform(Transform):
             return [], start
         return units, i
 
-    def _run_plan(self, units, inverse, tile16=False):
+    def _run_plan(self, units, inverse, tile16=0):
         """Concatenated weight / bias blobs and the composed tables of a run, cached until a weight or a
-        permutation changes.  (weights, biases, tables, f16 stream or None, K8x's (weights, biases, scales) or None)."""
+        permutation changes.  (weights, biases, tables, f16 stream or None, K8x's (weights, biases, scales) or None);
+        `tile16`: the mode of the f16 stream (ops.use_tile16)."""
         from .. import ops
         first = units[0][0]
         mlp = type(first).__name__ in ("AffineCouplingTransform", "AdditiveCouplingTransform")
         geometry = _run_geometry(units)   # one padded geometry for the run
-        f16 = (not mlp) and first._use_f16(geometry)
-        x3 = (not mlp) and first._use_f16x3(geometry)     # K8x: three f16 pieces per operand (engine "f16x3")
+        engine = None if mlp else first._whole_layer_engine(geometry)   # "k8x", "k8h" (the two-piece family) or "k8"
+        f16, x3 = engine == "k8h", engine == "k8x"
         # (the key reads version counters only; the layers' packed blobs are looked at on a miss)
         tile16 = tile16 if f16 else 0
         ids = units.__dict__.get("_ids") if isinstance(units, _Run) else None
@@ -321,7 +322,7 @@ class CompositeTransform(Transform):
             ids = tuple([id(c) for c, _ in units])
             if isinstance(units, _Run):
                 units.__dict__["_ids"] = ids
-        key = (inverse, f16, x3, tile16, geometry, first._log2e() if not mlp else None, first.conditioner_act_scale if f16 else None,
+        key = (inverse, engine, tile16, geometry, first._log2e() if not mlp else None, first.conditioner_act_scale if f16 else None,
                ids, _run_weights_fingerprint(units),
                tuple([None if p is None else _permutation_key(p) for _, p in units]))
         cache = self.__dict__.setdefault("_run_plans", {})
@@ -357,52 +358,24 @@ class CompositeTransform(Transform):
         """One launch for the run (ragged batches are padded to full 128-row blocks inside `ops`).  Returns
         the outputs (or log_prob with `standard_normal_log_prob`), or None when the kernel declines."""
         from .. import ops
+        from .coupling import _TILE16
         first = units[0][0]
         for _, p in units:
             if p is not None:
                 p._check(inputs)
-        # (batches that give a CU at most one 128-row block: the 16-sample-tile kernel K8s and its own stream)
-        act = first._block_activation() if hasattr(first, "_block_activation") else 0
-        tile16 = (hasattr(first, "_use_f16") and inputs.is_cuda
-                  and ops.use_tile16(inputs.shape[0], getattr(first, "num_bins", 0), context, inputs.device, act))
-        weights, biases, tables, plan_f16, plan_x3 = self._run_plan(units, inverse, tile16)
-        Dp, dt4, di_u, pad_value = _run_geometry(units)
-        pad = (Dp, pad_value)
-        if plan_x3 is not None:
-            head = ops.rqs_coupling_resnet_f16x3(
-                inputs, plan_x3, (weights, biases), tables, dt4, di_u, len(first.transform_net.blocks), first._spec(),
-                inverse, total, num_layers=len(units), standard_normal_log_prob=standard_normal_log_prob, pad=pad)
-            if head is not None:
-                return head[1] if standard_normal_log_prob else head[0]
+        geometry = _run_geometry(units)
         if type(first).__name__ in ("AffineCouplingTransform", "AdditiveCouplingTransform"):
+            weights, biases, tables, _, _ = self._run_plan(units, inverse)
             hidden_linears, residual_blocks = first._conditioner_shape()
             head = ops.affine_flow_mlp(
                 inputs, weights, biases, tables, first.num_transform_features, first.num_identity_features,
                 hidden_linears, first._activation_code(), inverse, total,
-                num_layers=len(units), standard_normal_log_prob=standard_normal_log_prob, pad=pad,
+                num_layers=len(units), standard_normal_log_prob=standard_normal_log_prob, pad=(geometry[0], geometry[3]),
                 residual_blocks=residual_blocks)
-        elif plan_f16 is not None:
-            head = ops.rqs_coupling_resnet_f16(
-                inputs, plan_f16, (weights, biases), tables, dt4,
-                di_u, len(first.transform_net.blocks), first._spec(), inverse,
-                total, num_layers=len(units), standard_normal_log_prob=standard_normal_log_prob, pad=pad,
-                context=context, tile16=tile16 if first._use_f16(_run_geometry(units)) else 0, activation=act)
-            if head is None and tile16:
-                # K8s declined (its ring + 16-row buffers + two copies of the parameter words exceed the LDS budget:
-                # about six blocks at D = 128): K8h takes these shapes -- its own stream, the same call
-                weights, biases, tables, plan_f16, _ = self._run_plan(units, inverse, False)
-                if plan_f16 is not None:
-                    head = ops.rqs_coupling_resnet_f16(
-                        inputs, plan_f16, (weights, biases), tables, dt4, di_u, len(first.transform_net.blocks),
-                        first._spec(), inverse, total, num_layers=len(units),
-                        standard_normal_log_prob=standard_normal_log_prob, pad=pad, context=context, tile16=False,
-                        activation=act)
         else:
-            head = ops.rqs_coupling_resnet(
-                inputs, weights, biases, tables, dt4, di_u,
-                len(first.transform_net.blocks), first._spec(), inverse, total,
-                log2e=first._log2e() if hasattr(first, "_log2e") else False, num_layers=len(units),
-                standard_normal_log_prob=standard_normal_log_prob, context=context, pad=pad, activation=act)
+            # (batches that give a CU at most one 128-row block: the 16-sample-tile kernels K8s / K8c and their own stream)
+            head = first._whole_layer_cascade(lambda engine: self._run_plan(units, inverse, _TILE16.get(engine, 0)), geometry,
+                                              inputs, context, inverse, total, len(units), standard_normal_log_prob)
         if head is None:
             return None
         return head[1] if standard_normal_log_prob else head[0]

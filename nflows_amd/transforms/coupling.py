@@ -640,7 +640,16 @@ class PiecewiseCouplingTransform(CouplingTransform):
         return self._piecewise_cdf(inputs, transform_params, inverse)
 
 
+_TILE16 = {"k8h": 0, "k8s": 1, "k8c": 2}   # the two-piece engines by their ops.use_tile16 mode
 _F16_PACK_SLOTS = ("_packed_resnet_f16_cache", "_packed_resnet_f16s_cache", "_packed_resnet_f16c_cache")   # K8h, K8s, K8c
+
+
+def _cached_pack(owner, slot, key, pack):
+    """`pack()`, kept in `owner.__dict__[slot]` with `key` and made again when the key changes"""
+    cached = owner.__dict__.get(slot)
+    if cached is None or cached[0] != key:
+        cached = owner.__dict__[slot] = (key, pack())
+    return cached[1]
 
 
 class PiecewiseRationalQuadraticCouplingTransform(PiecewiseCouplingTransform):
@@ -737,8 +746,8 @@ class PiecewiseRationalQuadraticCouplingTransform(PiecewiseCouplingTransform):
         split = None if self.tails == "linear" else (self.num_transform_features, self.num_identity_features)
         return ("k8", features, num_blocks, self.num_bins, self.tail_bound, self.tails, split,
                 self.min_bin_width, self.min_bin_height, self.min_derivative,
-                self._log2e(), self._use_f16(), self.conditioner_act_scale, ce, self.conditioner_engine,
-                self._block_activation())
+                self._log2e(), self.conditioner_engine == "f16x2" and self._whole_layer_engine() == "k8h",   # (_use_f16)
+                self.conditioner_act_scale, ce, self.conditioner_engine, self._block_activation())
 
     def _block_activation(self):
         """The whole-layer kernels' code of the conditioner blocks' activation (one for all blocks), or None"""
@@ -837,53 +846,90 @@ class PiecewiseRationalQuadraticCouplingTransform(PiecewiseCouplingTransform):
     # scale of the hidden activations' f16 pieces (a power of two; K8h)
     conditioner_act_scale = float(os.environ.get("NFA_K8_ACT_SCALE", "1"))
 
-    def _use_f16(self, geometry=None):
-        """K8h serves 8 and 10 bins; with a context up to 32 context features beside up to 32 identity features
-        (of the run's geometry) -- otherwise the bf16x3 kernel (K8) runs."""
+    def _whole_layer_engine(self, geometry=None, batch=None, context=None, device=None, act=None):
+        """The whole-layer kernel that serves this layer -- or a run it leads, `geometry` the run's (ops.fused_geometry):
+        "k8x" (engine "f16x3": ReLU blocks, no context), "k8h" (engine "f16x2"; with a context up to 32 context
+        features beside up to 32 identity features) or its 16-sample-tile forms "k8s" / "k8c" at the batches
+        ops.use_tile16 gives them (a call on the device: `batch`, `context`, `device`), otherwise "k8" (the bf16x3
+        kernel).  `act`: the blocks' activation code when the caller holds it (_block_activation)."""
+        engine = self.conditioner_engine
+        if (engine not in ("f16x2", "f16x3") or self.tails != "linear" or not ops.whole_layer_bins(self.num_bins)
+                or self._log2e()):
+            return "k8"
         ce = self._static_signature()[2]
-        return (self.conditioner_engine == "f16x2" and self.tails == "linear" and ops.whole_layer_bins(self.num_bins) and not self._log2e()
-                and (ce is None or (ce <= 32 and (geometry or self._fused_geometry())[2] <= 32)))
+        if engine == "f16x3":
+            relu = (act if act is not None else self._block_activation()) == N.ACTIVATION_RELU
+            return "k8x" if ce is None and relu else "k8"
+        if ce is not None and (ce > 32 or (geometry or self._fused_geometry())[2] > 32):
+            return "k8"
+        if device is None or device.type != "cuda":
+            return "k8h"
+        act = act if act is not None else self._block_activation()
+        return ("k8h", "k8s", "k8c")[ops.use_tile16(batch, self.num_bins, context, device, act)]
+
+    def _use_f16(self, geometry=None):
+        """The two-piece engine (K8h / K8s / K8c) serves this layer or the run (`_whole_layer_engine`)"""
+        return self.conditioner_engine == "f16x2" and self._whole_layer_engine(geometry) == "k8h"
 
     def _use_f16x3(self, geometry=None):
-        """K8x serves the whole-layer bin counts (ops.whole_layer_bins) with ReLU blocks and no context -- otherwise engine
-        "f16x3" means the bf16x3 kernel (K8)."""
-        return (self.conditioner_engine == "f16x3" and self.tails == "linear" and ops.whole_layer_bins(self.num_bins) and not self._log2e()
-                and self._static_signature()[2] is None and self._block_activation() == N.ACTIVATION_RELU)
+        """K8x serves this layer or the run (`_whole_layer_engine`)"""
+        return self.conditioner_engine == "f16x3" and self._whole_layer_engine(geometry) == "k8x"
+
+    def _whole_layer_cascade(self, plan, geometry, inputs, context, inverse, accumulate_into, num_layers=1,
+                             standard_normal_log_prob=False):
+        """Launches the whole-layer engines for this layer or for a run of `num_layers` layers it leads: the engine of
+        `_whole_layer_engine`; K8x declining goes to K8, K8s / K8c declining (over their LDS budget) to K8h with its
+        own stream, and without a K8h stream (non-finite weights) K8 runs.  `plan(engine)` -> (weights, biases, tables
+        of K8, the K8h / K8s / K8c stream or None, K8x's (weights, biases, scales) or None) of the layer or the run.
+        Returns what the ops launcher returns."""
+        act = self._block_activation()
+        engine = self._whole_layer_engine(geometry, inputs.shape[0], context, inputs.device, act)
+        weights, biases, tables, stream, packed_x3 = plan(engine)
+        Dp, dt4, di_u, pad_value = geometry
+        nb, spec = len(self.transform_net.blocks), self._spec()
+        run = dict(num_layers=num_layers, standard_normal_log_prob=standard_normal_log_prob, pad=(Dp, pad_value))
+        if engine == "k8x":
+            res = ops.rqs_coupling_resnet_f16x3(inputs, packed_x3, (weights, biases), tables, dt4, di_u, nb, spec, inverse,
+                                                accumulate_into, **run)
+            if res is not None:
+                return res
+        elif stream is not None:
+            res = ops.rqs_coupling_resnet_f16(inputs, stream, (weights, biases), tables, dt4, di_u, nb, spec, inverse,
+                                              accumulate_into, context=context, tile16=_TILE16[engine], activation=act, **run)
+            if res is None and engine != "k8h":
+                stream = plan("k8h")[3]
+                if stream is not None:
+                    res = ops.rqs_coupling_resnet_f16(inputs, stream, (weights, biases), tables, dt4, di_u, nb, spec,
+                                                      inverse, accumulate_into, context=context, activation=act, **run)
+            return res
+        return ops.rqs_coupling_resnet(inputs, weights, biases, tables, dt4, di_u, nb, spec, inverse, accumulate_into,
+                                       log2e=self._log2e(), context=context, activation=act, **run)
 
     def _packed_resnet_f16x3(self, geometry=None):
         """(weights, biases, scales) for K8x (ops.pack_resnet_conditioner_f16x3), per weight key"""
-        net = self.transform_net
         _, dt4, di_u, _ = geometry or self._fused_geometry()
-        key = (ops.K8X_ACT_SCALE, dt4, di_u) + _weights_key(self, net)
-        cached = self.__dict__.get("_packed_resnet_f16x3_cache")
-        if cached is None or cached[0] != key:
-            cached = (key, ops.pack_resnet_conditioner_f16x3(self._folded_net(), self.num_transform_features,
-                                                             self._transform_dim_multiplier(),
-                                                             pad_transform_to=dt4, pad_identity_to=di_u))
-            self.__dict__["_packed_resnet_f16x3_cache"] = cached
-        return cached[1]
+        key = (ops.K8X_ACT_SCALE, dt4, di_u) + _weights_key(self, self.transform_net)
+        return _cached_pack(self, "_packed_resnet_f16x3_cache", key,
+                            lambda: ops.pack_resnet_conditioner_f16x3(self._folded_net(), self.num_transform_features,
+                                                                      self._transform_dim_multiplier(),
+                                                                      pad_transform_to=dt4, pad_identity_to=di_u))
 
-    def _packed_resnet_f16(self, geometry=None, tile16=False):
+    def _packed_resnet_f16(self, geometry=None, tile16=0):
         """(weights, parameter words) for K8h, or -- `tile16` = 1 / 2 (ops.use_tile16) -- for K8s / K8c (the 16-sample-tile
         kernels of small batches)."""
-        net = self.transform_net
         _, dt4, di_u, _ = geometry or self._fused_geometry()
-        key = (self.conditioner_act_scale, dt4, di_u, tile16) + _weights_key(self, net)
-        slot = _F16_PACK_SLOTS[int(tile16)]
-        cached = self.__dict__.get(slot)
-        if cached is None or cached[0] != key:
-            cached = (key, ops.pack_resnet_conditioner_f16(self._folded_net(), self.num_transform_features,
-                                                           self._transform_dim_multiplier(),
-                                                           act_scale=self.conditioner_act_scale,
-                                                           pad_transform_to=dt4, pad_identity_to=di_u, tile16=bool(tile16),
-                                                           colsplit=int(tile16) == 2))
-            self.__dict__[slot] = cached
-        return cached[1]
+        key = (self.conditioner_act_scale, dt4, di_u, tile16) + _weights_key(self, self.transform_net)
+        return _cached_pack(self, _F16_PACK_SLOTS[tile16], key,
+                            lambda: ops.pack_resnet_conditioner_f16(self._folded_net(), self.num_transform_features,
+                                                                    self._transform_dim_multiplier(),
+                                                                    act_scale=self.conditioner_act_scale,
+                                                                    pad_transform_to=dt4, pad_identity_to=di_u,
+                                                                    tile16=bool(tile16), colsplit=tile16 == 2))
 
-    def _f16_stream(self, tables, tile16=False):
-        """K8h / K8s stream of this layer alone (its parameter stage carries `tables`), cached per table set."""
+    def _f16_stream(self, tables, tile16=0):
+        """K8h / K8s / K8c stream of this layer alone (its parameter stage carries `tables`), cached per table set."""
         pack = self._packed_resnet_f16(tile16=tile16)
-        key = (self.__dict__[_F16_PACK_SLOTS[int(tile16)]][0],
+        key = (self.__dict__[_F16_PACK_SLOTS[tile16]][0],
                tables.data_ptr(), tables._version)
         cache = self.__dict__.setdefault("_f16_stream_cache", {})
         hit = cache.get(key)
@@ -895,17 +941,12 @@ class PiecewiseRationalQuadraticCouplingTransform(PiecewiseCouplingTransform):
         return hit or None
 
     def _packed_resnet(self, geometry=None):
-        net = self.transform_net
         _, dt4, di_u, _ = geometry or self._fused_geometry()
-        key = (dt4, di_u, self._log2e()) + _weights_key(self, net)
-        cached = getattr(self, "_packed_resnet_cache", None)
-        if cached is None or cached[0] != key:
-            cached = (key, ops.pack_resnet_conditioner(self._folded_net(), self.num_transform_features,
-                                                       self._transform_dim_multiplier(),
-                                                       log2e=self._log2e(),
-                                                       pad_transform_to=dt4, pad_identity_to=di_u))
-            self._packed_resnet_cache = cached
-        return cached[1]
+        key = (dt4, di_u, self._log2e()) + _weights_key(self, self.transform_net)
+        return _cached_pack(self, "_packed_resnet_cache", key,
+                            lambda: ops.pack_resnet_conditioner(self._folded_net(), self.num_transform_features,
+                                                                self._transform_dim_multiplier(), log2e=self._log2e(),
+                                                                pad_transform_to=dt4, pad_identity_to=di_u))
 
     def _layer_tables(self, in_perm, out_scatter):
         key = tuple(None if t is None else (t.data_ptr(), t._version) for t in
@@ -925,33 +966,14 @@ class PiecewiseRationalQuadraticCouplingTransform(PiecewiseCouplingTransform):
     def _whole_layer(self, inputs, context, inverse, in_perm, out_scatter, accumulate_into):
         if not self._resnet_eligible(context):
             return None
-        wp, bp = self._packed_resnet()
         tables = self._layer_tables(in_perm, out_scatter)
-        nb = len(self.transform_net.blocks)
-        Dp, dt4, di, pad_value = self._fused_geometry()
-        spec = self._spec()
+
+        def plan(engine):
+            return (*self._packed_resnet(), tables,
+                    self._f16_stream(tables, _TILE16[engine]) if engine in _TILE16 else None,
+                    self._packed_resnet_f16x3() if engine == "k8x" else None)
         # (ragged batches are padded to full 128-row blocks, odd shapes to multiples of four columns, in `ops`)
-        act = self._block_activation()
-        if self._use_f16x3():
-            res = ops.rqs_coupling_resnet_f16x3(inputs, self._packed_resnet_f16x3(), (wp, bp), tables, dt4, di, nb, spec,
-                                                inverse, accumulate_into, pad=(Dp, pad_value))
-            if res is not None:
-                return res
-        tile16 = self._use_f16() and inputs.is_cuda and ops.use_tile16(inputs.shape[0], self.num_bins, context, inputs.device, act)
-        stream = self._f16_stream(tables, tile16) if self._use_f16() else None   # (None: non-finite weights -> exact kernel)
-        if stream is not None:
-            res = ops.rqs_coupling_resnet_f16(inputs, stream, (wp, bp), tables, dt4, di, nb, spec,
-                                              inverse, accumulate_into, pad=(Dp, pad_value), context=context,
-                                              tile16=tile16, activation=act)
-            if res is None and tile16:   # (K8s over its LDS budget: K8h with its own stream)
-                stream = self._f16_stream(tables, False)
-                if stream is not None:
-                    res = ops.rqs_coupling_resnet_f16(inputs, stream, (wp, bp), tables, dt4, di, nb, spec,
-                                                      inverse, accumulate_into, pad=(Dp, pad_value), context=context,
-                                                      tile16=False, activation=act)
-            return res
-        return ops.rqs_coupling_resnet(inputs, wp, bp, tables, dt4, di, nb, spec, inverse, accumulate_into,
-                                       log2e=self._log2e(), context=context, pad=(Dp, pad_value), activation=act)
+        return self._whole_layer_cascade(plan, self._fused_geometry(), inputs, context, inverse, accumulate_into)
 
     def _packed_final_linear(self, layer):
         split = self.final_linear_engine == "bf16x3"

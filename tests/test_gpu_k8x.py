@@ -160,7 +160,7 @@ def test_f16_range_of_the_three_piece_engine(f16x3, case):
 
 
 def test_ragged_batches_odd_feature_counts_and_single_layers(f16x3):
-    """What the host pads into the kernel's family (ops.fused_geometry, _on_full_blocks) -- 22 features under an
+    """What the host pads into the kernel's family (ops.fused_geometry, ops._whole_layer_launch) -- 22 features under an
     alternating mask (11 + 11: padded to 24 columns, 12 + 12), a batch of 1 000 rows, a 64-wide conditioner, d_i > 32
     (the four-k-step initial layer) -- and a single layer outside a run: K8x runs them all; results against K8's within
     fp32 rounding of the spline (both are held to the oracle elsewhere), pass-through columns bit-exact."""
