@@ -1,16 +1,21 @@
 #!/usr/bin/env python3
 """Headline benchmark: Flow.log_prob throughput of the 32-layer RQ-NSF coupling flow
-(dim=64, K=8) on MI355X, with the layer kernel's roofline fraction and the reference-CPU-path
-baseline (oracle/eager.py, the bit-identical port of the reference's CPU path).
+(dim=64, K=8) on MI355X, with the layer kernel's roofline fraction from the timed steps' own dispatch events.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 The workload is BASELINE configs[3] as named, at every N: a global batch of 262 144 rows, all of them on
 the one GPU at N = 1, sharded over the N ranks otherwise (one process per GPU, launched by
 torch.distributed.run; 32 768 rows per GPU at N = 8), one 16-byte all-reduce per step.  The total work
-is fixed, the per-GPU work shrinks as N grows ("scaling": "strong"); the figure at 65 536 rows per GPU
+is fixed, the per-GPU work shrinks as N grows ("scaling": "strong"); with --full the figure at 65 536 rows per GPU
 (round 1's single-GPU workload; weak scaling for N > 1) is added as an extra field.  A "step" is one full log_prob pass over the rank's rows (inputs already
 resident in HBM) plus the log-likelihood reduction.  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline figure needs: set-up, warm-up, the timed steps, --dump-outputs and the result
+line.  --full adds everything else after the timed steps: the fwd/inv consistency check and its float64 device path,
+the steady-state leg with clock and power, the sustained MFMA ceiling, K1's roofline, the HIP-graph replay, the other
+engines, batch sizes and BASELINE configurations, and the reference-CPU-path baseline (oracle/eager.py, the
+bit-identical port of the reference's CPU path); the --skip-* options, --no-cpu-baseline and --steady-seconds trim it.
 """
 import argparse
 import json
@@ -418,9 +423,17 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step returned (per-row log-densities, log-likelihood sum and count) "
                          "as DIR/<name>.npy, at most 64 MB in all")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure, after the timed steps (see the "
+                         "module docstring); without it a run does set-up, warm-up, the timed steps, --dump-outputs and "
+                         "the result line only")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:
+        args.steady_seconds = 0
+        args.no_cpu_baseline = args.skip_extra = args.skip_consistency = True
+        args.skip_mfma_ceiling = args.skip_k1_roofline = args.skip_graph = True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))

@@ -53,11 +53,12 @@ print("RCCL_OK", torch.cuda.nccl.version() if hasattr(torch.cuda, "nccl") else "
 
 def test_bench_two_rank_dry_run():
     """bench.py --gpus 2 through torch.distributed.run with the gloo stand-in backend: BASELINE
-    configs[3] as named (262 144 global rows, 131 072 per rank), one JSON line from rank 0."""
+    configs[3] as named (262 144 global rows, 131 072 per rank), one JSON line from rank 0; --full for the
+    65 536-rows-per-GPU extra."""
     env = dict(os.environ, NFA_BENCH_BACKEND="gloo", PYTHONPATH=ROOT, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
            "--steady-seconds", "0", "--skip-graph"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]

@@ -15,7 +15,7 @@ OUT=$ROOTDIR/gpurun_out/profiles_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-BENCH="python $ROOTDIR/bench.py --steps 3 --warmup 1 --no-cpu-baseline --skip-extra --skip-consistency --skip-mfma-ceiling --skip-graph"
+BENCH="python $ROOTDIR/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --skip-extra --skip-consistency --skip-mfma-ceiling --skip-graph"
 IO=135266304   # 262 144 rows x (256 B in + 256 B out + 4 B log-determinant)
 
 # engine : counter file : kernel-name pattern : algorithmic bytes per launch (rows' I/O + 32 layers' packed weights)
@@ -26,7 +26,7 @@ for spec in "f16x3:k8x:rqs_resnet_f16x3_kernel:$((IO + 32 * 1007616))" "f16x2:k8
     timeout 300 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/pmc_$NAME/$c -o p -- $BENCH --engine $ENGINE --skip-k1-roofline > $OUT/pmc_${NAME}_$c.log 2>&1
   done
   python $ROOTDIR/tools/pmc_traffic.py $OUT/pmc_$NAME $ROOTDIR/profiles/${NAME}_pmc_traffic.json $PATTERN $BYTES \
-    "python bench.py --steps 3 --warmup 1 --no-cpu-baseline --skip-extra --skip-consistency --skip-k1-roofline --engine $ENGINE"
+    "python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --skip-extra --skip-consistency --skip-k1-roofline --engine $ENGINE"
   cp $ROOTDIR/profiles/${NAME}_pmc_traffic.json $OUT/
   rm -rf $OUT/pmc_$NAME      # (the raw counter CSVs are large; keep only the summaries)
 done
@@ -35,17 +35,17 @@ if [ "${SKIP_K1:-0}" != "1" ]; then
     timeout 300 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/pmc_k1/$c -o p -- $BENCH --path k1 > $OUT/pmc_k1_$c.log 2>&1
   done
   python $ROOTDIR/tools/pmc_traffic.py $OUT/pmc_k1 $ROOTDIR/profiles/k1_pmc_traffic.json rqs_coupling_wavetile 907018240 \
-    "python bench.py --steps 3 --warmup 1 --no-cpu-baseline --skip-extra --skip-consistency --path k1"
+    "python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --skip-extra --skip-consistency --path k1"
   cp $ROOTDIR/profiles/k1_pmc_traffic.json $OUT/
   rm -rf $OUT/pmc_k1
 fi
 
-# the same command as the driver's (default steps), extras included: every engine's whole-layer kernel appears in the summary
-timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/stats -o k -- python $ROOTDIR/bench.py --no-cpu-baseline --skip-mfma-ceiling --skip-graph > $OUT/stats_bench.log 2>&1
+# the bench command at its default steps with --full, extras included: every engine's whole-layer kernel appears in the summary
+timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/stats -o k -- python $ROOTDIR/bench.py --full --no-cpu-baseline --skip-mfma-ceiling --skip-graph > $OUT/stats_bench.log 2>&1
 DB=$(find $OUT/stats -name '*.db' | head -1)
 python $ROOTDIR/tools/rocprof_summary.py "$DB" $OUT/${TAG}_kernel_stats_bench.csv
 rm -rf $OUT/stats
 
 cd $ROOTDIR
-timeout 900 python bench.py > $OUT/${TAG}_bench_1gpu.json 2> $OUT/bench.err
+timeout 900 python bench.py --full > $OUT/${TAG}_bench_1gpu.json 2> $OUT/bench.err
 tail -c 1500 $OUT/${TAG}_bench_1gpu.json

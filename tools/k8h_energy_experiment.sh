@@ -10,9 +10,9 @@ export TMPDIR=/tmp
 cd /tmp
 for v in default 2 16 18; do
   if [ $v = default ]; then unset NFLOWS_AMD_LIB; else export NFLOWS_AMD_LIB=$ROOTDIR/tools/bin/libnfa_k8h_aux$v.so; fi
-  python $ROOTDIR/bench.py --engine f16x2 --steps 40 --warmup 5 --no-cpu-baseline --skip-extra --skip-consistency --skip-k1-roofline --skip-graph --skip-mfma-ceiling > $OUT/energy_$v.json 2> $OUT/energy_$v.err
+  python $ROOTDIR/bench.py --full --engine f16x2 --steps 40 --warmup 5 --no-cpu-baseline --skip-extra --skip-consistency --skip-k1-roofline --skip-graph --skip-mfma-ceiling > $OUT/energy_$v.json 2> $OUT/energy_$v.err
   rm -rf $OUT/pmc_energy_$v
-  timeout 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc_energy_$v -o p -- python $ROOTDIR/bench.py --engine f16x2 --steps 3 --warmup 1 --no-cpu-baseline --skip-extra --skip-consistency --skip-k1-roofline --skip-graph --skip-mfma-ceiling > $OUT/pmc_energy_$v.log 2>&1
+  timeout 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc_energy_$v -o p -- python $ROOTDIR/bench.py --full --engine f16x2 --steps 3 --warmup 1 --no-cpu-baseline --skip-extra --skip-consistency --skip-k1-roofline --skip-graph --skip-mfma-ceiling > $OUT/pmc_energy_$v.log 2>&1
   python - $v $OUT <<'PY'
 import sys, json, glob, csv
 v, out = sys.argv[1], sys.argv[2]

@@ -36,7 +36,7 @@ def main(d, out, pat="rqs_coupling_pipelined", algorithmic=None, command=None):
            "algorithmic_bytes_per_launch": algorithmic if algorithmic is not None
            else 4 * (65536 * 64 * 2 + 65536 * 32 * 23 + 65536),
            "method": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE in separate passes over `%s`; "
-                     "gfx950 x2 correction on reads" % (command or "python bench.py --steps 3 --warmup 1 --no-cpu-baseline")}
+                     "gfx950 x2 correction on reads" % (command or "python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline")}
     try:  # the digest of the kernel's sources: bench.py quotes these counters only while they are unchanged
         sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
         import bench
