@@ -280,18 +280,21 @@ __global__ void __launch_bounds__(kBlock, 1) affine_mlp_kernel(const AffineMlpAr
 
 using namespace nfa;
 
+template <int IKS, bool ADDITIVE, bool RESNET>
+static void (*affine_mlp_instance(bool inverse))(const AffineMlpArgs) {
+    return inverse ? affine_mlp_kernel<true, IKS, ADDITIVE, RESNET> : affine_mlp_kernel<false, IKS, ADDITIVE, RESNET>;
+}
+
 extern "C" int nfa_affine_flow_mlp_f32(const float* inputs, const void* weights_packed, const float* bias_packed,
                                        const int32_t* tables, int32_t num_layers, float* outputs,
                                        float* logabsdet, int32_t* status, int64_t batch, int32_t features,
                                        int32_t num_transform, int32_t num_identity, int32_t hidden_features,
                                        int32_t num_hidden_layers, int32_t scale_activation, int32_t flags,
                                        void* stream) {
-    if (flags & ~(NFA_FLAG_INVERSE | NFA_FLAG_ACCUMULATE_LOGABSDET | NFA_FLAG_STANDARD_NORMAL_LOG_PROB |
-                  NFA_FLAG_SKIP_OUTPUTS | NFA_FLAG_PAD_COLUMNS_MASK | NFA_FLAG_RESIDUAL_BLOCKS))
-        return NFA_ERR_INVALID_ARGUMENT;
+    int activation = 0;   // (no activation bits here)
+    int rc = check_layer_flags(flags, NFA_FLAG_RESIDUAL_BLOCKS, &activation);
+    if (rc != NFA_OK) return rc;
     const bool resnet = (flags & NFA_FLAG_RESIDUAL_BLOCKS) != 0;
-    flags &= ~NFA_FLAG_RESIDUAL_BLOCKS;
-    if (!density_flags_valid(flags)) return NFA_ERR_INVALID_ARGUMENT;
     if (batch < 0 || features < 1 || num_transform < 1 || num_identity < 1 ||
         num_transform + num_identity > features || num_hidden_layers < 0 || num_layers < 1 ||
         (resnet && (num_hidden_layers & 1)))   // (residual blocks: two Linears each)
@@ -299,8 +302,7 @@ extern "C" int nfa_affine_flow_mlp_f32(const float* inputs, const void* weights_
     if (scale_activation != NFA_SCALE_DEFAULT && scale_activation != NFA_SCALE_GENERAL &&
         scale_activation != NFA_SCALE_ADDITIVE)
         return NFA_ERR_UNSUPPORTED;
-    if (hidden_features != 128 || num_transform > 64 || num_identity > 64 || features > 128 || (features & 3) != 0 ||
-        (batch & 127) != 0 || num_hidden_layers > 64 || num_layers > 4096)
+    if (!layer_family(batch, features, num_transform, num_identity, hidden_features, num_hidden_layers, num_layers))
         return NFA_ERR_UNSUPPORTED;
     if (batch == 0) return NFA_OK;
     if (!inputs || !weights_packed || !bias_packed || !tables || !logabsdet ||
@@ -308,6 +310,8 @@ extern "C" int nfa_affine_flow_mlp_f32(const float* inputs, const void* weights_
         return NFA_ERR_INVALID_ARGUMENT;
     const bool additive = scale_activation == NFA_SCALE_ADDITIVE;
     AffineMlpArgs a;
+    rc = fill_density(a, flags, features);
+    if (rc != NFA_OK) return rc;
     a.x = inputs;
     a.w = reinterpret_cast<const vec4f*>(weights_packed);
     a.bias = bias_packed;
@@ -327,51 +331,17 @@ extern "C" int nfa_affine_flow_mlp_f32(const float* inputs, const void* weights_
     a.num_stages = init_ks + 8 * num_hidden_layers + 2 * a.final_tiles;
     a.bias_per_layer = 128 + 128 * num_hidden_layers + 32 * a.final_tiles;
     a.accumulate = (flags & NFA_FLAG_ACCUMULATE_LOGABSDET) ? 1 : 0;
-    a.normal = (flags & NFA_FLAG_STANDARD_NORMAL_LOG_PROB) ? 1 : 0;
-    a.skip_out = (flags & NFA_FLAG_SKIP_OUTPUTS) ? 1 : 0;
-    a.Ds = density_columns(flags, features);
-    if (a.Ds < 1) return NFA_ERR_INVALID_ARGUMENT;
-    a.log_z = standard_normal_log_z(a.Ds);
     const size_t lds = (size_t)kRing * kStageVec4 * 16 + (size_t)(kBlock / kWave) * features * kRowPad * sizeof(float);
     int64_t blocks = batch >> 7;
     const int64_t cap = (int64_t)device_cu_count();   // (one workgroup per CU: 512 registers per wave)
     if (blocks > cap) blocks = cap;
     const bool inv = (flags & NFA_FLAG_INVERSE) != 0;
-    void (*kern)(const AffineMlpArgs) = nullptr;
-    const int which = (inv ? 1 : 0) + (init_ks == 4 ? 2 : 0) + (additive ? 4 : 0) + (resnet ? 8 : 0);
-    switch (which) {
-        case 8: kern = affine_mlp_kernel<false, 2, false, true>; break;
-        case 9: kern = affine_mlp_kernel<true, 2, false, true>; break;
-        case 10: kern = affine_mlp_kernel<false, 4, false, true>; break;
-        case 11: kern = affine_mlp_kernel<true, 4, false, true>; break;
-        case 12: kern = affine_mlp_kernel<false, 2, true, true>; break;
-        case 13: kern = affine_mlp_kernel<true, 2, true, true>; break;
-        case 14: kern = affine_mlp_kernel<false, 4, true, true>; break;
-        case 15: kern = affine_mlp_kernel<true, 4, true, true>; break;
-        case 0: kern = affine_mlp_kernel<false, 2, false>; break;
-        case 1: kern = affine_mlp_kernel<true, 2, false>; break;
-        case 2: kern = affine_mlp_kernel<false, 4, false>; break;
-        case 3: kern = affine_mlp_kernel<true, 4, false>; break;
-        case 4: kern = affine_mlp_kernel<false, 2, true>; break;
-        case 5: kern = affine_mlp_kernel<true, 2, true>; break;
-        case 6: kern = affine_mlp_kernel<false, 4, true>; break;
-        default: kern = affine_mlp_kernel<true, 4, true>; break;
-    }
+    void (*kern)(const AffineMlpArgs) =
+        resnet ? (init_ks == 4 ? (additive ? affine_mlp_instance<4, true, true>(inv) : affine_mlp_instance<4, false, true>(inv))
+                               : (additive ? affine_mlp_instance<2, true, true>(inv) : affine_mlp_instance<2, false, true>(inv)))
+               : (init_ks == 4 ? (additive ? affine_mlp_instance<4, true, false>(inv) : affine_mlp_instance<4, false, false>(inv))
+                               : (additive ? affine_mlp_instance<2, true, false>(inv) : affine_mlp_instance<2, false, false>(inv)));
     if (resnet) note_layer_kernel("affine_mlp_kernel<inverse=%d, init_ks=%d, additive=%d, resnet=1>", inv ? 1 : 0, init_ks, additive ? 1 : 0);
     else note_layer_kernel("affine_mlp_kernel<inverse=%d, init_ks=%d, additive=%d>", inv ? 1 : 0, init_ks, additive ? 1 : 0);
-    if (lds > 64 * 1024) {
-        static unsigned long long raised[16] = {};   // device masks (raise_dynamic_lds)
-        {
-            const int rc_lds = raise_dynamic_lds((const void*)kern, &raised[which], 160 * 1024 - 2048);
-            if (rc_lds != NFA_OK) return rc_lds;
-        }
-    }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    profile_next_launch(&e0, &e1);
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)blocks), block(kBlock);
-    if (e0) hipExtLaunchKernelGGL(kern, grid, block, lds, st, e0, e1, 0, a);
-    else hipLaunchKernelGGL(kern, grid, block, lds, st, a);
-    NFA_HIP_CHECK(hipGetLastError());
-    return NFA_OK;
+    return launch_kernel(kern, dim3((unsigned)blocks), dim3(kBlock), lds, (hipStream_t)stream, a, 160 * 1024 - 2048);
 }

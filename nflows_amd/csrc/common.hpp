@@ -2,6 +2,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 #include <stdint.h>
 
 #include "nflows_amd.h"
@@ -25,15 +26,25 @@ void note_layer_kernel(const char* fmt, ...) __attribute__((format(printf, 1, 2)
     } while (0)
 
 // hipFuncSetAttribute applies to the CURRENT device only: the opt-in to more than 64 KB of dynamic LDS is
-// remembered per (kernel, device) -- `seen` is one device bit mask per kernel instance.
-inline int raise_dynamic_lds(const void* kern, unsigned long long* seen, int bytes) {
-    int dev = 0;
-    NFA_HIP_CHECK(hipGetDevice(&dev));
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (dev < 64 && (*seen & bit)) return 0;
-    NFA_HIP_CHECK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    if (dev < 64) *seen |= bit;
-    return 0;
+// remembered per (kernel, device) pair, in a mutex-guarded set (rqs.hip).
+int raise_dynamic_lds(const void* kern, int bytes);
+
+// The tail of every layer-kernel launch: the opt-in to `lds_optin` bytes of dynamic LDS (default: the launch's own
+// `lds`) when the launch needs more than 64 KB, the event pair of the measurement aid when the launch is `profiled`,
+// the launch itself and its error check.
+template <typename A>
+inline int launch_kernel(void (*kern)(A), dim3 grid, dim3 block, size_t lds, hipStream_t st, const A& a,
+                         int lds_optin = 0, bool profiled = true) {
+    if (lds > 64 * 1024) {
+        const int rc = raise_dynamic_lds((const void*)kern, lds_optin ? lds_optin : (int)lds);
+        if (rc != NFA_OK) return rc;
+    }
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (profiled) profile_next_launch(&e0, &e1);
+    if (e0) hipExtLaunchKernelGGL(kern, grid, block, lds, st, e0, e1, 0, a);
+    else hipLaunchKernelGGL(kern, grid, block, lds, st, a);
+    NFA_HIP_CHECK(hipGetLastError());
+    return NFA_OK;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -249,4 +249,114 @@ static inline int density_columns(int32_t flags, int features) {
     return features - ((flags & NFA_FLAG_PAD_COLUMNS_MASK) >> NFA_FLAG_PAD_COLUMNS_SHIFT);
 }
 
+// ---- host side of the whole-layer launchers (K8, K8h, K8s, K8c, K8x, K11) ----
+
+// The flag word: bits outside the direction / accumulate / density flags and `extra` are invalid, and so are an
+// activation code above tanh (only where `extra` holds NFA_FLAG_ACTIVATION_MASK; *activation: the code, ReLU = 0)
+// and an invalid pair of density flags.
+static inline int check_layer_flags(int32_t flags, int32_t extra, int* activation) {
+    if (flags & ~(NFA_FLAG_INVERSE | NFA_FLAG_ACCUMULATE_LOGABSDET | NFA_FLAG_STANDARD_NORMAL_LOG_PROB |
+                  NFA_FLAG_SKIP_OUTPUTS | NFA_FLAG_PAD_COLUMNS_MASK | extra))
+        return NFA_ERR_INVALID_ARGUMENT;
+    *activation = (flags & NFA_FLAG_ACTIVATION_MASK) >> NFA_FLAG_ACTIVATION_SHIFT;
+    if (*activation > NFA_ACTIVATION_TANH || !density_flags_valid(flags)) return NFA_ERR_INVALID_ARGUMENT;
+    return NFA_OK;
+}
+
+// The sizes every whole-layer kernel serves: hidden width 128, d_t, d_i <= 64, D % 4 == 0, D <= 128, whole 128-row
+// blocks, up to 64 residual blocks (K11: hidden layers) and 4096 layers
+static inline bool layer_family(int64_t batch, int features, int dt, int di, int hidden, int blocks, int layers) {
+    return hidden == 128 && dt <= 64 && di <= 64 && features <= 128 && (features & 3) == 0 && (batch & 127) == 0 &&
+           blocks <= 64 && layers <= 4096;
+}
+
+// final-layer rows per transformed feature of the spline engines with linear tails: 23 logits padded to 24 at 8 bins
+// (two features share three 32-row tiles), otherwise 3 K - 1 padded to whole 16-row lane-half shares
+static inline int spline_rows_per_feature(int K) { return K == 8 ? 24 : 16 * ((3 * K - 1 + 15) / 16); }
+
+// What a whole-layer spline entry point forwards to its launcher; the buffers an engine does not take stay null.
+struct LayerCall {
+    const float* inputs;
+    const void* weights;                // packed weights (K8, K8x) or the parameter + weight stream (K8h, K8s, K8c)
+    const float* bias;                  // K8, K8x
+    const int32_t* tables;              // flow tables (K8, K8x) or final positions (K8h, K8s, K8c)
+    int32_t num_layers;
+    float* outputs;
+    float* logabsdet;
+    int32_t* redo;                      // the f16 engines' row-block words (K8's redo pass reads its own)
+    int32_t* status;
+    int64_t batch;
+    int32_t features, num_transform, num_identity, hidden_features, num_blocks;
+    const nfa_rqs_spec* spec;
+    int32_t flags;
+    void* stream;
+    const float* context;               // [batch, context_features] (K8, K8h)
+    int32_t context_features;
+    int32_t param_stages;               // the stream engines
+};
+
+// What an engine accepts beyond the shared family.
+struct LayerRules {
+    int32_t flags;      // flag bits beside the direction / accumulate / density ones (activation, log2(e) fold)
+    bool any_bins;      // 2 .. 16, 20, 24 and 32 bins; otherwise 8 only
+    bool tails_none;    // tails=None beside linear tails
+    bool stream;        // the parameters travel in the weight stream: param_stages >= 1
+};
+
+// The checks the spline engines share, in the order of their codes: argument errors, the spline's own (make_dev_spec),
+// then the family.  The engine's own checks of each kind follow it.
+static inline int check_layer_call(const LayerCall& c, const LayerRules& r, RqsDev* sp, int* activation) {
+    int rc = check_layer_flags(c.flags, r.flags, activation);
+    if (rc != NFA_OK) return rc;
+    if (c.batch < 0 || c.features < 1 || c.num_transform < 1 || c.num_identity < 1 || c.num_transform > c.features ||
+        c.num_identity > c.features || c.num_blocks < 0 || c.num_layers < 1 || c.context_features < 0 ||
+        (r.stream && c.param_stages < 1))
+        return NFA_ERR_INVALID_ARGUMENT;
+    rc = make_dev_spec(c.spec, sp);
+    if (rc != NFA_OK) return rc;
+    const int K = sp->K;
+    const bool bins = r.any_bins ? (K >= 2 && K <= 16) || K == 20 || K == 24 || K == 32 : K == 8;
+    if (!bins || !(sp->linear || r.tails_none) || sp->beta != 1.0f || (c.num_transform & 3) != 0 ||
+        !layer_family(c.batch, c.features, c.num_transform, c.num_identity, c.hidden_features, c.num_blocks,
+                      c.num_layers))
+        return NFA_ERR_UNSUPPORTED;
+    return NFA_OK;
+}
+
+// the buffers every spline engine reads or writes (the outputs unless NFA_FLAG_SKIP_OUTPUTS, the context when it has
+// columns)
+static inline bool layer_buffers_given(const LayerCall& c) {
+    return c.inputs && c.weights && c.tables && c.logabsdet && (c.outputs || (c.flags & NFA_FLAG_SKIP_OUTPUTS)) &&
+           (c.context_features == 0 || c.context);
+}
+
+// The density epilogue's fields of a kernel's Args: invalid when the pad columns leave no column to sum over.
+template <class A>
+static inline int fill_density(A& a, int32_t flags, int features) {
+    a.normal = (flags & NFA_FLAG_STANDARD_NORMAL_LOG_PROB) ? 1 : 0;
+    a.skip_out = (flags & NFA_FLAG_SKIP_OUTPUTS) ? 1 : 0;
+    a.Ds = density_columns(flags, features);
+    if (a.Ds < 1) return NFA_ERR_INVALID_ARGUMENT;
+    a.log_z = standard_normal_log_z(a.Ds);
+    return NFA_OK;
+}
+
+// The fields the spline engines' Args share, the density epilogue's included.
+template <class A>
+static inline int fill_layer_args(A& a, const LayerCall& c) {
+    a.x = c.inputs;
+    a.w = reinterpret_cast<const vec4f*>(c.weights);
+    a.out = c.outputs;
+    a.lad = c.logabsdet;
+    a.status = c.status;
+    a.batch = c.batch;
+    a.D = c.features;
+    a.dt = c.num_transform;
+    a.di = c.num_identity;
+    a.num_blocks = c.num_blocks;
+    a.num_layers = c.num_layers;
+    a.accumulate = (c.flags & NFA_FLAG_ACCUMULATE_LOGABSDET) ? 1 : 0;
+    return fill_density(a, c.flags, c.features);
+}
+
 }  // namespace nfa

@@ -76,6 +76,29 @@ struct Args {
                                 // (accumulators x kappa), packed row order (tile, lane-half, register)
 };
 
+typedef void (*KernelFn)(const Args);
+
+// Host side of K8h, K8s and K8c.  The words of a layer's parameter stages (column tables, the GEMMs' headers and
+// biases), or 0 when the call's `param_stages` (1 .. 4 stages of 2048 words) do not hold them.
+inline int param_words(const LayerCall& c, int K) {
+    const int words = kTabWords + (kHdr + 128) * (1 + (c.context_features > 0 ? 3 : 2) * c.num_blocks) + kHdr +
+                      c.num_transform * spline_rows_per_feature(K);
+    return c.param_stages * 2048 < words || c.param_stages > 4 ? 0 : words;
+}
+
+// Everything in Args but the stage count and the trace buffer.
+inline int fill_args(Args& a, const LayerCall& c, int param_words, int32_t* dbg_bins, float* dbg_logits) {
+    a.final_tab = c.tables;
+    a.redo = c.redo;
+    a.param_stages = c.param_stages;
+    a.param_words = param_words;
+    a.ctx = c.context_features > 0 ? c.context : nullptr;
+    a.ce = c.context_features;
+    a.dbg_bins = dbg_bins;
+    a.dbg_logits = dbg_logits;
+    return fill_layer_args(a, c);
+}
+
 // (debug stamps: the switch and the index are wave-uniform -- scalar registers -- and the pointer is rebuilt from the
 //  kernel arguments at every stamp: a per-lane pointer kept for the whole kernel cost three vector registers)
 #define NFA_HSTAMP()                                                                                   \

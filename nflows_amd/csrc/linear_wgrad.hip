@@ -468,14 +468,12 @@ extern "C" int nfa_linear_wgrad_batched_f32(int32_t count, const float* const* i
             hipLaunchKernelGGL((wgrad_partial_bf16_kernel<2, 2, 2, 2, 16>), grid, dim3(kBlock), lds, st, a);
         } else if (p.variant == 0 && bf16) {
             constexpr size_t lds = (size_t)kWgRing * kWgRows * (128 + 128) * 4;
-            static unsigned long long raised_b = 0;   // device mask (raise_dynamic_lds)
-            const int rc_lds = raise_dynamic_lds((const void*)wgrad_partial_bf16_kernel<2, 2, 2, 2, kWgRows>, &raised_b, (int)lds);
+            const int rc_lds = raise_dynamic_lds((const void*)wgrad_partial_bf16_kernel<2, 2, 2, 2, kWgRows>, (int)lds);
             if (rc_lds != NFA_OK) return rc_lds;
             hipLaunchKernelGGL((wgrad_partial_bf16_kernel<2, 2, 2, 2, kWgRows>), grid, dim3(kBlock), lds, st, a);
         } else if (p.variant == 0) {
             constexpr size_t lds = (size_t)kWgRing * kWgRows * (128 + 128) * 4;
-            static unsigned long long raised = 0;   // device mask (raise_dynamic_lds: the opt-in is per device)
-            const int rc_lds = raise_dynamic_lds((const void*)wgrad_partial_kernel<2, 2, 2, 2>, &raised, (int)lds);
+            const int rc_lds = raise_dynamic_lds((const void*)wgrad_partial_kernel<2, 2, 2, 2>, (int)lds);
             if (rc_lds != NFA_OK) return rc_lds;
             hipLaunchKernelGGL((wgrad_partial_kernel<2, 2, 2, 2>), grid, dim3(kBlock), lds, st, a);
         } else {

@@ -382,16 +382,7 @@ extern "C" int nfa_made_rqs_inverse_f32(const float* inputs, const float* step_b
     const int lps = lps_env && atoi(lps_env) == 32 ? 32 : 16;   // (measured: 32 is SLOWER, 2.15 vs 1.97 ms at configs[4] -- profiles/r4/k12_lanes_per_sample.txt)
     void (*kern)(const MadeInvArgs) = a.sp.K == 8 ? (lps == 32 ? made_rqs_inverse_kernel<8, 32> : made_rqs_inverse_kernel<8, 16>)
                                                   : (lps == 32 ? made_rqs_inverse_kernel<10, 32> : made_rqs_inverse_kernel<10, 16>);
-    if (lds > 64 * 1024) {
-        static unsigned long long raised[4] = {};   // device masks (raise_dynamic_lds)
-        const int which = (a.sp.K == 8 ? 0 : 1) + (lps == 32 ? 2 : 0);
-        {
-            const int rc_lds = raise_dynamic_lds((const void*)kern, &raised[which], 160 * 1024 - 4096);
-            if (rc_lds != NFA_OK) return rc_lds;
-        }
-    }
     note_layer_kernel("made_rqs_inverse_kernel<K=%d, lanes_per_sample=%d>", a.sp.K, lps);
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3((lps / 4) * kWave), lds, (hipStream_t)stream, a);
-    NFA_HIP_CHECK(hipGetLastError());
-    return NFA_OK;
+    return launch_kernel(kern, dim3((unsigned)blocks), dim3((lps / 4) * kWave), lds, (hipStream_t)stream, a,
+                         160 * 1024 - 4096, false);
 }

@@ -283,19 +283,11 @@ extern "C" int nfa_rqs_made_output_f32(const float* inputs, int64_t row_stride, 
     const int chunks = (a.groups + kMadeOutGroups - 1) / kMadeOutGroups;
     const size_t lds = (size_t)2 * kMadeOutTileVec4 * 16 + (size_t)kMadeOutGroups * 3 * 32 * sizeof(float) +
                        (size_t)(kBlock / kWave) * 32 * ((kMadeOutGroups * 4) | 1) * sizeof(float);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    profile_next_launch(&e0, &e1);
     hipStream_t st = (hipStream_t)stream;
     a.row_blocks = (int)(batch >> 7);
     const dim3 grid((unsigned)((batch >> 7) * chunks)), block(kBlock);
     const bool inverse = (flags & NFA_FLAG_INVERSE) != 0;
     void (*kern)(const MadeOutArgs) = inverse ? rqs_made_output_kernel<true> : rqs_made_output_kernel<false>;
     note_layer_kernel("rqs_made_output_kernel<inverse=%d>", inverse ? 1 : 0);
-    static unsigned long long raised[2] = {};   // device masks (raise_dynamic_lds)
-    const int rc_lds = raise_dynamic_lds((const void*)kern, &raised[inverse ? 1 : 0], (int)lds);
-    if (rc_lds != NFA_OK) return rc_lds;
-    if (e0) hipExtLaunchKernelGGL(kern, grid, block, lds, st, e0, e1, 0, a);
-    else hipLaunchKernelGGL(kern, grid, block, lds, st, a);
-    NFA_HIP_CHECK(hipGetLastError());
-    return NFA_OK;
+    return launch_kernel(kern, grid, block, lds, st, a);   // (two 48 KB weight tiles: always above 64 KB)
 }

@@ -865,14 +865,7 @@ extern "C" int nfa_resnet_hidden_forward_f32(const float* identity_inputs, const
     const size_t lds = (size_t)kTrainRing * kStageVec4 * 16 + (size_t)(kBlock / kWave) * kTrainTileFloats * sizeof(float);
     hipStream_t st = (hipStream_t)stream;
     void (*kern)(const TrainArgs) = init_ks == 2 ? resnet_hidden_forward_kernel<2> : resnet_hidden_forward_kernel<4>;
-    if (lds > 64 * 1024) {
-        static unsigned long long raised[2] = {};   // device masks (raise_dynamic_lds)
-        const int rc_lds = raise_dynamic_lds((const void*)kern, &raised[init_ks == 2 ? 0 : 1], (int)lds);
-        if (rc_lds != NFA_OK) return rc_lds;
-    }
-    hipLaunchKernelGGL(kern, train_grid(batch), dim3(kBlock), lds, st, a);
-    NFA_HIP_CHECK(hipGetLastError());
-    return NFA_OK;
+    return launch_kernel(kern, train_grid(batch), dim3(kBlock), lds, st, a, 0, false);
 }
 
 static int launch_train_backward(const float* grad_hidden, const float* grad_params, int32_t out_features,
@@ -927,14 +920,7 @@ static int launch_train_backward(const float* grad_hidden, const float* grad_par
     else
         kern = num_blocks == 0 ? resnet_hidden_backward_kernel<0> : num_blocks == 1 ? resnet_hidden_backward_kernel<1>
                : num_blocks == 2 ? resnet_hidden_backward_kernel<2> : resnet_hidden_backward_kernel<3>;
-    if (lds > 64 * 1024) {
-        static unsigned long long raised[8] = {};   // device masks (raise_dynamic_lds)
-        const int rc_lds = raise_dynamic_lds((const void*)kern, &raised[num_blocks + (with_final ? 4 : 0)], (int)lds);
-        if (rc_lds != NFA_OK) return rc_lds;
-    }
-    hipLaunchKernelGGL(kern, grid, block, lds, st, a);
-    NFA_HIP_CHECK(hipGetLastError());
-    return NFA_OK;
+    return launch_kernel(kern, grid, block, lds, st, a, 0, false);
 }
 
 extern "C" int nfa_resnet_hidden_backward_f32(const float* grad_hidden, const void* weights_packed, const float* saved,

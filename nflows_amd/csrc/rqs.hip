@@ -33,6 +33,8 @@
 #include <string.h>
 
 #include <mutex>
+#include <set>
+#include <utility>
 #include <vector>
 
 
@@ -648,25 +650,23 @@ void note_layer_kernel(const char* fmt, ...) {
     va_end(ap);
 }
 
-template <typename Kernel>
-static void launch_k1(Kernel kernel, dim3 grid, dim3 block, size_t lds, hipStream_t st, const CouplingArgs& a) {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    profile_next_launch(&e0, &e1);
-    if (e0)
-        hipExtLaunchKernelGGL(kernel, grid, block, lds, st, e0, e1, 0, a);
-    else
-        hipLaunchKernelGGL(kernel, grid, block, lds, st, a);
+int raise_dynamic_lds(const void* kern, int bytes) {
+    static std::mutex mu;
+    static std::set<std::pair<const void*, int>> raised;   // (kernel, device) pairs already opted in
+    int dev = 0;
+    NFA_HIP_CHECK(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(mu);
+    if (raised.count({kern, dev})) return NFA_OK;
+    NFA_HIP_CHECK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    raised.insert({kern, dev});
+    return NFA_OK;
 }
 
 template <int KT, int BLOCK>
 static int launch_coupling(const CouplingArgs& a, int inverse, dim3 grid, size_t lds, hipStream_t st) {
     note_layer_kernel("rqs_coupling_kernel<K=%d, inverse=%d, block=%d>", KT, inverse ? 1 : 0, BLOCK);
-    if (inverse)
-        launch_k1(rqs_coupling_kernel<KT, true, BLOCK>, grid, dim3(BLOCK), lds, st, a);
-    else
-        launch_k1(rqs_coupling_kernel<KT, false, BLOCK>, grid, dim3(BLOCK), lds, st, a);
-    NFA_HIP_CHECK(hipGetLastError());
-    return NFA_OK;
+    return launch_kernel(inverse ? rqs_coupling_kernel<KT, true, BLOCK> : rqs_coupling_kernel<KT, false, BLOCK>, grid,
+                         dim3(BLOCK), lds, st, a);
 }
 
 template <int KT>
@@ -696,35 +696,22 @@ static int launch_wavetile(const CouplingArgs& a, int inverse, hipStream_t st) {
     const int64_t need = (tiles + kBlock / kWave - 1) / (kBlock / kWave);
     if (g > need) g = need;
     note_layer_kernel("rqs_coupling_wavetile<K=%d, inverse=%d> (%d workgroups per CU)", KT, inverse ? 1 : 0, per_cu);
-    launch_k1(kern, dim3((unsigned)g), dim3(kBlock), lds, st, a);
-    NFA_HIP_CHECK(hipGetLastError());
-    return NFA_OK;
+    return launch_kernel(kern, dim3((unsigned)g), dim3(kBlock), lds, st, a);
 }
 
 template <int KT>
 static int launch_pipelined(const CouplingArgs& a, int inverse, dim3 grid, size_t lds, hipStream_t st) {
     note_layer_kernel("rqs_coupling_pipelined<K=%d, inverse=%d, linear=%d>", KT, inverse ? 1 : 0, a.sp.linear ? 1 : 0);
+    void (*kern)(const CouplingArgs) = nullptr;
     if (a.bins) {   // (the instances that store the chosen bins: same arithmetic, one more store)
-        if (a.sp.linear) {
-            if (inverse) launch_k1(rqs_coupling_pipelined<KT, true, true, true>, grid, dim3(kBlock), lds, st, a);
-            else launch_k1(rqs_coupling_pipelined<KT, false, true, true>, grid, dim3(kBlock), lds, st, a);
-        } else {
-            if (inverse) launch_k1(rqs_coupling_pipelined<KT, true, false, true>, grid, dim3(kBlock), lds, st, a);
-            else launch_k1(rqs_coupling_pipelined<KT, false, false, true>, grid, dim3(kBlock), lds, st, a);
-        }
+        if (a.sp.linear) kern = inverse ? rqs_coupling_pipelined<KT, true, true, true> : rqs_coupling_pipelined<KT, false, true, true>;
+        else kern = inverse ? rqs_coupling_pipelined<KT, true, false, true> : rqs_coupling_pipelined<KT, false, false, true>;
     } else if (a.sp.linear) {
-        if (inverse)
-            launch_k1(rqs_coupling_pipelined<KT, true, true>, grid, dim3(kBlock), lds, st, a);
-        else
-            launch_k1(rqs_coupling_pipelined<KT, false, true>, grid, dim3(kBlock), lds, st, a);
+        kern = inverse ? rqs_coupling_pipelined<KT, true, true> : rqs_coupling_pipelined<KT, false, true>;
     } else {
-        if (inverse)
-            launch_k1(rqs_coupling_pipelined<KT, true, false>, grid, dim3(kBlock), lds, st, a);
-        else
-            launch_k1(rqs_coupling_pipelined<KT, false, false>, grid, dim3(kBlock), lds, st, a);
+        kern = inverse ? rqs_coupling_pipelined<KT, true, false> : rqs_coupling_pipelined<KT, false, false>;
     }
-    NFA_HIP_CHECK(hipGetLastError());
-    return NFA_OK;
+    return launch_kernel(kern, grid, dim3(kBlock), lds, st, a);
 }
 
 template <int KT>

@@ -32,84 +32,64 @@
 
 using namespace nfa;
 
-static int launch_resnet_layers(const float* inputs, const void* weights_packed, const float* bias_packed,
-                                const int32_t* tables, int32_t num_layers, float* outputs, float* logabsdet,
-                                int32_t* status, int64_t batch, int32_t features, int32_t num_transform,
-                                int32_t num_identity, int32_t hidden_features, int32_t num_blocks,
-                                const nfa_rqs_spec* spec, int32_t flags, void* stream,
-                                const int32_t* redo = nullptr, const float* context = nullptr,
-                                int32_t context_features = 0, float* dbg_logits = nullptr) {
-    if (flags & ~(NFA_FLAG_INVERSE | NFA_FLAG_ACCUMULATE_LOGABSDET | NFA_FLAG_LOGITS_LOG2E |
-                  NFA_FLAG_STANDARD_NORMAL_LOG_PROB | NFA_FLAG_SKIP_OUTPUTS | NFA_FLAG_PAD_COLUMNS_MASK |
-                  NFA_FLAG_ACTIVATION_MASK))
-        return NFA_ERR_INVALID_ARGUMENT;
-    const int activation = (flags & NFA_FLAG_ACTIVATION_MASK) >> NFA_FLAG_ACTIVATION_SHIFT;
-    if (activation > NFA_ACTIVATION_TANH) return NFA_ERR_INVALID_ARGUMENT;
-    flags &= ~NFA_FLAG_ACTIVATION_MASK;
-    if (!density_flags_valid(flags)) return NFA_ERR_INVALID_ARGUMENT;
-    if (batch < 0 || features < 1 || num_transform < 1 || num_identity < 1 ||
-        num_transform > features || num_identity > features || num_blocks < 0 || num_layers < 1)
-        return NFA_ERR_INVALID_ARGUMENT;
+template <int PRE, int PIPE, int KB, bool CTX = false>
+static ResnetKernelFn resnet_pick(bool inverse, int init_ks) {
+    return init_ks == 4 ? (inverse ? rqs_resnet_kernel<true, PRE, 4, PIPE, KB, CTX> : rqs_resnet_kernel<false, PRE, 4, PIPE, KB, CTX>)
+                        : (inverse ? rqs_resnet_kernel<true, PRE, 2, PIPE, KB, CTX> : rqs_resnet_kernel<false, PRE, 2, PIPE, KB, CTX>);
+}
+
+// The instance of a launch, one ordered decision: tails=None, the diagnostic instances, a context or an activation or a
+// bin count beyond the tuned 8 / 10 bins with ReLU (their own translation units), then the tuned instances: a context
+// (the woven default form), 10 bins (woven or plain), the log2(e) fold (woven or plain) and 8 bins (pipe 2, 1 or 0).
+static ResnetKernelFn resnet_kernel(bool inverse, int init_ks, int K, int activation, bool with_ctx, bool l2e, int pipe,
+                                    bool no_tails, bool dbg) {
+    const bool tuned = (K == 8 || K == 10) && activation == NFA_ACTIVATION_RELU;
+    if (no_tails) return resnet_tails_kernel(K, inverse, init_ks);
+    if (dbg) return resnet_debug_kernel(inverse, init_ks);
+    if (with_ctx && !tuned) return resnet_context_kernel(K, activation, inverse, init_ks);
+    if (activation != NFA_ACTIVATION_RELU) return resnet_activation_kernel(activation, K, inverse, init_ks);
+    if (!tuned) return resnet_bins_kernel(K, inverse, init_ks);
+    if (with_ctx) return K == 10 ? resnet_pick<1, 2, 10, true>(inverse, init_ks) : resnet_pick<1, 2, 8, true>(inverse, init_ks);
+    if (K == 10) return pipe ? resnet_pick<1, 2, 10>(inverse, init_ks) : resnet_pick<1, 0, 10>(inverse, init_ks);
+    if (l2e) return pipe ? resnet_pick<2, 2, 8>(inverse, init_ks) : resnet_pick<2, 0, 8>(inverse, init_ks);
+    return pipe == 2 ? resnet_pick<1, 2, 8>(inverse, init_ks)
+                     : pipe ? resnet_pick<1, 1, 8>(inverse, init_ks) : resnet_pick<1, 0, 8>(inverse, init_ks);
+}
+
+// redo: the second pass over the row blocks an f16 engine flagged (not the measured kernel: no profile events, the
+// last layer kernel's label stays the first pass's)
+static int launch_resnet_layers(const LayerCall& c, const int32_t* redo = nullptr, float* dbg_logits = nullptr) {
     ResnetArgs a;
-    int rc = make_dev_spec(spec, &a.sp);
+    int activation = 0;
+    int rc = check_layer_call(c, {NFA_FLAG_LOGITS_LOG2E | NFA_FLAG_ACTIVATION_MASK, true, true, false}, &a.sp, &activation);
     if (rc != NFA_OK) return rc;
+    const bool relu = activation == NFA_ACTIVATION_RELU, l2e = (c.flags & NFA_FLAG_LOGITS_LOG2E) != 0;
     const bool any_bins = a.sp.K != 8 && a.sp.K != 10;   // 2 .. 16, 20, 24, 32 bins: the plain loop, no log2(e) fold
-    // activations other than ReLU: 8 or 10 bins, the plain loop, no log2(e) fold
-    if (activation != NFA_ACTIVATION_RELU && (any_bins || (flags & NFA_FLAG_LOGITS_LOG2E)))
-        return NFA_ERR_UNSUPPORTED;
+    const bool no_tails = !a.sp.linear, with_ctx = c.context_features > 0;
+    // activations other than ReLU: 8 or 10 bins, the plain loop, no log2(e) fold; the log2(e) fold: 8 bins
+    if ((!relu && (any_bins || l2e)) || (l2e && a.sp.K != 8)) return NFA_ERR_UNSUPPORTED;
     // tails=None (round 6): 3 K + 1 logits per feature, the plain loop, ReLU, no context, no log2(e) fold, no redo role
-    const bool no_tails = !a.sp.linear;
-    if (no_tails && (activation != NFA_ACTIVATION_RELU || (flags & NFA_FLAG_LOGITS_LOG2E) || context_features > 0 || dbg_logits || redo))
-        return NFA_ERR_UNSUPPORTED;
-    const int rows_per_feature = no_tails ? 16 * ((3 * a.sp.K + 1 + 15) / 16) : a.sp.K == 8 ? 24 : 16 * ((3 * a.sp.K - 1 + 15) / 16);
-    if (a.sp.beta != 1.0f) return NFA_ERR_UNSUPPORTED;  // (identity initialisation: functional callers only)
-    const bool bins_served = (a.sp.K >= 2 && a.sp.K <= 16) || a.sp.K == 20 || a.sp.K == 24 || a.sp.K == 32;
-    if (!bins_served || (a.sp.K != 8 && (flags & NFA_FLAG_LOGITS_LOG2E)) ||
-        hidden_features != 128 || (num_transform & 3) != 0 ||
-        num_transform > 64 || num_identity > 64 || features > 128 || (features & 3) != 0 ||
-        (batch & 127) != 0 || num_blocks > 64 || num_layers > 4096)
-        return NFA_ERR_UNSUPPORTED;
-    const bool with_ctx = context_features > 0;
-    if (context_features < 0) return NFA_ERR_INVALID_ARGUMENT;
-    // with a context: 8 bins, the default evaluation, identity features + context within the initial
-    // layer's 64 input columns
-    if (with_ctx && ((flags & NFA_FLAG_LOGITS_LOG2E) || num_identity + context_features > 64))
-        return NFA_ERR_UNSUPPORTED;
-    if (batch == 0) return NFA_OK;
-    if (!inputs || !weights_packed || !bias_packed || !tables || !logabsdet ||
-        (!outputs && !(flags & NFA_FLAG_SKIP_OUTPUTS)) || (with_ctx && !context))
-        return NFA_ERR_INVALID_ARGUMENT;
-    a.ctx = with_ctx ? context : nullptr;
-    a.ce = context_features;
-    a.dbg_logits = dbg_logits;
+    if (no_tails && (!relu || l2e || with_ctx || dbg_logits || redo)) return NFA_ERR_UNSUPPORTED;
+    // with a context: the default evaluation, identity features + context within the initial layer's 64 input columns
+    if (with_ctx && (l2e || c.num_identity + c.context_features > 64)) return NFA_ERR_UNSUPPORTED;
+    if (c.batch == 0) return NFA_OK;
+    if (!layer_buffers_given(c) || !c.bias) return NFA_ERR_INVALID_ARGUMENT;
     // the diagnostic instances (nfa_rqs_flow_resnet_logits_f32): the bench's kernel family only
-    if (dbg_logits && (a.sp.K != 8 || with_ctx || activation != NFA_ACTIVATION_RELU || (flags & NFA_FLAG_LOGITS_LOG2E) || redo))
-        return NFA_ERR_UNSUPPORTED;
-    a.normal = (flags & NFA_FLAG_STANDARD_NORMAL_LOG_PROB) ? 1 : 0;
-    a.skip_out = (flags & NFA_FLAG_SKIP_OUTPUTS) ? 1 : 0;
-    a.Ds = density_columns(flags, features);
-    if (a.Ds < 1) return NFA_ERR_INVALID_ARGUMENT;
-    a.log_z = standard_normal_log_z(a.Ds);
-    a.x = inputs;
-    a.w = reinterpret_cast<const vec4f*>(weights_packed);
-    a.bias = bias_packed;
-    a.tables = tables;
-    a.out = outputs;
-    a.lad = logabsdet;
-    a.status = status;
-    a.batch = batch;
-    a.D = features;
-    a.dt = num_transform;
-    a.di = num_identity;
-    a.num_blocks = num_blocks;
-    a.num_layers = num_layers;
-    const int init_ks = num_identity + context_features > 32 ? 4 : 2;
-    a.num_stages = init_ks + (with_ctx ? (context_features <= 16 ? 17 : 20) : 16) * num_blocks +
-                   2 * (num_transform * rows_per_feature / 32);
-    a.bias_per_layer = 128 + (with_ctx ? 384 : 256) * num_blocks + num_transform * rows_per_feature;
-    a.accumulate = (flags & NFA_FLAG_ACCUMULATE_LOGABSDET) ? 1 : 0;
+    if (dbg_logits && (a.sp.K != 8 || with_ctx || !relu || l2e || redo)) return NFA_ERR_UNSUPPORTED;
+    rc = fill_layer_args(a, c);
+    if (rc != NFA_OK) return rc;
+    a.bias = c.bias;
+    a.tables = c.tables;
+    a.ctx = with_ctx ? c.context : nullptr;
+    a.ce = c.context_features;
+    a.dbg_logits = dbg_logits;
     a.trace = g_k7_trace;
     a.redo = redo;
+    const int rows_per_feature = no_tails ? 16 * ((3 * a.sp.K + 1 + 15) / 16) : spline_rows_per_feature(a.sp.K);
+    const int init_ks = c.num_identity + c.context_features > 32 ? 4 : 2;
+    a.num_stages = init_ks + (with_ctx ? (c.context_features <= 16 ? 17 : 20) : 16) * c.num_blocks +
+                   2 * (c.num_transform * rows_per_feature / 32);
+    a.bias_per_layer = 128 + (with_ctx ? 384 : 256) * c.num_blocks + c.num_transform * rows_per_feature;
     // final layer with the spline evaluation woven into its MFMAs (not with the log2(e) fold):
     //   2 (default)  woven, FlatSteps<FAST>: cheaper rounding sequence, same error class
     //   1            woven, same results bit for bit as the plain loop
@@ -118,106 +98,30 @@ static int launch_resnet_layers(const float* inputs, const void* weights_packed,
         const char* e = getenv("NFA_K8_PIPE");
         return e ? atoi(e) : 2;
     }();
-    // (with the log2(e) fold only the default woven form exists)
-    const bool pipe = !no_tails && !dbg_logits && !any_bins && activation == NFA_ACTIVATION_RELU && use_pipe && ((a.sp.K == 8 && (!(flags & NFA_FLAG_LOGITS_LOG2E) || use_pipe == 2)) ||
-                                  (a.sp.K == 10 && use_pipe == 2));
+    // `pipe`: the woven form in use, 0 for the plain loop (with the log2(e) fold and at 10 bins only the default woven
+    // form exists)
+    const int pipe = !no_tails && !dbg_logits && !any_bins && relu && use_pipe &&
+                             ((a.sp.K == 8 && (!l2e || use_pipe == 2)) || (a.sp.K == 10 && use_pipe == 2))
+                         ? use_pipe : 0;
     // a context: the woven default form at 8 / 10 bins with ReLU; the plain loop for the other bin counts and
     // activations (round 5: rqs_resnet_ctx.hip)
-    const bool more_ctx = with_ctx && (any_bins || activation != NFA_ACTIVATION_RELU);
-    if (with_ctx && !more_ctx && !(pipe && use_pipe == 2)) return NFA_ERR_UNSUPPORTED;
-    const size_t lds = (size_t)kRing * kStageVec4 * 16 + (size_t)(kBlock / kWave) * features * kRowPad * sizeof(float) +
-                       (pipe ? (size_t)num_transform * rows_per_feature * sizeof(float) : 0) +
-                       (size_t)(kBlock / kWave) * context_features * kRowPad * sizeof(float) +
+    if (with_ctx && !any_bins && relu && pipe != 2) return NFA_ERR_UNSUPPORTED;
+    const size_t lds = (size_t)kRing * kStageVec4 * 16 + (size_t)(kBlock / kWave) * c.features * kRowPad * sizeof(float) +
+                       (pipe ? (size_t)c.num_transform * rows_per_feature * sizeof(float) : 0) +
+                       (size_t)(kBlock / kWave) * c.context_features * kRowPad * sizeof(float) +
                        (with_ctx ? (size_t)(kBlock / kWave) * 64 * kWave * sizeof(float) : 0);
-    int64_t blocks = batch >> 7;
+    int64_t blocks = c.batch >> 7;
     const int64_t per_cu = lds + 2048 <= 80 * 1024 ? 2 : 1;
     const int64_t cap = (int64_t)device_cu_count() * per_cu;
     if (blocks > cap) blocks = cap;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (!redo) profile_next_launch(&e0, &e1);  // (the second pass is not the measured kernel)
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)blocks), block(kBlock);
-    const bool inv = (flags & NFA_FLAG_INVERSE) != 0, l2e = (flags & NFA_FLAG_LOGITS_LOG2E) != 0;
-    void (*kern)(const ResnetArgs) = nullptr;
-#define NFA_K8_PICK(INV_, PRE_)                                                                    \
-    kern = init_ks == 4 ? rqs_resnet_kernel<INV_, PRE_, 4> : rqs_resnet_kernel<INV_, PRE_, 2>
-    if (inv) {
-        if (l2e) NFA_K8_PICK(true, 2);
-        else NFA_K8_PICK(true, 1);
-    } else {
-        if (l2e) NFA_K8_PICK(false, 2);
-        else NFA_K8_PICK(false, 1);
-    }
-#undef NFA_K8_PICK
-    if (a.sp.K == 10 && pipe) {
-        if (init_ks == 4) kern = inv ? rqs_resnet_kernel<true, 1, 4, 2, 10> : rqs_resnet_kernel<false, 1, 4, 2, 10>;
-        else kern = inv ? rqs_resnet_kernel<true, 1, 2, 2, 10> : rqs_resnet_kernel<false, 1, 2, 2, 10>;
-    } else if (a.sp.K == 10) {
-        if (init_ks == 4) kern = inv ? rqs_resnet_kernel<true, 1, 4, 0, 10> : rqs_resnet_kernel<false, 1, 4, 0, 10>;
-        else kern = inv ? rqs_resnet_kernel<true, 1, 2, 0, 10> : rqs_resnet_kernel<false, 1, 2, 0, 10>;
-    } else if (pipe && use_pipe == 2 && l2e) {
-        if (init_ks == 4) kern = inv ? rqs_resnet_kernel<true, 2, 4, 2> : rqs_resnet_kernel<false, 2, 4, 2>;
-        else kern = inv ? rqs_resnet_kernel<true, 2, 2, 2> : rqs_resnet_kernel<false, 2, 2, 2>;
-    } else if (pipe && use_pipe == 2) {
-        if (init_ks == 4) kern = inv ? rqs_resnet_kernel<true, 1, 4, 2> : rqs_resnet_kernel<false, 1, 4, 2>;
-        else kern = inv ? rqs_resnet_kernel<true, 1, 2, 2> : rqs_resnet_kernel<false, 1, 2, 2>;
-    } else if (pipe) {
-        if (init_ks == 4) kern = inv ? rqs_resnet_kernel<true, 1, 4, 1> : rqs_resnet_kernel<false, 1, 4, 1>;
-        else kern = inv ? rqs_resnet_kernel<true, 1, 2, 1> : rqs_resnet_kernel<false, 1, 2, 1>;
-    }
-    if (activation != NFA_ACTIVATION_RELU) kern = resnet_activation_kernel(activation, a.sp.K, inv, init_ks);
-    else if (any_bins) kern = resnet_bins_kernel(a.sp.K, inv, init_ks);
-    if ((activation != NFA_ACTIVATION_RELU || any_bins) && !kern) return NFA_ERR_UNSUPPORTED;
-    if (more_ctx) {
-        kern = resnet_context_kernel(a.sp.K, activation, inv, init_ks);
-        if (!kern) return NFA_ERR_UNSUPPORTED;
-    } else if (with_ctx && a.sp.K == 10) {
-        if (init_ks == 4) kern = inv ? rqs_resnet_kernel<true, 1, 4, 2, 10, true> : rqs_resnet_kernel<false, 1, 4, 2, 10, true>;
-        else kern = inv ? rqs_resnet_kernel<true, 1, 2, 2, 10, true> : rqs_resnet_kernel<false, 1, 2, 2, 10, true>;
-    } else if (with_ctx) {
-        if (init_ks == 4) kern = inv ? rqs_resnet_kernel<true, 1, 4, 2, 8, true> : rqs_resnet_kernel<false, 1, 4, 2, 8, true>;
-        else kern = inv ? rqs_resnet_kernel<true, 1, 2, 2, 8, true> : rqs_resnet_kernel<false, 1, 2, 2, 8, true>;
-    }
-    if (dbg_logits) kern = resnet_debug_kernel(inv, init_ks);
-    if (no_tails) {
-        kern = resnet_tails_kernel(a.sp.K, inv, init_ks);
-        if (!kern) return NFA_ERR_UNSUPPORTED;
-    }
+    const bool inv = (c.flags & NFA_FLAG_INVERSE) != 0;
+    const ResnetKernelFn kern = resnet_kernel(inv, init_ks, a.sp.K, activation, with_ctx, l2e, pipe, no_tails, dbg_logits);
+    if (!kern) return NFA_ERR_UNSUPPORTED;
     if (!redo)
         note_layer_kernel("rqs_resnet_kernel<inverse=%d, init_ks=%d, pipe=%d, K=%d, ctx=%d, act=%d%s>", inv ? 1 : 0, init_ks,
-                          pipe ? use_pipe : 0, a.sp.K, with_ctx ? 1 : 0, activation, no_tails ? ", tails=none" : "");
-    if (with_ctx && lds > 64 * 1024) {
-        static unsigned long long raised_ctx[8 + 31 * 4 + 3 * 8] = {};   // device masks (raise_dynamic_lds)
-        const int which = (inv ? 1 : 0) + (init_ks == 4 ? 2 : 0) +
-                          (!more_ctx ? (a.sp.K == 10 ? 4 : 0)
-                                     : 8 + (any_bins ? (a.sp.K - 2) * 4 : 31 * 4 + (activation - 1) * 8 + (a.sp.K == 10 ? 4 : 0)));
-        {
-            const int rc_lds = raise_dynamic_lds((const void*)kern, &raised_ctx[which], 160 * 1024 - 2048);
-            if (rc_lds != NFA_OK) return rc_lds;
-        }
-    } else if (no_tails && lds > 64 * 1024) {
-        static unsigned long long raised_tails[31 * 4] = {};
-        const int rc_lds = raise_dynamic_lds((const void*)kern, &raised_tails[(a.sp.K - 2) * 4 + (inv ? 1 : 0) + (init_ks == 4 ? 2 : 0)], 160 * 1024 - 2048);
-        if (rc_lds != NFA_OK) return rc_lds;
-    } else if (dbg_logits && lds > 64 * 1024) {
-        static unsigned long long raised_dbg[4] = {};
-        const int rc_lds = raise_dynamic_lds((const void*)kern, &raised_dbg[(inv ? 1 : 0) + (init_ks == 4 ? 2 : 0)], 160 * 1024 - 2048);
-        if (rc_lds != NFA_OK) return rc_lds;
-    } else if (lds > 64 * 1024) {
-        static unsigned long long raised[32 + 31 * 4 + 3 * 8] = {};   // device masks (raise_dynamic_lds)  // opt in to > 64 KB of dynamic LDS once per kernel
-        const int which = activation != NFA_ACTIVATION_RELU ? 32 + 31 * 4 + (activation - 1) * 8 + (a.sp.K == 10 ? 4 : 0) + (inv ? 1 : 0) + (init_ks == 4 ? 2 : 0)
-                          : any_bins ? 32 + (a.sp.K - 2) * 4 + (inv ? 1 : 0) + (init_ks == 4 ? 2 : 0) : a.sp.K == 10 ? (pipe ? 24 : 12) + (inv ? 1 : 0) + (init_ks == 4 ? 2 : 0)
-                          : (pipe && use_pipe == 2) ? 16 + (inv ? 1 : 0) + (init_ks == 4 ? 2 : 0) + (l2e ? 4 : 0)
-                          : pipe ? 8 + (inv ? 1 : 0) + (init_ks == 4 ? 2 : 0) : (inv ? 1 : 0) + (l2e ? 2 : 0) + (init_ks == 4 ? 4 : 0);
-        {
-            const int rc_lds = raise_dynamic_lds((const void*)kern, &raised[which], 160 * 1024 - 2048);
-            if (rc_lds != NFA_OK) return rc_lds;
-        }
-    }
-    if (e0) hipExtLaunchKernelGGL(kern, grid, block, lds, st, e0, e1, 0, a);
-    else hipLaunchKernelGGL(kern, grid, block, lds, st, a);
-    NFA_HIP_CHECK(hipGetLastError());
-    return NFA_OK;
+                          pipe, a.sp.K, with_ctx ? 1 : 0, activation, no_tails ? ", tails=none" : "");
+    return launch_kernel(kern, dim3((unsigned)blocks), dim3(kBlock), lds, (hipStream_t)c.stream, a, 160 * 1024 - 2048,
+                         !redo);
 }
 
 extern "C" int nfa_rqs_coupling_resnet_f32(const float* inputs, const void* weights_packed,
@@ -227,9 +131,9 @@ extern "C" int nfa_rqs_coupling_resnet_f32(const float* inputs, const void* weig
                                            int32_t num_identity, int32_t hidden_features,
                                            int32_t num_blocks, const nfa_rqs_spec* spec, int32_t flags,
                                            void* stream) {
-    return launch_resnet_layers(inputs, weights_packed, bias_packed, layer_tables, 1, outputs, logabsdet, status,
-                                batch, features, num_transform, num_identity, hidden_features, num_blocks, spec,
-                                flags, stream);
+    return launch_resnet_layers({inputs, weights_packed, bias_packed, layer_tables, 1, outputs, logabsdet, nullptr, status,
+                                 batch, features, num_transform, num_identity, hidden_features, num_blocks, spec, flags,
+                                 stream, nullptr, 0, 0});
 }
 
 extern "C" int nfa_rqs_flow_resnet_f32(const float* inputs, const void* weights_packed,
@@ -239,9 +143,9 @@ extern "C" int nfa_rqs_flow_resnet_f32(const float* inputs, const void* weights_
                                        int32_t num_transform, int32_t num_identity,
                                        int32_t hidden_features, int32_t num_blocks,
                                        const nfa_rqs_spec* spec, int32_t flags, void* stream) {
-    return launch_resnet_layers(inputs, weights_packed, bias_packed, flow_tables, num_layers, outputs, logabsdet,
-                                status, batch, features, num_transform, num_identity, hidden_features, num_blocks,
-                                spec, flags, stream);
+    return launch_resnet_layers({inputs, weights_packed, bias_packed, flow_tables, num_layers, outputs, logabsdet, nullptr,
+                                 status, batch, features, num_transform, num_identity, hidden_features, num_blocks, spec,
+                                 flags, stream, nullptr, 0, 0});
 }
 
 // the diagnostic instances: the same launch with the LAST layer's logits stored (include/nflows_amd.h)
@@ -253,9 +157,10 @@ extern "C" int nfa_rqs_flow_resnet_logits_f32(const float* inputs, const void* w
                                               int32_t hidden_features, int32_t num_blocks,
                                               const nfa_rqs_spec* spec, int32_t flags, void* stream, float* logits) {
     if (!logits) return NFA_ERR_INVALID_ARGUMENT;
-    return launch_resnet_layers(inputs, weights_packed, bias_packed, flow_tables, num_layers, outputs, logabsdet,
-                                status, batch, features, num_transform, num_identity, hidden_features, num_blocks,
-                                spec, flags, stream, nullptr, nullptr, 0, logits);
+    return launch_resnet_layers({inputs, weights_packed, bias_packed, flow_tables, num_layers, outputs, logabsdet, nullptr,
+                                 status, batch, features, num_transform, num_identity, hidden_features, num_blocks, spec,
+                                 flags, stream, nullptr, 0, 0},
+                                nullptr, logits);
 }
 
 extern "C" int nfa_rqs_flow_resnet_redo_f32(const float* inputs, const void* weights_packed,
@@ -266,9 +171,10 @@ extern "C" int nfa_rqs_flow_resnet_redo_f32(const float* inputs, const void* wei
                                             int32_t hidden_features, int32_t num_blocks,
                                             const nfa_rqs_spec* spec, int32_t flags, void* stream) {
     if (!redo_blocks) return NFA_ERR_INVALID_ARGUMENT;
-    return launch_resnet_layers(inputs, weights_packed, bias_packed, flow_tables, num_layers, outputs, logabsdet,
-                                status, batch, features, num_transform, num_identity, hidden_features, num_blocks,
-                                spec, flags, stream, redo_blocks);
+    return launch_resnet_layers({inputs, weights_packed, bias_packed, flow_tables, num_layers, outputs, logabsdet, nullptr,
+                                 status, batch, features, num_transform, num_identity, hidden_features, num_blocks, spec,
+                                 flags, stream, nullptr, 0, 0},
+                                redo_blocks);
 }
 
 extern "C" int nfa_rqs_flow_resnet_context_f32(const float* inputs, const float* context, int32_t context_features,
@@ -279,9 +185,9 @@ extern "C" int nfa_rqs_flow_resnet_context_f32(const float* inputs, const float*
                                                int32_t hidden_features, int32_t num_blocks,
                                                const nfa_rqs_spec* spec, int32_t flags, void* stream) {
     if (context_features < 1) return NFA_ERR_INVALID_ARGUMENT;
-    return launch_resnet_layers(inputs, weights_packed, bias_packed, flow_tables, num_layers, outputs, logabsdet,
-                                status, batch, features, num_transform, num_identity, hidden_features, num_blocks,
-                                spec, flags, stream, nullptr, context, context_features);
+    return launch_resnet_layers({inputs, weights_packed, bias_packed, flow_tables, num_layers, outputs, logabsdet, nullptr,
+                                 status, batch, features, num_transform, num_identity, hidden_features, num_blocks, spec,
+                                 flags, stream, context, context_features, 0});
 }
 
 extern "C" int nfa_rqs_flow_resnet_context_redo_f32(const float* inputs, const float* context,
@@ -293,7 +199,8 @@ extern "C" int nfa_rqs_flow_resnet_context_redo_f32(const float* inputs, const f
                                                     int32_t hidden_features, int32_t num_blocks,
                                                     const nfa_rqs_spec* spec, int32_t flags, void* stream) {
     if (context_features < 1 || !redo_blocks) return NFA_ERR_INVALID_ARGUMENT;
-    return launch_resnet_layers(inputs, weights_packed, bias_packed, flow_tables, num_layers, outputs, logabsdet,
-                                status, batch, features, num_transform, num_identity, hidden_features, num_blocks,
-                                spec, flags, stream, redo_blocks, context, context_features);
+    return launch_resnet_layers({inputs, weights_packed, bias_packed, flow_tables, num_layers, outputs, logabsdet, nullptr,
+                                 status, batch, features, num_transform, num_identity, hidden_features, num_blocks, spec,
+                                 flags, stream, context, context_features, 0},
+                                redo_blocks);
 }

@@ -58,90 +58,78 @@
 
 using namespace nfa;
 
-static int launch_f16(const float* inputs, const float* context, int32_t context_features, const void* stream_packed,
-                      int32_t param_stages, const int32_t* final_positions, int32_t num_layers, float* outputs,
-                      float* logabsdet, int32_t* redo_blocks, int32_t* status, int64_t batch, int32_t features,
-                      int32_t num_transform, int32_t num_identity, int32_t hidden_features, int32_t num_blocks,
-                      const nfa_rqs_spec* spec, int32_t flags, void* stream, int32_t* dbg_bins = nullptr,
-                      float* dbg_logits = nullptr) {
-    if (flags & ~(NFA_FLAG_INVERSE | NFA_FLAG_ACCUMULATE_LOGABSDET | NFA_FLAG_STANDARD_NORMAL_LOG_PROB |
-                  NFA_FLAG_SKIP_OUTPUTS | NFA_FLAG_PAD_COLUMNS_MASK | NFA_FLAG_ACTIVATION_MASK))
-        return NFA_ERR_INVALID_ARGUMENT;
-    const int activation = (flags & NFA_FLAG_ACTIVATION_MASK) >> NFA_FLAG_ACTIVATION_SHIFT;
-    if (activation > NFA_ACTIVATION_TANH) return NFA_ERR_INVALID_ARGUMENT;
-    flags &= ~NFA_FLAG_ACTIVATION_MASK;
-    if (!density_flags_valid(flags)) return NFA_ERR_INVALID_ARGUMENT;
-    if (batch < 0 || features < 1 || num_transform < 1 || num_identity < 1 ||
-        num_transform > features || num_identity > features || num_blocks < 0 || num_layers < 1 || param_stages < 1)
-        return NFA_ERR_INVALID_ARGUMENT;
+template <int IKS, int NW, int KB, bool CTX = false, int RING = k8h::kRing>
+static k8h::KernelFn f16_instance(bool inverse) {
+    return inverse ? k8h::rqs_resnet_f16_kernel<true, IKS, NW, KB, CTX, RING> : k8h::rqs_resnet_f16_kernel<false, IKS, NW, KB, CTX, RING>;
+}
+
+// The instance of a launch, one ordered decision: the diagnostic instances, a context or an activation or a bin count
+// beyond the tuned 8 / 10 bins with ReLU (their own translation units), then the tuned instances (the elastic stream
+// of the experiment builds, a context: init_ks 4).
+static k8h::KernelFn f16_kernel(bool inverse, int init_ks, int waves, int K, int activation, bool with_ctx, bool elastic,
+                                bool dbg) {
+    const bool tuned = (K == 8 || K == 10) && activation == NFA_ACTIVATION_RELU;
+    if (dbg) return k8h::debug_kernel(inverse, init_ks, waves);
+    if (with_ctx && !tuned) {   // (round 5: rqs_resnet_f16_ctx_{a,b}.hip)
+        const k8h::KernelFn kern = k8h::context_kernel_a(K, activation, inverse, waves);
+        return kern ? kern : k8h::context_kernel_b(K, activation, inverse, waves);
+    }
+    if (activation != NFA_ACTIVATION_RELU) return k8h::activation_kernel(activation, K, inverse, init_ks, waves);
+    if (!tuned)
+        return K <= 9 ? k8h::bins_kernel_a(K, inverse, init_ks, waves)
+               : K <= 16 ? k8h::bins_kernel_b(K, inverse, init_ks, waves) : k8h::bins_kernel_c(K, inverse, init_ks, waves);
+#ifdef NFA_K8H_ELASTIC   // (experiment builds only: measured 3 % slower than the rigid stream, profiles/r3/k8h_elastic_stream.txt)
+    if (elastic)
+        return init_ks == 4 ? f16_instance<4, 8, 8, false, k8h::kRingElastic>(inverse)
+                            : f16_instance<2, 8, 8, false, k8h::kRingElastic>(inverse);
+#else
+    (void)elastic;
+#endif
+    const bool k10 = K == 10;
+    if (with_ctx)
+        return waves == 8 ? (k10 ? f16_instance<4, 8, 10, true>(inverse) : f16_instance<4, 8, 8, true>(inverse))
+                          : (k10 ? f16_instance<4, 4, 10, true>(inverse) : f16_instance<4, 4, 8, true>(inverse));
+    if (waves == 8)
+        return init_ks == 4 ? (k10 ? f16_instance<4, 8, 10>(inverse) : f16_instance<4, 8, 8>(inverse))
+                            : (k10 ? f16_instance<2, 8, 10>(inverse) : f16_instance<2, 8, 8>(inverse));
+    return init_ks == 4 ? (k10 ? f16_instance<4, 4, 10>(inverse) : f16_instance<4, 4, 8>(inverse))
+                        : (k10 ? f16_instance<2, 4, 10>(inverse) : f16_instance<2, 4, 8>(inverse));
+}
+
+static int launch_f16(const LayerCall& c, int32_t* dbg_bins = nullptr, float* dbg_logits = nullptr) {
     k8h::Args a;
-    int rc = make_dev_spec(spec, &a.sp);
+    int activation = 0;
+    int rc = check_layer_call(c, {NFA_FLAG_ACTIVATION_MASK, true, false, true}, &a.sp, &activation);
     if (rc != NFA_OK) return rc;
-    if (a.sp.beta != 1.0f) return NFA_ERR_UNSUPPORTED;
     // bin counts: 8 and 10 have their own final-layer loops; 2 .. 16 and 20, 24, 32 otherwise
-    const bool any_bins = a.sp.K != 8 && a.sp.K != 10;
+    const bool any_bins = a.sp.K != 8 && a.sp.K != 10, with_ctx = c.context_features > 0;
     // activations other than ReLU: the two tuned bin counts (with or, round 5, without a context)
     if (activation != NFA_ACTIVATION_RELU && any_bins) return NFA_ERR_UNSUPPORTED;
-    const bool bins_served = (a.sp.K >= 2 && a.sp.K <= 16) || a.sp.K == 20 || a.sp.K == 24 || a.sp.K == 32;
-    if (!bins_served || !a.sp.linear || hidden_features != 128 || (num_transform & 3) != 0 || num_transform > 64 ||
-        num_identity > 64 || features > 128 || (features & 3) != 0 || (batch & 127) != 0 || num_blocks > 64 ||
-        num_layers > 4096)
-        return NFA_ERR_UNSUPPORTED;
-    const bool with_ctx = context_features > 0;
-    if (context_features < 0) return NFA_ERR_INVALID_ARGUMENT;
     // with a context: two identity k-steps + two context k-steps in the initial layer
-    if (with_ctx && (context_features > 32 || num_identity > 32)) return NFA_ERR_UNSUPPORTED;
-    // rows of the final layer per transformed feature: 23 logits padded to 24 (8 bins: two features share three
-    // tiles), otherwise 3 K - 1 padded to whole 16-row lane-half shares
-    const int rows_per_feature = a.sp.K == 8 ? 24 : 16 * ((3 * a.sp.K - 1 + 15) / 16);
-    const int param_words = k8h::kTabWords + (k8h::kHdr + 128) * (1 + (with_ctx ? 3 : 2) * num_blocks) + k8h::kHdr +
-                            num_transform * rows_per_feature;
-    if (param_stages * 2048 < param_words || param_stages > 4) return NFA_ERR_INVALID_ARGUMENT;
-    if (batch == 0) return NFA_OK;
-    if (!inputs || !stream_packed || !final_positions || !logabsdet || !redo_blocks ||
-        (!outputs && !(flags & NFA_FLAG_SKIP_OUTPUTS)) || (with_ctx && !context))
-        return NFA_ERR_INVALID_ARGUMENT;
-    a.ctx = with_ctx ? context : nullptr;
-    a.ce = context_features;
-    a.dbg_bins = dbg_bins;
-    a.dbg_logits = dbg_logits;
+    if (with_ctx && (c.context_features > 32 || c.num_identity > 32)) return NFA_ERR_UNSUPPORTED;
+    const int param_words = k8h::param_words(c, a.sp.K);
+    if (!param_words) return NFA_ERR_INVALID_ARGUMENT;
+    if (c.batch == 0) return NFA_OK;
+    if (!layer_buffers_given(c) || !c.redo) return NFA_ERR_INVALID_ARGUMENT;
     // the diagnostic instances (nfa_rqs_flow_resnet_f16x2_bins_f32): the bench's kernel family only
     if (dbg_bins && (a.sp.K != 8 || with_ctx || activation != NFA_ACTIVATION_RELU)) return NFA_ERR_UNSUPPORTED;
-    a.normal = (flags & NFA_FLAG_STANDARD_NORMAL_LOG_PROB) ? 1 : 0;
-    a.skip_out = (flags & NFA_FLAG_SKIP_OUTPUTS) ? 1 : 0;
-    a.Ds = density_columns(flags, features);
-    if (a.Ds < 1) return NFA_ERR_INVALID_ARGUMENT;
-    a.log_z = standard_normal_log_z(a.Ds);
-    a.x = inputs;
-    a.w = reinterpret_cast<const vec4f*>(stream_packed);
-    a.final_tab = final_positions;
-    a.out = outputs;
-    a.lad = logabsdet;
-    a.redo = redo_blocks;
-    a.status = status;
-    a.batch = batch;
-    a.D = features;
-    a.dt = num_transform;
-    a.di = num_identity;
-    a.num_blocks = num_blocks;
-    a.num_layers = num_layers;
-    a.param_stages = param_stages;
-    a.param_words = param_words;
-    const int init_ks = (with_ctx || num_identity > 32) ? 4 : 2;
-    a.num_stages = param_stages + init_ks / 2 + (with_ctx ? 9 : 8) * num_blocks + num_transform * rows_per_feature / 32;
-    a.accumulate = (flags & NFA_FLAG_ACCUMULATE_LOGABSDET) ? 1 : 0;
+    rc = k8h::fill_args(a, c, param_words, dbg_bins, dbg_logits);
+    if (rc != NFA_OK) return rc;
+    const int init_ks = (with_ctx || c.num_identity > 32) ? 4 : 2;
+    a.num_stages = c.param_stages + init_ks / 2 + (with_ctx ? 9 : 8) * c.num_blocks +
+                   c.num_transform * spline_rows_per_feature(a.sp.K) / 32;
     a.trace = g_k7_trace;
     // workgroups of eight waves (256 rows, one per CU, one weight stream per CU) when the batch gives
     // every CU one; otherwise four waves (128 rows)
     const int cus = device_cu_count();
     static const int force_nw = getenv("NFA_K8H_WAVES") ? atoi(getenv("NFA_K8H_WAVES")) : 0;
     static const int force_ring = getenv("NFA_K8H_RING") ? atoi(getenv("NFA_K8H_RING")) : 0;   // 5: elastic stream (experiment, slower)
-    int nw = ((batch & 255) == 0 && (batch >> 8) >= cus) ? 8 : 4;
-    if (force_nw == 4 || (force_nw == 8 && (batch & 255) == 0)) nw = force_nw;
+    int nw = ((c.batch & 255) == 0 && (c.batch >> 8) >= cus) ? 8 : 4;
+    if (force_nw == 4 || (force_nw == 8 && (c.batch & 255) == 0)) nw = force_nw;
     const size_t lds_static = 1024;   // s_final, s_bad, s_sync (rounded up)
     const size_t lds_cap = 160 * 1024 - lds_static;
     auto lds_for = [&](int n, int ring) {
-        return (size_t)ring * k8h::kStageVec4 * 16 + (size_t)n * features * k8h::kRowPad * sizeof(float) +
+        return (size_t)ring * k8h::kStageVec4 * 16 + (size_t)n * c.features * k8h::kRowPad * sizeof(float) +
                (size_t)2 * ((param_words + 3) & ~3) * sizeof(float);
     };
     if (lds_for(nw, k8h::kRing) > lds_cap) nw = 4;
@@ -155,90 +143,17 @@ static int launch_f16(const float* inputs, const float* context, int32_t context
     (void)force_ring;
 #endif
     const size_t lds_launch = lds_for(nw, elastic ? k8h::kRingElastic : k8h::kRing);
-    int64_t blocks = batch / (32 * nw);
+    int64_t blocks = c.batch / (32 * nw);
     const int64_t per_cu = (nw == 4 && lds_launch + 2048 <= 80 * 1024) ? 2 : 1;
     const int64_t cap = (int64_t)cus * per_cu;
     if (blocks > cap) blocks = cap;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    profile_next_launch(&e0, &e1);
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)blocks), block(nw * kWave);
-    const bool inv = (flags & NFA_FLAG_INVERSE) != 0;
-    void (*kern)(const k8h::Args) = nullptr;
-    int which = with_ctx ? 16 + (inv ? 1 : 0) + (nw == 8 ? 2 : 0) + (a.sp.K == 10 ? 4 : 0)
-                         : (inv ? 1 : 0) + (init_ks == 4 ? 2 : 0) + (nw == 8 ? 4 : 0) + (a.sp.K == 10 ? 8 : 0);
-    if (elastic) which = 24 + (inv ? 1 : 0) + (init_ks == 4 ? 2 : 0);
-    if (any_bins) which = 32 + (a.sp.K - 2) * 8 + (inv ? 1 : 0) + (init_ks == 4 ? 2 : 0) + (nw == 8 ? 4 : 0);
-    constexpr int kWhichContext = 32 + 31 * 8 + 3 * 16 + 8;   // (behind the diagnostic instances' eight)
-    const bool more_ctx = with_ctx && (any_bins || activation != NFA_ACTIVATION_RELU);
-    if (dbg_bins) {
-        which = 32 + 31 * 8 + 3 * 16 + (inv ? 1 : 0) + (init_ks == 4 ? 2 : 0) + (nw == 8 ? 4 : 0);
-        kern = k8h::debug_kernel(inv, init_ks, nw);
-        if (!kern) return NFA_ERR_UNSUPPORTED;
-    } else if (more_ctx) {
-        // a context beyond 8 / 10 bins with ReLU (round 5): rqs_resnet_f16_ctx_{a,b}.hip
-        which = kWhichContext + (any_bins ? (a.sp.K - 2) * 4 : 31 * 4 + (activation - 1) * 8 + (a.sp.K == 10 ? 4 : 0)) +
-                (inv ? 1 : 0) + (nw == 8 ? 2 : 0);
-        kern = k8h::context_kernel_a(a.sp.K, activation, inv, nw);
-        if (!kern) kern = k8h::context_kernel_b(a.sp.K, activation, inv, nw);
-        if (!kern) return NFA_ERR_UNSUPPORTED;
-    } else if (activation != NFA_ACTIVATION_RELU) {
-        which = 32 + 31 * 8 + (activation - 1) * 16 + (a.sp.K == 10 ? 8 : 0) + (inv ? 1 : 0) + (init_ks == 4 ? 2 : 0) + (nw == 8 ? 4 : 0);
-        kern = k8h::activation_kernel(activation, a.sp.K, inv, init_ks, nw);
-    } else if (any_bins) {
-        kern = a.sp.K <= 9 ? k8h::bins_kernel_a(a.sp.K, inv, init_ks, nw)
-               : a.sp.K <= 16 ? k8h::bins_kernel_b(a.sp.K, inv, init_ks, nw) : k8h::bins_kernel_c(a.sp.K, inv, init_ks, nw);
-    }
-    if (dbg_bins || more_ctx) {
-    } else if (activation != NFA_ACTIVATION_RELU || any_bins) {
-        if (!kern) return NFA_ERR_UNSUPPORTED;
-    }
-    else switch (which) {
-#ifdef NFA_K8H_ELASTIC   // (experiment builds only: measured 3 % slower than the rigid stream, profiles/r3/k8h_elastic_stream.txt)
-        case 24: kern = k8h::rqs_resnet_f16_kernel<false, 2, 8, 8, false, k8h::kRingElastic>; break;
-        case 25: kern = k8h::rqs_resnet_f16_kernel<true, 2, 8, 8, false, k8h::kRingElastic>; break;
-        case 26: kern = k8h::rqs_resnet_f16_kernel<false, 4, 8, 8, false, k8h::kRingElastic>; break;
-        case 27: kern = k8h::rqs_resnet_f16_kernel<true, 4, 8, 8, false, k8h::kRingElastic>; break;
-#endif
-        case 16: kern = k8h::rqs_resnet_f16_kernel<false, 4, 4, 8, true>; break;
-        case 17: kern = k8h::rqs_resnet_f16_kernel<true, 4, 4, 8, true>; break;
-        case 18: kern = k8h::rqs_resnet_f16_kernel<false, 4, 8, 8, true>; break;
-        case 19: kern = k8h::rqs_resnet_f16_kernel<true, 4, 8, 8, true>; break;
-        case 20: kern = k8h::rqs_resnet_f16_kernel<false, 4, 4, 10, true>; break;
-        case 21: kern = k8h::rqs_resnet_f16_kernel<true, 4, 4, 10, true>; break;
-        case 22: kern = k8h::rqs_resnet_f16_kernel<false, 4, 8, 10, true>; break;
-        case 23: kern = k8h::rqs_resnet_f16_kernel<true, 4, 8, 10, true>; break;
-        case 0: kern = k8h::rqs_resnet_f16_kernel<false, 2, 4>; break;
-        case 1: kern = k8h::rqs_resnet_f16_kernel<true, 2, 4>; break;
-        case 2: kern = k8h::rqs_resnet_f16_kernel<false, 4, 4>; break;
-        case 3: kern = k8h::rqs_resnet_f16_kernel<true, 4, 4>; break;
-        case 4: kern = k8h::rqs_resnet_f16_kernel<false, 2, 8>; break;
-        case 5: kern = k8h::rqs_resnet_f16_kernel<true, 2, 8>; break;
-        case 6: kern = k8h::rqs_resnet_f16_kernel<false, 4, 8>; break;
-        case 7: kern = k8h::rqs_resnet_f16_kernel<true, 4, 8>; break;
-        case 8: kern = k8h::rqs_resnet_f16_kernel<false, 2, 4, 10>; break;
-        case 9: kern = k8h::rqs_resnet_f16_kernel<true, 2, 4, 10>; break;
-        case 10: kern = k8h::rqs_resnet_f16_kernel<false, 4, 4, 10>; break;
-        case 11: kern = k8h::rqs_resnet_f16_kernel<true, 4, 4, 10>; break;
-        case 12: kern = k8h::rqs_resnet_f16_kernel<false, 2, 8, 10>; break;
-        case 13: kern = k8h::rqs_resnet_f16_kernel<true, 2, 8, 10>; break;
-        case 14: kern = k8h::rqs_resnet_f16_kernel<false, 4, 8, 10>; break;
-        default: kern = k8h::rqs_resnet_f16_kernel<true, 4, 8, 10>; break;
-    }
+    const bool inv = (c.flags & NFA_FLAG_INVERSE) != 0;
+    const k8h::KernelFn kern = f16_kernel(inv, init_ks, nw, a.sp.K, activation, with_ctx, elastic, dbg_bins);
+    if (!kern) return NFA_ERR_UNSUPPORTED;
     static const char* const act_names[] = {"relu", "leaky_relu", "elu", "tanh"};
     note_layer_kernel("k8h::rqs_resnet_f16_kernel<inverse=%d, init_ks=%d, waves=%d, K=%d, ctx=%d, ring=%d, act=%s>", inv ? 1 : 0,
                       init_ks, nw, a.sp.K, with_ctx ? 1 : 0, elastic ? k8h::kRingElastic : k8h::kRing, act_names[activation]);
-    if (lds_launch > 64 * 1024) {
-        static unsigned long long raised[32 + 31 * 8 + 3 * 16 + 8 + 31 * 4 + 3 * 8] = {};   // device masks (raise_dynamic_lds)
-        {
-            const int rc_lds = raise_dynamic_lds((const void*)kern, &raised[which], (int)lds_cap);
-            if (rc_lds != NFA_OK) return rc_lds;
-        }
-    }
-    if (e0) hipExtLaunchKernelGGL(kern, grid, block, lds_launch, st, e0, e1, 0, a);
-    else hipLaunchKernelGGL(kern, grid, block, lds_launch, st, a);
-    NFA_HIP_CHECK(hipGetLastError());
-    return NFA_OK;
+    return launch_kernel(kern, dim3((unsigned)blocks), dim3(nw * kWave), lds_launch, (hipStream_t)c.stream, a, (int)lds_cap);
 }
 
 extern "C" int nfa_rqs_flow_resnet_f16x2_f32(const float* inputs, const void* stream_packed, int32_t param_stages,
@@ -247,9 +162,9 @@ extern "C" int nfa_rqs_flow_resnet_f16x2_f32(const float* inputs, const void* st
                                              int32_t features, int32_t num_transform, int32_t num_identity,
                                              int32_t hidden_features, int32_t num_blocks,
                                              const nfa_rqs_spec* spec, int32_t flags, void* stream) {
-    return launch_f16(inputs, nullptr, 0, stream_packed, param_stages, final_positions, num_layers, outputs, logabsdet,
-                      redo_blocks, status, batch, features, num_transform, num_identity, hidden_features, num_blocks,
-                      spec, flags, stream);
+    return launch_f16({inputs, stream_packed, nullptr, final_positions, num_layers, outputs, logabsdet, redo_blocks, status,
+                       batch, features, num_transform, num_identity, hidden_features, num_blocks, spec, flags, stream,
+                       nullptr, 0, param_stages});
 }
 
 // the same launch through the diagnostic instances: bin_idx [batch, num_transform] receives the bin every evaluation of
@@ -261,9 +176,10 @@ extern "C" int nfa_rqs_flow_resnet_f16x2_bins_f32(const float* inputs, const voi
                                                   int32_t hidden_features, int32_t num_blocks,
                                                   const nfa_rqs_spec* spec, int32_t flags, void* stream, int32_t* bin_idx) {
     if (!bin_idx) return NFA_ERR_INVALID_ARGUMENT;
-    return launch_f16(inputs, nullptr, 0, stream_packed, param_stages, final_positions, num_layers, outputs, logabsdet,
-                      redo_blocks, status, batch, features, num_transform, num_identity, hidden_features, num_blocks,
-                      spec, flags, stream, bin_idx);
+    return launch_f16({inputs, stream_packed, nullptr, final_positions, num_layers, outputs, logabsdet, redo_blocks, status,
+                       batch, features, num_transform, num_identity, hidden_features, num_blocks, spec, flags, stream,
+                       nullptr, 0, param_stages},
+                      bin_idx);
 }
 
 // the diagnostic instances once more, with the logits of the LAST layer (the final Linear's accumulators x kappa: the
@@ -276,9 +192,10 @@ extern "C" int nfa_rqs_flow_resnet_f16x2_logits_f32(const float* inputs, const v
                                                     const nfa_rqs_spec* spec, int32_t flags, void* stream, int32_t* bin_idx,
                                                     float* logits) {
     if (!bin_idx || !logits) return NFA_ERR_INVALID_ARGUMENT;
-    return launch_f16(inputs, nullptr, 0, stream_packed, param_stages, final_positions, num_layers, outputs, logabsdet,
-                      redo_blocks, status, batch, features, num_transform, num_identity, hidden_features, num_blocks,
-                      spec, flags, stream, bin_idx, logits);
+    return launch_f16({inputs, stream_packed, nullptr, final_positions, num_layers, outputs, logabsdet, redo_blocks, status,
+                       batch, features, num_transform, num_identity, hidden_features, num_blocks, spec, flags, stream,
+                       nullptr, 0, param_stages},
+                      bin_idx, logits);
 }
 
 extern "C" int nfa_rqs_flow_resnet_context_f16x2_f32(const float* inputs, const float* context,
@@ -290,7 +207,7 @@ extern "C" int nfa_rqs_flow_resnet_context_f16x2_f32(const float* inputs, const 
                                                      int32_t hidden_features, int32_t num_blocks,
                                                      const nfa_rqs_spec* spec, int32_t flags, void* stream) {
     if (context_features < 1) return NFA_ERR_INVALID_ARGUMENT;
-    return launch_f16(inputs, context, context_features, stream_packed, param_stages, final_positions, num_layers,
-                      outputs, logabsdet, redo_blocks, status, batch, features, num_transform, num_identity,
-                      hidden_features, num_blocks, spec, flags, stream);
+    return launch_f16({inputs, stream_packed, nullptr, final_positions, num_layers, outputs, logabsdet, redo_blocks, status,
+                       batch, features, num_transform, num_identity, hidden_features, num_blocks, spec, flags, stream,
+                       context, context_features, param_stages});
 }

@@ -974,7 +974,6 @@ __global__ void __launch_bounds__(NW * kWave, 2) rqs_resnet_f16_kernel(const Arg
 
 namespace nfa {
 namespace k8h {
-typedef void (*KernelFn)(const Args);
 // the instances of the other translation units: nullptr when the unit does not hold the combination
 KernelFn bins_kernel_a(int K, bool inverse, int init_ks, int waves);     // 2 .. 7, 9 bins
 KernelFn bins_kernel_b(int K, bool inverse, int init_ks, int waves);     // 11 .. 16 bins

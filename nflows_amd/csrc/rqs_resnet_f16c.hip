@@ -559,64 +559,36 @@ __global__ void zero_words_kernel(int32_t* p, int n) {
 
 using namespace nfa;
 
+template <int IKS, int RT, int OCC>
+static k8h::KernelFn f16c_instance(bool inverse) {
+    return inverse ? k8c::rqs_resnet_f16c_kernel<true, IKS, RT, OCC> : k8c::rqs_resnet_f16c_kernel<false, IKS, RT, OCC>;
+}
+
 extern "C" int nfa_rqs_flow_resnet_f16x2_colsplit_f32(const float* inputs, const void* stream_packed, int32_t param_stages,
                                                       const int32_t* final_positions, int32_t num_layers, float* outputs,
                                                       float* logabsdet, int32_t* redo_blocks, int32_t* status, int64_t batch,
                                                       int32_t features, int32_t num_transform, int32_t num_identity,
                                                       int32_t hidden_features, int32_t num_blocks, const nfa_rqs_spec* spec,
                                                       int32_t flags, void* stream) {
-    if (flags & ~(NFA_FLAG_INVERSE | NFA_FLAG_ACCUMULATE_LOGABSDET | NFA_FLAG_STANDARD_NORMAL_LOG_PROB |
-                  NFA_FLAG_SKIP_OUTPUTS | NFA_FLAG_PAD_COLUMNS_MASK))
-        return NFA_ERR_INVALID_ARGUMENT;
-    if (!density_flags_valid(flags)) return NFA_ERR_INVALID_ARGUMENT;
-    if (batch < 0 || features < 1 || num_transform < 1 || num_identity < 1 || num_transform > features ||
-        num_identity > features || num_blocks < 0 || num_layers < 1 || param_stages < 1)
-        return NFA_ERR_INVALID_ARGUMENT;
+    const LayerCall c{inputs, stream_packed, nullptr, final_positions, num_layers, outputs, logabsdet, redo_blocks, status,
+                      batch, features, num_transform, num_identity, hidden_features, num_blocks, spec, flags, stream,
+                      nullptr, 0, param_stages};
     k8h::Args a;
-    int rc = make_dev_spec(spec, &a.sp);
+    int activation = 0;
+    int rc = check_layer_call(c, {0, false, false, true}, &a.sp, &activation);
     if (rc != NFA_OK) return rc;
-    if (a.sp.beta != 1.0f) return NFA_ERR_UNSUPPORTED;
-    if (a.sp.K != 8 || !a.sp.linear || hidden_features != 128 || (num_transform & 3) != 0 || num_transform > 64 ||
-        num_identity > 64 || features > 128 || (features & 3) != 0 || (batch & 127) != 0 || num_blocks > 64 ||
-        num_layers > 4096)
-        return NFA_ERR_UNSUPPORTED;
-    const int param_words = k8h::kTabWords + (k8h::kHdr + 128) * (1 + 2 * num_blocks) + k8h::kHdr + num_transform * 24;
-    if (param_stages * 2048 < param_words || param_stages > 4) return NFA_ERR_INVALID_ARGUMENT;
+    const int param_words = k8h::param_words(c, 8);
+    if (!param_words) return NFA_ERR_INVALID_ARGUMENT;
     if (param_stages != 1) return NFA_ERR_UNSUPPORTED;   // (the next layer's words travel in two registers per thread)
     if (batch == 0) return NFA_OK;
-    if (!inputs || !stream_packed || !final_positions || !logabsdet || !redo_blocks ||
-        (!outputs && !(flags & NFA_FLAG_SKIP_OUTPUTS)))
-        return NFA_ERR_INVALID_ARGUMENT;
-    a.ctx = nullptr;
-    a.ce = 0;
-    a.dbg_bins = nullptr;
-    a.dbg_logits = nullptr;
-    a.normal = (flags & NFA_FLAG_STANDARD_NORMAL_LOG_PROB) ? 1 : 0;
-    a.skip_out = (flags & NFA_FLAG_SKIP_OUTPUTS) ? 1 : 0;
-    a.Ds = density_columns(flags, features);
-    if (a.Ds < 1) return NFA_ERR_INVALID_ARGUMENT;
-    a.log_z = standard_normal_log_z(a.Ds);
-    a.x = inputs;
-    a.w = reinterpret_cast<const vec4f*>(stream_packed);
-    a.final_tab = final_positions;
-    a.out = outputs;
-    a.lad = logabsdet;
-    a.redo = redo_blocks;
-    a.status = status;
-    a.batch = batch;
-    a.D = features;
-    a.dt = num_transform;
-    a.di = num_identity;
-    a.num_blocks = num_blocks;
-    a.num_layers = num_layers;
-    a.param_stages = param_stages;
-    a.param_words = param_words;
+    if (!layer_buffers_given(c) || !redo_blocks) return NFA_ERR_INVALID_ARGUMENT;
+    rc = k8h::fill_args(a, c, param_words, nullptr, nullptr);
+    if (rc != NFA_OK) return rc;
     const int init_ks = num_identity > 32 ? 2 : 1;
     // stages per layer: parameters, one per k-step of the initial layer, four per hidden Linear, twelve per round of four
     // groups of four transformed features
     const int rounds = (num_transform / 4 + 3) / 4;
     a.num_stages = param_stages + init_ks + 8 * num_blocks + 12 * rounds;
-    a.accumulate = (flags & NFA_FLAG_ACCUMULATE_LOGABSDET) ? 1 : 0;
     a.trace = nullptr;
 #ifdef NFA_K8C_TRACE
     static unsigned long long* trace_dev = nullptr;
@@ -637,34 +609,15 @@ extern "C" int nfa_rqs_flow_resnet_f16x2_colsplit_f32(const float* inputs, const
     if (lds > lds_cap) return NFA_ERR_UNSUPPORTED;
     int64_t blocks = batch / k8c::rows_of(RT);
     if (blocks > (int64_t)cus * occ) blocks = (int64_t)cus * occ;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    profile_next_launch(&e0, &e1);
     hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)blocks), block(k8c::kThreads);
     const bool inv = (flags & NFA_FLAG_INVERSE) != 0;
-    void (*kern)(const k8h::Args) = nullptr;
-    const int which = (inv ? 1 : 0) + (init_ks == 2 ? 2 : 0) + (RT == 2 ? 4 : 0);
-    switch (which) {
-        case 0: kern = k8c::rqs_resnet_f16c_kernel<false, 1, 4, 1>; break;
-        case 1: kern = k8c::rqs_resnet_f16c_kernel<true, 1, 4, 1>; break;
-        case 2: kern = k8c::rqs_resnet_f16c_kernel<false, 2, 4, 1>; break;
-        case 3: kern = k8c::rqs_resnet_f16c_kernel<true, 2, 4, 1>; break;
-        case 4: kern = k8c::rqs_resnet_f16c_kernel<false, 1, 2, 2>; break;
-        case 5: kern = k8c::rqs_resnet_f16c_kernel<true, 1, 2, 2>; break;
-        case 6: kern = k8c::rqs_resnet_f16c_kernel<false, 2, 2, 2>; break;
-        default: kern = k8c::rqs_resnet_f16c_kernel<true, 2, 2, 2>; break;
-    }
+    const k8h::KernelFn kern = RT == 2 ? (init_ks == 2 ? f16c_instance<2, 2, 2>(inv) : f16c_instance<1, 2, 2>(inv))
+                                       : (init_ks == 2 ? f16c_instance<2, 4, 1>(inv) : f16c_instance<1, 4, 1>(inv));
     note_layer_kernel("k8c::rqs_resnet_f16c_kernel<inverse=%d, init_ks=%d, waves=4, rows=%d, per_cu=%d, K=8>", inv ? 1 : 0, init_ks, 16 * RT, occ);
     hipLaunchKernelGGL(k8c::zero_words_kernel, dim3((unsigned)((batch / 128 + 255) / 256)), dim3(256), 0, st, redo_blocks,
                        (int)(batch / 128));
-    if (lds > 64 * 1024) {
-        static unsigned long long raised[8] = {};   // device masks (raise_dynamic_lds)
-        const int rc_lds = raise_dynamic_lds((const void*)kern, &raised[which], (int)lds_cap);
-        if (rc_lds != NFA_OK) return rc_lds;
-    }
-    if (e0) hipExtLaunchKernelGGL(kern, grid, block, lds, st, e0, e1, 0, a);
-    else hipLaunchKernelGGL(kern, grid, block, lds, st, a);
-    NFA_HIP_CHECK(hipGetLastError());
+    rc = launch_kernel(kern, dim3((unsigned)blocks), dim3(k8c::kThreads), lds, st, a, (int)lds_cap);
+    if (rc != NFA_OK) return rc;
 #ifdef NFA_K8C_TRACE
     {
         static int calls = 0;

@@ -559,119 +559,63 @@ __global__ void zero_words_kernel(int32_t* p, int n) {
 
 using namespace nfa;
 
-static int launch_tile16(const float* inputs, const void* stream_packed, int32_t param_stages,
-                         const int32_t* final_positions, int32_t num_layers, float* outputs, float* logabsdet,
-                         int32_t* redo_blocks, int32_t* status, int64_t batch, int32_t features, int32_t num_transform,
-                         int32_t num_identity, int32_t hidden_features, int32_t num_blocks, const nfa_rqs_spec* spec,
-                         int32_t flags, void* stream, int32_t* dbg_bins) {
-    if (flags & ~(NFA_FLAG_INVERSE | NFA_FLAG_ACCUMULATE_LOGABSDET | NFA_FLAG_STANDARD_NORMAL_LOG_PROB |
-                  NFA_FLAG_SKIP_OUTPUTS | NFA_FLAG_PAD_COLUMNS_MASK))
-        return NFA_ERR_INVALID_ARGUMENT;
-    if (!density_flags_valid(flags)) return NFA_ERR_INVALID_ARGUMENT;
-    if (batch < 0 || features < 1 || num_transform < 1 || num_identity < 1 || num_transform > features ||
-        num_identity > features || num_blocks < 0 || num_layers < 1 || param_stages < 1)
-        return NFA_ERR_INVALID_ARGUMENT;
+template <int IKS, int RING, int NW = k8s::kWavesPerGroup, bool DBG = false>
+static k8h::KernelFn f16s_instance(bool inverse) {
+    return inverse ? k8s::rqs_resnet_f16s_kernel<true, IKS, RING, NW, DBG> : k8s::rqs_resnet_f16s_kernel<false, IKS, RING, NW, DBG>;
+}
+
+// The instance of a launch: the diagnostic instances (d_i <= 32), the 64-row form (four waves, ring 4), the 128-row form
+// with ring 7 or 4.
+static k8h::KernelFn f16s_kernel(bool inverse, int init_ks, bool half, int ring, bool dbg) {
+    if (dbg) return half ? f16s_instance<1, 4, 4, true>(inverse) : f16s_instance<1, 7, k8s::kWavesPerGroup, true>(inverse);
+    if (half) return init_ks == 2 ? f16s_instance<2, 4, 4>(inverse) : f16s_instance<1, 4, 4>(inverse);
+    if (ring == 7) return init_ks == 2 ? f16s_instance<2, 7>(inverse) : f16s_instance<1, 7>(inverse);
+    return init_ks == 2 ? f16s_instance<2, 4>(inverse) : f16s_instance<1, 4>(inverse);
+}
+
+static int launch_tile16(const LayerCall& c, int32_t* dbg_bins) {
     k8h::Args a;
-    int rc = make_dev_spec(spec, &a.sp);
+    int activation = 0;
+    int rc = check_layer_call(c, {0, false, false, true}, &a.sp, &activation);
     if (rc != NFA_OK) return rc;
-    if (a.sp.beta != 1.0f) return NFA_ERR_UNSUPPORTED;
-    if (a.sp.K != 8 || !a.sp.linear || hidden_features != 128 || (num_transform & 3) != 0 || num_transform > 64 ||
-        num_identity > 64 || features > 128 || (features & 3) != 0 || (batch & 127) != 0 || num_blocks > 64 ||
-        num_layers > 4096)
-        return NFA_ERR_UNSUPPORTED;
-    const int param_words = k8h::kTabWords + (k8h::kHdr + 128) * (1 + 2 * num_blocks) + k8h::kHdr + num_transform * 24;
-    if (param_stages * 2048 < param_words || param_stages > 4) return NFA_ERR_INVALID_ARGUMENT;
-    if (batch == 0) return NFA_OK;
-    if (!inputs || !stream_packed || !final_positions || !logabsdet || !redo_blocks ||
-        (!outputs && !(flags & NFA_FLAG_SKIP_OUTPUTS)))
-        return NFA_ERR_INVALID_ARGUMENT;
-    a.ctx = nullptr;
-    a.ce = 0;
-    a.dbg_bins = dbg_bins;
-    a.dbg_logits = nullptr;
-    a.normal = (flags & NFA_FLAG_STANDARD_NORMAL_LOG_PROB) ? 1 : 0;
-    a.skip_out = (flags & NFA_FLAG_SKIP_OUTPUTS) ? 1 : 0;
-    a.Ds = density_columns(flags, features);
-    if (a.Ds < 1) return NFA_ERR_INVALID_ARGUMENT;
-    a.log_z = standard_normal_log_z(a.Ds);
-    a.x = inputs;
-    a.w = reinterpret_cast<const vec4f*>(stream_packed);
-    a.final_tab = final_positions;
-    a.out = outputs;
-    a.lad = logabsdet;
-    a.redo = redo_blocks;
-    a.status = status;
-    a.batch = batch;
-    a.D = features;
-    a.dt = num_transform;
-    a.di = num_identity;
-    a.num_blocks = num_blocks;
-    a.num_layers = num_layers;
-    a.param_stages = param_stages;
-    a.param_words = param_words;
-    const int init_ks = num_identity > 32 ? 2 : 1;
+    const int param_words = k8h::param_words(c, 8);
+    if (!param_words) return NFA_ERR_INVALID_ARGUMENT;
+    if (c.batch == 0) return NFA_OK;
+    if (!layer_buffers_given(c) || !c.redo) return NFA_ERR_INVALID_ARGUMENT;
+    rc = k8h::fill_args(a, c, param_words, dbg_bins, nullptr);
+    if (rc != NFA_OK) return rc;
+    const int init_ks = c.num_identity > 32 ? 2 : 1;
     // stages per layer: parameters, one per k-step of the initial layer, four per hidden Linear, three per group
     // of four transformed features -- the same count as K8h's stream
-    a.num_stages = param_stages + (init_ks == 2 ? 2 : 1) + 8 * num_blocks + num_transform * 24 / 32;
-    a.accumulate = (flags & NFA_FLAG_ACCUMULATE_LOGABSDET) ? 1 : 0;
+    a.num_stages = c.param_stages + (init_ks == 2 ? 2 : 1) + 8 * c.num_blocks + c.num_transform * 24 / 32;
     a.trace = nullptr;
     const size_t lds_cap = 160 * 1024 - 1024;
     const int cus = device_cu_count();
     // fewer 64-row blocks than CUs: four-wave workgroups (one wave per SIMD) spread the batch over twice the CUs
     static const int half_env = getenv("NFA_K8S_HALF") ? atoi(getenv("NFA_K8S_HALF")) : 1;
-    const bool half = half_env == 2 || (half_env == 1 && batch / 64 <= cus);
+    const bool half = half_env == 2 || (half_env == 1 && c.batch / 64 <= cus);
     const int nw = half ? 4 : k8s::kWavesPerGroup;
     auto lds_for = [&](int ring) {
-        return (size_t)ring * k8h::kStageVec4 * 16 + (size_t)nw * features * k8s::kRowPad16 * sizeof(float) +
+        return (size_t)ring * k8h::kStageVec4 * 16 + (size_t)nw * c.features * k8s::kRowPad16 * sizeof(float) +
                (size_t)2 * ((param_words + 3) & ~3) * sizeof(float);
     };
     static const int ring_env = getenv("NFA_K8S_RING") ? atoi(getenv("NFA_K8S_RING")) : 7;
     const int ring = (!half && ring_env == 7 && lds_for(7) <= lds_cap) ? 7 : 4;
     const size_t lds_launch = lds_for(ring);
     if (lds_launch > lds_cap) return NFA_ERR_UNSUPPORTED;
-    int64_t blocks = batch / (16 * nw);
+    // the diagnostic instances: d_i <= 32, the two workgroup forms the launcher picks by itself
+    if (dbg_bins && (init_ks != 1 || (!half && ring != 7))) return NFA_ERR_UNSUPPORTED;
+    int64_t blocks = c.batch / (16 * nw);
     if (blocks > cus) blocks = cus;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    profile_next_launch(&e0, &e1);
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)blocks), block(nw * kWave);
-    const bool inv = (flags & NFA_FLAG_INVERSE) != 0;
-    void (*kern)(const k8h::Args) = nullptr;
-    int which = half ? 8 + (inv ? 1 : 0) + (init_ks == 2 ? 2 : 0) : (inv ? 1 : 0) + (init_ks == 2 ? 2 : 0) + (ring == 7 ? 4 : 0);
-    if (dbg_bins) {   // the diagnostic instances: d_i <= 32, the two workgroup forms the launcher picks by itself
-        if (init_ks != 1 || (!half && ring != 7)) return NFA_ERR_UNSUPPORTED;
-        which = 12 + (inv ? 1 : 0) + (half ? 2 : 0);
-        kern = half ? (inv ? k8s::rqs_resnet_f16s_kernel<true, 1, 4, 4, true> : k8s::rqs_resnet_f16s_kernel<false, 1, 4, 4, true>)
-                    : (inv ? k8s::rqs_resnet_f16s_kernel<true, 1, 7, k8s::kWavesPerGroup, true>
-                           : k8s::rqs_resnet_f16s_kernel<false, 1, 7, k8s::kWavesPerGroup, true>);
-    } else switch (which) {
-        case 0: kern = k8s::rqs_resnet_f16s_kernel<false, 1, 4>; break;
-        case 1: kern = k8s::rqs_resnet_f16s_kernel<true, 1, 4>; break;
-        case 2: kern = k8s::rqs_resnet_f16s_kernel<false, 2, 4>; break;
-        case 3: kern = k8s::rqs_resnet_f16s_kernel<true, 2, 4>; break;
-        case 4: kern = k8s::rqs_resnet_f16s_kernel<false, 1, 7>; break;
-        case 5: kern = k8s::rqs_resnet_f16s_kernel<true, 1, 7>; break;
-        case 6: kern = k8s::rqs_resnet_f16s_kernel<false, 2, 7>; break;
-        case 7: kern = k8s::rqs_resnet_f16s_kernel<true, 2, 7>; break;
-        case 8: kern = k8s::rqs_resnet_f16s_kernel<false, 1, 4, 4>; break;
-        case 9: kern = k8s::rqs_resnet_f16s_kernel<true, 1, 4, 4>; break;
-        case 10: kern = k8s::rqs_resnet_f16s_kernel<false, 2, 4, 4>; break;
-        default: kern = k8s::rqs_resnet_f16s_kernel<true, 2, 4, 4>; break;
-    }
+    hipStream_t st = (hipStream_t)c.stream;
+    const bool inv = (c.flags & NFA_FLAG_INVERSE) != 0;
     note_layer_kernel("k8s::rqs_resnet_f16s_kernel<inverse=%d, init_ks=%d, waves=%d, K=8, ring=%d>", inv ? 1 : 0, init_ks, nw, ring);
     // (a kernel, not hipMemsetAsync: captured into a HIP graph the memset NODE cost ~2 ms per replay -- GraphedLogProb at
     //  <= 16 384 rows took 2.8 ms where the launches themselves take 0.6, tools/small_batch_probe.py)
-    if (half) hipLaunchKernelGGL(k8s::zero_words_kernel, dim3((unsigned)((batch / 128 + 255) / 256)), dim3(256), 0, st,
-                                 redo_blocks, (int)(batch / 128));
-    if (lds_launch > 64 * 1024) {
-        static unsigned long long raised[16] = {};   // device masks (raise_dynamic_lds)
-        const int rc_lds = raise_dynamic_lds((const void*)kern, &raised[which], (int)lds_cap);
-        if (rc_lds != NFA_OK) return rc_lds;
-    }
-    if (e0) hipExtLaunchKernelGGL(kern, grid, block, lds_launch, st, e0, e1, 0, a);
-    else hipLaunchKernelGGL(kern, grid, block, lds_launch, st, a);
-    NFA_HIP_CHECK(hipGetLastError());
-    return NFA_OK;
+    if (half) hipLaunchKernelGGL(k8s::zero_words_kernel, dim3((unsigned)((c.batch / 128 + 255) / 256)), dim3(256), 0, st,
+                                 c.redo, (int)(c.batch / 128));
+    return launch_kernel(f16s_kernel(inv, init_ks, half, ring, dbg_bins), dim3((unsigned)blocks), dim3(nw * kWave),
+                         lds_launch, st, a, (int)lds_cap);
 }
 
 extern "C" int nfa_rqs_flow_resnet_f16x2_tile16_f32(const float* inputs, const void* stream_packed, int32_t param_stages,
@@ -680,9 +624,10 @@ extern "C" int nfa_rqs_flow_resnet_f16x2_tile16_f32(const float* inputs, const v
                                                     int32_t features, int32_t num_transform, int32_t num_identity,
                                                     int32_t hidden_features, int32_t num_blocks, const nfa_rqs_spec* spec,
                                                     int32_t flags, void* stream) {
-    return launch_tile16(inputs, stream_packed, param_stages, final_positions, num_layers, outputs, logabsdet, redo_blocks,
-                         status, batch, features, num_transform, num_identity, hidden_features, num_blocks, spec, flags,
-                         stream, nullptr);
+    return launch_tile16({inputs, stream_packed, nullptr, final_positions, num_layers, outputs, logabsdet, redo_blocks,
+                          status, batch, features, num_transform, num_identity, hidden_features, num_blocks, spec, flags,
+                          stream, nullptr, 0, param_stages},
+                         nullptr);
 }
 
 // the same launch through the diagnostic instances (see nfa_rqs_flow_resnet_f16x2_bins_f32)
@@ -694,7 +639,8 @@ extern "C" int nfa_rqs_flow_resnet_f16x2_tile16_bins_f32(const float* inputs, co
                                                          const nfa_rqs_spec* spec, int32_t flags, void* stream,
                                                          int32_t* bin_idx) {
     if (!bin_idx) return NFA_ERR_INVALID_ARGUMENT;
-    return launch_tile16(inputs, stream_packed, param_stages, final_positions, num_layers, outputs, logabsdet, redo_blocks,
-                         status, batch, features, num_transform, num_identity, hidden_features, num_blocks, spec, flags,
-                         stream, bin_idx);
+    return launch_tile16({inputs, stream_packed, nullptr, final_positions, num_layers, outputs, logabsdet, redo_blocks,
+                          status, batch, features, num_transform, num_identity, hidden_features, num_blocks, spec, flags,
+                          stream, nullptr, 0, param_stages},
+                         bin_idx);
 }

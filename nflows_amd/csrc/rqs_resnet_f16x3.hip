@@ -46,102 +46,53 @@
 
 using namespace nfa;
 
-static int launch_f16x3(const float* inputs, const void* weights_packed, const float* bias_packed, const float* scales,
-                        const int32_t* tables, int32_t num_layers, float* outputs, float* logabsdet, int32_t* redo_blocks,
-                        int32_t* status, int64_t batch, int32_t features, int32_t num_transform, int32_t num_identity,
-                        int32_t hidden_features, int32_t num_blocks, float act_scale, const nfa_rqs_spec* spec,
-                        int32_t flags, void* stream, float* dbg_logits = nullptr) {
-    if (flags & ~(NFA_FLAG_INVERSE | NFA_FLAG_ACCUMULATE_LOGABSDET | NFA_FLAG_STANDARD_NORMAL_LOG_PROB |
-                  NFA_FLAG_SKIP_OUTPUTS | NFA_FLAG_PAD_COLUMNS_MASK | NFA_FLAG_ACTIVATION_MASK))
-        return NFA_ERR_INVALID_ARGUMENT;
-    const int activation = (flags & NFA_FLAG_ACTIVATION_MASK) >> NFA_FLAG_ACTIVATION_SHIFT;
-    if (activation > NFA_ACTIVATION_TANH) return NFA_ERR_INVALID_ARGUMENT;
-    flags &= ~NFA_FLAG_ACTIVATION_MASK;
-    if (!density_flags_valid(flags)) return NFA_ERR_INVALID_ARGUMENT;
-    if (batch < 0 || features < 1 || num_transform < 1 || num_identity < 1 || num_transform > features ||
-        num_identity > features || num_blocks < 0 || num_layers < 1)
-        return NFA_ERR_INVALID_ARGUMENT;
+// The instance of a launch: 8 bins (the diagnostic instances beside), the other bin counts in their own translation units.
+static k8x::KernelFn f16x3_kernel(bool inverse, int init_ks, int K, bool dbg) {
+    if (K != 8) {
+        const k8x::KernelFn kern = k8x::bins_kernel_a(K, inverse, init_ks);
+        return kern ? kern : k8x::bins_kernel_b(K, inverse, init_ks);
+    }
+    if (init_ks == 4)
+        return dbg ? (inverse ? k8x::rqs_resnet_f16x3_kernel<true, 4, true> : k8x::rqs_resnet_f16x3_kernel<false, 4, true>)
+                   : (inverse ? k8x::rqs_resnet_f16x3_kernel<true, 4> : k8x::rqs_resnet_f16x3_kernel<false, 4>);
+    return dbg ? (inverse ? k8x::rqs_resnet_f16x3_kernel<true, 2, true> : k8x::rqs_resnet_f16x3_kernel<false, 2, true>)
+               : (inverse ? k8x::rqs_resnet_f16x3_kernel<true, 2> : k8x::rqs_resnet_f16x3_kernel<false, 2>);
+}
+
+static int launch_f16x3(const LayerCall& c, const float* scales, float act_scale, float* dbg_logits = nullptr) {
     // (a power of two: the pieces' scale must come out again exactly)
     int exponent = 0;
     if (!(act_scale > 0.0f) || frexpf(act_scale, &exponent) != 0.5f) return NFA_ERR_INVALID_ARGUMENT;
     k8x::Args a;
-    int rc = make_dev_spec(spec, &a.sp);
+    int activation = 0;
+    int rc = check_layer_call(c, {NFA_FLAG_ACTIVATION_MASK, true, false, false}, &a.sp, &activation);
     if (rc != NFA_OK) return rc;
-    if (a.sp.beta != 1.0f || activation != NFA_ACTIVATION_RELU) return NFA_ERR_UNSUPPORTED;
-    const bool bins_served = (a.sp.K >= 2 && a.sp.K <= 16) || a.sp.K == 20 || a.sp.K == 24 || a.sp.K == 32;
-    if (!bins_served || (dbg_logits && a.sp.K != 8) || !a.sp.linear || hidden_features != 128 || (num_transform & 3) != 0 || num_transform > 64 ||
-        num_identity > 64 || features > 128 || (features & 3) != 0 || (batch & 127) != 0 || num_blocks > 64 ||
-        num_layers > 4096)
-        return NFA_ERR_UNSUPPORTED;
-    if (batch == 0) return NFA_OK;
-    if (!inputs || !weights_packed || !bias_packed || !scales || !tables || !logabsdet || !redo_blocks ||
-        (!outputs && !(flags & NFA_FLAG_SKIP_OUTPUTS)))
-        return NFA_ERR_INVALID_ARGUMENT;
-    a.normal = (flags & NFA_FLAG_STANDARD_NORMAL_LOG_PROB) ? 1 : 0;
-    a.skip_out = (flags & NFA_FLAG_SKIP_OUTPUTS) ? 1 : 0;
-    a.Ds = density_columns(flags, features);
-    if (a.Ds < 1) return NFA_ERR_INVALID_ARGUMENT;
-    a.log_z = standard_normal_log_z(a.Ds);
+    if (activation != NFA_ACTIVATION_RELU || (dbg_logits && a.sp.K != 8)) return NFA_ERR_UNSUPPORTED;
+    if (c.batch == 0) return NFA_OK;
+    if (!layer_buffers_given(c) || !c.bias || !scales || !c.redo) return NFA_ERR_INVALID_ARGUMENT;
+    rc = fill_layer_args(a, c);
+    if (rc != NFA_OK) return rc;
     a.act_scale = act_scale;
-    a.x = inputs;
-    a.w = reinterpret_cast<const vec4f*>(weights_packed);
-    a.bias = bias_packed;
+    a.bias = c.bias;
     a.scales = scales;
-    a.tables = tables;
-    a.out = outputs;
-    a.lad = logabsdet;
-    a.redo = redo_blocks;
-    a.status = status;
-    a.batch = batch;
-    a.D = features;
-    a.dt = num_transform;
-    a.di = num_identity;
-    a.num_blocks = num_blocks;
-    a.num_layers = num_layers;
+    a.tables = c.tables;
+    a.redo = c.redo;
     a.dbg_logits = dbg_logits;
-    const int init_ks = num_identity > 32 ? 4 : 2;
-    const int rows_per_feature = a.sp.K == 8 ? 24 : 16 * ((3 * a.sp.K - 1 + 15) / 16);
-    a.num_stages = init_ks + 16 * num_blocks + 2 * (num_transform * rows_per_feature / 32);
-    a.bias_per_layer = 128 + 256 * num_blocks + num_transform * rows_per_feature;
-    a.accumulate = (flags & NFA_FLAG_ACCUMULATE_LOGABSDET) ? 1 : 0;
-    const size_t lds = (size_t)kRing * kStageVec4 * 16 + (size_t)(kBlock / kWave) * features * kRowPad * sizeof(float) +
-                       (size_t)num_transform * rows_per_feature * sizeof(float);
-    int64_t blocks = batch >> 7;
+    const int init_ks = c.num_identity > 32 ? 4 : 2;
+    const int rows_per_feature = spline_rows_per_feature(a.sp.K);
+    a.num_stages = init_ks + 16 * c.num_blocks + 2 * (c.num_transform * rows_per_feature / 32);
+    a.bias_per_layer = 128 + 256 * c.num_blocks + c.num_transform * rows_per_feature;
+    const size_t lds = (size_t)kRing * kStageVec4 * 16 + (size_t)(kBlock / kWave) * c.features * kRowPad * sizeof(float) +
+                       (size_t)c.num_transform * rows_per_feature * sizeof(float);
+    int64_t blocks = c.batch >> 7;
     const int64_t per_cu = lds + 2048 <= 80 * 1024 ? 2 : 1;
     const int64_t cap = (int64_t)device_cu_count() * per_cu;
     if (blocks > cap) blocks = cap;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    profile_next_launch(&e0, &e1);
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)blocks), block(kBlock);
-    const bool inv = (flags & NFA_FLAG_INVERSE) != 0;
-    void (*kern)(const k8x::Args) = nullptr;
-    int which = (inv ? 1 : 0) + (init_ks == 4 ? 2 : 0) + (dbg_logits ? 4 : 0);
-    if (a.sp.K != 8) {
-        which = 8 + (a.sp.K - 2) * 4 + (inv ? 1 : 0) + (init_ks == 4 ? 2 : 0);
-        kern = k8x::bins_kernel_a(a.sp.K, inv, init_ks);
-        if (!kern) kern = k8x::bins_kernel_b(a.sp.K, inv, init_ks);
-        if (!kern) return NFA_ERR_UNSUPPORTED;
-    } else switch (which) {
-        case 0: kern = k8x::rqs_resnet_f16x3_kernel<false, 2>; break;
-        case 1: kern = k8x::rqs_resnet_f16x3_kernel<true, 2>; break;
-        case 2: kern = k8x::rqs_resnet_f16x3_kernel<false, 4>; break;
-        case 3: kern = k8x::rqs_resnet_f16x3_kernel<true, 4>; break;
-        case 4: kern = k8x::rqs_resnet_f16x3_kernel<false, 2, true>; break;
-        case 5: kern = k8x::rqs_resnet_f16x3_kernel<true, 2, true>; break;
-        case 6: kern = k8x::rqs_resnet_f16x3_kernel<false, 4, true>; break;
-        default: kern = k8x::rqs_resnet_f16x3_kernel<true, 4, true>; break;
-    }
+    const bool inv = (c.flags & NFA_FLAG_INVERSE) != 0;
+    const k8x::KernelFn kern = f16x3_kernel(inv, init_ks, a.sp.K, dbg_logits);
+    if (!kern) return NFA_ERR_UNSUPPORTED;
     note_layer_kernel("k8x::rqs_resnet_f16x3_kernel<inverse=%d, init_ks=%d, K=%d, dbg=%d>", inv ? 1 : 0, init_ks, a.sp.K, dbg_logits ? 1 : 0);
-    if (lds > 64 * 1024) {
-        static unsigned long long raised[8 + 31 * 4] = {};   // device masks (raise_dynamic_lds)
-        const int rc_lds = raise_dynamic_lds((const void*)kern, &raised[which], 160 * 1024 - 2048);
-        if (rc_lds != NFA_OK) return rc_lds;
-    }
-    if (e0) hipExtLaunchKernelGGL(kern, grid, block, lds, st, e0, e1, 0, a);
-    else hipLaunchKernelGGL(kern, grid, block, lds, st, a);
-    NFA_HIP_CHECK(hipGetLastError());
-    return NFA_OK;
+    return launch_kernel(kern, dim3((unsigned)blocks), dim3(kBlock), lds, (hipStream_t)c.stream, a, 160 * 1024 - 2048);
 }
 
 extern "C" int nfa_rqs_flow_resnet_f16x3_f32(const float* inputs, const void* weights_packed, const float* bias_packed,
@@ -150,9 +101,10 @@ extern "C" int nfa_rqs_flow_resnet_f16x3_f32(const float* inputs, const void* we
                                              int64_t batch, int32_t features, int32_t num_transform,
                                              int32_t num_identity, int32_t hidden_features, int32_t num_blocks,
                                              float act_scale, const nfa_rqs_spec* spec, int32_t flags, void* stream) {
-    return launch_f16x3(inputs, weights_packed, bias_packed, scales, flow_tables, num_layers, outputs, logabsdet,
-                        redo_blocks, status, batch, features, num_transform, num_identity, hidden_features, num_blocks,
-                        act_scale, spec, flags, stream);
+    return launch_f16x3({inputs, weights_packed, bias_packed, flow_tables, num_layers, outputs, logabsdet, redo_blocks,
+                         status, batch, features, num_transform, num_identity, hidden_features, num_blocks, spec, flags,
+                         stream, nullptr, 0, 0},
+                        scales, act_scale);
 }
 
 extern "C" int nfa_rqs_flow_resnet_f16x3_logits_f32(const float* inputs, const void* weights_packed,
@@ -164,7 +116,8 @@ extern "C" int nfa_rqs_flow_resnet_f16x3_logits_f32(const float* inputs, const v
                                                     float act_scale, const nfa_rqs_spec* spec, int32_t flags,
                                                     void* stream, float* logits) {
     if (!logits) return NFA_ERR_INVALID_ARGUMENT;
-    return launch_f16x3(inputs, weights_packed, bias_packed, scales, flow_tables, num_layers, outputs, logabsdet,
-                        redo_blocks, status, batch, features, num_transform, num_identity, hidden_features, num_blocks,
-                        act_scale, spec, flags, stream, logits);
+    return launch_f16x3({inputs, weights_packed, bias_packed, flow_tables, num_layers, outputs, logabsdet, redo_blocks,
+                         status, batch, features, num_transform, num_identity, hidden_features, num_blocks, spec, flags,
+                         stream, nullptr, 0, 0},
+                        scales, act_scale, logits);
 }
