@@ -32,11 +32,12 @@
 extern "C" {
 #endif
 
-#define NFA_ABI_VERSION 14 /* bumped whenever a packed layout, a flag set or an entry point changes (round 3: 3 .. 7; round 4: 8,
+#define NFA_ABI_VERSION 15 /* bumped whenever a packed layout, a flag set or an entry point changes (round 3: 3 .. 7; round 4: 8,
                               9: whole-layer kernels for 2 .. 16 bins, nfa_resnet_backward_f32, W_f^T in K14's backward stream;
                               round 5: 10: `bin_idx` outputs of the spline kernels, nfa_searchsorted_f32; 11: NFA_FLAG_RESIDUAL_BLOCKS;
                               round 6: 12: nfa_rqs_flow_resnet_f16x3_f32 (K8x), the *_logits_f32 diagnostic entries,
-                              NFA_FLAG_ALL_PRODUCTS, nfa_weights_checksum_*) */
+                              NFA_FLAG_ALL_PRODUCTS, nfa_weights_checksum_*;
+                              15: nfa_lu_linear_f32, nfa_lu_linear_backward_f32) */
 
 /* return codes */
 #define NFA_OK 0
@@ -856,6 +857,49 @@ int nfa_affine_autoregressive_f32(const float *inputs, const float *params, floa
  */
 int nfa_permute_cols_b32(const void *inputs, const int64_t *perm, void *outputs, int32_t *status,
                          int64_t batch, int32_t features, void *stream);
+
+/*
+ * K16.  The LU-parameterised linear layer, both directions, from the module's own parameter tensors:
+ *   LULinear.forward_no_cache / inverse_no_cache   transforms/lu.py:56-91
+ *   LULinear._create_lower_upper, upper_diag, logabsdet   lu.py:44-54, 119-130
+ * and optionally the Permutation next to the layer       permutations.py:27-39
+ *   forward   outputs = L (U inputs) + bias,          logabsdet = +sum_i log U_ii
+ *   inverse   outputs = U^-1 (L^-1 (inputs - bias)),  logabsdet = -sum_i log U_ii   (two substitutions)
+ *
+ *   inputs         [batch, features]
+ *   lower_entries  [features (features-1) / 2]: L's strict lower triangle in np.tril_indices(features, -1) order,
+ *                  element (i, j), i > j, at i (i-1) / 2 + j; L's diagonal is 1
+ *   upper_entries  [features (features-1) / 2]: U's strict upper triangle in np.triu_indices(features, 1) order,
+ *                  element (i, j), j > i, at i features - i (i+1) / 2 + (j - i - 1)
+ *   unconstrained_upper_diag [features]: U_ii = softplus(.) + eps (F.softplus: beta 1, threshold 20), evaluated in
+ *                  float64 and rounded once, as is the log-determinant (one number per layer: the correctly rounded
+ *                  value is never further from the float64 result than another float32 evaluation)
+ *   bias           [features]
+ *   in_perm        [features] int64 or NULL: the layer sees inputs[:, in_perm]
+ *   out_scatter    [features] int64 or NULL: layer column c is stored at outputs[:, out_scatter[c]]
+ *   outputs        [batch, features]
+ *   logabsdet      [batch]; every row receives the same value (added to it with NFA_FLAG_ACCUMULATE_LOGABSDET)
+ *   flags          NFA_FLAG_INVERSE | NFA_FLAG_ACCUMULATE_LOGABSDET
+ * Every workgroup expands the factors into LDS itself: there is no packed form, and a changed parameter is seen by the
+ * next call.  A row's result depends on that row and the parameters only (not on batch, tile or grid).
+ * Supported: 2 <= features <= 128; otherwise NFA_ERR_UNSUPPORTED.  batch == 0 is a no-op.
+ */
+int nfa_lu_linear_f32(const float *inputs, const float *lower_entries, const float *upper_entries,
+                      const float *unconstrained_upper_diag, const float *bias, const int64_t *in_perm,
+                      const int64_t *out_scatter, float *outputs, float *logabsdet, int32_t *status,
+                      int64_t batch, int32_t features, double eps, int32_t flags, void *stream);
+
+/*
+ * K16-backward.  Input gradient of nfa_lu_linear_f32 (same parameters, in_perm / out_scatter and
+ * flags & NFA_FLAG_INVERSE as the forward call): the same two triangular steps with the factors transposed,
+ *   forward:  grad_inputs = U^T (L^T grad_outputs)      inverse:  grad_inputs = L^-T (U^-T grad_outputs)
+ * The parameter gradients are batch reductions ([features, features] products) the caller runs on the device's
+ * library GEMM (nflows_amd/autograd.py: LULinear).
+ */
+int nfa_lu_linear_backward_f32(const float *grad_outputs, const float *lower_entries, const float *upper_entries,
+                               const float *unconstrained_upper_diag, const int64_t *in_perm,
+                               const int64_t *out_scatter, float *grad_inputs, int32_t *status, int64_t batch,
+                               int32_t features, double eps, int32_t flags, void *stream);
 
 /*
  * K3.  Per-sample reduction: torchutils.sum_except_batch, utils/torchutils.py:19-24.

@@ -34,7 +34,7 @@ ACTIVATION_RELU, ACTIVATION_LEAKY_RELU, ACTIVATION_ELU, ACTIVATION_TANH = 0, 1, 
 TAILS_NONE, TAILS_LINEAR = 0, 1
 SCALE_DEFAULT, SCALE_GENERAL, SCALE_ADDITIVE, SCALE_GIVEN, SCALE_SOFTPLUS = 0, 1, 2, 3, 4
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 EXPORTS = (
     "nfa_abi_version",
@@ -80,6 +80,8 @@ EXPORTS = (
     "nfa_affine_coupling_f32",
     "nfa_affine_autoregressive_f32",
     "nfa_permute_cols_b32",
+    "nfa_lu_linear_f32",
+    "nfa_lu_linear_backward_f32",
     "nfa_rowsum_f32",
     "nfa_standard_normal_log_prob_f32",
     "nfa_sum_count_f64",
@@ -219,6 +221,10 @@ def _declare(lib):
     lib.nfa_affine_autoregressive_f32.argtypes = [vp, vp, vp, vp, i64, i32, i32, vp]
     lib.nfa_permute_cols_b32.restype = ctypes.c_int
     lib.nfa_permute_cols_b32.argtypes = [vp, vp, vp, vp, i64, i32, vp]
+    lib.nfa_lu_linear_f32.restype = ctypes.c_int
+    lib.nfa_lu_linear_f32.argtypes = [vp] * 10 + [i64, i32, ctypes.c_double, i32, vp]
+    lib.nfa_lu_linear_backward_f32.restype = ctypes.c_int
+    lib.nfa_lu_linear_backward_f32.argtypes = [vp] * 8 + [i64, i32, ctypes.c_double, i32, vp]
     lib.nfa_rowsum_f32.restype = ctypes.c_int
     lib.nfa_rowsum_f32.argtypes = [vp, vp, i64, i64, vp]
     lib.nfa_standard_normal_log_prob_f32.restype = ctypes.c_int

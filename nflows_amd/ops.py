@@ -511,6 +511,69 @@ def permute_cols(inputs, permutation):
     return out
 
 
+def lu_linear(inputs, lower_entries, upper_entries, unconstrained_upper_diag, bias, eps=1e-3, inverse=False,
+              in_perm=None, out_scatter=None, accumulate_into=None):
+    """K16 -- the LU-parameterised linear layer from the module's own parameter tensors (transforms/lu.py):
+    forward y = L (U x) + b, inverse x = U^-1 (L^-1 (y - b)) by substitution; inputs [B, D], 2 <= D <= 128.
+    Returns (outputs [B, D], logabsdet [B]).  `in_perm` / `out_scatter` / `accumulate_into` as `rqs_coupling`.
+    Differentiable in the inputs and all four parameters (K16-backward and the device's GEMM) when one requires grad."""
+    N.require_device_f32("inputs", inputs, 2)
+    dev = inputs.device
+    B, D = inputs.shape
+    tri = D * (D - 1) // 2
+    params = (lower_entries, upper_entries, unconstrained_upper_diag, bias)
+    for name, t, n in zip(("lower_entries", "upper_entries", "unconstrained_upper_diag", "bias"), params, (tri, tri, D, D)):
+        N.require_device_f32(name, t, 1)
+        if t.device != dev:
+            raise ValueError("%s is on %s, inputs on %s" % (name, t.device, dev))
+        if t.numel() != n:
+            raise ValueError("%s must have %d entries for %d features, got %d" % (name, n, D, t.numel()))
+    perm = _idx("in_perm", in_perm, dev, D)
+    scat = _idx("out_scatter", out_scatter, dev, D)
+    if AG.needs_grad(inputs, *params):
+        out, lad = AG.LULinear.apply(inputs.contiguous(), lower_entries, upper_entries, unconstrained_upper_diag, bias,
+                                     float(eps), bool(inverse), perm, scat)
+        if accumulate_into is not None:
+            accumulate_into += lad
+            lad = accumulate_into
+        return out, lad
+    return _lu_linear_launch(inputs, params, float(eps), inverse, perm, scat, accumulate_into)
+
+
+def _lu_linear_launch(inputs, params, eps, inverse, perm, scat, accumulate_into):
+    dev = inputs.device
+    B, D = inputs.shape
+    x = inputs.detach().contiguous()
+    lower, upper, udiag, bias = (t.detach().contiguous() for t in params)
+    out = torch.empty_like(x)
+    lad, flags = _lad_buffer(accumulate_into, B, dev, inverse)
+    hook = _launch_hook
+    with torch.cuda.device(dev):
+        token = hook.begin("lu_linear") if hook is not None else None
+        rc = N.load().nfa_lu_linear_f32(N.ptr(x), N.ptr(lower), N.ptr(upper), N.ptr(udiag), N.ptr(bias), N.ptr(perm),
+                                        N.ptr(scat), N.ptr(out), N.ptr(lad), N.ptr(_status_word(dev)), B, D, eps, flags,
+                                        N.stream_handle(dev))
+        if hook is not None:
+            hook.end(token, 4 * (2 * B * D + B))
+    N.check(rc)   # (a shape the kernel does not serve is an error here: there is no second path for float32 rows)
+    return out, lad
+
+
+def _lu_linear_backward_launch(grad_outputs, params, eps, inverse, perm, scat):
+    """K16-backward: the input gradient (the transposed triangular steps)."""
+    dev = grad_outputs.device
+    B, D = grad_outputs.shape
+    g = grad_outputs.detach().contiguous()
+    lower, upper, udiag = (t.detach().contiguous() for t in params[:3])
+    g_in = torch.empty_like(g)
+    with torch.cuda.device(dev):
+        rc = N.load().nfa_lu_linear_backward_f32(N.ptr(g), N.ptr(lower), N.ptr(upper), N.ptr(udiag), N.ptr(perm),
+                                                 N.ptr(scat), N.ptr(g_in), N.ptr(_status_word(dev)), B, D, eps,
+                                                 N.FLAG_INVERSE if inverse else 0, N.stream_handle(dev))
+    N.check(rc)
+    return g_in
+
+
 def rowsum(x):
     """K3 -- torch.sum over everything but the batch dimension."""
     N.require_device_f32("x", x)

@@ -6,6 +6,8 @@ from .coupling import (AdditiveCouplingTransform, AffineCouplingTransform, Coupl
                        PiecewiseQuadraticCouplingTransform,
                        PiecewiseRationalQuadraticCouplingTransform)
 from .permutations import Permutation, RandomPermutation, ReversePermutation
+from .linear import Linear
+from .lu import LULinear
 from . import splines
 from .autoregressive import (AutoregressiveTransform, MaskedAffineAutoregressiveTransform,
                              MaskedPiecewiseCubicAutoregressiveTransform,
