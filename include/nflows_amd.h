@@ -32,12 +32,13 @@
 extern "C" {
 #endif
 
-#define NFA_ABI_VERSION 15 /* bumped whenever a packed layout, a flag set or an entry point changes (round 3: 3 .. 7; round 4: 8,
+#define NFA_ABI_VERSION 16 /* bumped whenever a packed layout, a flag set or an entry point changes (round 3: 3 .. 7; round 4: 8,
                               9: whole-layer kernels for 2 .. 16 bins, nfa_resnet_backward_f32, W_f^T in K14's backward stream;
                               round 5: 10: `bin_idx` outputs of the spline kernels, nfa_searchsorted_f32; 11: NFA_FLAG_RESIDUAL_BLOCKS;
                               round 6: 12: nfa_rqs_flow_resnet_f16x3_f32 (K8x), the *_logits_f32 diagnostic entries,
                               NFA_FLAG_ALL_PRODUCTS, nfa_weights_checksum_*;
-                              15: nfa_lu_linear_f32, nfa_lu_linear_backward_f32) */
+                              15: nfa_lu_linear_f32, nfa_lu_linear_backward_f32;
+                              16: nfa_norm_* (K17) */
 
 /* return codes */
 #define NFA_OK 0
@@ -900,6 +901,64 @@ int nfa_lu_linear_backward_f32(const float *grad_outputs, const float *lower_ent
                                const float *unconstrained_upper_diag, const int64_t *in_perm,
                                const int64_t *out_scatter, float *grad_inputs, int32_t *status, int64_t batch,
                                int32_t features, double eps, int32_t flags, void *stream);
+
+/*
+ * K17.  The normalisation transforms (transforms/normalization.py: BatchNorm :72-141, ActNorm :144-218), float32
+ * [batch, features] rows, 1 <= features <= 1024 (otherwise NFA_ERR_UNSUPPORTED), on the caller's stream.
+ *
+ * Column reductions.  The batch is cut into nfa_norm_slab_count(batch, features) row slabs -- a function of (batch,
+ * features) only --, every slab is reduced in float64, the slabs are folded in a fixed order by a second small kernel and each
+ * result is rounded once.  No atomics: the same input gives the same bits on every run.
+ *   workspace   nfa_norm_workspace_bytes(batch, features) bytes, owned by the caller, need not be initialised, is
+ *               scratch during the call and must not be shared between streams that may run concurrently
+ *   nfa_norm_column_stats_f32: mean[c] = inputs.mean(0), var[c] = inputs.var(0) (unbiased), both [features] float32;
+ *               batch >= 2 (the unbiased variance of one row is NaN: NFA_ERR_UNSUPPORTED); stats_f64: NULL, or float64
+ *               [2][features] that receives (mean, var) before their rounding to float32 (ActNorm's initialisation derives
+ *               -log(std) and -mean / std from them and rounds those once)
+ *   nfa_norm_column_sums_f32:  sums[c] = sum_b g[b, gc], sums[features + c] = sum_b g[b, gc] * u[b, uc], float64, with
+ *               gc = g_columns[c], uc = u_columns[c] (int64 [features], NULL: c); batch == 0 gives zeros
+ */
+size_t nfa_norm_workspace_bytes(int64_t batch, int32_t features);
+int nfa_norm_slab_count(int64_t batch, int32_t features);
+int nfa_norm_column_stats_f32(const float *inputs, float *mean, float *var, double *stats_f64, void *workspace,
+                              int64_t batch, int32_t features, void *stream);
+int nfa_norm_column_sums_f32(const float *g, const float *u, const int64_t *g_columns, const int64_t *u_columns,
+                             double *sums, void *workspace, int32_t *status, int64_t batch, int32_t features,
+                             void *stream);
+
+/*
+ * K17, the per-column map: outputs[b, c] = a[c] * ((inputs[b, c] - m[c]) / s[c]) + t[c], evaluated in this order
+ * (no contraction, correctly rounded division: the reference's rounding sequence), from the module's own tensors:
+ *   kind 0 (BatchNorm)  p0 = unconstrained_weight, p1 = bias, p2 = mean, p3 = var (batch statistics or the running buffers);
+ *                       weight = softplus(p0) + eps, sd = sqrt(p3 + eps)
+ *        forward  a = weight, m = mean, s = sd, t = bias      logabsdet = sum_c log(weight) - 0.5 log(var + eps)
+ *        inverse  a = sd, m = bias, s = weight, t = mean      logabsdet = minus that
+ *   kind 1 (ActNorm)    p0 = log_scale, p1 = shift (p2, p3, eps unused)
+ *        forward  a = exp(log_scale), m = 0, s = 1, t = shift   logabsdet = sum_c log_scale
+ *        inverse  a = 1, m = shift, s = exp(log_scale), t = 0   logabsdet = minus that
+ * The constants are derived once per workgroup in float64 and rounded once, as is the log-determinant (one number per
+ * call, stored to every row; added with NFA_FLAG_ACCUMULATE_LOGABSDET).  Nothing is packed or cached.
+ *   in_perm / out_scatter  as nfa_lu_linear_f32;  flags  NFA_FLAG_INVERSE | NFA_FLAG_ACCUMULATE_LOGABSDET
+ * batch == 0 is a no-op.
+ * nfa_norm_map_backward_f32: the input gradient with fixed statistics, grad_inputs = (grad_outputs * a) / s, same
+ * parameters, in_perm / out_scatter and flags & NFA_FLAG_INVERSE as the forward call.
+ * nfa_norm_batch_backward_f32: the input gradient of the BatchNorm forward with batch statistics,
+ *   grad_inputs = c0 * ((g - c1) - xh * c2) - c3 * (x - mean),  xh = (x - mean) / s,
+ * coefficients [6][features] = mean, s, c0 = weight / s, c1 = G1 / B, c2 = G2 / (B - 1), c3 = L / ((B - 1) (var + eps))
+ * (G1 = sum g, G2 = sum g xh, L = sum of the incoming log-determinant gradient; formed by the caller from
+ * nfa_norm_column_sums_f32 in float64).
+ */
+int nfa_norm_map_f32(const float *inputs, const float *p0, const float *p1, const float *p2, const float *p3,
+                     const int64_t *in_perm, const int64_t *out_scatter, float *outputs, float *logabsdet,
+                     int32_t *status, int64_t batch, int32_t features, double eps, int32_t kind, int32_t flags,
+                     void *stream);
+int nfa_norm_map_backward_f32(const float *grad_outputs, const float *p0, const float *p1, const float *p2,
+                              const float *p3, const int64_t *in_perm, const int64_t *out_scatter, float *grad_inputs,
+                              int32_t *status, int64_t batch, int32_t features, double eps, int32_t kind, int32_t flags,
+                              void *stream);
+int nfa_norm_batch_backward_f32(const float *grad_outputs, const float *inputs, const float *coefficients,
+                                const int64_t *in_perm, const int64_t *out_scatter, float *grad_inputs, int32_t *status,
+                                int64_t batch, int32_t features, void *stream);
 
 /*
  * K3.  Per-sample reduction: torchutils.sum_except_batch, utils/torchutils.py:19-24.

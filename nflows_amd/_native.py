@@ -34,7 +34,7 @@ ACTIVATION_RELU, ACTIVATION_LEAKY_RELU, ACTIVATION_ELU, ACTIVATION_TANH = 0, 1, 
 TAILS_NONE, TAILS_LINEAR = 0, 1
 SCALE_DEFAULT, SCALE_GENERAL, SCALE_ADDITIVE, SCALE_GIVEN, SCALE_SOFTPLUS = 0, 1, 2, 3, 4
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 EXPORTS = (
     "nfa_abi_version",
@@ -82,6 +82,13 @@ EXPORTS = (
     "nfa_permute_cols_b32",
     "nfa_lu_linear_f32",
     "nfa_lu_linear_backward_f32",
+    "nfa_norm_workspace_bytes",
+    "nfa_norm_slab_count",
+    "nfa_norm_column_stats_f32",
+    "nfa_norm_column_sums_f32",
+    "nfa_norm_map_f32",
+    "nfa_norm_map_backward_f32",
+    "nfa_norm_batch_backward_f32",
     "nfa_rowsum_f32",
     "nfa_standard_normal_log_prob_f32",
     "nfa_sum_count_f64",
@@ -225,6 +232,20 @@ def _declare(lib):
     lib.nfa_lu_linear_f32.argtypes = [vp] * 10 + [i64, i32, ctypes.c_double, i32, vp]
     lib.nfa_lu_linear_backward_f32.restype = ctypes.c_int
     lib.nfa_lu_linear_backward_f32.argtypes = [vp] * 8 + [i64, i32, ctypes.c_double, i32, vp]
+    lib.nfa_norm_workspace_bytes.restype = ctypes.c_size_t
+    lib.nfa_norm_workspace_bytes.argtypes = [i64, i32]
+    lib.nfa_norm_slab_count.restype = ctypes.c_int
+    lib.nfa_norm_slab_count.argtypes = [i64, i32]
+    lib.nfa_norm_column_stats_f32.restype = ctypes.c_int
+    lib.nfa_norm_column_stats_f32.argtypes = [vp] * 5 + [i64, i32, vp]
+    lib.nfa_norm_column_sums_f32.restype = ctypes.c_int
+    lib.nfa_norm_column_sums_f32.argtypes = [vp] * 7 + [i64, i32, vp]
+    lib.nfa_norm_map_f32.restype = ctypes.c_int
+    lib.nfa_norm_map_f32.argtypes = [vp] * 10 + [i64, i32, ctypes.c_double, i32, i32, vp]
+    lib.nfa_norm_map_backward_f32.restype = ctypes.c_int
+    lib.nfa_norm_map_backward_f32.argtypes = [vp] * 9 + [i64, i32, ctypes.c_double, i32, i32, vp]
+    lib.nfa_norm_batch_backward_f32.restype = ctypes.c_int
+    lib.nfa_norm_batch_backward_f32.argtypes = [vp] * 7 + [i64, i32, vp]
     lib.nfa_rowsum_f32.restype = ctypes.c_int
     lib.nfa_rowsum_f32.argtypes = [vp, vp, i64, i64, vp]
     lib.nfa_standard_normal_log_prob_f32.restype = ctypes.c_int

@@ -328,6 +328,79 @@ class LULinear(torch.autograd.Function):
         return tuple(grads) + (None, None, None, None)
 
 
+class NormMap(torch.autograd.Function):
+    """K17 forward and its gradients (BatchNorm / ActNorm, ops.batch_norm / ops.act_norm).
+
+    The input gradient is one element-wise kernel.  Everything that is summed over the batch -- G1 = sum g and
+    Gu = sum g * u per column, u the layer's input -- comes from K17's column reduction in float64; the parameter gradients
+    and the coefficients of the batch-statistics gradient are [D] float64 expressions of G1, Gu and L = sum grad_logabsdet,
+    rounded once (they are not hot).  With y = a ((u - m) / s) + t:
+      BatchNorm forward   d bias = G1          d weight = (Gu - mean G1) / sd + L / weight
+      BatchNorm inverse   d bias = -(sd / w) G1   d weight = -(sd / w^2) (Gu - bias G1) - L / weight
+      ActNorm forward     d shift = G1         d log_scale = scale Gu + L
+      ActNorm inverse     d shift = -G1 / scale   d log_scale = -(Gu - shift G1) / scale - L
+    and d unconstrained_weight = d weight * softplus'.  With batch statistics the mean and the unbiased variance depend on
+    the inputs:  grad_x = (w / s) (g - G1 / B - xh G2 / (B - 1)) - L (x - mean) / ((B - 1) (var + eps)),  G2 = sum g xh."""
+
+    @staticmethod
+    def forward(ctx, inputs, kind, eps, inverse, batch_statistics, perm, scat, *params):
+        from . import ops
+        out, lad = ops._norm_map_launch(inputs, kind, params, eps, inverse, perm, scat, None)
+        ctx.save_for_backward(inputs, perm, scat, *params)
+        ctx.kind, ctx.eps, ctx.inverse, ctx.batch_statistics = kind, eps, inverse, batch_statistics
+        return out, lad
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out, g_lad):
+        from . import ops
+        inputs, perm, scat = ctx.saved_tensors[:3]
+        params = ctx.saved_tensors[3:]
+        kind, eps, inverse = ctx.kind, ctx.eps, ctx.inverse
+        f64 = torch.float64
+        g_out = torch.zeros_like(inputs) if g_out is None else g_out.contiguous()
+        rows = inputs.shape[0]
+        L = g_lad.to(f64).sum() if g_lad is not None else torch.zeros((), dtype=f64, device=inputs.device)
+        need_params = any(ctx.needs_input_grad[7:9])
+        G1 = Gu = None
+        if need_params or ctx.batch_statistics:
+            G1, Gu = ops.column_sums(g_out, inputs, g_columns=scat, u_columns=perm)   # in the layer's own column order
+        d0 = d1 = None
+        if kind == ops.NORM_BATCH_NORM:
+            logits, bias, mean, var = (t.to(f64) for t in params)
+            weight = torch.nn.functional.softplus(logits) + eps
+            ve = var + eps
+            sd = torch.sqrt(ve)
+            if G1 is not None:
+                if not inverse:
+                    G2 = (Gu - mean * G1) / sd
+                    d_weight, d1 = G2 + L / weight, G1
+                else:
+                    d_weight, d1 = -(sd / (weight * weight)) * (Gu - bias * G1) - L / weight, -(sd / weight) * G1
+                d0 = d_weight * torch.where(logits > 20.0, torch.ones_like(logits), torch.sigmoid(logits))
+        else:
+            log_scale, shift = (t.to(f64) for t in params)
+            scale = torch.exp(log_scale)
+            if G1 is not None:
+                if not inverse:
+                    d0, d1 = scale * Gu + L, G1
+                else:
+                    d0, d1 = -(Gu - shift * G1) / scale - L, -G1 / scale
+        g_in = None
+        if ctx.needs_input_grad[0]:
+            if ctx.batch_statistics:
+                s32 = sd.float().to(f64)   # the divisor the forward kernel used
+                G2 = (Gu - mean * G1) / s32
+                coef = torch.stack((mean, s32, weight / s32, G1 / rows, G2 / (rows - 1), L / ((rows - 1) * ve))).float()
+                g_in = ops._norm_batch_backward_launch(g_out, inputs, coef, perm, scat)
+            else:
+                g_in = ops._norm_map_backward_launch(g_out, kind, params, eps, inverse, perm, scat)
+        grads = [g_in, None, None, None, None, None, None,
+                 d0.to(params[0].dtype) if d0 is not None and ctx.needs_input_grad[7] else None,
+                 d1.to(params[1].dtype) if d1 is not None and ctx.needs_input_grad[8] else None]
+        return tuple(grads) + (None,) * (len(params) - 2)
+
+
 class Linear(torch.autograd.Function):
     """y = x W^T + b (the conditioner layers).  Forward and the input gradient are library GEMMs;
     the weight and bias gradients -- a product whose reduction runs over the whole batch into a tiny

@@ -1,1 +1,3 @@
 from .base import Flow
+from .autoregressive import MaskedAutoregressiveFlow
+from .realnvp import SimpleRealNVP

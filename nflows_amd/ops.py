@@ -574,6 +574,157 @@ def _lu_linear_backward_launch(grad_outputs, params, eps, inverse, perm, scat):
     return g_in
 
 
+NORM_MAX_FEATURES = 1024
+NORM_BATCH_NORM, NORM_ACT_NORM = 0, 1
+
+
+def _norm_workspace(batch, features, device):
+    nbytes = N.load().nfa_norm_workspace_bytes(batch, features)
+    return torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=device)   # (scratch of this call; the allocator keeps it stream-ordered)
+
+
+def column_stats(inputs, return_f64=False):
+    """K17 -- (inputs.mean(0), inputs.var(0)) of float32 [B, D] rows, B >= 2, D <= 1024: one pass, float64 accumulation
+    in row slabs merged in a fixed order, each statistic rounded once; the same bits on every run.  No gradient.
+    `return_f64`: a third result, float64 [2, D] = (mean, var) before that rounding."""
+    N.require_device_f32("inputs", inputs, 2)
+    B, D = inputs.shape
+    dev = inputs.device
+    x = inputs.detach().contiguous()
+    mean = torch.empty(D, dtype=torch.float32, device=dev)
+    var = torch.empty(D, dtype=torch.float32, device=dev)
+    wide = torch.empty(2, D, dtype=torch.float64, device=dev) if return_f64 else None
+    ws = _norm_workspace(B, D, dev)
+    hook = _launch_hook
+    with torch.cuda.device(dev):
+        token = hook.begin("norm_stats") if hook is not None else None
+        rc = N.load().nfa_norm_column_stats_f32(N.ptr(x), N.ptr(mean), N.ptr(var), N.ptr(wide), N.ptr(ws), B, D,
+                                                N.stream_handle(dev))
+        if hook is not None:
+            hook.end(token, 4 * B * D)
+    N.check(rc)
+    return (mean, var, wide) if return_f64 else (mean, var)
+
+
+def column_sums(g, u, g_columns=None, u_columns=None):
+    """K17 -- float64 [2, D]: sum_b g[b, gc] and sum_b g[b, gc] * u[b, uc] (gc = g_columns[c], uc = u_columns[c]; None: c)
+    for two float32 [B, D] tensors, by the slab scheme of `column_stats`.  The batch reductions of the backward passes."""
+    N.require_device_f32("g", g, 2)
+    N.require_device_f32("u", u, 2)
+    if g.shape != u.shape:
+        raise ValueError("g and u must have the same shape")
+    B, D = g.shape
+    dev = g.device
+    gc, uc = _idx("g_columns", g_columns, dev, D), _idx("u_columns", u_columns, dev, D)
+    g, u = g.detach().contiguous(), u.detach().contiguous()
+    sums = torch.empty(2, D, dtype=torch.float64, device=dev)
+    ws = _norm_workspace(B, D, dev)
+    with torch.cuda.device(dev):
+        rc = N.load().nfa_norm_column_sums_f32(N.ptr(g), N.ptr(u), N.ptr(gc), N.ptr(uc), N.ptr(sums), N.ptr(ws),
+                                               N.ptr(_status_word(dev)), B, D, N.stream_handle(dev))
+    N.check(rc)
+    return sums
+
+
+def _norm_params(inputs, kind, params):
+    N.require_device_f32("inputs", inputs, 2)
+    D = inputs.shape[1]
+    names = ("unconstrained_weight", "bias", "mean", "var") if kind == NORM_BATCH_NORM else ("log_scale", "shift")
+    if len(params) != len(names):
+        raise ValueError("expected the tensors %s" % (names,))
+    for name, t in zip(names, params):
+        N.require_device_f32(name, t, 1)
+        if t.device != inputs.device:
+            raise ValueError("%s is on %s, inputs on %s" % (name, t.device, inputs.device))
+        if t.numel() != D:
+            raise ValueError("%s must have %d entries, got %d" % (name, D, t.numel()))
+
+
+def batch_norm(inputs, unconstrained_weight, bias, mean, var, eps=1e-5, inverse=False, batch_statistics=False,
+               in_perm=None, out_scatter=None, accumulate_into=None):
+    """K17 -- BatchNorm's map from the module's own tensors (transforms/normalization.py):
+    forward weight * ((x - mean) / sqrt(var + eps)) + bias, inverse sqrt(var + eps) * ((x - bias) / weight) + mean, with
+    weight = softplus(unconstrained_weight) + eps; inputs [B, D], D <= 1024.  Returns (outputs, logabsdet [B]).
+    `batch_statistics`: `mean` / `var` are `column_stats(inputs[:, in_perm])` (training mode) and the gradient flows through
+    them; otherwise they are constants (the running buffers).  `in_perm` / `out_scatter` / `accumulate_into` as `lu_linear`.
+    Differentiable in the inputs, `unconstrained_weight` and `bias`."""
+    params = (unconstrained_weight, bias, mean, var)
+    _norm_params(inputs, NORM_BATCH_NORM, params)
+    if inverse and batch_statistics:
+        raise ValueError("the inverse takes fixed statistics")
+    return _norm(inputs, NORM_BATCH_NORM, params, float(eps), bool(inverse), bool(batch_statistics), in_perm, out_scatter,
+                 accumulate_into)
+
+
+def act_norm(inputs, log_scale, shift, inverse=False, in_perm=None, out_scatter=None, accumulate_into=None):
+    """K17 -- ActNorm's map: forward exp(log_scale) * x + shift, inverse (x - shift) / exp(log_scale); inputs [B, D],
+    D <= 1024.  Returns (outputs, logabsdet [B]).  Differentiable in the inputs and both parameters."""
+    params = (log_scale, shift)
+    _norm_params(inputs, NORM_ACT_NORM, params)
+    return _norm(inputs, NORM_ACT_NORM, params, 0.0, bool(inverse), False, in_perm, out_scatter, accumulate_into)
+
+
+def _norm(inputs, kind, params, eps, inverse, batch_statistics, in_perm, out_scatter, accumulate_into):
+    dev = inputs.device
+    D = inputs.shape[1]
+    perm = _idx("in_perm", in_perm, dev, D)
+    scat = _idx("out_scatter", out_scatter, dev, D)
+    if AG.needs_grad(inputs, *params[:2]):
+        out, lad = AG.NormMap.apply(inputs.contiguous(), kind, eps, inverse, batch_statistics, perm, scat, *params)
+        if accumulate_into is not None:
+            accumulate_into += lad
+            lad = accumulate_into
+        return out, lad
+    return _norm_map_launch(inputs, kind, params, eps, inverse, perm, scat, accumulate_into)
+
+
+def _norm_map_launch(inputs, kind, params, eps, inverse, perm, scat, accumulate_into):
+    dev = inputs.device
+    B, D = inputs.shape
+    x = inputs.detach().contiguous()
+    p = [t.detach().contiguous() for t in params] + [None] * (4 - len(params))
+    out = torch.empty_like(x)
+    lad, flags = _lad_buffer(accumulate_into, B, dev, inverse)
+    hook = _launch_hook
+    with torch.cuda.device(dev):
+        token = hook.begin("norm_map") if hook is not None else None
+        rc = N.load().nfa_norm_map_f32(N.ptr(x), N.ptr(p[0]), N.ptr(p[1]), N.ptr(p[2]), N.ptr(p[3]), N.ptr(perm),
+                                       N.ptr(scat), N.ptr(out), N.ptr(lad), N.ptr(_status_word(dev)), B, D, eps, kind,
+                                       flags, N.stream_handle(dev))
+        if hook is not None:
+            hook.end(token, 4 * (2 * B * D + B))
+    N.check(rc)
+    return out, lad
+
+
+def _norm_map_backward_launch(grad_outputs, kind, params, eps, inverse, perm, scat):
+    """K17: the input gradient with fixed statistics, (g * a) / s."""
+    dev = grad_outputs.device
+    B, D = grad_outputs.shape
+    g = grad_outputs.detach().contiguous()
+    p = [t.detach().contiguous() for t in params] + [None] * (4 - len(params))
+    g_in = torch.empty_like(g)
+    with torch.cuda.device(dev):
+        rc = N.load().nfa_norm_map_backward_f32(N.ptr(g), N.ptr(p[0]), N.ptr(p[1]), N.ptr(p[2]), N.ptr(p[3]), N.ptr(perm),
+                                                N.ptr(scat), N.ptr(g_in), N.ptr(_status_word(dev)), B, D, eps, kind,
+                                                N.FLAG_INVERSE if inverse else 0, N.stream_handle(dev))
+    N.check(rc)
+    return g_in
+
+
+def _norm_batch_backward_launch(grad_outputs, inputs, coefficients, perm, scat):
+    """K17: the input gradient of BatchNorm with batch statistics (`coefficients`: float32 [6, D], include/nflows_amd.h)."""
+    dev = grad_outputs.device
+    B, D = grad_outputs.shape
+    g, x, c = grad_outputs.detach().contiguous(), inputs.detach().contiguous(), coefficients.contiguous()
+    g_in = torch.empty_like(g)
+    with torch.cuda.device(dev):
+        rc = N.load().nfa_norm_batch_backward_f32(N.ptr(g), N.ptr(x), N.ptr(c), N.ptr(perm), N.ptr(scat), N.ptr(g_in),
+                                                  N.ptr(_status_word(dev)), B, D, N.stream_handle(dev))
+    N.check(rc)
+    return g_in
+
+
 def rowsum(x):
     """K3 -- torch.sum over everything but the batch dimension."""
     N.require_device_f32("x", x)

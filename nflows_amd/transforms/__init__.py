@@ -8,6 +8,7 @@ from .coupling import (AdditiveCouplingTransform, AffineCouplingTransform, Coupl
 from .permutations import Permutation, RandomPermutation, ReversePermutation
 from .linear import Linear
 from .lu import LULinear
+from .normalization import ActNorm, BatchNorm
 from . import splines
 from .autoregressive import (AutoregressiveTransform, MaskedAffineAutoregressiveTransform,
                              MaskedPiecewiseCubicAutoregressiveTransform,
