@@ -343,5 +343,5 @@ extern "C" int nfa_affine_flow_mlp_f32(const float* inputs, const void* weights_
                                : (additive ? affine_mlp_instance<2, true, false>(inv) : affine_mlp_instance<2, false, false>(inv)));
     if (resnet) note_layer_kernel("affine_mlp_kernel<inverse=%d, init_ks=%d, additive=%d, resnet=1>", inv ? 1 : 0, init_ks, additive ? 1 : 0);
     else note_layer_kernel("affine_mlp_kernel<inverse=%d, init_ks=%d, additive=%d>", inv ? 1 : 0, init_ks, additive ? 1 : 0);
-    return launch_kernel(kern, dim3((unsigned)blocks), dim3(kBlock), lds, (hipStream_t)stream, a, 160 * 1024 - 2048);
+    return launch_kernel(kern, dim3((unsigned)blocks), dim3(kBlock), lds, (hipStream_t)stream, a, kCuLds - 2048);
 }

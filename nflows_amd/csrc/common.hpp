@@ -5,13 +5,14 @@
 #include <hip/hip_ext.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "nflows_amd.h"
+#include "launch_plan.hpp"   // kBlock, kWave, the LDS sizes, tile and grid planning (host only, no HIP)
 
 namespace nfa {
 
-constexpr int kBlock = 256;  // 4 wave64 per workgroup
-constexpr int kWave = 64;
-
+// the library's process state lives in runtime.hip
 int set_hip_error(hipError_t e);  // records e (thread-local) and returns NFA_ERR_HIP
 int device_cu_count();            // multiProcessorCount of the current device (cached)
 // measurement aid (nfa_profile_*): event pair for the next layer-kernel launch, or nulls
@@ -26,25 +27,31 @@ void note_layer_kernel(const char* fmt, ...) __attribute__((format(printf, 1, 2)
     } while (0)
 
 // hipFuncSetAttribute applies to the CURRENT device only: the opt-in to more than 64 KB of dynamic LDS is
-// remembered per (kernel, device) pair, in a mutex-guarded set (rqs.hip).
+// remembered per (kernel, device) pair, in a mutex-guarded set (runtime.hip).
 int raise_dynamic_lds(const void* kern, int bytes);
 
-// The tail of every layer-kernel launch: the opt-in to `lds_optin` bytes of dynamic LDS (default: the launch's own
-// `lds`) when the launch needs more than 64 KB, the event pair of the measurement aid when the launch is `profiled`,
-// the launch itself and its error check.
-template <typename A>
-inline int launch_kernel(void (*kern)(A), dim3 grid, dim3 block, size_t lds, hipStream_t st, const A& a,
-                         int lds_optin = 0, bool profiled = true) {
-    if (lds > 64 * 1024) {
+// The tail of every kernel launch: the opt-in to `lds_optin` bytes of dynamic LDS (default: the launch's own `lds`) when
+// the launch needs more than 64 KB, the event pair of the measurement aid when the launch is `profiled`, the launch
+// itself and its error check.  launch_kernel_args takes the kernel's arguments one by one (converted to the kernel's
+// parameter types); launch_kernel is the usual case of one argument struct.
+template <typename... P>
+inline int launch_kernel_args(void (*kern)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, int lds_optin,
+                              bool profiled, std::common_type_t<P>... args) {
+    if (lds > (size_t)kDefaultDynLds) {
         const int rc = raise_dynamic_lds((const void*)kern, lds_optin ? lds_optin : (int)lds);
         if (rc != NFA_OK) return rc;
     }
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (profiled) profile_next_launch(&e0, &e1);
-    if (e0) hipExtLaunchKernelGGL(kern, grid, block, lds, st, e0, e1, 0, a);
-    else hipLaunchKernelGGL(kern, grid, block, lds, st, a);
+    if (e0) hipExtLaunchKernelGGL(kern, grid, block, lds, st, e0, e1, 0, args...);
+    else hipLaunchKernelGGL(kern, grid, block, lds, st, args...);
     NFA_HIP_CHECK(hipGetLastError());
     return NFA_OK;
+}
+template <typename A>
+inline int launch_kernel(void (*kern)(A), dim3 grid, dim3 block, size_t lds, hipStream_t st, const A& a,
+                         int lds_optin = 0, bool profiled = true) {
+    return launch_kernel_args(kern, grid, block, lds, st, lds_optin, profiled, a);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -146,10 +153,5 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
-inline int round_up4(int n) { return (n + 3) & ~3; }
-
 }  // namespace nfa
 #include "affine_math.hpp"   // scale activations and the per-element map of the affine layers (K2, K2b, K11)
-namespace nfa {
-
-}  // namespace nfa

@@ -1,0 +1,90 @@
+// Host-side launch planning of the per-layer kernels: tile sizes and grid sizes as plain functions of the problem and
+// the device's CU count.  No HIP, no state, no side effects (tests/test_launch_plan_host.py compiles it for the host).
+#pragma once
+
+#include <stddef.h>
+#include <stdint.h>
+
+namespace nfa {
+
+constexpr int kBlock = 256;  // 4 wave64 per workgroup
+constexpr int kWave = 64;
+constexpr int kDefaultDynLds = 64 * 1024;  // dynamic LDS a launch may ask for without an opt-in
+constexpr int kCuLds = 160 * 1024;         // LDS of one CU
+
+inline int round_up4(int n) { return (n + 3) & ~3; }
+
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// ------------------------------------------------------------------------------------------
+// Sample tiles: R whole samples per workgroup.
+
+// about `lanes` items per tile (d_t items per sample; D where nothing is transformed), at least 1, at most the batch
+inline int sample_rows(int lanes, int dt, int D, int64_t batch) {
+    int R = dt > 0 ? lanes / dt : lanes / (D < lanes ? D : lanes);
+    if (R < 1) R = 1;
+    if ((int64_t)R > batch) R = (int)batch;
+    return R;
+}
+
+struct SampleTile {
+    int R = 0;       // samples per tile
+    int C = 0;       // splines per chunk (0 = the whole tile's parameters at once)
+    size_t lds = 0;  // bytes of the tile's LDS image
+    bool ok = false;
+};
+
+// sample_rows(), halved until the image of lds_floats(r, chunk) floats fits `budget` bytes.  With P > 0 (parameters per
+// spline: K1 and its backward) a single sample that does not fit streams its parameters through LDS in chunks of C
+// splines, a multiple of kBlock, beside `chunk_fixed` bytes of everything else.  lds_floats may record the offsets it
+// lays out: its last call is the one for the tile returned.  !ok: no tile fits, or one has 2^16 items or more.
+template <typename F>
+inline SampleTile plan_sample_tile(int lanes, int dt, int D, int64_t batch, size_t budget, F&& lds_floats, int P = 0,
+                                   size_t chunk_fixed = 0) {
+    SampleTile t;
+    t.R = sample_rows(lanes, dt, D, batch);
+    while (t.R > 1 && (size_t)lds_floats(t.R, 0) * 4 > budget) t.R >>= 1;
+    if (P > 0 && t.R == 1 && (size_t)lds_floats(1, 0) * 4 > budget) {
+        if (chunk_fixed + (size_t)kBlock * P * 4 > budget) return t;
+        t.C = (int)((budget - chunk_fixed) / ((size_t)P * 4));
+        t.C = (t.C / kBlock) * kBlock;
+        if (t.C >= dt) t.C = 0;
+    }
+    t.lds = (size_t)lds_floats(t.R, t.C) * 4;
+    t.ok = t.lds <= budget && (int64_t)t.R * dt < 65536 && (int64_t)t.R * D < 65536;
+    return t;
+}
+
+// the layouts the pipelined K1 kernels take: whole float4s per sample, a tile within one pass of the workgroup
+inline bool aligned_tile(int dt, int D, int P, int R, int64_t batch) {
+    return dt > 0 && (dt * P) % 4 == 0 && D % 4 == 0 && R * dt <= kBlock && R * D <= 2 * kBlock && (int64_t)R <= batch;
+}
+
+// "full tiles through one kernel, the rows behind them through another": the rows of the first part
+inline int64_t full_rows(int64_t batch, int64_t rows_per_tile) { return (batch / rows_per_tile) * rows_per_tile; }
+
+// ------------------------------------------------------------------------------------------
+// Element tiles: T elements per workgroup, kBlock halved down to `floor` until bytes(T) fits `budget`; 0 = none fits.
+template <typename F>
+inline int plan_element_tile(int floor, size_t budget, F&& bytes) {
+    int T = kBlock;
+    while (T > floor && (size_t)bytes(T) > budget) T >>= 1;
+    return (size_t)bytes(T) <= budget ? T : 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// Persistent grids: the workgroups that are resident together, at most one per tile.
+inline int64_t persistent_grid(int cus, int per_cu, int64_t tiles) {
+    const int64_t g = (int64_t)cus * per_cu;
+    return g > tiles ? tiles : g;
+}
+// ... where LDS decides residency: `lds` bytes of dynamic LDS (+ 256 of static arrays and granule) per workgroup, at
+// most `cap` workgroups per CU
+inline int64_t persistent_grid(int cus, size_t lds, int cap, int64_t tiles) {
+    int per_cu = (int)((size_t)kCuLds / (lds + 256));
+    if (per_cu > cap) per_cu = cap;
+    if (per_cu < 1) per_cu = 1;
+    return persistent_grid(cus, per_cu, tiles);
+}
+
+}  // namespace nfa

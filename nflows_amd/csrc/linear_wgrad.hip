@@ -463,30 +463,27 @@ extern "C" int nfa_linear_wgrad_batched_f32(int32_t count, const float* const* i
         // engine of the 128 x 128 result blocks: "bf16x3" (default since round 4) or "f32" (NFA_K10_ENGINE)
         const char* eng = wgrad_engine_env();
         const bool bf16 = !eng || eng[0] != 'f';
+        // (the ring of row stages in LDS: 32-row stages of 128 + 128 columns need the opt-in beyond 64 KB)
+        void (*kern)(const WgradArgs) = nullptr;
+        size_t lds = (size_t)kWgRing * kWgRows * (128 + 128) * 4;
         if (p.variant == 0 && bf16 && p.rows == 16) {
-            constexpr size_t lds = (size_t)kWgRing * 16 * (128 + 128) * 4;
-            hipLaunchKernelGGL((wgrad_partial_bf16_kernel<2, 2, 2, 2, 16>), grid, dim3(kBlock), lds, st, a);
+            lds = (size_t)kWgRing * 16 * (128 + 128) * 4;
+            kern = wgrad_partial_bf16_kernel<2, 2, 2, 2, 16>;
         } else if (p.variant == 0 && bf16) {
-            constexpr size_t lds = (size_t)kWgRing * kWgRows * (128 + 128) * 4;
-            const int rc_lds = raise_dynamic_lds((const void*)wgrad_partial_bf16_kernel<2, 2, 2, 2, kWgRows>, (int)lds);
-            if (rc_lds != NFA_OK) return rc_lds;
-            hipLaunchKernelGGL((wgrad_partial_bf16_kernel<2, 2, 2, 2, kWgRows>), grid, dim3(kBlock), lds, st, a);
+            kern = wgrad_partial_bf16_kernel<2, 2, 2, 2, kWgRows>;
         } else if (p.variant == 0) {
-            constexpr size_t lds = (size_t)kWgRing * kWgRows * (128 + 128) * 4;
-            const int rc_lds = raise_dynamic_lds((const void*)wgrad_partial_kernel<2, 2, 2, 2>, (int)lds);
-            if (rc_lds != NFA_OK) return rc_lds;
-            hipLaunchKernelGGL((wgrad_partial_kernel<2, 2, 2, 2>), grid, dim3(kBlock), lds, st, a);
+            kern = wgrad_partial_kernel<2, 2, 2, 2>;
         } else {
-            constexpr size_t lds = (size_t)kWgRing * kWgRows * (128 + 32) * 4;
-            hipLaunchKernelGGL((wgrad_partial_kernel<1, 1, 4, 1>), grid, dim3(kBlock), lds, st, a);
+            lds = (size_t)kWgRing * kWgRows * (128 + 32) * 4;
+            kern = wgrad_partial_kernel<1, 1, 4, 1>;
         }
-        NFA_HIP_CHECK(hipGetLastError());
+        const int rc = launch_kernel(kern, grid, dim3(kBlock), lds, st, a, 0, false);
+        if (rc != NFA_OK) return rc;
     }
     const int64_t n = (int64_t)O * I + O;   // (problems without a bias gradient skip the last O elements themselves)
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((n + 63) / 64), (unsigned)count), dim3(kBlock), 0, st,
-                       static_cast<const float*>(workspace), r, I, O, p.ksplit, (int64_t)p.stages_total * p.rows, batch);
-    NFA_HIP_CHECK(hipGetLastError());
-    return NFA_OK;
+    return launch_kernel_args(wgrad_reduce_kernel, dim3((unsigned)((n + 63) / 64), (unsigned)count), dim3(kBlock), 0, st, 0,
+                              false, static_cast<const float*>(workspace), r, I, O, p.ksplit,
+                              (int64_t)p.stages_total * p.rows, batch);
 }
 
 extern "C" int nfa_linear_wgrad_f32(const float* inputs, const float* grad_outputs, float* grad_weight,

@@ -245,8 +245,8 @@ int lu_launch(int mode, const float* inputs, const float* lower, const float* up
     int R = 64, best = 0;
     for (int r = kBlock; r >= 64; r -= 64) {
         const size_t lds = lu_lds_bytes(DP, r);
-        if (lds > (size_t)160 * 1024) continue;
-        int blocks = (int)(((size_t)160 * 1024) / lds);
+        if (lds > (size_t)kCuLds) continue;
+        int blocks = (int)((size_t)kCuLds / lds);
         if (blocks > 8) blocks = 8;
         int waves = blocks * (r / 64);
         if (waves > 16) waves = 16;
@@ -258,7 +258,7 @@ int lu_launch(int mode, const float* inputs, const float* lower, const float* up
     if (best == 0) return NFA_ERR_UNSUPPORTED;
     while (R > 64 && (batch + R - 1) / R < (int64_t)cus) R -= 64;
     const size_t lds = lu_lds_bytes(DP, R);
-    int per_cu = (int)(((size_t)160 * 1024) / lds);
+    int per_cu = (int)((size_t)kCuLds / lds);
     if (per_cu > 8) per_cu = 8;
     LuArgs a;
     a.x = inputs;
@@ -287,7 +287,7 @@ int lu_launch(int mode, const float* inputs, const float* lower, const float* up
                            : mode == kLuInverse     ? lu_linear_kernel<kLuInverse>
                            : mode == kLuForwardGrad ? lu_linear_kernel<kLuForwardGrad>
                                                     : lu_linear_kernel<kLuInverseGrad>;
-    return launch_kernel(kern, dim3((unsigned)g), dim3((unsigned)R), lds, (hipStream_t)stream, a, 160 * 1024, false);
+    return launch_kernel(kern, dim3((unsigned)g), dim3((unsigned)R), lds, (hipStream_t)stream, a, kCuLds, false);
 }
 
 }  // namespace

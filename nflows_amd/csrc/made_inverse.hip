@@ -359,7 +359,7 @@ extern "C" int nfa_made_rqs_inverse_f32(const float* inputs, const float* step_b
         return NFA_ERR_INVALID_ARGUMENT;
     const size_t px = (((size_t)a.Xp >> 2) + 15) & ~(size_t)15, ph = (((size_t)a.Hp >> 2) + 15) & ~(size_t)15;   // chunks per sample
     const size_t lds = ((px + (size_t)a.num_vectors * ph) * 4 * kMadeSamples + 2 * (size_t)a.max_block) * sizeof(float);
-    if (lds + 4096 > 160 * 1024) return NFA_ERR_UNSUPPORTED;   // (+ the 2 KB of logits and alignment)
+    if (lds + 4096 > (size_t)kCuLds) return NFA_ERR_UNSUPPORTED;   // (+ the 2 KB of logits and alignment)
     if (batch == 0) return NFA_OK;
     if (!inputs || !step_blocks || !block_starts || !outputs || !logabsdet || !hidden_out) return NFA_ERR_INVALID_ARGUMENT;
     a.z = inputs;
@@ -384,5 +384,5 @@ extern "C" int nfa_made_rqs_inverse_f32(const float* inputs, const float* step_b
                                                   : (lps == 32 ? made_rqs_inverse_kernel<10, 32> : made_rqs_inverse_kernel<10, 16>);
     note_layer_kernel("made_rqs_inverse_kernel<K=%d, lanes_per_sample=%d>", a.sp.K, lps);
     return launch_kernel(kern, dim3((unsigned)blocks), dim3((lps / 4) * kWave), lds, (hipStream_t)stream, a,
-                         160 * 1024 - 4096, false);
+                         kCuLds - 4096, false);
 }

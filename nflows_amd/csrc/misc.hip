@@ -1,5 +1,5 @@
 // Affine / additive coupling (K2), autoregressive affine (K2b), column permutation (K4),
-// per-sample row sum (K3), standard-normal log-prob epilogue, and the library's host utilities.
+// per-sample row sum (K3), standard-normal log-prob epilogue, searchsorted.
 // gfx950 (MI355X) only.  Reference lines are cited in include/nflows_amd.h.
 
 #include "common.hpp"
@@ -7,26 +7,6 @@
 #include <math.h>
 
 namespace nfa {
-
-static thread_local int g_last_hip_error = 0;
-
-int set_hip_error(hipError_t e) {
-    g_last_hip_error = (int)e;
-    return NFA_ERR_HIP;
-}
-
-int device_cu_count() {
-    static int cached[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (cached[dev] == 0) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-            n = 256;
-        cached[dev] = n;
-    }
-    return cached[dev];
-}
 
 // ------------------------------------------------------------------------------------------
 // K2: fused affine / additive coupling.  Same tile scheme as the spline layer: R whole samples
@@ -254,33 +234,13 @@ __global__ void __launch_bounds__(kBlock) rowsum_kernel(const float* __restrict_
 }
 
 static dim3 wave_per_row_grid(int64_t rows) {
-    int64_t blocks = (rows + (kBlock / kWave) - 1) / (kBlock / kWave);
-    const int64_t cap = (int64_t)device_cu_count() * 8;
-    if (blocks > cap) blocks = cap;
-    if (blocks < 1) blocks = 1;
-    return dim3((unsigned)blocks);
+    const int64_t blocks = persistent_grid(device_cu_count(), 8, (rows + (kBlock / kWave) - 1) / (kBlock / kWave));
+    return dim3((unsigned)(blocks < 1 ? 1 : blocks));
 }
-
-constexpr int kMaxDynLdsMisc = 64 * 1024;
 
 }  // namespace nfa
 
 using namespace nfa;
-
-extern "C" int nfa_abi_version(void) { return NFA_ABI_VERSION; }
-extern "C" const char* nfa_build_arch(void) { return "gfx950"; }
-extern "C" int nfa_last_hip_error(void) { return g_last_hip_error; }
-extern "C" const char* nfa_strerror(int code) {
-    switch (code) {
-        case NFA_OK: return "ok";
-        case NFA_ERR_INVALID_ARGUMENT: return "invalid argument";
-        case NFA_ERR_UNSUPPORTED: return "unsupported configuration for the fused kernel";
-        case NFA_ERR_MIN_BIN_WIDTH: return "Minimal bin width too large for the number of bins";
-        case NFA_ERR_MIN_BIN_HEIGHT: return "Minimal bin height too large for the number of bins";
-        case NFA_ERR_HIP: return "HIP runtime error";
-        default: return "unknown error";
-    }
-}
 
 extern "C" int nfa_affine_coupling_f32(const float* inputs, const float* params, const float* scale,
                                        const int64_t* transform_idx, const int64_t* in_perm,
@@ -302,10 +262,7 @@ extern "C" int nfa_affine_coupling_f32(const float* inputs, const float* params,
     AffineArgs a;
     const int D = features, dt = num_transform;
     a.pcols = scale_activation == NFA_SCALE_ADDITIVE ? dt : 2 * dt;
-    int R = dt > 0 ? kBlock / dt : kBlock / (D < kBlock ? D : kBlock);
-    if (R < 1) R = 1;
-    if ((int64_t)R > batch) R = (int)batch;
-    auto lds_floats = [&](int r) {
+    auto lds_floats = [&](int r, int) {
         int o = round_up4(r * a.pcols) + 4;
         a.off_sc = o;
         o += (scale_activation == NFA_SCALE_GIVEN ? round_up4(r * dt) + 4 : 0);
@@ -319,9 +276,8 @@ extern "C" int nfa_affine_coupling_f32(const float* inputs, const float* params,
         o += dt + 2 * D + (D + 3) / 4;
         return o;
     };
-    while (R > 1 && (size_t)lds_floats(R) * 4 > (size_t)kMaxDynLdsMisc) R >>= 1;
-    const size_t lds = (size_t)lds_floats(R) * 4;
-    if (lds > (size_t)kMaxDynLdsMisc || (int64_t)R * D >= 65536) return NFA_ERR_UNSUPPORTED;
+    const SampleTile t = plan_sample_tile(kBlock, dt, D, batch, kDefaultDynLds, lds_floats);
+    if (!t.ok) return NFA_ERR_UNSUPPORTED;
     a.x = inputs;
     a.params = params;
     a.scale = scale;
@@ -334,22 +290,14 @@ extern "C" int nfa_affine_coupling_f32(const float* inputs, const float* params,
     a.batch = batch;
     a.D = D;
     a.dt = dt;
-    a.R = R;
+    a.R = t.R;
     a.activation = scale_activation;
     a.inverse = inverse;
     a.accumulate = (flags & NFA_FLAG_ACCUMULATE_LOGABSDET) ? 1 : 0;
     a.div_dt = make_fastdiv((uint32_t)(dt > 0 ? dt : 1));
     a.div_D = make_fastdiv((uint32_t)D);
-    const int64_t tiles = (batch + R - 1) / R;
-    int per_cu = (int)((size_t)(160 * 1024) / (lds + 256));
-    if (per_cu > 8) per_cu = 8;
-    if (per_cu < 1) per_cu = 1;
-    int64_t g = (int64_t)device_cu_count() * per_cu;
-    if (g > tiles) g = tiles;
-    hipLaunchKernelGGL(affine_coupling_kernel, dim3((unsigned)g), dim3(kBlock), lds,
-                       (hipStream_t)stream, a);
-    NFA_HIP_CHECK(hipGetLastError());
-    return NFA_OK;
+    const int64_t g = persistent_grid(device_cu_count(), t.lds, 8, (batch + t.R - 1) / t.R);
+    return launch_kernel(affine_coupling_kernel, dim3((unsigned)g), dim3(kBlock), t.lds, (hipStream_t)stream, a, 0, false);
 }
 
 extern "C" int nfa_affine_autoregressive_f32(const float* inputs, const float* params, float* outputs,
@@ -358,10 +306,8 @@ extern "C" int nfa_affine_autoregressive_f32(const float* inputs, const float* p
     if (batch < 0 || features < 1) return NFA_ERR_INVALID_ARGUMENT;
     if (batch == 0) return NFA_OK;
     if (!inputs || !params || !outputs || !logabsdet) return NFA_ERR_INVALID_ARGUMENT;
-    hipLaunchKernelGGL(affine_ar_kernel, wave_per_row_grid(batch), dim3(kBlock), 0,
-                       (hipStream_t)stream, inputs, params, outputs, logabsdet, batch, features, inverse);
-    NFA_HIP_CHECK(hipGetLastError());
-    return NFA_OK;
+    return launch_kernel_args(affine_ar_kernel, wave_per_row_grid(batch), dim3(kBlock), 0, (hipStream_t)stream, 0, false,
+                              inputs, params, outputs, logabsdet, batch, features, inverse);
 }
 
 extern "C" int nfa_permute_cols_b32(const void* inputs, const int64_t* perm, void* outputs,
@@ -372,9 +318,7 @@ extern "C" int nfa_permute_cols_b32(const void* inputs, const int64_t* perm, voi
     if (features > 6000) return NFA_ERR_UNSUPPORTED;  // one row (x2) + index must fit in 64 KiB LDS
     PermArgs a;
     const int D = features;
-    int R = (4 * kBlock) / D;  // ~4 words per lane
-    if (R < 1) R = 1;
-    if ((int64_t)R > batch) R = (int)batch;
+    const int R = sample_rows(4 * kBlock, 0, D, batch);  // ~4 words per lane
     a.x = static_cast<const float*>(inputs);
     a.perm = perm;
     a.out = static_cast<float*>(outputs);
@@ -386,13 +330,9 @@ extern "C" int nfa_permute_cols_b32(const void* inputs, const int64_t* perm, voi
     a.off_out = round_up4(R * D) + 4;
     a.off_idx = a.off_out + round_up4(R * D) + 4;
     const size_t lds = (size_t)(a.off_idx + D) * 4;
-    if (lds > (size_t)kMaxDynLdsMisc) return NFA_ERR_UNSUPPORTED;
-    const int64_t tiles = (batch + R - 1) / R;
-    int64_t g = (int64_t)device_cu_count() * 8;
-    if (g > tiles) g = tiles;
-    hipLaunchKernelGGL(permute_cols_kernel, dim3((unsigned)g), dim3(kBlock), lds, (hipStream_t)stream, a);
-    NFA_HIP_CHECK(hipGetLastError());
-    return NFA_OK;
+    if (lds > (size_t)kDefaultDynLds) return NFA_ERR_UNSUPPORTED;
+    const int64_t g = persistent_grid(device_cu_count(), 8, (batch + R - 1) / R);
+    return launch_kernel(permute_cols_kernel, dim3((unsigned)g), dim3(kBlock), lds, (hipStream_t)stream, a, 0, false);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -451,20 +391,16 @@ extern "C" int nfa_sum_count_f64(const float* values, int64_t n, double* out, vo
     if (blocks < 1) blocks = 1;
     double* partial = reinterpret_cast<double*>(workspace);
     unsigned* ticket = reinterpret_cast<unsigned*>(partial + kSumBlocks);
-    hipLaunchKernelGGL(sum_count_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, values, n,
-                       out, partial, ticket);
-    NFA_HIP_CHECK(hipGetLastError());
-    return NFA_OK;
+    return launch_kernel_args(sum_count_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, 0, false,
+                              values, n, out, partial, ticket);
 }
 
 extern "C" int nfa_rowsum_f32(const float* x, float* out, int64_t rows, int64_t cols, void* stream) {
     if (rows < 0 || cols < 0) return NFA_ERR_INVALID_ARGUMENT;
     if (rows == 0) return NFA_OK;
     if (!out || (cols > 0 && !x)) return NFA_ERR_INVALID_ARGUMENT;
-    hipLaunchKernelGGL((rowsum_kernel<false>), wave_per_row_grid(rows), dim3(kBlock), 0,
-                       (hipStream_t)stream, x, (const float*)nullptr, out, rows, cols, 0.0f);
-    NFA_HIP_CHECK(hipGetLastError());
-    return NFA_OK;
+    return launch_kernel_args(rowsum_kernel<false>, wave_per_row_grid(rows), dim3(kBlock), 0, (hipStream_t)stream, 0, false,
+                              x, nullptr, out, rows, cols, 0.0f);
 }
 
 extern "C" int nfa_standard_normal_log_prob_f32(const float* z, const float* logabsdet, float* out,
@@ -473,10 +409,8 @@ extern "C" int nfa_standard_normal_log_prob_f32(const float* z, const float* log
     if (rows == 0) return NFA_OK;
     if (!z || !out) return NFA_ERR_INVALID_ARGUMENT;
     const float log_z = (float)(0.5 * (double)cols * log(2.0 * 3.14159265358979323846));
-    hipLaunchKernelGGL((rowsum_kernel<true>), wave_per_row_grid(rows), dim3(kBlock), 0,
-                       (hipStream_t)stream, z, logabsdet, out, rows, cols, log_z);
-    NFA_HIP_CHECK(hipGetLastError());
-    return NFA_OK;
+    return launch_kernel_args(rowsum_kernel<true>, wave_per_row_grid(rows), dim3(kBlock), 0, (hipStream_t)stream, 0, false,
+                              z, logabsdet, out, rows, cols, log_z);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -555,22 +489,17 @@ extern "C" int nfa_searchsorted_f32(const float* bin_locations, int64_t row_stri
     a.dense = 0;
     if (row_stride == num_knots && num_knots <= 4096) {
         auto bytes = [&](int t) { return (size_t)(round_up4(t * num_knots) + 8) * 4; };
-        while (T > 1 && bytes(T) > (size_t)kMaxDynLdsMisc) T >>= 1;
-        if (bytes(T) <= (size_t)kMaxDynLdsMisc) {   // (a longer row is read in place)
+        const int fit = plan_element_tile(1, kDefaultDynLds, bytes);
+        if (fit > 0) {   // (a longer row is read in place)
+            T = fit;
             lds = bytes(T);
             a.dense = 1;
-        } else {
-            T = kBlock;
         }
     } else if (row_stride == 0) {
         lds = (size_t)round_up4(num_knots) * 4;
-        if (lds > (size_t)kMaxDynLdsMisc) return NFA_ERR_UNSUPPORTED;
+        if (lds > (size_t)kDefaultDynLds) return NFA_ERR_UNSUPPORTED;
     }
     a.T = T;
-    const int64_t tiles = (n + T - 1) / T;
-    int64_t g = (int64_t)device_cu_count() * 8;
-    if (g > tiles) g = tiles;
-    hipLaunchKernelGGL(searchsorted_kernel, dim3((unsigned)g), dim3(kBlock), lds, (hipStream_t)stream, a);
-    NFA_HIP_CHECK(hipGetLastError());
-    return NFA_OK;
+    const int64_t g = persistent_grid(device_cu_count(), 8, (n + T - 1) / T);
+    return launch_kernel(searchsorted_kernel, dim3((unsigned)g), dim3(kBlock), lds, (hipStream_t)stream, a, 0, false);
 }

@@ -976,7 +976,5 @@ extern "C" int nfa_pack_resnet_hidden_train_f32(const float* initial_weight, con
     a.out_features = out_features;
     a.final_tiles = (out_features + 31) / 32;
     const int stages = a.init_ks + 32 * num_blocks + 2 * a.final_tiles + 2 * ((num_identity + 31) / 32) + (out_features + 15) / 16;
-    hipLaunchKernelGGL(pack_resnet_hidden_kernel, dim3(stages + 1), dim3(kBlock), 0, (hipStream_t)stream, a);
-    NFA_HIP_CHECK(hipGetLastError());
-    return NFA_OK;
+    return launch_kernel(pack_resnet_hidden_kernel, dim3(stages + 1), dim3(kBlock), 0, (hipStream_t)stream, a, 0, false);
 }

@@ -25,17 +25,8 @@
 
 #include "rqs_math.hpp"
 
-#include <hip/hip_ext.h>
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
 #include <stdlib.h>
-#include <string.h>
-
-#include <mutex>
-#include <set>
-#include <utility>
-#include <vector>
 
 
 namespace nfa {
@@ -611,57 +602,6 @@ __global__ void __launch_bounds__(kBlock) rqs_coupling_wavetile(const CouplingAr
 }
 
 // ------------------------------------------------------------------------------------------
-constexpr int kMaxDynLds = 64 * 1024;
-
-// ---- optional measurement aid (bench.py): per-launch begin/end timestamps of the K1 kernels.
-// hipExtLaunchKernelGGL attaches a start and a stop event to the dispatch itself, so
-// hipEventElapsedTime(start, stop) is the kernel's own duration on its stream (what rocprofv3's
-// kernel trace reports), free of launch gaps.  Off by default; the only global state in the library.
-struct ProfileState {
-    std::mutex mu;
-    bool enabled = false;
-    size_t capacity = 0;
-    std::vector<hipEvent_t> start, stop;
-};
-static ProfileState g_profile;
-
-// Hands out a start/stop event pair for the next profiled launch (null when profiling is off or
-// the budget is used up).  Shared with the other translation units through common.hpp.
-void profile_next_launch(hipEvent_t* start, hipEvent_t* stop) {
-    *start = *stop = nullptr;
-    std::lock_guard<std::mutex> lock(g_profile.mu);
-    if (g_profile.enabled && g_profile.start.size() < g_profile.capacity) {
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) {
-            g_profile.start.push_back(e0);
-            g_profile.stop.push_back(e1);
-            *start = e0;
-            *stop = e1;
-        }
-    }
-}
-
-static thread_local char g_last_layer_kernel[192] = "";
-
-void note_layer_kernel(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_last_layer_kernel, sizeof(g_last_layer_kernel), fmt, ap);
-    va_end(ap);
-}
-
-int raise_dynamic_lds(const void* kern, int bytes) {
-    static std::mutex mu;
-    static std::set<std::pair<const void*, int>> raised;   // (kernel, device) pairs already opted in
-    int dev = 0;
-    NFA_HIP_CHECK(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(mu);
-    if (raised.count({kern, dev})) return NFA_OK;
-    NFA_HIP_CHECK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    raised.insert({kern, dev});
-    return NFA_OK;
-}
-
 template <int KT, int BLOCK>
 static int launch_coupling(const CouplingArgs& a, int inverse, dim3 grid, size_t lds, hipStream_t st) {
     note_layer_kernel("rqs_coupling_kernel<K=%d, inverse=%d, block=%d>", KT, inverse ? 1 : 0, BLOCK);
@@ -679,23 +619,18 @@ static int launch_wavetile(const CouplingArgs& a, int inverse, hipStream_t st) {
                : (inverse ? rqs_coupling_wavetile<KT, true> : rqs_coupling_wavetile<KT, false>);
     // persistent: exactly the workgroups that are resident together (registers and LDS decide)
     // (per device: occupancy is a property of the device the launch goes to)
-    static int per_cu_cache[64][4] = {};
+    static int resident_cache[64][4] = {};
     int dev = 0;
     NFA_HIP_CHECK(hipGetDevice(&dev));
-    int& per_cu = per_cu_cache[dev & 63][(inverse ? 1 : 0) + (a.bins ? 2 : 0)];
-    if (per_cu == 0) {
+    int& resident = resident_cache[dev & 63][(inverse ? 1 : 0) + (a.bins ? 2 : 0)];
+    if (resident == 0) {
         int n = 0;
         NFA_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, kBlock, lds));
-        per_cu = n > 0 ? n : 1;
-        const char* e = getenv("NFA_K1_WT_PER_CU");   // (experiments: fewer resident workgroups)
-        if (e && atoi(e) > 0 && atoi(e) < per_cu) per_cu = atoi(e);
+        resident = n > 0 ? n : 1;
     }
-    const int log_dt = __builtin_ctz((unsigned)a.dt);
-    const int64_t tiles = a.batch >> (6 - log_dt);
-    int64_t g = (int64_t)device_cu_count() * per_cu;
-    const int64_t need = (tiles + kBlock / kWave - 1) / (kBlock / kWave);
-    if (g > need) g = need;
-    note_layer_kernel("rqs_coupling_wavetile<K=%d, inverse=%d> (%d workgroups per CU)", KT, inverse ? 1 : 0, per_cu);
+    const int64_t tiles = a.batch / (64 / a.dt);   // (64 / d_t rows per wave tile, one wave per tile)
+    const int64_t g = persistent_grid(device_cu_count(), resident, (tiles + kBlock / kWave - 1) / (kBlock / kWave));
+    note_layer_kernel("rqs_coupling_wavetile<K=%d, inverse=%d> (%d workgroups per CU)", KT, inverse ? 1 : 0, resident);
     return launch_kernel(kern, dim3((unsigned)g), dim3(kBlock), lds, st, a);
 }
 
@@ -716,13 +651,21 @@ static int launch_pipelined(const CouplingArgs& a, int inverse, dim3 grid, size_
 
 template <int KT>
 static int launch_elementwise(const ElementwiseArgs& a, int inverse, dim3 grid, size_t lds, hipStream_t st) {
-    if (inverse)
-        hipLaunchKernelGGL((rqs_elementwise_kernel<KT, true>), grid, dim3(kBlock), lds, st, a);
-    else
-        hipLaunchKernelGGL((rqs_elementwise_kernel<KT, false>), grid, dim3(kBlock), lds, st, a);
-    NFA_HIP_CHECK(hipGetLastError());
-    return NFA_OK;
+    return launch_kernel(inverse ? rqs_elementwise_kernel<KT, true> : rqs_elementwise_kernel<KT, false>, grid, dim3(kBlock),
+                         lds, st, a, 0, false);
 }
+
+// The launchers' instances, in a fixed order: the order of first use decides where each kernel lands in the code object,
+// and the cascade below is free to change without moving them.
+template int launch_wavetile<8>(const CouplingArgs&, int, hipStream_t);
+template int launch_wavetile<10>(const CouplingArgs&, int, hipStream_t);
+template int launch_coupling<10, kBlock>(const CouplingArgs&, int, dim3, size_t, hipStream_t);
+template int launch_coupling<8, kBlock>(const CouplingArgs&, int, dim3, size_t, hipStream_t);
+template int launch_pipelined<4>(const CouplingArgs&, int, dim3, size_t, hipStream_t);
+template int launch_pipelined<10>(const CouplingArgs&, int, dim3, size_t, hipStream_t);
+template int launch_pipelined<8>(const CouplingArgs&, int, dim3, size_t, hipStream_t);
+template int launch_coupling<4, kBlock>(const CouplingArgs&, int, dim3, size_t, hipStream_t);
+template int launch_coupling<0, kBlock>(const CouplingArgs&, int, dim3, size_t, hipStream_t);
 
 }  // namespace nfa
 
@@ -746,41 +689,26 @@ extern "C" int nfa_rqs_coupling_f32(const float* inputs, const float* params,
         return NFA_ERR_INVALID_ARGUMENT;
     if (features > 65535) return NFA_ERR_UNSUPPORTED;
 
-    const int P = a.sp.P, D = features, dt = num_transform;
-    const int BT = kBlock;
-    // samples per tile: aim at one item per lane, whole samples, LDS within budget
-    int R = dt > 0 ? BT / dt : BT / (D < BT ? D : BT);
-    if (R < 1) R = 1;
-    if ((int64_t)R > batch) R = (int)batch;
-    int C = 0;  // splines per chunk (0 = whole tile)
-    auto lds_floats = [&](int r, int* ox, int* oo, int* ol, int* oi) {
-        const int chunk_items = C > 0 ? C : r * dt;
-        int o = round_up4(chunk_items * P) + 4;
-        *ox = o;
+    // 1. the plan: about one item per lane, whole samples, LDS within budget
+    const int P = a.sp.P, K = a.sp.K, D = features, dt = num_transform;
+    auto lds_floats = [&](int r, int chunk) {
+        int o = round_up4((chunk > 0 ? chunk : r * dt) * P) + 4;
+        a.off_x = o;
         o += round_up4(r * D) + 4;
-        *oo = o;
+        a.off_out = o;
         o += round_up4(r * D) + 4;
-        *ol = o;
-        o += round_up4(C > 0 ? kBlock : (r * dt > kBlock / kWave ? r * dt : kBlock / kWave));
-        *oi = o;
+        a.off_lad = o;
+        o += round_up4(chunk > 0 ? kBlock : (r * dt > kBlock / kWave ? r * dt : kBlock / kWave));
+        a.off_idx = o;
         o += dt + 2 * D + (D + 3) / 4;
         return o;
     };
-    int ox, oo, ol, oi;
-    while (R > 1 && (size_t)lds_floats(R, &ox, &oo, &ol, &oi) * 4 > (size_t)kMaxDynLds) R >>= 1;
-    if (R == 1 && (size_t)lds_floats(1, &ox, &oo, &ol, &oi) * 4 > (size_t)kMaxDynLds) {
-        // one sample does not fit: stream its parameters through LDS in chunks of C splines
-        const size_t fixed = (size_t)(2 * (round_up4(D) + 4) + kBlock + dt + 2 * D + (D + 3) / 4 + 8) * 4;
-        if (fixed + (size_t)kBlock * P * 4 > (size_t)kMaxDynLds) return NFA_ERR_UNSUPPORTED;
-        C = (int)(((size_t)kMaxDynLds - fixed) / ((size_t)P * 4));
-        C = (C / kBlock) * kBlock;
-        if (C >= dt) C = 0;
-    }
-    const size_t lds = (size_t)lds_floats(R, &ox, &oo, &ol, &oi) * 4;
-    if (lds > (size_t)kMaxDynLds || (int64_t)R * dt >= 65536 || (int64_t)R * D >= 65536)
-        return NFA_ERR_UNSUPPORTED;
-    a.C = C > 0 ? C : R * dt;
-
+    const size_t chunk_fixed = (size_t)(2 * (round_up4(D) + 4) + kBlock + dt + 2 * D + (D + 3) / 4 + 8) * 4;
+    const SampleTile t = plan_sample_tile(kBlock, dt, D, batch, kDefaultDynLds, lds_floats, P, chunk_fixed);
+    if (!t.ok) return NFA_ERR_UNSUPPORTED;
+    const int R = t.R;
+    const size_t lds = t.lds;
+    a.C = t.C > 0 ? t.C : R * dt;
     a.x = inputs;
     a.params = params;
     a.tidx = transform_idx;
@@ -797,20 +725,8 @@ extern "C" int nfa_rqs_coupling_f32(const float* inputs, const float* params,
     a.accumulate = (flags & NFA_FLAG_ACCUMULATE_LOGABSDET) ? 1 : 0;
     a.div_dt = make_fastdiv((uint32_t)(dt > 0 ? dt : 1));
     a.div_D = make_fastdiv((uint32_t)D);
-    a.off_x = ox;
-    a.off_out = oo;
-    a.off_lad = ol;
-    a.off_idx = oi;
 
-    const int64_t tiles = (batch + R - 1) / R;
     const int cus = device_cu_count();
-    int per_cu = (int)((size_t)(160 * 1024) / (lds + 256));
-    const int cap = 8;
-    if (per_cu > cap) per_cu = cap;
-    if (per_cu < 1) per_cu = 1;
-    int64_t g = (int64_t)cus * per_cu;
-    if (g > tiles) g = tiles;
-    const dim3 grid((unsigned)g);
     hipStream_t st = (hipStream_t)stream;
     // aligned layouts take the software-pipelined kernel
     static const int use_pipe = [] {
@@ -818,68 +734,51 @@ extern "C" int nfa_rqs_coupling_f32(const float* inputs, const float* params,
         return e ? atoi(e) : 1;
     }();
     const int nv = (int)(((int64_t)R * dt * P / 4 + kBlock - 1) / kBlock);
-    const bool aligned = dt > 0 && (dt * P) % 4 == 0 && D % 4 == 0 && R * dt <= kBlock &&
-                         R * D <= 2 * kBlock && (int64_t)R <= batch &&
-                         (reinterpret_cast<uintptr_t>(params) & 15) == 0 &&
-                         (reinterpret_cast<uintptr_t>(inputs) & 15) == 0 &&
-                         (reinterpret_cast<uintptr_t>(outputs) & 15) == 0;
-    const bool pipe_k = a.sp.K == 4 || a.sp.K == 8 || a.sp.K == 10;
-    if (use_pipe && aligned && pipe_k && nv <= (3 * a.sp.K + 4) / 4) {
-        const int64_t full_rows = (batch / R) * R;
-        CouplingArgs f = a;
-        f.batch = full_rows;
-        // wave tiles (LDS-DMA, no workgroup barriers) where the layout allows: linear tails, 8 / 10 bins, d_t a
-        // power of two with D = 2 d_t; NFA_K1_WAVETILE=0 keeps the register-pipelined kernel (A/B runs)
-        // (read per launch on purpose: tests/test_gpu_steep.py and bench.py switch it between launches of one process)
-        const char* wt_env = getenv("NFA_K1_WAVETILE");
-        const bool wavetile = (!wt_env || atoi(wt_env) != 0) && a.sp.linear && (a.sp.K == 8 || a.sp.K == 10) &&
-                              dt >= 4 && dt <= 64 && (dt & (dt - 1)) == 0 && D == 2 * dt && a.sp.P == 3 * a.sp.K - 1 &&
-                              (reinterpret_cast<uintptr_t>(logabsdet) & 3) == 0;
-        const int64_t wt_rows = wavetile ? (batch >> (6 - __builtin_ctz((unsigned)dt))) << (6 - __builtin_ctz((unsigned)dt)) : 0;
-        if (wavetile && wt_rows > 0) {
-            // whole wave tiles (64 / d_t rows each); the < 64 / d_t rows behind them go to the generic kernel below
-            f.batch = wt_rows;
-            const int wrc = a.sp.K == 8 ? launch_wavetile<8>(f, inverse, st) : launch_wavetile<10>(f, inverse, st);
-            if (wrc != NFA_OK) return wrc;
-            if (wt_rows == batch) return NFA_OK;
-            a.x = inputs + wt_rows * D;
-            a.params = params + wt_rows * (int64_t)dt * P;
-            a.out = outputs + wt_rows * D;
-            a.lad = logabsdet + wt_rows;
-            if (bin_idx) a.bins = bin_idx + wt_rows * dt;
-            a.batch = batch - wt_rows;
-            return a.sp.K == 10 ? launch_coupling<10, kBlock>(a, inverse, dim3(1), lds, st)
-                                : launch_coupling<8, kBlock>(a, inverse, dim3(1), lds, st);
-        } else {
+    const bool aligned = aligned_tile(dt, D, P, R, batch) && aligned16(params) && aligned16(inputs) && aligned16(outputs);
+    const bool pipe_k = K == 4 || K == 8 || K == 10;
+    const bool pipelined = use_pipe && aligned && pipe_k && nv <= (3 * K + 4) / 4;
+    // wave tiles (LDS-DMA, no workgroup barriers) where the layout allows: linear tails, 8 / 10 bins, d_t a
+    // power of two with D = 2 d_t; NFA_K1_WAVETILE=0 keeps the register-pipelined kernel (A/B runs)
+    // (read per launch on purpose: tests/test_gpu_steep.py and bench.py switch it between launches of one process)
+    const char* wt_env = pipelined ? getenv("NFA_K1_WAVETILE") : nullptr;
+    const bool wavetile = pipelined && (!wt_env || atoi(wt_env) != 0) && a.sp.linear && (K == 8 || K == 10) &&
+                          dt >= 4 && dt <= 64 && (dt & (dt - 1)) == 0 && D == 2 * dt && P == 3 * K - 1 &&
+                          (reinterpret_cast<uintptr_t>(logabsdet) & 3) == 0;
+
+    // 2. whole wave tiles (64 / d_t rows each), 3. otherwise full rows of R through the pipelined kernel
+    const int64_t wt_rows = wavetile ? full_rows(batch, 64 / dt) : 0;
+    int64_t done = 0;   // rows the tiled kernels take
+    CouplingArgs f = a;
+    if (wt_rows > 0) {
+        f.batch = wt_rows;
+        rc = K == 8 ? launch_wavetile<8>(f, inverse, st) : launch_wavetile<10>(f, inverse, st);
+        done = f.batch;
+    } else if (pipelined) {
+        f.batch = full_rows(batch, R);
         // one block fewer per CU than LDS alone would allow: the prefetch registers cost occupancy
         // (K = 4 needs only ~76 VGPRs: 6 waves per SIMD)
-        const int pipe_blocks = a.sp.K <= 4 ? 6 : NFA_PIPE_WAVES;
-        int64_t gp = (int64_t)cus * (per_cu > pipe_blocks ? pipe_blocks : per_cu);
-        if (gp > full_rows / R) gp = full_rows / R;
-        const dim3 pgrid((unsigned)gp);
-        int prc;
-        switch (a.sp.K) {
-            case 4: prc = launch_pipelined<4>(f, inverse, pgrid, lds, st); break;
-            case 10: prc = launch_pipelined<10>(f, inverse, pgrid, lds, st); break;
-            default: prc = launch_pipelined<8>(f, inverse, pgrid, lds, st); break;
+        const dim3 pgrid((unsigned)persistent_grid(cus, lds, K <= 4 ? 6 : NFA_PIPE_WAVES, f.batch / R));
+        switch (K) {
+            case 4: rc = launch_pipelined<4>(f, inverse, pgrid, lds, st); break;
+            case 10: rc = launch_pipelined<10>(f, inverse, pgrid, lds, st); break;
+            default: rc = launch_pipelined<8>(f, inverse, pgrid, lds, st); break;
         }
-        if (prc != NFA_OK) return prc;
-        }
-        if (full_rows == batch) return NFA_OK;
-        // leftover rows (< R): generic kernel on the tail of every array
-        a.x = inputs + full_rows * D;
-        a.params = params + full_rows * (int64_t)dt * P;
-        a.out = outputs + full_rows * D;
-        a.lad = logabsdet + full_rows;
-        if (bin_idx) a.bins = bin_idx + full_rows * dt;
-        a.batch = batch - full_rows;
-        switch (a.sp.K) {
-            case 4: return launch_coupling<4, kBlock>(a, inverse, dim3(1), lds, st);
-            case 10: return launch_coupling<10, kBlock>(a, inverse, dim3(1), lds, st);
-            default: return launch_coupling<8, kBlock>(a, inverse, dim3(1), lds, st);
-        }
+        done = f.batch;
     }
-    switch (a.sp.K) {
+    if (rc != NFA_OK || done == batch) return rc;
+
+    // 4. the generic kernel: everything, or the leftover rows (fewer than a tile) in one workgroup on the tail of every array
+    dim3 grid((unsigned)persistent_grid(cus, lds, 8, (batch + R - 1) / R));
+    if (done > 0) {
+        a.x += done * D;
+        a.params += done * (int64_t)dt * P;
+        a.out += done * D;
+        a.lad += done;
+        if (a.bins) a.bins += done * dt;
+        a.batch -= done;
+        grid = dim3(1);
+    }
+    switch (K) {
         case 4: return launch_coupling<4, kBlock>(a, inverse, grid, lds, st);
         case 8: return launch_coupling<8, kBlock>(a, inverse, grid, lds, st);
         case 10: return launch_coupling<10, kBlock>(a, inverse, grid, lds, st);
@@ -922,58 +821,17 @@ extern "C" int nfa_rqs_elementwise_f32(const float* inputs, const float* uw, int
     a.packed = (uh == uw + K) && (a.nd == 0 || ud == uw + 2 * K) && stride_w == P && stride_h == P &&
                (a.nd == 0 || stride_d == P);
     a.slot = P | 1;
-    int T = kBlock;
     auto lds_bytes = [&](int t) {
         return a.packed ? (size_t)(round_up4(t * P) + 8) * 4 : (size_t)t * a.slot * 4;
     };
-    while (T > 1 && lds_bytes(T) > (size_t)kMaxDynLds) T >>= 1;
+    const int T = plan_element_tile(1, kDefaultDynLds, lds_bytes);
+    if (T == 0) return NFA_ERR_UNSUPPORTED;
     const size_t lds = lds_bytes(T);
-    if (lds > (size_t)kMaxDynLds) return NFA_ERR_UNSUPPORTED;
     a.T = T;
-    const int64_t tiles = (n + T - 1) / T;
-    const int cus = device_cu_count();
-    int per_cu = (int)((size_t)(160 * 1024) / (lds + 256));
-    if (per_cu > 8) per_cu = 8;
-    if (per_cu < 1) per_cu = 1;
-    int64_t g = (int64_t)cus * per_cu;
-    if (g > tiles) g = tiles;
-    const dim3 grid((unsigned)g);
+    const dim3 grid((unsigned)persistent_grid(device_cu_count(), lds, 8, (n + T - 1) / T));
     hipStream_t st = (hipStream_t)stream;
     switch (K) {
         case 8: return launch_elementwise<8>(a, inverse, grid, lds, st);
         default: return launch_elementwise<0>(a, inverse, grid, lds, st);
     }
-}
-
-
-extern "C" int nfa_last_layer_kernel(char* buffer, int32_t capacity) {
-    if (capacity < 0 || (capacity > 0 && !buffer)) return NFA_ERR_INVALID_ARGUMENT;
-    if (capacity > 0) snprintf(buffer, (size_t)capacity, "%s", g_last_layer_kernel);
-    return (int)strlen(g_last_layer_kernel);
-}
-
-extern "C" int nfa_profile_enable(int32_t max_launches) {
-    if (max_launches < 0) return NFA_ERR_INVALID_ARGUMENT;
-    std::lock_guard<std::mutex> lock(g_profile.mu);
-    g_profile.enabled = max_launches > 0;
-    g_profile.capacity = (size_t)max_launches;
-    return NFA_OK;
-}
-
-extern "C" int nfa_profile_collect(float* durations_ms, int32_t capacity, int32_t* count) {
-    if (!count || capacity < 0 || (capacity > 0 && !durations_ms)) return NFA_ERR_INVALID_ARGUMENT;
-    std::lock_guard<std::mutex> lock(g_profile.mu);
-    int32_t n = 0;
-    for (size_t i = 0; i < g_profile.start.size(); ++i) {
-        NFA_HIP_CHECK(hipEventSynchronize(g_profile.stop[i]));
-        float ms = 0.0f;
-        NFA_HIP_CHECK(hipEventElapsedTime(&ms, g_profile.start[i], g_profile.stop[i]));
-        if (n < capacity) durations_ms[n++] = ms;
-        (void)hipEventDestroy(g_profile.start[i]);
-        (void)hipEventDestroy(g_profile.stop[i]);
-    }
-    g_profile.start.clear();
-    g_profile.stop.clear();
-    *count = n;
-    return NFA_OK;
 }

@@ -479,34 +479,18 @@ __global__ void __launch_bounds__(kBlock, 3) rqs_coupling_backward_pipelined(con
     if (my_status && a.status) atomicOr(a.status, my_status);
 }
 
-constexpr int kMaxDynLdsBwd = 64 * 1024;
-
 template <int KT>
 static int launch_backward_pipelined(const BwdArgs& a, int inverse, dim3 grid, size_t lds, hipStream_t st) {
-    if (a.sp.linear) {
-        if (inverse)
-            hipLaunchKernelGGL((rqs_coupling_backward_pipelined<KT, true, true>), grid, dim3(kBlock), lds, st, a);
-        else
-            hipLaunchKernelGGL((rqs_coupling_backward_pipelined<KT, false, true>), grid, dim3(kBlock), lds, st, a);
-    } else {
-        if (inverse)
-            hipLaunchKernelGGL((rqs_coupling_backward_pipelined<KT, true, false>), grid, dim3(kBlock), lds, st, a);
-        else
-            hipLaunchKernelGGL((rqs_coupling_backward_pipelined<KT, false, false>), grid, dim3(kBlock), lds, st, a);
-    }
-    NFA_HIP_CHECK(hipGetLastError());
-    return NFA_OK;
+    void (*kern)(const BwdArgs) = nullptr;
+    if (a.sp.linear) kern = inverse ? rqs_coupling_backward_pipelined<KT, true, true> : rqs_coupling_backward_pipelined<KT, false, true>;
+    else kern = inverse ? rqs_coupling_backward_pipelined<KT, true, false> : rqs_coupling_backward_pipelined<KT, false, false>;
+    return launch_kernel(kern, grid, dim3(kBlock), lds, st, a, 0, false);
 }
-
 
 template <int KT>
 static int launch_backward(const BwdArgs& a, int inverse, dim3 grid, size_t lds, hipStream_t st) {
-    if (inverse)
-        hipLaunchKernelGGL((rqs_coupling_backward_kernel<KT, true>), grid, dim3(kBlock), lds, st, a);
-    else
-        hipLaunchKernelGGL((rqs_coupling_backward_kernel<KT, false>), grid, dim3(kBlock), lds, st, a);
-    NFA_HIP_CHECK(hipGetLastError());
-    return NFA_OK;
+    return launch_kernel(inverse ? rqs_coupling_backward_kernel<KT, true> : rqs_coupling_backward_kernel<KT, false>, grid,
+                         dim3(kBlock), lds, st, a, 0, false);
 }
 
 }  // namespace nfa
@@ -531,13 +515,8 @@ extern "C" int nfa_rqs_coupling_backward_f32(const float* inputs, const float* p
         return NFA_ERR_INVALID_ARGUMENT;
     if (features > 65535) return NFA_ERR_UNSUPPORTED;
     const int P = a.sp.P, D = features, dt = num_transform;
-    int R = dt > 0 ? kBlock / dt : kBlock / (D < kBlock ? D : kBlock);
-    if (R < 1) R = 1;
-    if ((int64_t)R > batch) R = (int)batch;
-    int C = 0;
-    auto lds_floats = [&](int r) {
-        const int chunk_items = C > 0 ? C : r * dt;
-        int o = round_up4(chunk_items * P) + 8;
+    auto lds_floats = [&](int r, int chunk) {
+        int o = round_up4((chunk > 0 ? chunk : r * dt) * P) + 8;
         a.off_x = o;
         o += round_up4(r * D) + 4;
         a.off_gy = o;
@@ -548,18 +527,12 @@ extern "C" int nfa_rqs_coupling_backward_f32(const float* inputs, const float* p
         o += dt + 2 * D + (D + 3) / 4;
         return o;
     };
-    while (R > 1 && (size_t)lds_floats(R) * 4 > (size_t)kMaxDynLdsBwd) R >>= 1;
-    if (R == 1 && (size_t)lds_floats(1) * 4 > (size_t)kMaxDynLdsBwd) {
-        const size_t fixed = (size_t)(3 * (round_up4(D) + 4) + dt + 2 * D + (D + 3) / 4 + 16) * 4;
-        if (fixed + (size_t)kBlock * P * 4 > (size_t)kMaxDynLdsBwd) return NFA_ERR_UNSUPPORTED;
-        C = (int)(((size_t)kMaxDynLdsBwd - fixed) / ((size_t)P * 4));
-        C = (C / kBlock) * kBlock;
-        if (C >= dt) C = 0;
-    }
-    const size_t lds = (size_t)lds_floats(R) * 4;
-    if (lds > (size_t)kMaxDynLdsBwd || (int64_t)R * dt >= 65536 || (int64_t)R * D >= 65536)
-        return NFA_ERR_UNSUPPORTED;
-    a.C = C > 0 ? C : (R * dt > 0 ? R * dt : 1);
+    const size_t chunk_fixed = (size_t)(3 * (round_up4(D) + 4) + dt + 2 * D + (D + 3) / 4 + 16) * 4;
+    const SampleTile t = plan_sample_tile(kBlock, dt, D, batch, kDefaultDynLds, lds_floats, P, chunk_fixed);
+    if (!t.ok) return NFA_ERR_UNSUPPORTED;
+    const int R = t.R;
+    const size_t lds = t.lds;
+    a.C = t.C > 0 ? t.C : (R * dt > 0 ? R * dt : 1);
     a.x = inputs;
     a.params = params;
     a.tidx = transform_idx;
@@ -576,41 +549,35 @@ extern "C" int nfa_rqs_coupling_backward_f32(const float* inputs, const float* p
     a.R = R;
     a.div_dt = make_fastdiv((uint32_t)(dt > 0 ? dt : 1));
     a.div_D = make_fastdiv((uint32_t)D);
-    const int64_t tiles = (batch + R - 1) / R;
-    int per_cu = (int)((size_t)(160 * 1024) / (lds + 256));
-    if (per_cu > 6) per_cu = 6;
-    if (per_cu < 1) per_cu = 1;
-    int64_t g = (int64_t)device_cu_count() * per_cu;
-    if (g > tiles) g = tiles;
+    const int cus = device_cu_count();
     const int inverse = flags & NFA_FLAG_INVERSE;
+    hipStream_t st = (hipStream_t)stream;
     // aligned layouts with K = 8 take the software-pipelined kernel; leftover rows (< R) follow in
     // one workgroup of the generic kernel
     static const int use_pipe = [] {
         const char* e = getenv("NFA_K1_BWD_PIPELINE");
         return e ? atoi(e) : 1;
     }();
-    auto aligned16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    if (use_pipe && a.sp.K == 8 && C == 0 && dt > 0 && (dt * P) % 4 == 0 && D % 4 == 0 && R * dt <= kBlock &&
-        R * D <= 2 * kBlock && (int64_t)R <= batch && aligned16(params) && aligned16(inputs) &&
+    dim3 grid((unsigned)persistent_grid(cus, lds, 6, (batch + R - 1) / R));
+    if (use_pipe && a.sp.K == 8 && t.C == 0 && aligned_tile(dt, D, P, R, batch) && aligned16(params) && aligned16(inputs) &&
         aligned16(grad_outputs) && aligned16(grad_inputs) && aligned16(grad_params)) {
-        const int64_t full_rows = (batch / R) * R;
+        const int64_t done = full_rows(batch, R);
         BwdArgs f = a;
-        f.batch = full_rows;
-        int64_t gp = (int64_t)device_cu_count() * (per_cu > 3 ? 3 : per_cu);
-        if (gp > full_rows / R) gp = full_rows / R;
-        rc = launch_backward_pipelined<8>(f, inverse, dim3((unsigned)gp), lds, (hipStream_t)stream);
-        if (rc != NFA_OK || full_rows == batch) return rc;
-        a.x = inputs + full_rows * D;
-        a.params = params + full_rows * (int64_t)dt * P;
-        a.gout = grad_outputs + full_rows * D;
-        a.glad = grad_logabsdet ? grad_logabsdet + full_rows : nullptr;
-        a.gin = grad_inputs + full_rows * D;
-        a.gparams = grad_params + full_rows * (int64_t)dt * P;
-        a.batch = batch - full_rows;
-        return launch_backward<8>(a, inverse, dim3(1), lds, (hipStream_t)stream);
+        f.batch = done;
+        const dim3 pgrid((unsigned)persistent_grid(cus, lds, 3, done / R));
+        rc = launch_backward_pipelined<8>(f, inverse, pgrid, lds, st);
+        if (rc != NFA_OK || done == batch) return rc;
+        a.x += done * D;
+        a.params += done * (int64_t)dt * P;
+        a.gout += done * D;
+        if (a.glad) a.glad += done;
+        a.gin += done * D;
+        a.gparams += done * (int64_t)dt * P;
+        a.batch -= done;
+        grid = dim3(1);
     }
     switch (a.sp.K) {
-        case 8: return launch_backward<8>(a, inverse, dim3((unsigned)g), lds, (hipStream_t)stream);
-        default: return launch_backward<0>(a, inverse, dim3((unsigned)g), lds, (hipStream_t)stream);
+        case 8: return launch_backward<8>(a, inverse, grid, lds, st);
+        default: return launch_backward<0>(a, inverse, grid, lds, st);
     }
 }

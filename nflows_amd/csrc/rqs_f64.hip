@@ -93,9 +93,7 @@ static int fill_f64(Rqs64Args& a, const double* inputs, const double* unnormaliz
 }
 
 static unsigned grid_f64(int64_t n) {
-    int64_t blocks = (n + kBlock - 1) / kBlock;
-    const int64_t cap = (int64_t)device_cu_count() * 16;
-    return (unsigned)(blocks > cap ? cap : blocks);
+    return (unsigned)persistent_grid(device_cu_count(), 16, (n + kBlock - 1) / kBlock);
 }
 
 }  // namespace nfa
@@ -118,9 +116,7 @@ extern "C" int nfa_rqs_elementwise_f64(const double* inputs, const double* unnor
     a.lad = logabsdet;
     a.bins = bin_idx;
     a.status = status;
-    hipLaunchKernelGGL(rqs_elementwise_f64_kernel, dim3(grid_f64(n)), dim3(kBlock), 0, (hipStream_t)stream, a);
-    NFA_HIP_CHECK(hipGetLastError());
-    return NFA_OK;
+    return launch_kernel(rqs_elementwise_f64_kernel, dim3(grid_f64(n)), dim3(kBlock), 0, (hipStream_t)stream, a, 0, false);
 }
 
 extern "C" int nfa_rqs_elementwise_backward_f64(const double* inputs, const double* unnormalized_widths,
@@ -147,7 +143,6 @@ extern "C" int nfa_rqs_elementwise_backward_f64(const double* inputs, const doub
     b.guw = grad_widths;
     b.guh = grad_heights;
     b.gud = grad_derivatives;
-    hipLaunchKernelGGL(rqs_elementwise_backward_f64_kernel, dim3(grid_f64(n)), dim3(kBlock), 0, (hipStream_t)stream, b);
-    NFA_HIP_CHECK(hipGetLastError());
-    return NFA_OK;
+    return launch_kernel(rqs_elementwise_backward_f64_kernel, dim3(grid_f64(n)), dim3(kBlock), 0, (hipStream_t)stream, b, 0,
+                         false);
 }

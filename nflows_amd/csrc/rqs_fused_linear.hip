@@ -314,30 +314,18 @@ extern "C" int nfa_rqs_coupling_fused_linear_f32(const float* inputs, const floa
     a.div_D = make_fastdiv((uint32_t)features);
     a.accumulate = (flags & NFA_FLAG_ACCUMULATE_LOGABSDET) ? 1 : 0;
     a.trace = g_k7_trace;
-    const int64_t cap = (int64_t)device_cu_count() * 2;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    profile_next_launch(&e0, &e1);
+    const int cus = device_cu_count();
     hipStream_t st = (hipStream_t)stream;
     const dim3 block(kBlock);
     const bool inverse = (flags & NFA_FLAG_INVERSE) != 0;
     note_layer_kernel("%s<inverse=%d>", split_bf16 ? "rqs_fused_linear_bf16_kernel" : "rqs_fused_linear_kernel", inverse ? 1 : 0);
     const size_t ybytes = (size_t)(kBlock / kWave) * 32 * (num_transform | 1) * sizeof(float);
     if (split_bf16) {
-        int64_t blocks = batch >> 7;
-        if (blocks > cap) blocks = cap;
-        const dim3 grid((unsigned)blocks);
+        const dim3 grid((unsigned)persistent_grid(cus, 2, batch >> 7));
         const size_t lds = ybytes + 2 * kWTileVec4 * 16;
-        auto kern = inverse ? rqs_fused_linear_bf16_kernel<true> : rqs_fused_linear_bf16_kernel<false>;
-        if (e0) hipExtLaunchKernelGGL(kern, grid, block, lds, st, e0, e1, 0, a);
-        else hipLaunchKernelGGL(kern, grid, block, lds, st, a);
-    } else {
-        int64_t blocks = ((batch >> 5) + 3) / 4;
-        if (blocks > cap) blocks = cap;
-        const dim3 grid((unsigned)blocks);
-        auto kern = inverse ? rqs_fused_linear_kernel<true> : rqs_fused_linear_kernel<false>;
-        if (e0) hipExtLaunchKernelGGL(kern, grid, block, ybytes, st, e0, e1, 0, a);
-        else hipLaunchKernelGGL(kern, grid, block, ybytes, st, a);
+        return launch_kernel(inverse ? rqs_fused_linear_bf16_kernel<true> : rqs_fused_linear_bf16_kernel<false>, grid, block,
+                             lds, st, a);
     }
-    NFA_HIP_CHECK(hipGetLastError());
-    return NFA_OK;
+    const dim3 grid((unsigned)persistent_grid(cus, 2, ((batch >> 5) + 3) / 4));
+    return launch_kernel(inverse ? rqs_fused_linear_kernel<true> : rqs_fused_linear_kernel<false>, grid, block, ybytes, st, a);
 }

@@ -120,7 +120,7 @@ static int launch_resnet_layers(const LayerCall& c, const int32_t* redo = nullpt
     if (!redo)
         note_layer_kernel("rqs_resnet_kernel<inverse=%d, init_ks=%d, pipe=%d, K=%d, ctx=%d, act=%d%s>", inv ? 1 : 0, init_ks,
                           pipe, a.sp.K, with_ctx ? 1 : 0, activation, no_tails ? ", tails=none" : "");
-    return launch_kernel(kern, dim3((unsigned)blocks), dim3(kBlock), lds, (hipStream_t)c.stream, a, 160 * 1024 - 2048,
+    return launch_kernel(kern, dim3((unsigned)blocks), dim3(kBlock), lds, (hipStream_t)c.stream, a, kCuLds - 2048,
                          !redo);
 }
 

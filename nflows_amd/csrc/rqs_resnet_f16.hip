@@ -127,7 +127,7 @@ static int launch_f16(const LayerCall& c, int32_t* dbg_bins = nullptr, float* db
     int nw = ((c.batch & 255) == 0 && (c.batch >> 8) >= cus) ? 8 : 4;
     if (force_nw == 4 || (force_nw == 8 && (c.batch & 255) == 0)) nw = force_nw;
     const size_t lds_static = 1024;   // s_final, s_bad, s_sync (rounded up)
-    const size_t lds_cap = 160 * 1024 - lds_static;
+    const size_t lds_cap = kCuLds - lds_static;
     auto lds_for = [&](int n, int ring) {
         return (size_t)ring * k8h::kStageVec4 * 16 + (size_t)n * c.features * k8h::kRowPad * sizeof(float) +
                (size_t)2 * ((param_words + 3) & ~3) * sizeof(float);

@@ -605,7 +605,7 @@ extern "C" int nfa_rqs_flow_resnet_f16x2_colsplit_f32(const float* inputs, const
     const int occ = RT == 2 ? 2 : 1;
     const size_t lds = (size_t)2 * k8c::x_vec4_of(RT) * 16 + (size_t)features * k8c::row_pad_of(RT) * sizeof(float) +
                        (size_t)2 * ((param_words + 3) & ~3) * sizeof(float);
-    const size_t lds_cap = 160 * 1024 - 8192;   // (beside 4.6 KB of static arrays)
+    const size_t lds_cap = kCuLds - 8192;   // (beside 4.6 KB of static arrays)
     if (lds > lds_cap) return NFA_ERR_UNSUPPORTED;
     int64_t blocks = batch / k8c::rows_of(RT);
     if (blocks > (int64_t)cus * occ) blocks = (int64_t)cus * occ;
@@ -614,8 +614,9 @@ extern "C" int nfa_rqs_flow_resnet_f16x2_colsplit_f32(const float* inputs, const
     const k8h::KernelFn kern = RT == 2 ? (init_ks == 2 ? f16c_instance<2, 2, 2>(inv) : f16c_instance<1, 2, 2>(inv))
                                        : (init_ks == 2 ? f16c_instance<2, 4, 1>(inv) : f16c_instance<1, 4, 1>(inv));
     note_layer_kernel("k8c::rqs_resnet_f16c_kernel<inverse=%d, init_ks=%d, waves=4, rows=%d, per_cu=%d, K=8>", inv ? 1 : 0, init_ks, 16 * RT, occ);
-    hipLaunchKernelGGL(k8c::zero_words_kernel, dim3((unsigned)((batch / 128 + 255) / 256)), dim3(256), 0, st, redo_blocks,
-                       (int)(batch / 128));
+    rc = launch_kernel_args(k8c::zero_words_kernel, dim3((unsigned)((batch / 128 + 255) / 256)), dim3(256), 0, st, 0, false,
+                            redo_blocks, (int)(batch / 128));
+    if (rc != NFA_OK) return rc;
     rc = launch_kernel(kern, dim3((unsigned)blocks), dim3(k8c::kThreads), lds, st, a, (int)lds_cap);
     if (rc != NFA_OK) return rc;
 #ifdef NFA_K8C_TRACE

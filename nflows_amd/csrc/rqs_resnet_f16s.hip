@@ -589,7 +589,7 @@ static int launch_tile16(const LayerCall& c, int32_t* dbg_bins) {
     // of four transformed features -- the same count as K8h's stream
     a.num_stages = c.param_stages + (init_ks == 2 ? 2 : 1) + 8 * c.num_blocks + c.num_transform * 24 / 32;
     a.trace = nullptr;
-    const size_t lds_cap = 160 * 1024 - 1024;
+    const size_t lds_cap = kCuLds - 1024;
     const int cus = device_cu_count();
     // fewer 64-row blocks than CUs: four-wave workgroups (one wave per SIMD) spread the batch over twice the CUs
     static const int half_env = getenv("NFA_K8S_HALF") ? atoi(getenv("NFA_K8S_HALF")) : 1;
@@ -612,8 +612,11 @@ static int launch_tile16(const LayerCall& c, int32_t* dbg_bins) {
     note_layer_kernel("k8s::rqs_resnet_f16s_kernel<inverse=%d, init_ks=%d, waves=%d, K=8, ring=%d>", inv ? 1 : 0, init_ks, nw, ring);
     // (a kernel, not hipMemsetAsync: captured into a HIP graph the memset NODE cost ~2 ms per replay -- GraphedLogProb at
     //  <= 16 384 rows took 2.8 ms where the launches themselves take 0.6, tools/small_batch_probe.py)
-    if (half) hipLaunchKernelGGL(k8s::zero_words_kernel, dim3((unsigned)((c.batch / 128 + 255) / 256)), dim3(256), 0, st,
-                                 c.redo, (int)(c.batch / 128));
+    if (half) {
+        const int rc = launch_kernel_args(k8s::zero_words_kernel, dim3((unsigned)((c.batch / 128 + 255) / 256)), dim3(256), 0,
+                                          st, 0, false, c.redo, (int)(c.batch / 128));
+        if (rc != NFA_OK) return rc;
+    }
     return launch_kernel(f16s_kernel(inv, init_ks, half, ring, dbg_bins), dim3((unsigned)blocks), dim3(nw * kWave),
                          lds_launch, st, a, (int)lds_cap);
 }

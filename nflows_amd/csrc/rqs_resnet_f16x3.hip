@@ -92,7 +92,7 @@ static int launch_f16x3(const LayerCall& c, const float* scales, float act_scale
     const k8x::KernelFn kern = f16x3_kernel(inv, init_ks, a.sp.K, dbg_logits);
     if (!kern) return NFA_ERR_UNSUPPORTED;
     note_layer_kernel("k8x::rqs_resnet_f16x3_kernel<inverse=%d, init_ks=%d, K=%d, dbg=%d>", inv ? 1 : 0, init_ks, a.sp.K, dbg_logits ? 1 : 0);
-    return launch_kernel(kern, dim3((unsigned)blocks), dim3(kBlock), lds, (hipStream_t)c.stream, a, 160 * 1024 - 2048);
+    return launch_kernel(kern, dim3((unsigned)blocks), dim3(kBlock), lds, (hipStream_t)c.stream, a, kCuLds - 2048);
 }
 
 extern "C" int nfa_rqs_flow_resnet_f16x3_f32(const float* inputs, const void* weights_packed, const float* bias_packed,

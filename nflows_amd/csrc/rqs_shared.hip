@@ -176,10 +176,7 @@ extern "C" int nfa_rqs_shared_f32(const float* inputs, const float* unnormalized
         return NFA_ERR_INVALID_ARGUMENT;
     const int K = a.sp.K, F = features;
     const int64_t tab = (int64_t)F * 3 * (K + 1);
-    int R = (4 * kBlock) / F;  // ~4 elements per lane per tile
-    if (R < 1) R = 1;
-    if ((int64_t)R > batch) R = (int)batch;
-    auto lds_floats = [&](int r) {
+    auto lds_floats = [&](int r, int) {
         int64_t o = (tab + 3) & ~3;
         a.off_x = (int)o;
         o += round_up4(r * F) + 8;
@@ -189,9 +186,8 @@ extern "C" int nfa_rqs_shared_f32(const float* inputs, const float* unnormalized
         o += round_up4(F * (2 * K + a.sp.nd));
         return o;
     };
-    while (R > 1 && lds_floats(R) * 4 > 64 * 1024) R >>= 1;
-    const int64_t lds = lds_floats(R) * 4;
-    if (lds > 64 * 1024 || (int64_t)R * F >= 65536) return NFA_ERR_UNSUPPORTED;
+    const SampleTile t = plan_sample_tile(4 * kBlock, 0, F, batch, kDefaultDynLds, lds_floats);  // ~4 elements per lane per tile
+    if (!t.ok) return NFA_ERR_UNSUPPORTED;
     a.x = inputs;
     a.uw = unnormalized_widths;
     a.uh = unnormalized_heights;
@@ -201,20 +197,9 @@ extern "C" int nfa_rqs_shared_f32(const float* inputs, const float* unnormalized
     a.status = status;
     a.batch = batch;
     a.F = F;
-    a.R = R;
+    a.R = t.R;
     a.div_F = make_fastdiv((uint32_t)F);
-    const int64_t tiles = (batch + R - 1) / R;
-    int per_cu = (int)((160 * 1024) / (lds + 256));
-    if (per_cu > 8) per_cu = 8;
-    if (per_cu < 1) per_cu = 1;
-    int64_t g = (int64_t)device_cu_count() * per_cu;
-    if (g > tiles) g = tiles;
-    if (flags & NFA_FLAG_INVERSE)
-        hipLaunchKernelGGL((rqs_shared_kernel<true>), dim3((unsigned)g), dim3(kBlock), (size_t)lds,
-                           (hipStream_t)stream, a);
-    else
-        hipLaunchKernelGGL((rqs_shared_kernel<false>), dim3((unsigned)g), dim3(kBlock), (size_t)lds,
-                           (hipStream_t)stream, a);
-    NFA_HIP_CHECK(hipGetLastError());
-    return NFA_OK;
+    const int64_t g = persistent_grid(device_cu_count(), t.lds, 8, (batch + t.R - 1) / t.R);
+    return launch_kernel((flags & NFA_FLAG_INVERSE) ? rqs_shared_kernel<true> : rqs_shared_kernel<false>, dim3((unsigned)g),
+                         dim3(kBlock), t.lds, (hipStream_t)stream, a, 0, false);
 }

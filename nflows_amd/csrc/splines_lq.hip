@@ -425,38 +425,28 @@ __global__ void __launch_bounds__(kBlock) spline_lq_kernel(const LqArgs a) {
 static int launch_lq(LqArgs& a, int kind, int inverse, hipStream_t st) {
     const int K = a.K;
     a.slot = (kind == kLinear ? K : (kind == kCubic ? 2 * K + 2 : 2 * K + 1)) | 1;  // odd stride: conflict-free per-lane walks
-    int T = kBlock;
-    while (T > 32 && (size_t)T * a.slot * 4 > (size_t)64 * 1024) T >>= 1;
-    if ((size_t)T * a.slot * 4 > (size_t)64 * 1024) return NFA_ERR_UNSUPPORTED;
+    const int T = plan_element_tile(32, kDefaultDynLds, [&](int t) { return (size_t)t * a.slot * 4; });
+    if (T == 0) return NFA_ERR_UNSUPPORTED;
     a.T = T;
     const size_t lds = (size_t)T * a.slot * 4 + 64;  // + slack of the staged tile image (tile_load)
-    const int64_t tiles = (a.n + T - 1) / T;
-    int per_cu = (int)((size_t)(160 * 1024) / (lds + 256));
-    per_cu = per_cu > 8 ? 8 : (per_cu < 1 ? 1 : per_cu);
-    int64_t g = (int64_t)device_cu_count() * per_cu;
-    if (g > tiles) g = tiles;
-    const dim3 grid((unsigned)g), block((unsigned)T);
-#define NFA_LQ_LAUNCH(KIND_, KT_)                                                                       \
-    do {                                                                                              \
-        if (inverse) hipLaunchKernelGGL((spline_lq_kernel<KIND_, KT_, true>), grid, block, lds, st, a); \
-        else hipLaunchKernelGGL((spline_lq_kernel<KIND_, KT_, false>), grid, block, lds, st, a);       \
-    } while (0)
+    const dim3 grid((unsigned)persistent_grid(device_cu_count(), lds, 8, (a.n + T - 1) / T)), block((unsigned)T);
+    void (*kern)(const LqArgs) = nullptr;
+#define NFA_LQ_PICK(KIND_, KT_) kern = inverse ? spline_lq_kernel<KIND_, KT_, true> : spline_lq_kernel<KIND_, KT_, false>
     if (kind == kLinear) {
-        if (K == 8) NFA_LQ_LAUNCH(kLinear, 8);
-        else if (K == 10) NFA_LQ_LAUNCH(kLinear, 10);   // the reference's default num_bins
-        else NFA_LQ_LAUNCH(kLinear, 0);
+        if (K == 8) NFA_LQ_PICK(kLinear, 8);
+        else if (K == 10) NFA_LQ_PICK(kLinear, 10);   // the reference's default num_bins
+        else NFA_LQ_PICK(kLinear, 0);
     } else if (kind == kQuadratic) {
-        if (K == 8) NFA_LQ_LAUNCH(kQuadratic, 8);
-        else if (K == 10) NFA_LQ_LAUNCH(kQuadratic, 10);
-        else NFA_LQ_LAUNCH(kQuadratic, 0);
+        if (K == 8) NFA_LQ_PICK(kQuadratic, 8);
+        else if (K == 10) NFA_LQ_PICK(kQuadratic, 10);
+        else NFA_LQ_PICK(kQuadratic, 0);
     } else {
-        if (K == 8) NFA_LQ_LAUNCH(kCubic, 8);
-        else if (K == 10) NFA_LQ_LAUNCH(kCubic, 10);
-        else NFA_LQ_LAUNCH(kCubic, 0);
+        if (K == 8) NFA_LQ_PICK(kCubic, 8);
+        else if (K == 10) NFA_LQ_PICK(kCubic, 10);
+        else NFA_LQ_PICK(kCubic, 0);
     }
-#undef NFA_LQ_LAUNCH
-    NFA_HIP_CHECK(hipGetLastError());
-    return NFA_OK;
+#undef NFA_LQ_PICK
+    return launch_kernel(kern, grid, block, lds, st, a, 0, false);
 }
 
 static int fill_common(LqArgs& a, const nfa_rqs_spec* spec) {
@@ -983,21 +973,14 @@ __global__ void __launch_bounds__(kBlock) cubic_spline_backward_kernel(const LqB
 static int launch_lq_backward(LqBwdArgs& b, int kind, int inverse, hipStream_t st) {
     const int K = b.f.K;
     b.f.slot = (kind == kLinear ? K : (kind == kCubic ? 4 * K : 5 * K + 3)) | 1;  // odd stride: conflict-free per-lane walks
-    int T = kBlock;
-    while (T > 64 && (size_t)T * b.f.slot * 4 > (size_t)64 * 1024) T >>= 1;
-    if ((size_t)T * b.f.slot * 4 > (size_t)64 * 1024) return NFA_ERR_UNSUPPORTED;
+    const int T = plan_element_tile(64, kDefaultDynLds, [&](int t) { return (size_t)t * b.f.slot * 4; });
+    if (T == 0) return NFA_ERR_UNSUPPORTED;
     const size_t lds = (size_t)T * b.f.slot * 4;
-    int64_t g = (b.n + T - 1) / T;
-    const int64_t cap = (int64_t)device_cu_count() * 8;
-    if (g > cap) g = cap;
-    const dim3 grid((unsigned)g), block((unsigned)T);
+    const dim3 grid((unsigned)persistent_grid(device_cu_count(), 8, (b.n + T - 1) / T)), block((unsigned)T);
+    void (*kern)(const LqBwdArgs) = nullptr;
     // K = 8 (the benchmark configurations) and K = 10 (the reference's default num_bins) are compiled with
     // the bin count as a constant; every other K runs the generic instance (same arithmetic, same results)
-#define NFA_LQB(KERNEL_, ...)                                                                     \
-    do {                                                                                          \
-        if (inverse) hipLaunchKernelGGL((KERNEL_<__VA_ARGS__, true>), grid, block, lds, st, b);   \
-        else hipLaunchKernelGGL((KERNEL_<__VA_ARGS__, false>), grid, block, lds, st, b);          \
-    } while (0)
+#define NFA_LQB(KERNEL_, ...) kern = inverse ? KERNEL_<__VA_ARGS__, true> : KERNEL_<__VA_ARGS__, false>
     if (kind == kLinear) {
         if (K == 8) NFA_LQB(linear_spline_backward_kernel, 8);
         else if (K == 10) NFA_LQB(linear_spline_backward_kernel, 10);
@@ -1015,8 +998,7 @@ static int launch_lq_backward(LqBwdArgs& b, int kind, int inverse, hipStream_t s
         else NFA_LQB(cubic_spline_backward_kernel, 0);
     }
 #undef NFA_LQB
-    NFA_HIP_CHECK(hipGetLastError());
-    return NFA_OK;
+    return launch_kernel(kern, grid, block, lds, st, b, 0, false);
 }
 
 }  // namespace nfa
