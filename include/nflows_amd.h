@@ -32,13 +32,14 @@
 extern "C" {
 #endif
 
-#define NFA_ABI_VERSION 16 /* bumped whenever a packed layout, a flag set or an entry point changes (round 3: 3 .. 7; round 4: 8,
+#define NFA_ABI_VERSION 17 /* bumped whenever a packed layout, a flag set or an entry point changes (round 3: 3 .. 7; round 4: 8,
                               9: whole-layer kernels for 2 .. 16 bins, nfa_resnet_backward_f32, W_f^T in K14's backward stream;
                               round 5: 10: `bin_idx` outputs of the spline kernels, nfa_searchsorted_f32; 11: NFA_FLAG_RESIDUAL_BLOCKS;
                               round 6: 12: nfa_rqs_flow_resnet_f16x3_f32 (K8x), the *_logits_f32 diagnostic entries,
                               NFA_FLAG_ALL_PRODUCTS, nfa_weights_checksum_*;
                               15: nfa_lu_linear_f32, nfa_lu_linear_backward_f32;
-                              16: nfa_norm_* (K17) */
+                              16: nfa_norm_* (K17);
+                              17: nfa_nonlin_* (K18) */
 
 /* return codes */
 #define NFA_OK 0
@@ -959,6 +960,49 @@ int nfa_norm_map_backward_f32(const float *grad_outputs, const float *p0, const 
 int nfa_norm_batch_backward_f32(const float *grad_outputs, const float *inputs, const float *coefficients,
                                 const int64_t *in_perm, const int64_t *out_scatter, float *grad_inputs, int32_t *status,
                                 int64_t batch, int32_t features, void *stream);
+
+/*
+ * K18.  The elementwise nonlinearity transforms (transforms/nonlinearities.py: Exp :18-32, Tanh :35-48, LogTanh :51-113,
+ * LeakyReLU :116-136, Sigmoid :139-169 / Logit :172-174, CauchyCDF :192-211 / CauchyCDFInverse :214-216) on a float32
+ * [batch, n] view, n = the product of all non-batch dimensions (the reference sums over everything but dimension 0), n >= 1.
+ * One launch writes outputs[b, i] = f(inputs[b, i]) and logabsdet[b] = sum_i log |f'(inputs[b, i])|; with
+ * NFA_FLAG_INVERSE f is the inverse map (Logit = Sigmoid inverse, CauchyCDFInverse = CauchyCDF inverse).
+ *   kind / p0, p1, p2 (constants fixed at construction, by value)
+ *     NFA_NONLIN_EXP         -
+ *     NFA_NONLIN_TANH        -
+ *     NFA_NONLIN_LOG_TANH    p0 = cut_point, p1 = alpha, p2 = beta (float64 on the host, as the reference's numpy)
+ *     NFA_NONLIN_LEAKY_RELU  p0 = negative_slope (> 0)
+ *     NFA_NONLIN_SIGMOID     p0 = eps (the inverse clamps to [eps, 1 - eps] first); `temperature`: the module's [1]
+ *                            float32 tensor on the device, read by the kernel as it is (nothing packed or cached)
+ *     NFA_NONLIN_CAUCHY_CDF  -
+ * The row sum runs in float64 in a fixed order that depends on (batch, n) only -- several rows per workgroup for
+ * n <= 2048, otherwise nfa_nonlin_pieces(batch, n) pieces per row, each reduced by one workgroup, folded in piece order by a
+ * second small launch -- and is rounded once: no atomics, the same bits on every run.
+ *   workspace   nfa_nonlin_workspace_bytes(batch, n) bytes (0: may be NULL), scratch of this call
+ *   status      NFA_STATUS_OUTSIDE_DOMAIN where the reference raises InputOutsideDomain: Sigmoid inverse and CauchyCDF inverse
+ *               outside [0, 1], Tanh inverse at |x| >= 1, Exp inverse at x <= 0; such an element's output is unspecified
+ *   flags       NFA_FLAG_INVERSE | NFA_FLAG_ACCUMULATE_LOGABSDET;  batch == 0 is a no-op.
+ * nfa_nonlin_backward_f32: grad_inputs = grad_outputs * dy/dx + grad_logabsdet[row] * d(contribution)/dx from the inputs of
+ * the pass that is differentiated (same kind, constants and flags & NFA_FLAG_INVERSE); grad_temperature (Sigmoid only,
+ * may be NULL): one float32, the sum over all elements in float64 -- one partial per workgroup, folded in a fixed order,
+ * rounded once; it needs nfa_nonlin_backward_workspace_bytes(batch, n) bytes of workspace.
+ */
+#define NFA_NONLIN_EXP 0
+#define NFA_NONLIN_TANH 1
+#define NFA_NONLIN_LOG_TANH 2
+#define NFA_NONLIN_LEAKY_RELU 3
+#define NFA_NONLIN_SIGMOID 4
+#define NFA_NONLIN_CAUCHY_CDF 5
+int nfa_nonlin_pieces(int64_t batch, int64_t n);
+size_t nfa_nonlin_workspace_bytes(int64_t batch, int64_t n);
+size_t nfa_nonlin_backward_workspace_bytes(int64_t batch, int64_t n);
+int nfa_nonlin_f32(const float *inputs, const float *temperature, float *outputs, float *logabsdet, void *workspace,
+                   int32_t *status, int64_t batch, int64_t n, int32_t kind, double p0, double p1, double p2,
+                   int32_t flags, void *stream);
+int nfa_nonlin_backward_f32(const float *inputs, const float *temperature, const float *grad_outputs,
+                            const float *grad_logabsdet, float *grad_inputs, float *grad_temperature, void *workspace,
+                            int64_t batch, int64_t n, int32_t kind, double p0, double p1, double p2, int32_t flags,
+                            void *stream);
 
 /*
  * K3.  Per-sample reduction: torchutils.sum_except_batch, utils/torchutils.py:19-24.

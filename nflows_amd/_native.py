@@ -32,9 +32,10 @@ FLAG_PAD_COLUMNS_SHIFT = 8   # bits 8-10: trailing pad columns the density epilo
 FLAG_ACTIVATION_SHIFT = 12   # bits 12-14: activation of the conditioner's residual blocks in the whole-layer kernels
 ACTIVATION_RELU, ACTIVATION_LEAKY_RELU, ACTIVATION_ELU, ACTIVATION_TANH = 0, 1, 2, 3
 TAILS_NONE, TAILS_LINEAR = 0, 1
+NONLIN_EXP, NONLIN_TANH, NONLIN_LOG_TANH, NONLIN_LEAKY_RELU, NONLIN_SIGMOID, NONLIN_CAUCHY_CDF = 0, 1, 2, 3, 4, 5
 SCALE_DEFAULT, SCALE_GENERAL, SCALE_ADDITIVE, SCALE_GIVEN, SCALE_SOFTPLUS = 0, 1, 2, 3, 4
 
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 EXPORTS = (
     "nfa_abi_version",
@@ -89,6 +90,11 @@ EXPORTS = (
     "nfa_norm_map_f32",
     "nfa_norm_map_backward_f32",
     "nfa_norm_batch_backward_f32",
+    "nfa_nonlin_pieces",
+    "nfa_nonlin_workspace_bytes",
+    "nfa_nonlin_backward_workspace_bytes",
+    "nfa_nonlin_f32",
+    "nfa_nonlin_backward_f32",
     "nfa_rowsum_f32",
     "nfa_standard_normal_log_prob_f32",
     "nfa_sum_count_f64",
@@ -246,6 +252,16 @@ def _declare(lib):
     lib.nfa_norm_map_backward_f32.argtypes = [vp] * 9 + [i64, i32, ctypes.c_double, i32, i32, vp]
     lib.nfa_norm_batch_backward_f32.restype = ctypes.c_int
     lib.nfa_norm_batch_backward_f32.argtypes = [vp] * 7 + [i64, i32, vp]
+    lib.nfa_nonlin_pieces.restype = ctypes.c_int
+    lib.nfa_nonlin_pieces.argtypes = [i64, i64]
+    for fn in (lib.nfa_nonlin_workspace_bytes, lib.nfa_nonlin_backward_workspace_bytes):
+        fn.restype = ctypes.c_size_t
+        fn.argtypes = [i64, i64]
+    f64 = ctypes.c_double
+    lib.nfa_nonlin_f32.restype = ctypes.c_int
+    lib.nfa_nonlin_f32.argtypes = [vp] * 6 + [i64, i64, i32, f64, f64, f64, i32, vp]
+    lib.nfa_nonlin_backward_f32.restype = ctypes.c_int
+    lib.nfa_nonlin_backward_f32.argtypes = [vp] * 7 + [i64, i64, i32, f64, f64, f64, i32, vp]
     lib.nfa_rowsum_f32.restype = ctypes.c_int
     lib.nfa_rowsum_f32.argtypes = [vp, vp, i64, i64, vp]
     lib.nfa_standard_normal_log_prob_f32.restype = ctypes.c_int

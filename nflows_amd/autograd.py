@@ -328,6 +328,31 @@ class LULinear(torch.autograd.Function):
         return tuple(grads) + (None, None, None, None)
 
 
+class Nonlinearity(torch.autograd.Function):
+    """K18 forward + K18-backward (ops.nonlinearity): the input gradient from the saved inputs in one launch, Sigmoid's
+    temperature gradient from per-workgroup float64 partials folded in a fixed order."""
+
+    @staticmethod
+    def forward(ctx, inputs, temperature, code, constants, inverse):
+        from . import ops
+        out, lad = ops._nonlinearity_launch(inputs, temperature, code, constants, inverse, None)
+        ctx.save_for_backward(inputs, temperature)
+        ctx.code, ctx.constants, ctx.inverse = code, constants, inverse
+        return out, lad
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out, g_lad):
+        from . import ops
+        inputs, temperature = ctx.saved_tensors
+        g_out = torch.zeros_like(inputs) if g_out is None else g_out
+        g_lad = inputs.new_zeros(inputs.shape[0]) if g_lad is None else g_lad
+        want_t = temperature is not None and ctx.needs_input_grad[1]
+        g_in, g_t = ops._nonlinearity_backward_launch(inputs, temperature, g_out, g_lad, ctx.code, ctx.constants,
+                                                      ctx.inverse, want_t)
+        return (g_in if ctx.needs_input_grad[0] else None), g_t, None, None, None
+
+
 class NormMap(torch.autograd.Function):
     """K17 forward and its gradients (BatchNorm / ActNorm, ops.batch_norm / ops.act_norm).
 

@@ -87,4 +87,54 @@ inline int64_t persistent_grid(int cus, size_t lds, int cap, int64_t tiles) {
     return persistent_grid(cus, per_cu, tiles);
 }
 
+// ------------------------------------------------------------------------------------------
+// Row sums of an elementwise map over [batch, n] rows (K18): who visits which element, and in which order a row's terms are
+// added.  A function of (batch, n) only -- not of the device --, so the same shape gives the same bits everywhere.
+//   n <= kRowSumTile  "rows": a workgroup takes `rows` whole rows, one contiguous range of rows * n <= kRowSumTile elements
+//                     (a multiple of four rows where four fit: the range then starts on a float4 whatever n is); the terms
+//                     of a row are added by `group` lanes (a power of two <= 64: lane g takes terms g, g + group, ... in
+//                     order, the lanes are merged in a shuffle tree), about eight terms per lane.
+//   n >  kRowSumTile  "pieces": a row is cut into `pieces` ranges of `piece` elements (a multiple of four; the last one
+//                     shorter), one workgroup each: as many as fill kRowSumGroups workgroups, none shorter than half a tile.
+//                     pieces > 1: the piece sums go to a float64 workspace [batch][pieces] and a second launch adds a
+//                     row's pieces in piece order.
+constexpr int kRowSumTile = 2048;     // elements of a workgroup's range in the rows regime: eight per lane
+constexpr int kRowSumGroups = 1024;   // workgroups worth cutting rows for
+
+struct RowSumPlan {
+    int rows = 0;        // rows regime: rows per workgroup (0: pieces regime)
+    int group = 1;       // rows regime: lanes that share a row's sum
+    int pieces = 1;      // pieces regime: workgroups per row
+    int64_t piece = 0;   // pieces regime: elements per piece
+    int64_t groups = 0;  // workgroups of the launch
+    bool vec4 = false;   // float4 lanes (given 16-byte aligned tensors)
+};
+
+inline RowSumPlan plan_row_sum(int64_t batch, int64_t n) {
+    RowSumPlan p;
+    if (batch < 1 || n < 1) return p;
+    if (n <= kRowSumTile) {
+        int R = (int)(kRowSumTile / n);
+        if (R >= 4) R &= ~3;
+        p.rows = R;
+        int G = 1;
+        while (G < kWave && (int64_t)G * 8 < n) G <<= 1;
+        p.group = G;
+        p.groups = (batch + R - 1) / R;
+        p.vec4 = R % 4 == 0 || n % 4 == 0;
+        return p;
+    }
+    int64_t S = (kRowSumGroups + batch - 1) / batch;
+    const int64_t most = n / (kRowSumTile / 2);
+    if (S > most) S = most;
+    if (S < 1) S = 1;
+    int64_t len = (n + S - 1) / S;
+    len = (len + 3) & ~(int64_t)3;
+    p.piece = len;
+    p.pieces = (int)((n + len - 1) / len);
+    p.groups = batch * p.pieces;
+    p.vec4 = n % 4 == 0;
+    return p;
+}
+
 }  // namespace nfa

@@ -725,6 +725,87 @@ def _norm_batch_backward_launch(grad_outputs, inputs, coefficients, perm, scat):
     return g_in
 
 
+# K18: the elementwise nonlinearities.  (kind, inverse) pairs whose map has a bounded domain: the reference raises
+# InputOutsideDomain there by reading the tensor's min / max back (a sync), the kernel leaves it in the status word
+NONLIN_KINDS = {"exp": N.NONLIN_EXP, "tanh": N.NONLIN_TANH, "log_tanh": N.NONLIN_LOG_TANH, "leaky_relu": N.NONLIN_LEAKY_RELU,
+                "sigmoid": N.NONLIN_SIGMOID, "cauchy_cdf": N.NONLIN_CAUCHY_CDF}
+_NONLIN_BOUNDED_INVERSE = (N.NONLIN_EXP, N.NONLIN_TANH, N.NONLIN_SIGMOID, N.NONLIN_CAUCHY_CDF)
+
+
+def nonlinearity(inputs, kind, constants=(), temperature=None, inverse=False, accumulate_into=None):
+    """K18 -- an elementwise nonlinearity transform (transforms/nonlinearities.py) in one launch: float32 `inputs` of rank
+    >= 2, `kind` a key of NONLIN_KINDS, `constants` the scalars fixed at construction (log_tanh: cut_point, alpha, beta;
+    leaky_relu: negative_slope; sigmoid: eps), `temperature` Sigmoid's [1] tensor, read on the device as it is.  Returns
+    (outputs like inputs, logabsdet [B] = the sum over everything but dimension 0, in float64 in a fixed order, rounded
+    once).  Differentiable in the inputs and the temperature.  Inputs outside the domain of an inverse (Sigmoid, Tanh, Exp,
+    CauchyCDF) raise InputOutsideDomain like the constrained splines do."""
+    N.require_device_f32("inputs", inputs)
+    if inputs.dim() < 2:
+        raise ValueError("inputs must have a batch dimension and at least one more, got shape %s" % (tuple(inputs.shape),))
+    code = NONLIN_KINDS[kind]
+    p = tuple(float(c) for c in constants) + (0.0,) * (3 - len(constants))
+    dev = inputs.device
+    if code == N.NONLIN_SIGMOID:
+        N.require_device_f32("temperature", temperature, 1)
+        if temperature.device != dev or temperature.numel() != 1:
+            raise ValueError("temperature must be a [1] tensor on the inputs' device")
+    else:
+        temperature = None
+    if AG.needs_grad(inputs, temperature):
+        out, lad = AG.Nonlinearity.apply(inputs.contiguous(), temperature, code, p, bool(inverse))
+        if accumulate_into is not None:
+            accumulate_into += lad
+            lad = accumulate_into
+    else:
+        out, lad = _nonlinearity_launch(inputs, temperature, code, p, inverse, accumulate_into)
+    if (inverse and code in _NONLIN_BOUNDED_INVERSE) or _error_mode == "immediate":
+        check_status(dev)
+    return out, lad
+
+
+def _nonlinearity_launch(inputs, temperature, code, p, inverse, accumulate_into):
+    dev = inputs.device
+    x = inputs.detach().contiguous()
+    B = x.shape[0]
+    n = x.numel() // B if B else max(int(np.prod(x.shape[1:])), 1)
+    t = None if temperature is None else temperature.detach().contiguous()
+    out = torch.empty_like(x)
+    lad, flags = _lad_buffer(accumulate_into, B, dev, inverse)
+    lib = N.load()
+    nbytes = lib.nfa_nonlin_workspace_bytes(B, n)
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev) if nbytes else None
+    hook = _launch_hook
+    with torch.cuda.device(dev):
+        token = hook.begin("nonlin") if hook is not None else None
+        rc = lib.nfa_nonlin_f32(N.ptr(x), N.ptr(t), N.ptr(out), N.ptr(lad), N.ptr(ws), N.ptr(_status_word(dev)), B, n, code,
+                                p[0], p[1], p[2], flags, N.stream_handle(dev))
+        if hook is not None:
+            hook.end(token, 4 * (2 * B * n + B))
+    N.check(rc)
+    return out, lad
+
+
+def _nonlinearity_backward_launch(inputs, temperature, grad_outputs, grad_logabsdet, code, p, inverse, want_temperature):
+    """K18-backward: (grad_inputs, grad_temperature [1] or None) from the saved inputs of the differentiated pass."""
+    dev = inputs.device
+    x = inputs.detach().contiguous()
+    B = x.shape[0]
+    n = x.numel() // B if B else 1
+    t = None if temperature is None else temperature.detach().contiguous()
+    g, gl = grad_outputs.detach().contiguous(), grad_logabsdet.detach().contiguous()
+    g_in = torch.empty_like(x)
+    lib = N.load()
+    g_t = ws = None
+    if want_temperature:
+        g_t = torch.zeros(1, dtype=torch.float32, device=dev)
+        ws = torch.empty(max(lib.nfa_nonlin_backward_workspace_bytes(B, n) // 8, 1), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.nfa_nonlin_backward_f32(N.ptr(x), N.ptr(t), N.ptr(g), N.ptr(gl), N.ptr(g_in), N.ptr(g_t), N.ptr(ws), B, n,
+                                         code, p[0], p[1], p[2], N.FLAG_INVERSE if inverse else 0, N.stream_handle(dev))
+    N.check(rc)
+    return g_in, g_t
+
+
 def rowsum(x):
     """K3 -- torch.sum over everything but the batch dimension."""
     N.require_device_f32("x", x)

@@ -16,5 +16,6 @@ from .autoregressive import (AutoregressiveTransform, MaskedAffineAutoregressive
                              MaskedPiecewiseQuadraticAutoregressiveTransform,
                              MaskedPiecewiseRationalQuadraticAutoregressiveTransform)
 from .made import MADE
-from .nonlinearities import (PiecewiseCubicCDF, PiecewiseLinearCDF, PiecewiseQuadraticCDF,
-                            PiecewiseRationalQuadraticCDF)
+from .nonlinearities import (CauchyCDF, CauchyCDFInverse, CompositeCDFTransform, Exp, GatedLinearUnit, LeakyReLU, Logit,
+                            LogTanh, PiecewiseCubicCDF, PiecewiseLinearCDF, PiecewiseQuadraticCDF,
+                            PiecewiseRationalQuadraticCDF, Sigmoid, Tanh)
