@@ -32,14 +32,15 @@
 extern "C" {
 #endif
 
-#define NFA_ABI_VERSION 17 /* bumped whenever a packed layout, a flag set or an entry point changes (round 3: 3 .. 7; round 4: 8,
+#define NFA_ABI_VERSION 18 /* bumped whenever a packed layout, a flag set or an entry point changes (round 3: 3 .. 7; round 4: 8,
                               9: whole-layer kernels for 2 .. 16 bins, nfa_resnet_backward_f32, W_f^T in K14's backward stream;
                               round 5: 10: `bin_idx` outputs of the spline kernels, nfa_searchsorted_f32; 11: NFA_FLAG_RESIDUAL_BLOCKS;
                               round 6: 12: nfa_rqs_flow_resnet_f16x3_f32 (K8x), the *_logits_f32 diagnostic entries,
                               NFA_FLAG_ALL_PRODUCTS, nfa_weights_checksum_*;
                               15: nfa_lu_linear_f32, nfa_lu_linear_backward_f32;
                               16: nfa_norm_* (K17);
-                              17: nfa_nonlin_* (K18) */
+                              17: nfa_nonlin_* (K18);
+                              18: nfa_lu_conv1x1_f32, nfa_lu_conv1x1_backward_f32 (K19) */
 
 /* return codes */
 #define NFA_OK 0
@@ -902,6 +903,38 @@ int nfa_lu_linear_backward_f32(const float *grad_outputs, const float *lower_ent
                                const float *unconstrained_upper_diag, const int64_t *in_perm,
                                const int64_t *out_scatter, float *grad_inputs, int32_t *status, int64_t batch,
                                int32_t features, double eps, int32_t flags, void *stream);
+
+/*
+ * K19.  The invertible 1x1 convolution: K16's layer over the channel dimension of a contiguous [batch, channels, height,
+ * width] tensor, with the module's fixed channel permutation inside the launch:
+ *   OneByOneConvolution.forward / inverse   transforms/conv.py:17-47
+ *   per pixel (b, :, h, w):
+ *   forward   outputs = L (U inputs[channel_perm]) + bias
+ *   inverse   outputs[channel_perm] = U^-1 (L^-1 (inputs - bias))
+ * The four parameter tensors, eps and flags are those of nfa_lu_linear_f32 (features = channels) and go through the same
+ * kernel body: a pixel's result equals, bit for bit, K16's on that pixel's channels as a row, and depends on that pixel
+ * and the parameters only.  The tensor is read and written in place in NCHW -- element c of pixel p of image b at
+ * b C HW + channel_perm[c] HW + p, 64-bit offsets -- plane by plane, never transposed in memory.
+ *   channel_perm   [channels] int64 or NULL (identity); an entry outside [0, channels) sets NFA_STATUS_BAD_INDEX
+ *   logabsdet      [batch]: one value per image, +- height width sum_i log U_ii, formed in float64 and rounded once
+ *                  (added to the entry with NFA_FLAG_ACCUMULATE_LOGABSDET); independent of grid and tile
+ * NFA_ERR_INVALID_ARGUMENT: a NULL data pointer, batch < 0, channels < 1, height or width <= 0, eps < 0, unknown flags.
+ * NFA_ERR_UNSUPPORTED: channels < 2 or > 128.  batch == 0 is a no-op.
+ */
+int nfa_lu_conv1x1_f32(const float *inputs, const float *lower_entries, const float *upper_entries,
+                       const float *unconstrained_upper_diag, const float *bias, const int64_t *channel_perm,
+                       float *outputs, float *logabsdet, int32_t *status, int64_t batch, int32_t channels,
+                       int32_t height, int32_t width, double eps, int32_t flags, void *stream);
+
+/*
+ * K19-backward.  Input gradient of nfa_lu_conv1x1_f32 (same parameters, channel_perm and flags & NFA_FLAG_INVERSE as the
+ * forward call): K16-backward's transposed steps per pixel, the channel gather and scatter swapped.  No bias, no
+ * logabsdet; the parameter gradients are the caller's (nflows_amd/autograd.py: LUConv1x1).
+ */
+int nfa_lu_conv1x1_backward_f32(const float *grad_outputs, const float *lower_entries, const float *upper_entries,
+                                const float *unconstrained_upper_diag, const int64_t *channel_perm, float *grad_inputs,
+                                int32_t *status, int64_t batch, int32_t channels, int32_t height, int32_t width,
+                                double eps, int32_t flags, void *stream);
 
 /*
  * K17.  The normalisation transforms (transforms/normalization.py: BatchNorm :72-141, ActNorm :144-218), float32

@@ -35,7 +35,7 @@ TAILS_NONE, TAILS_LINEAR = 0, 1
 NONLIN_EXP, NONLIN_TANH, NONLIN_LOG_TANH, NONLIN_LEAKY_RELU, NONLIN_SIGMOID, NONLIN_CAUCHY_CDF = 0, 1, 2, 3, 4, 5
 SCALE_DEFAULT, SCALE_GENERAL, SCALE_ADDITIVE, SCALE_GIVEN, SCALE_SOFTPLUS = 0, 1, 2, 3, 4
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 EXPORTS = (
     "nfa_abi_version",
@@ -83,6 +83,8 @@ EXPORTS = (
     "nfa_permute_cols_b32",
     "nfa_lu_linear_f32",
     "nfa_lu_linear_backward_f32",
+    "nfa_lu_conv1x1_f32",
+    "nfa_lu_conv1x1_backward_f32",
     "nfa_norm_workspace_bytes",
     "nfa_norm_slab_count",
     "nfa_norm_column_stats_f32",
@@ -238,6 +240,10 @@ def _declare(lib):
     lib.nfa_lu_linear_f32.argtypes = [vp] * 10 + [i64, i32, ctypes.c_double, i32, vp]
     lib.nfa_lu_linear_backward_f32.restype = ctypes.c_int
     lib.nfa_lu_linear_backward_f32.argtypes = [vp] * 8 + [i64, i32, ctypes.c_double, i32, vp]
+    lib.nfa_lu_conv1x1_f32.restype = ctypes.c_int
+    lib.nfa_lu_conv1x1_f32.argtypes = [vp] * 9 + [i64, i32, i32, i32, ctypes.c_double, i32, vp]
+    lib.nfa_lu_conv1x1_backward_f32.restype = ctypes.c_int
+    lib.nfa_lu_conv1x1_backward_f32.argtypes = [vp] * 7 + [i64, i32, i32, i32, ctypes.c_double, i32, vp]
     lib.nfa_norm_workspace_bytes.restype = ctypes.c_size_t
     lib.nfa_norm_workspace_bytes.argtypes = [i64, i32]
     lib.nfa_norm_slab_count.restype = ctypes.c_int

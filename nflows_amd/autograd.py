@@ -266,6 +266,38 @@ class StandardNormalLogProb(torch.autograd.Function):
         return g_z, (g if ctx.has_lad else None)
 
 
+def _lu_parameter_grads(seen, g_seen, lower, upper, udiag, bias, eps, inverse, lad_weight):
+    """The four parameter gradients of the LU layer from float64 rows: `seen` [rows, D] the layer's inputs and `g_seen`
+    the gradients of its outputs, both as the layer itself sees them (after the gather / before the scatter);
+    `lad_weight` = d loss / d (sum_i log U_ii) as a float64 scalar tensor, or None.  Formulas: LULinear's docstring."""
+    # float64, rounded once: a parameter gradient is ONE number summed over the whole batch (features = 2 has a
+    # single lower entry) -- nothing averages its rounding error out.  (Cost under training: not measured.)
+    from .transforms.lu import dense_factors, solve_rows
+    f64 = torch.float64
+    logits = udiag.to(f64)
+    diag = torch.nn.functional.softplus(logits) + eps
+    dense_l, dense_u = dense_factors(lower.to(f64), upper.to(f64), diag)
+    D = seen.shape[1]
+    rows, cols = torch.tril_indices(D, D, -1, device=seen.device)
+    urows, ucols = torch.triu_indices(D, D, 1, device=seen.device)
+    if not inverse:
+        a, g, sign = seen, g_seen, 1.0           # y = L (U a) + b,  g = dloss / dy
+    else:
+        # x = U^-1 L^-1 (y - b): the x side and the y-side gradient g = W^-T gx, both re-solved in float64 from
+        # the saved inputs (the float32 output's own rounding would otherwise be the gradient's error)
+        a = solve_rows(dense_l, dense_u, seen - bias.to(f64))
+        g = solve_rows(dense_u.t(), dense_l.t(), g_seen)   # W^T = U^T L^T: lower factor U^T, upper factor L^T
+        sign = -1.0
+    d_l = sign * (g.t() @ (a @ dense_u.t()))
+    d_u = sign * ((g @ dense_l).t() @ a)
+    d_diag = torch.diagonal(d_u)
+    if lad_weight is not None:
+        d_diag = d_diag + sign * lad_weight / diag
+    return (d_l[rows, cols].to(lower.dtype), d_u[urows, ucols].to(upper.dtype),
+            (d_diag * torch.where(logits > 20.0, torch.ones_like(logits), torch.sigmoid(logits))).to(udiag.dtype),
+            (sign * g.sum(0)).to(bias.dtype))
+
+
 class LULinear(torch.autograd.Function):
     """K16 forward + K16-backward.  The kernel gives the input gradient; the parameter gradients are [D, D] reductions
     over the batch on the device's library GEMM in float64 (rounded once: every entry is one number summed over the whole
@@ -295,37 +327,53 @@ class LULinear(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             grads[0] = ops._lu_linear_backward_launch(g_out, (lower, upper, udiag), ctx.eps, inverse, perm, scat)
         if any(ctx.needs_input_grad[1:5]):
-            # float64, rounded once: a parameter gradient is ONE number summed over the whole batch (features = 2 has a
-            # single lower entry) -- nothing averages its rounding error out.  (Cost under training: not measured.)
-            from .transforms.lu import dense_factors, solve_rows
             f64 = torch.float64
-            logits = udiag.to(f64)
-            diag = torch.nn.functional.softplus(logits) + ctx.eps
-            dense_l, dense_u = dense_factors(lower.to(f64), upper.to(f64), diag)
-            D = inputs.shape[1]
-            rows, cols = torch.tril_indices(D, D, -1, device=inputs.device)
-            urows, ucols = torch.triu_indices(D, D, 1, device=inputs.device)
             # the rows as the layer itself sees them (without the fused permutation / scatter)
             seen = inputs.to(f64) if perm is None else inputs.to(f64).index_select(1, perm)
             g_seen = g_out.to(f64) if scat is None else g_out.to(f64).index_select(1, scat)
-            if not inverse:
-                a, g, sign = seen, g_seen, 1.0           # y = L (U a) + b,  g = dloss / dy
-            else:
-                # x = U^-1 L^-1 (y - b): the x side and the y-side gradient g = W^-T gx, both re-solved in float64 from
-                # the saved inputs (the float32 output's own rounding would otherwise be the gradient's error)
-                a = solve_rows(dense_l, dense_u, seen - bias.to(f64))
-                g = solve_rows(dense_u.t(), dense_l.t(), g_seen)   # W^T = U^T L^T: lower factor U^T, upper factor L^T
-                sign = -1.0
-            d_l = sign * (g.t() @ (a @ dense_u.t()))
-            d_u = sign * ((g @ dense_l).t() @ a)
-            grads[1] = d_l[rows, cols].to(lower.dtype)
-            grads[2] = d_u[urows, ucols].to(upper.dtype)
-            d_diag = torch.diagonal(d_u)
-            if g_lad is not None:
-                d_diag = d_diag + sign * g_lad.to(f64).sum() / diag
-            grads[3] = (d_diag * torch.where(logits > 20.0, torch.ones_like(logits), torch.sigmoid(logits))).to(udiag.dtype)
-            grads[4] = (sign * g.sum(0)).to(bias.dtype)
+            grads[1:5] = _lu_parameter_grads(seen, g_seen, lower, upper, udiag, bias, ctx.eps, inverse,
+                                             None if g_lad is None else g_lad.to(f64).sum())
         return tuple(grads) + (None, None, None, None)
+
+
+class LUConv1x1(torch.autograd.Function):
+    """K19 forward + K19-backward.  The kernel gives the input gradient; the parameter gradients are LULinear's float64
+    formulas with the pixels as rows ([B HW, C] after the channel gather: forward the inputs' planes channel_perm,
+    inverse the output gradient's).  logabsdet[b] = +- HW sum_i log U_ii, so its term into the diagonal logits is
+    +- HW sum_b grad_logabsdet[b] / U_ii."""
+
+    @staticmethod
+    def forward(ctx, inputs, lower, upper, udiag, bias, eps, inverse, perm):
+        from . import ops
+        out, lad = ops._lu_conv1x1_launch(inputs, (lower, upper, udiag, bias), eps, inverse, perm, None)
+        ctx.save_for_backward(inputs, lower, upper, udiag, bias, perm)
+        ctx.eps, ctx.inverse = eps, inverse
+        return out, lad
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out, g_lad):
+        from . import ops
+        inputs, lower, upper, udiag, bias, perm = ctx.saved_tensors
+        inverse = ctx.inverse
+        g_out = torch.zeros_like(inputs) if g_out is None else g_out.contiguous()
+        grads = [None] * 5
+        if ctx.needs_input_grad[0]:
+            grads[0] = ops._lu_conv1x1_backward_launch(g_out, (lower, upper, udiag), ctx.eps, inverse, perm)
+        if any(ctx.needs_input_grad[1:5]):
+            f64 = torch.float64
+            C, hw = inputs.shape[1], inputs.shape[2] * inputs.shape[3]
+
+            def pixel_rows(t, gathered):
+                t = t.to(f64)
+                if gathered and perm is not None:
+                    t = t.index_select(1, perm)
+                return t.permute(0, 2, 3, 1).reshape(-1, C)
+
+            grads[1:5] = _lu_parameter_grads(pixel_rows(inputs, not inverse), pixel_rows(g_out, inverse), lower, upper,
+                                             udiag, bias, ctx.eps, inverse,
+                                             None if g_lad is None else hw * g_lad.to(f64).sum())
+        return tuple(grads) + (None, None, None)
 
 
 class Nonlinearity(torch.autograd.Function):

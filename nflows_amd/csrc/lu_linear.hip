@@ -20,6 +20,14 @@
 // The diagonal and the log-determinant are computed in float64 from the float32 logits (features values per
 // workgroup) and rounded once: logabsdet is ONE number per layer, so its error is not averaged over anything -- the
 // correctly rounded value is the only one that is never further from the float64 result than another float32 evaluation.
+//
+// K19: the same layer over the channel dimension of a contiguous [B, C, H, W] tensor (reference: transforms/conv.py,
+// OneByOneConvolution) is a second addressing mode of this kernel (NCHW = true).  A "row" is a pixel g in [0, B HW),
+// b = g / HW, p = g % HW; its element c sits at b C HW + perm[c] HW + p.  A lane still owns one row, so in NCHW it
+// loads and stores its own column of the tile channel by channel: the lanes of a wave touch consecutive addresses of one
+// plane, and the coalesced read already IS the column-major tile -- no transposition in either direction, the channel
+// permutation is "read plane perm[c]".  logabsdet is one value per image, +- HW sum_i log U_ii (float64, rounded once),
+// written by the lane that owns the image's pixel 0.  Everything between load and store is K16's code.
 #include "common.hpp"
 
 namespace nfa {
@@ -41,7 +49,8 @@ struct LuArgs {
     float* out;
     float* lad;
     int32_t* status;
-    int64_t batch;
+    int64_t batch;   // rows: the [batch, features] rows of K16, the batch * height * width pixels of K19
+    int64_t hw;      // K19: height * width
     double eps;
     int D, DP, R, RS;
     int accumulate;
@@ -119,7 +128,7 @@ __device__ __forceinline__ void tri_apply(const float* __restrict__ M, int DP, i
     }
 }
 
-template <int MODE>
+template <int MODE, bool NCHW>
 __global__ void __launch_bounds__(kBlock) lu_linear_kernel(const LuArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int D = a.D, DP = a.DP, R = a.R, RS = a.RS;
@@ -170,6 +179,7 @@ __global__ void __launch_bounds__(kBlock) lu_linear_kernel(const LuArgs a) {
     if (tid == 0) {   // one fixed order, whatever the grid
         double s = 0.0;
         for (int c = 0; c < D; ++c) s += s_logd[c];
+        if (NCHW) s *= (double)a.hw;   // every pixel of an image contributes the same term
         s_lad[0] = (float)(MODE == kLuInverse ? -s : s);
     }
     __syncthreads();
@@ -180,14 +190,35 @@ __global__ void __launch_bounds__(kBlock) lu_linear_kernel(const LuArgs a) {
     for (int64_t tile = blockIdx.x; tile < num_tiles; tile += gridDim.x) {
         const int64_t row0 = tile * R;
         const int rows = (int)((a.batch - row0) < R ? (a.batch - row0) : R);
-        const float* src = a.x + row0 * D;
-        // ---- coalesced read of rows * D floats -> column-major tile (gather through in_perm, minus the bias going back)
-        for (int e = tid; e < rows * D; e += R) {
-            const int r = (int)fastdiv((uint32_t)e, a.div_D);
-            const int c = e - r * D;
-            float val = src[r * D + s_perm[c]];
-            if (MODE == kLuInverse) val -= s_bias[c];
-            s_tile[c * RS + r] = val;
+        // K19: this lane's pixel -- image b, position p; element c at pix + plane * hw (64-bit: B C HW may pass 2^31)
+        int64_t img = 0, pix = 0;
+        bool first_pixel = false;
+        if (NCHW && tid < rows) {
+            img = (row0 + tid) / a.hw;
+            const int64_t p = (row0 + tid) - img * a.hw;
+            first_pixel = p == 0;
+            pix = img * D * a.hw + p;
+        }
+        if (NCHW) {
+            // ---- channel by channel: the wave reads consecutive pixels of plane perm[c] into column c of the tile
+            if (tid < rows) {
+#pragma unroll 4
+                for (int c = 0; c < D; ++c) {
+                    float val = a.x[pix + s_perm[c] * a.hw];
+                    if (MODE == kLuInverse) val -= s_bias[c];
+                    s_tile[c * RS + tid] = val;
+                }
+            }
+        } else {
+            const float* src = a.x + row0 * D;
+            // ---- coalesced read of rows * D floats -> column-major tile (gather through in_perm, minus the bias going back)
+            for (int e = tid; e < rows * D; e += R) {
+                const int r = (int)fastdiv((uint32_t)e, a.div_D);
+                const int c = e - r * D;
+                float val = src[r * D + s_perm[c]];
+                if (MODE == kLuInverse) val -= s_bias[c];
+                s_tile[c * RS + r] = val;
+            }
         }
         for (int e = tid; e < (DP - D) * R; e += R) {   // identity padding: zeros stay zeros
             const int c = D + e / R;
@@ -211,17 +242,32 @@ __global__ void __launch_bounds__(kBlock) lu_linear_kernel(const LuArgs a) {
             tri_apply<true, true, true>(s_M, DP, nb, col, RS);      // gy = L^-T gz
         }
         __syncthreads();
-        float* dst = a.out + row0 * D;
-        for (int e = tid; e < rows * D; e += R) {
-            const int r = (int)fastdiv((uint32_t)e, a.div_D);
-            const int c = e - r * D;
-            float val = s_tile[c * RS + r];
-            if (MODE == kLuForward) val += s_bias[c];
-            dst[r * D + s_scat[c]] = val;
-        }
-        if (kHasBias && a.lad && tid < rows) {
-            float* l = a.lad + row0 + tid;
-            *l = a.accumulate ? *l + layer_lad : layer_lad;
+        if (NCHW) {
+            if (tid < rows) {
+#pragma unroll 4
+                for (int c = 0; c < D; ++c) {
+                    float val = s_tile[c * RS + tid];
+                    if (MODE == kLuForward) val += s_bias[c];
+                    a.out[pix + s_scat[c] * a.hw] = val;
+                }
+            }
+            if (kHasBias && a.lad && first_pixel) {   // one value per image, from the lane that owns its pixel 0
+                float* l = a.lad + img;
+                *l = a.accumulate ? *l + layer_lad : layer_lad;
+            }
+        } else {
+            float* dst = a.out + row0 * D;
+            for (int e = tid; e < rows * D; e += R) {
+                const int r = (int)fastdiv((uint32_t)e, a.div_D);
+                const int c = e - r * D;
+                float val = s_tile[c * RS + r];
+                if (MODE == kLuForward) val += s_bias[c];
+                dst[r * D + s_scat[c]] = val;
+            }
+            if (kHasBias && a.lad && tid < rows) {
+                float* l = a.lad + row0 + tid;
+                *l = a.accumulate ? *l + layer_lad : layer_lad;
+            }
         }
         __syncthreads();
     }
@@ -230,7 +276,8 @@ __global__ void __launch_bounds__(kBlock) lu_linear_kernel(const LuArgs a) {
 
 int lu_launch(int mode, const float* inputs, const float* lower, const float* upper, const float* udiag,
               const float* bias, const int64_t* in_perm, const int64_t* out_scatter, float* outputs, float* logabsdet,
-              int32_t* status, int64_t batch, int32_t features, double eps, int accumulate, void* stream) {
+              int32_t* status, int64_t batch, int32_t features, double eps, int accumulate, void* stream,
+              int64_t hw = 0) {   // hw > 0: K19, `batch` images of `features` planes of hw pixels
     if (batch < 0 || features < 1) return NFA_ERR_INVALID_ARGUMENT;
     if (features < 2 || features > kLuMaxFeatures) return NFA_ERR_UNSUPPORTED;
     if (!(eps >= 0.0)) return NFA_ERR_INVALID_ARGUMENT;
@@ -239,6 +286,7 @@ int lu_launch(int mode, const float* inputs, const float* lower, const float* up
     if (!inputs || !lower || !upper || !udiag || !outputs) return NFA_ERR_INVALID_ARGUMENT;
     if (has_bias && (!bias || !logabsdet)) return NFA_ERR_INVALID_ARGUMENT;
     const int D = features, DP = (D + kLuBlk - 1) / kLuBlk * kLuBlk;
+    if (hw > 0) batch *= hw;   // from here on: rows
     const int cus = device_cu_count();
     // rows per workgroup (= its lanes): the most waves a CU can hold under the 160 KB of LDS, more workgroups on a
     // tie (their load / compute / store phases overlap), and small enough that every CU gets a tile
@@ -272,6 +320,7 @@ int lu_launch(int mode, const float* inputs, const float* lower, const float* up
     a.lad = logabsdet;
     a.status = status;
     a.batch = batch;
+    a.hw = hw;
     a.eps = eps;
     a.D = D;
     a.DP = DP;
@@ -283,10 +332,12 @@ int lu_launch(int mode, const float* inputs, const float* lower, const float* up
     const int64_t tiles = (batch + R - 1) / R;
     int64_t g = (int64_t)cus * per_cu;
     if (g > tiles) g = tiles;
-    void (*kern)(LuArgs) = mode == kLuForward       ? lu_linear_kernel<kLuForward>
-                           : mode == kLuInverse     ? lu_linear_kernel<kLuInverse>
-                           : mode == kLuForwardGrad ? lu_linear_kernel<kLuForwardGrad>
-                                                    : lu_linear_kernel<kLuInverseGrad>;
+    void (*const kerns[2][4])(LuArgs) = {
+        {lu_linear_kernel<kLuForward, false>, lu_linear_kernel<kLuInverse, false>,
+         lu_linear_kernel<kLuForwardGrad, false>, lu_linear_kernel<kLuInverseGrad, false>},
+        {lu_linear_kernel<kLuForward, true>, lu_linear_kernel<kLuInverse, true>,
+         lu_linear_kernel<kLuForwardGrad, true>, lu_linear_kernel<kLuInverseGrad, true>}};
+    void (*kern)(LuArgs) = kerns[hw > 0][mode];
     return launch_kernel(kern, dim3((unsigned)g), dim3((unsigned)R), lds, (hipStream_t)stream, a, kCuLds, false);
 }
 
@@ -313,4 +364,33 @@ extern "C" int nfa_lu_linear_backward_f32(const float* grad_outputs, const float
                           lower_entries, upper_entries, unconstrained_upper_diag, nullptr,
                           /*gather=*/out_scatter, /*scatter=*/in_perm,   // the transposes of the forward call's two
                           grad_inputs, nullptr, status, batch, features, eps, 0, stream);
+}
+
+// K19: the layer over the channels of [batch, channels, height, width]; channel_perm is the module's fixed permutation,
+// gathered going forward (the layer sees inputs[:, channel_perm]) and scattered coming back.
+extern "C" int nfa_lu_conv1x1_f32(const float* inputs, const float* lower_entries, const float* upper_entries,
+                                  const float* unconstrained_upper_diag, const float* bias, const int64_t* channel_perm,
+                                  float* outputs, float* logabsdet, int32_t* status, int64_t batch, int32_t channels,
+                                  int32_t height, int32_t width, double eps, int32_t flags, void* stream) {
+    if (flags & ~(NFA_FLAG_INVERSE | NFA_FLAG_ACCUMULATE_LOGABSDET)) return NFA_ERR_INVALID_ARGUMENT;
+    if (height <= 0 || width <= 0) return NFA_ERR_INVALID_ARGUMENT;
+    const bool inverse = (flags & NFA_FLAG_INVERSE) != 0;
+    return nfa::lu_launch(inverse ? nfa::kLuInverse : nfa::kLuForward, inputs, lower_entries, upper_entries,
+                          unconstrained_upper_diag, bias, inverse ? nullptr : channel_perm,
+                          inverse ? channel_perm : nullptr, outputs, logabsdet, status, batch, channels, eps,
+                          (flags & NFA_FLAG_ACCUMULATE_LOGABSDET) ? 1 : 0, stream, (int64_t)height * width);
+}
+
+extern "C" int nfa_lu_conv1x1_backward_f32(const float* grad_outputs, const float* lower_entries,
+                                           const float* upper_entries, const float* unconstrained_upper_diag,
+                                           const int64_t* channel_perm, float* grad_inputs, int32_t* status,
+                                           int64_t batch, int32_t channels, int32_t height, int32_t width, double eps,
+                                           int32_t flags, void* stream) {
+    if (flags & ~NFA_FLAG_INVERSE) return NFA_ERR_INVALID_ARGUMENT;
+    if (height <= 0 || width <= 0) return NFA_ERR_INVALID_ARGUMENT;
+    const bool inverse = (flags & NFA_FLAG_INVERSE) != 0;
+    return nfa::lu_launch(inverse ? nfa::kLuInverseGrad : nfa::kLuForwardGrad, grad_outputs, lower_entries,
+                          upper_entries, unconstrained_upper_diag, nullptr,
+                          /*gather=*/inverse ? channel_perm : nullptr, /*scatter=*/inverse ? nullptr : channel_perm,
+                          grad_inputs, nullptr, status, batch, channels, eps, 0, stream, (int64_t)height * width);
 }

@@ -574,6 +574,69 @@ def _lu_linear_backward_launch(grad_outputs, params, eps, inverse, perm, scat):
     return g_in
 
 
+def lu_conv1x1(inputs, lower_entries, upper_entries, unconstrained_upper_diag, bias, eps=1e-3, inverse=False,
+               channel_perm=None, accumulate_into=None):
+    """K19 -- the invertible 1x1 convolution (transforms/conv.py): K16's layer over the channels of a float32
+    [B, C, H, W] tensor, 2 <= C <= 128, per pixel  forward y = L (U x[channel_perm]) + b,  inverse
+    x[channel_perm] = U^-1 (L^-1 (y - b)); the tensor stays NCHW, the permutation is part of the launch.
+    Returns (outputs [B, C, H, W], logabsdet [B] = +- H W sum log U_ii).  `accumulate_into` as `lu_linear`.
+    Differentiable in the inputs and all four parameters (K19-backward and the device's GEMM) when one requires grad."""
+    N.require_device_f32("inputs", inputs, 4)
+    dev = inputs.device
+    C = inputs.shape[1]
+    tri = C * (C - 1) // 2
+    params = (lower_entries, upper_entries, unconstrained_upper_diag, bias)
+    for name, t, n in zip(("lower_entries", "upper_entries", "unconstrained_upper_diag", "bias"), params, (tri, tri, C, C)):
+        N.require_device_f32(name, t, 1)
+        if t.device != dev:
+            raise ValueError("%s is on %s, inputs on %s" % (name, t.device, dev))
+        if t.numel() != n:
+            raise ValueError("%s must have %d entries for %d channels, got %d" % (name, n, C, t.numel()))
+    perm = _idx("channel_perm", channel_perm, dev, C)
+    if AG.needs_grad(inputs, *params):
+        out, lad = AG.LUConv1x1.apply(inputs.contiguous(), lower_entries, upper_entries, unconstrained_upper_diag, bias,
+                                      float(eps), bool(inverse), perm)
+        if accumulate_into is not None:
+            accumulate_into += lad
+            lad = accumulate_into
+        return out, lad
+    return _lu_conv1x1_launch(inputs, params, float(eps), inverse, perm, accumulate_into)
+
+
+def _lu_conv1x1_launch(inputs, params, eps, inverse, perm, accumulate_into):
+    dev = inputs.device
+    B, C, H, W = inputs.shape
+    x = inputs.detach().contiguous()
+    lower, upper, udiag, bias = (t.detach().contiguous() for t in params)
+    out = torch.empty_like(x)
+    lad, flags = _lad_buffer(accumulate_into, B, dev, inverse)
+    hook = _launch_hook
+    with torch.cuda.device(dev):
+        token = hook.begin("lu_conv1x1") if hook is not None else None
+        rc = N.load().nfa_lu_conv1x1_f32(N.ptr(x), N.ptr(lower), N.ptr(upper), N.ptr(udiag), N.ptr(bias), N.ptr(perm),
+                                         N.ptr(out), N.ptr(lad), N.ptr(_status_word(dev)), B, C, H, W, eps, flags,
+                                         N.stream_handle(dev))
+        if hook is not None:
+            hook.end(token, 4 * (2 * B * C * H * W + B))
+    N.check(rc)   # (a shape the kernel does not serve is an error here, as in lu_linear)
+    return out, lad
+
+
+def _lu_conv1x1_backward_launch(grad_outputs, params, eps, inverse, perm):
+    """K19-backward: the input gradient (the transposed triangular steps, gather and scatter swapped)."""
+    dev = grad_outputs.device
+    B, C, H, W = grad_outputs.shape
+    g = grad_outputs.detach().contiguous()
+    lower, upper, udiag = (t.detach().contiguous() for t in params[:3])
+    g_in = torch.empty_like(g)
+    with torch.cuda.device(dev):
+        rc = N.load().nfa_lu_conv1x1_backward_f32(N.ptr(g), N.ptr(lower), N.ptr(upper), N.ptr(udiag), N.ptr(perm),
+                                                  N.ptr(g_in), N.ptr(_status_word(dev)), B, C, H, W, eps,
+                                                  N.FLAG_INVERSE if inverse else 0, N.stream_handle(dev))
+    N.check(rc)
+    return g_in
+
+
 NORM_MAX_FEATURES = 1024
 NORM_BATCH_NORM, NORM_ACT_NORM = 0, 1
 

@@ -8,6 +8,8 @@ from .coupling import (AdditiveCouplingTransform, AffineCouplingTransform, Coupl
 from .permutations import Permutation, RandomPermutation, ReversePermutation
 from .linear import Linear
 from .lu import LULinear
+from .conv import OneByOneConvolution
+from .reshape import SqueezeTransform
 from .normalization import ActNorm, BatchNorm
 from . import splines
 from .autoregressive import (AutoregressiveTransform, MaskedAffineAutoregressiveTransform,
