@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define NFA_ABI_VERSION 18 /* bumped whenever a packed layout, a flag set or an entry point changes (round 3: 3 .. 7; round 4: 8,
+#define NFA_ABI_VERSION 19 /* bumped whenever a packed layout, a flag set or an entry point changes (round 3: 3 .. 7; round 4: 8,
                               9: whole-layer kernels for 2 .. 16 bins, nfa_resnet_backward_f32, W_f^T in K14's backward stream;
                               round 5: 10: `bin_idx` outputs of the spline kernels, nfa_searchsorted_f32; 11: NFA_FLAG_RESIDUAL_BLOCKS;
                               round 6: 12: nfa_rqs_flow_resnet_f16x3_f32 (K8x), the *_logits_f32 diagnostic entries,
@@ -40,7 +40,8 @@ extern "C" {
                               15: nfa_lu_linear_f32, nfa_lu_linear_backward_f32;
                               16: nfa_norm_* (K17);
                               17: nfa_nonlin_* (K18);
-                              18: nfa_lu_conv1x1_f32, nfa_lu_conv1x1_backward_f32 (K19) */
+                              18: nfa_lu_conv1x1_f32, nfa_lu_conv1x1_backward_f32 (K19);
+                              19: nfa_diag_normal_*, nfa_mog_* (K20) */
 
 /* return codes */
 #define NFA_OK 0
@@ -1036,6 +1037,55 @@ int nfa_nonlin_backward_f32(const float *inputs, const float *temperature, const
                             const float *grad_logabsdet, float *grad_inputs, float *grad_temperature, void *workspace,
                             int64_t batch, int64_t n, int32_t kind, double p0, double p1, double p2, int32_t flags,
                             void *stream);
+
+/*
+ * K20.  The learned base densities in one launch each: one float32 log_prob[batch], every row's terms summed in float64 in
+ * the order K18's plan fixes from the shape alone (several rows per workgroup for n <= 2048, otherwise pieces of a row, one
+ * workgroup each, folded in piece order by a second small launch) and rounded once.  No atomics: the same bits on every
+ * run, a row's result does not depend on the other rows.  The per-element arithmetic runs in float64 from the float32
+ * operands.  `add` (may be NULL): a float32 [batch] term -- the flow's logabsdet, flows/base.py:49 -- added inside the
+ * float64 sum before the single rounding, as nfa_standard_normal_log_prob_f32 does.  batch == 0 is a no-op.
+ *   workspace   nfa_diag_normal_workspace_bytes / nfa_mog_workspace_bytes(batch, n) bytes (0: may be NULL), scratch of
+ *               the call
+ *
+ * nfa_diag_normal_log_prob_f32 (distributions/normal.py:95-114 ConditionalDiagonalNormal, :155-174 DiagonalNormal):
+ *   log_prob[b] = -0.5 sum_i ((x[b, i] - m[b, i]) exp(-ls[b, i]))^2 - sum_i ls[b, i] - log_z (+ add[b])
+ *   inputs        [batch, n], the flattened view of a contiguous tensor of rank >= 2
+ *   means, log_stds   m[b, i] = means[b * param_stride + i], ls likewise; param_stride in elements: 0 = one shared row
+ *                 (DiagonalNormal's [1, n] parameters), 2n with log_stds = means + n = the two halves of the encoder's
+ *                 [batch, 2n] output read in place (ConditionalDiagonalNormal), n = two separate [batch, n] tensors
+ *   log_z         the module's float64 buffer, by value
+ * nfa_diag_normal_backward_f32: one launch from the operands of the pass that is differentiated and g = grad_log_prob
+ * [batch]; with e2 = exp(-2 ls): grad_inputs = -g (x - m) e2; grad_means[b * grad_param_stride + i] = -grad_inputs and
+ * grad_log_stds[...] = g ((x - m)^2 e2 - 1) (both may be NULL and are then not written: for a shared row the caller sums
+ * over the batch -- sum_b grad_log_stds = -sum_b grad_inputs (x - m) - sum_b g, from nfa_norm_column_sums_f32).  The gradient
+ * of `add` is g itself.
+ *
+ * nfa_mog_log_prob_f32 (nn/nde/made.py:328-353, MixtureOfGaussiansMADE.log_prob behind the MADE's forward pass):
+ *   inputs        [batch, features]
+ *   outputs       [batch, features * components * 3], the MADE's final-layer output read in place in the reference's
+ *                 interleaving (..., components, 3) = logit, mean, unconstrained std
+ *   per element (b, d): lsm = log_softmax(logits), std_k = softplus(u_k) + epsilon (softplus with its threshold of 20),
+ *                 t_k = lsm_k - 0.5 (log 2pi + 2 log std_k + ((x - m_k) / std_k)^2), the element's term is logsumexp_k t_k
+ *                 with its maximum subtracted; log_prob[b] = sum_d term (+ add[b])
+ *   components    1 .. 64 (NFA_ERR_UNSUPPORTED above); 1 gives lsm = 0 exactly
+ * nfa_mog_backward_f32: one launch; with r_k = exp(t_k - lse) and g = grad_log_prob[b]:
+ *   grad_outputs[b, d, k, :] = g (r_k - softmax_k), g r_k (x - m_k) / std_k^2,
+ *                              g r_k (((x - m_k) / std_k)^2 - 1) / std_k * softplus'(u_k);   grad_inputs = -sum_k d/dm_k
+ */
+size_t nfa_diag_normal_workspace_bytes(int64_t batch, int64_t n);
+size_t nfa_mog_workspace_bytes(int64_t batch, int64_t features);
+int nfa_diag_normal_log_prob_f32(const float *inputs, const float *means, const float *log_stds, const float *add,
+                                 float *log_prob, void *workspace, int64_t batch, int64_t n, int64_t param_stride,
+                                 double log_z, void *stream);
+int nfa_diag_normal_backward_f32(const float *inputs, const float *means, const float *log_stds,
+                                 const float *grad_log_prob, float *grad_inputs, float *grad_means, float *grad_log_stds,
+                                 int64_t batch, int64_t n, int64_t param_stride, int64_t grad_param_stride, void *stream);
+int nfa_mog_log_prob_f32(const float *inputs, const float *outputs, const float *add, float *log_prob, void *workspace,
+                         int64_t batch, int64_t features, int32_t components, double epsilon, void *stream);
+int nfa_mog_backward_f32(const float *inputs, const float *outputs, const float *grad_log_prob, float *grad_inputs,
+                         float *grad_outputs, int64_t batch, int64_t features, int32_t components, double epsilon,
+                         void *stream);
 
 /*
  * K3.  Per-sample reduction: torchutils.sum_except_batch, utils/torchutils.py:19-24.

@@ -35,7 +35,7 @@ TAILS_NONE, TAILS_LINEAR = 0, 1
 NONLIN_EXP, NONLIN_TANH, NONLIN_LOG_TANH, NONLIN_LEAKY_RELU, NONLIN_SIGMOID, NONLIN_CAUCHY_CDF = 0, 1, 2, 3, 4, 5
 SCALE_DEFAULT, SCALE_GENERAL, SCALE_ADDITIVE, SCALE_GIVEN, SCALE_SOFTPLUS = 0, 1, 2, 3, 4
 
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 EXPORTS = (
     "nfa_abi_version",
@@ -97,6 +97,12 @@ EXPORTS = (
     "nfa_nonlin_backward_workspace_bytes",
     "nfa_nonlin_f32",
     "nfa_nonlin_backward_f32",
+    "nfa_diag_normal_workspace_bytes",
+    "nfa_mog_workspace_bytes",
+    "nfa_diag_normal_log_prob_f32",
+    "nfa_diag_normal_backward_f32",
+    "nfa_mog_log_prob_f32",
+    "nfa_mog_backward_f32",
     "nfa_rowsum_f32",
     "nfa_standard_normal_log_prob_f32",
     "nfa_sum_count_f64",
@@ -268,6 +274,17 @@ def _declare(lib):
     lib.nfa_nonlin_f32.argtypes = [vp] * 6 + [i64, i64, i32, f64, f64, f64, i32, vp]
     lib.nfa_nonlin_backward_f32.restype = ctypes.c_int
     lib.nfa_nonlin_backward_f32.argtypes = [vp] * 7 + [i64, i64, i32, f64, f64, f64, i32, vp]
+    for fn in (lib.nfa_diag_normal_workspace_bytes, lib.nfa_mog_workspace_bytes):
+        fn.restype = ctypes.c_size_t
+        fn.argtypes = [i64, i64]
+    lib.nfa_diag_normal_log_prob_f32.restype = ctypes.c_int
+    lib.nfa_diag_normal_log_prob_f32.argtypes = [vp] * 6 + [i64, i64, i64, f64, vp]
+    lib.nfa_diag_normal_backward_f32.restype = ctypes.c_int
+    lib.nfa_diag_normal_backward_f32.argtypes = [vp] * 7 + [i64, i64, i64, i64, vp]
+    lib.nfa_mog_log_prob_f32.restype = ctypes.c_int
+    lib.nfa_mog_log_prob_f32.argtypes = [vp] * 5 + [i64, i64, i32, f64, vp]
+    lib.nfa_mog_backward_f32.restype = ctypes.c_int
+    lib.nfa_mog_backward_f32.argtypes = [vp] * 5 + [i64, i64, i32, f64, vp]
     lib.nfa_rowsum_f32.restype = ctypes.c_int
     lib.nfa_rowsum_f32.argtypes = [vp, vp, i64, i64, vp]
     lib.nfa_standard_normal_log_prob_f32.restype = ctypes.c_int

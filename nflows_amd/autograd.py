@@ -266,6 +266,53 @@ class StandardNormalLogProb(torch.autograd.Function):
         return g_z, (g if ctx.has_lad else None)
 
 
+class DiagNormalLogProb(torch.autograd.Function):
+    """K20 "diag" forward + backward (ops.diag_normal_log_prob): one launch from the saved operands; per-row parameters get
+    their gradients from that launch (the packed [B, 2 N] encoder output as one [B, 2 N] tensor), the shared row from K17's
+    float64 column reduction.  The gradient of `logabsdet` is grad_log_prob itself."""
+
+    @staticmethod
+    def forward(ctx, inputs, means, log_stds, log_z, logabsdet):
+        from . import ops
+        out = ops._diag_normal_launch(inputs, means, log_stds, log_z, logabsdet)
+        ctx.packed = log_stds is None
+        ctx.save_for_backward(inputs, means, *(() if log_stds is None else (log_stds,)))
+        ctx.has_add = logabsdet is not None
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        from . import ops
+        inputs, means = ctx.saved_tensors[:2]
+        log_stds = None if ctx.packed else ctx.saved_tensors[2]
+        want_params = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        g_x, g_m, g_ls = ops._diag_normal_backward_launch(inputs, means, log_stds, g, want_params)
+        return (g_x if ctx.needs_input_grad[0] else None, g_m if ctx.needs_input_grad[1] else None,
+                g_ls if (not ctx.packed and ctx.needs_input_grad[2]) else None, None, g if ctx.has_add else None)
+
+
+class MoGLogProb(torch.autograd.Function):
+    """K20 "mog" forward + backward (ops.mog_log_prob): grad_outputs and grad_inputs in one launch from the saved operands."""
+
+    @staticmethod
+    def forward(ctx, inputs, outputs, num_components, epsilon, logabsdet):
+        from . import ops
+        out = ops._mog_launch(inputs, outputs, num_components, epsilon, logabsdet)
+        ctx.save_for_backward(inputs, outputs)
+        ctx.K, ctx.epsilon, ctx.has_add = num_components, epsilon, logabsdet is not None
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        from . import ops
+        inputs, outputs = ctx.saved_tensors
+        g_x, g_o = ops._mog_backward_launch(inputs, outputs, g, ctx.K, ctx.epsilon)
+        return (g_x if ctx.needs_input_grad[0] else None, g_o if ctx.needs_input_grad[1] else None, None, None,
+                g if ctx.has_add else None)
+
+
 def _lu_parameter_grads(seen, g_seen, lower, upper, udiag, bias, eps, inverse, lad_weight):
     """The four parameter gradients of the LU layer from float64 rows: `seen` [rows, D] the layer's inputs and `g_seen`
     the gradients of its outputs, both as the layer itself sees them (after the gather / before the scatter);

@@ -137,4 +137,17 @@ inline RowSumPlan plan_row_sum(int64_t batch, int64_t n) {
     return p;
 }
 
+// ------------------------------------------------------------------------------------------
+// K20 "mog" (density.hip): a workgroup's range of elements comes from plan_row_sum(batch, features); an element's 3K
+// parameters are contiguous, so the range's parameters are one contiguous range too and go through LDS in sub-tiles of
+// T elements, T a power of two <= kBlock.  Beside the sub-tile the kernel holds kRowSumTile float64 terms and the waves'
+// partial sums in static LDS; the whole stays within the 64 KB a launch gets without an opt-in.  Lane l always takes
+// the elements l, l + kBlock, ... of the range, whatever T is: sub-tiling changes no summation order.
+constexpr int kMogStaticLds = kRowSumTile * 8 + 1024;
+// the LDS image of T elements: tile_load's 16-byte window around T * 3K floats
+inline size_t mog_tile_bytes(int T, int K) { return ((size_t)T * 3 * K + 8) * 4; }
+inline int plan_mog_tile(int K) {
+    return plan_element_tile(1, (size_t)(kDefaultDynLds - kMogStaticLds), [K](int T) { return mog_tile_bytes(T, K); });
+}
+
 }  // namespace nfa

@@ -20,6 +20,7 @@
 // temperature one float64 partial per workgroup, folded by a single workgroup in a fixed order and rounded once.
 #include "common.hpp"
 #include "nonlin_math.hpp"
+#include "row_sum.hpp"   // the row sums' device code, shared with K20
 
 namespace nfa {
 namespace {
@@ -38,39 +39,6 @@ struct NonlinArgs {
     int rows, group, pieces, accumulate;
     FastDiv div_n;
 };
-
-template <int V>
-__device__ __forceinline__ void nonlin_load(const float* src, float* v) {
-    if (V == 4) {
-        const float4 q = *reinterpret_cast<const float4*>(src);
-        v[0] = q.x;
-        v[1] = q.y;
-        v[2] = q.z;
-        v[3] = q.w;
-    } else {
-        v[0] = *src;
-    }
-}
-
-template <int V>
-__device__ __forceinline__ void nonlin_store(float* dst, const float* v) {
-    if (V == 4) *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
-    else *dst = v[0];
-}
-
-// the sum of `v` over the workgroup's lanes: a shuffle tree per wave, the waves in wave order; valid in lane 0
-__device__ __forceinline__ double nonlin_block_sum(double v, double* s_w, int tid) {
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
-    if ((tid & (kWave - 1)) == 0) s_w[tid / kWave] = v;
-    __syncthreads();
-    double total = 0.0;
-    if (tid == 0) {
-#pragma unroll
-        for (int w = 0; w < kBlock / kWave; ++w) total += s_w[w];
-    }
-    return total;
-}
 
 __device__ __forceinline__ void nonlin_put_lad(const NonlinArgs& p, int64_t row, double sum) {
     const float v = (float)(sum * p.scale);
@@ -94,14 +62,14 @@ __global__ void __launch_bounds__(kBlock) nonlin_kernel(const NonlinArgs p) {
         const int body = V == 4 ? (count & ~3) : count;
         for (int i = tid * V; i < body; i += kBlock * V) {
             float v[V], o[V];
-            nonlin_load<V>(src + i, v);
+            rowsum_load<V>(src + i, v);
 #pragma unroll
             for (int j = 0; j < V; ++j) {
                 double y;
                 bad |= nonlin_eval<KIND, INVERSE>(v[j], k, y, s_c[i + j]);
                 o[j] = (float)y;
             }
-            nonlin_store<V>(dst + i, o);
+            rowsum_store<V>(dst + i, o);
         }
         if (V == 4 && body + tid < count) {   // what is left of a range that is no whole number of float4s
             double y;
@@ -109,18 +77,7 @@ __global__ void __launch_bounds__(kBlock) nonlin_kernel(const NonlinArgs p) {
             dst[body + tid] = (float)y;
         }
         __syncthreads();
-        const int G = p.group, per_pass = kBlock / G;
-        const int g = tid & (G - 1), slot = tid / G;
-        for (int r0 = 0; r0 < rows; r0 += per_pass) {
-            const int r = r0 + slot;
-            double acc = 0.0;
-            if (r < rows) {
-                const double* c = s_c + r * n;
-                for (int i = g; i < n; i += G) acc += c[i];
-            }
-            for (int off = G >> 1; off > 0; off >>= 1) acc += __shfl_down(acc, off, G);
-            if (r < rows && g == 0) nonlin_put_lad(p, row0 + r, acc);
-        }
+        rowsum_rows(s_c, rows, n, p.group, tid, [&](int r, double sum) { nonlin_put_lad(p, row0 + r, sum); });
     } else {   // ---- one piece of one row
         const int64_t row = (int64_t)blockIdx.x / p.pieces;
         const int piece = (int)((int64_t)blockIdx.x - row * p.pieces);
@@ -131,7 +88,7 @@ __global__ void __launch_bounds__(kBlock) nonlin_kernel(const NonlinArgs p) {
         double acc = 0.0;
         for (int64_t i = (int64_t)tid * V; i < len; i += kBlock * V) {
             float v[V], o[V];
-            nonlin_load<V>(src + i, v);
+            rowsum_load<V>(src + i, v);
 #pragma unroll
             for (int j = 0; j < V; ++j) {
                 double y, c;
@@ -139,9 +96,9 @@ __global__ void __launch_bounds__(kBlock) nonlin_kernel(const NonlinArgs p) {
                 o[j] = (float)y;
                 acc += c;
             }
-            nonlin_store<V>(dst + i, o);
+            rowsum_store<V>(dst + i, o);
         }
-        const double total = nonlin_block_sum(acc, s_w, tid);
+        const double total = rowsum_block_sum(acc, s_w, tid);
         if (tid == 0) {
             if (p.pieces == 1) nonlin_put_lad(p, row, total);
             else p.ws[row * p.pieces + piece] = total;
@@ -154,9 +111,7 @@ __global__ void __launch_bounds__(kBlock) nonlin_kernel(const NonlinArgs p) {
 __global__ void __launch_bounds__(kBlock) nonlin_fold_kernel(const NonlinArgs p) {
     const int64_t row = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (row >= p.batch) return;
-    double acc = 0.0;
-    for (int s = 0; s < p.pieces; ++s) acc += p.ws[row * p.pieces + s];
-    nonlin_put_lad(p, row, acc);
+    nonlin_put_lad(p, row, rowsum_pieces(p.ws, row, p.pieces));
 }
 
 template <int KIND, bool INVERSE, int V>
@@ -175,8 +130,8 @@ __global__ void __launch_bounds__(kBlock) nonlin_backward_kernel(const NonlinArg
         const int body = V == 4 ? (count & ~3) : count;
         for (int i = tid * V; i < body; i += kBlock * V) {
             float v[V], g[V], o[V];
-            nonlin_load<V>(p.x + base + i, v);
-            nonlin_load<V>(p.g_out + base + i, g);
+            rowsum_load<V>(p.x + base + i, v);
+            rowsum_load<V>(p.g_out + base + i, g);
 #pragma unroll
             for (int j = 0; j < V; ++j) {
                 const float gl = p.g_lad[row0 + (int)fastdiv((uint32_t)(i + j), p.div_n)];
@@ -185,7 +140,7 @@ __global__ void __launch_bounds__(kBlock) nonlin_backward_kernel(const NonlinArg
                 o[j] = (float)((double)g[j] * dy + (double)gl * dc);
                 if (want_t) acc += (double)g[j] * dy_t + (double)gl * dc_t;
             }
-            nonlin_store<V>(p.out + base + i, o);
+            rowsum_store<V>(p.out + base + i, o);
         }
         if (V == 4 && body + tid < count) {
             const int i = body + tid;
@@ -204,8 +159,8 @@ __global__ void __launch_bounds__(kBlock) nonlin_backward_kernel(const NonlinArg
         const float gl = p.g_lad[row];
         for (int64_t i = (int64_t)tid * V; i < len; i += kBlock * V) {
             float v[V], g[V], o[V];
-            nonlin_load<V>(p.x + base + i, v);
-            nonlin_load<V>(p.g_out + base + i, g);
+            rowsum_load<V>(p.x + base + i, v);
+            rowsum_load<V>(p.g_out + base + i, g);
 #pragma unroll
             for (int j = 0; j < V; ++j) {
                 double dy, dc, dy_t, dc_t;
@@ -213,11 +168,11 @@ __global__ void __launch_bounds__(kBlock) nonlin_backward_kernel(const NonlinArg
                 o[j] = (float)((double)g[j] * dy + (double)gl * dc);
                 if (want_t) acc += (double)g[j] * dy_t + (double)gl * dc_t;
             }
-            nonlin_store<V>(p.out + base + i, o);
+            rowsum_store<V>(p.out + base + i, o);
         }
     }
     if (want_t) {   // (workgroup-uniform)
-        const double total = nonlin_block_sum(acc, s_w, tid);
+        const double total = rowsum_block_sum(acc, s_w, tid);
         if (tid == 0) p.ws[blockIdx.x] = total;
     }
 }
@@ -233,7 +188,7 @@ __global__ void __launch_bounds__(kBlock) nonlin_temperature_fold_kernel(const N
     __shared__ double s_w[kBlock / kWave];
     double acc = 0.0;
     for (int64_t i = threadIdx.x; i < p.count; i += kBlock) acc += p.partials[i];
-    const double total = nonlin_block_sum(acc, s_w, threadIdx.x);
+    const double total = rowsum_block_sum(acc, s_w, threadIdx.x);
     if (threadIdx.x == 0) p.out[0] = (float)total;
 }
 

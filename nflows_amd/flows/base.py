@@ -2,7 +2,7 @@
 
 The caller of the hot path: `log_prob` = transform forward + base log-density, `sample` = base
 draw + transform inverse.  With a `StandardNormal` base on the GPU the base density and the final
-`+ logabsdet` (flows/base.py:49) are one kernel.
+`+ logabsdet` (flows/base.py:49) are one kernel; so are they with a `DiagonalNormal` or `ConditionalDiagonalNormal` base (K20).
 """
 from inspect import signature
 
@@ -11,7 +11,7 @@ from torch import nn
 
 from .. import ops
 from ..distributions.base import Distribution
-from ..distributions.normal import StandardNormal
+from ..distributions.normal import ConditionalDiagonalNormal, DiagonalNormal, StandardNormal
 from ..utils import torchutils
 
 
@@ -49,6 +49,11 @@ class Flow(Distribution):
             if noise.shape[1:] != base._shape:
                 raise ValueError("Expected input of shape {}, got {}".format(base._shape, noise.shape[1:]))
             return ops.standard_normal_log_prob(noise, logabsdet)
+        if type(base) in (DiagonalNormal, ConditionalDiagonalNormal) and noise.is_cuda and noise.dtype == torch.float32:
+            # K20 adds the logabsdet inside its float64 row sum, before the single rounding (the last layer may hand over a
+            # column slice of a padded tensor: the kernel takes contiguous rows, as ops.standard_normal_log_prob makes them)
+            return base.log_prob(noise.contiguous(), context=embedded if self._context_used_in_base else None,
+                                 logabsdet=logabsdet.contiguous())
         return self._base_log_prob(noise, embedded) + logabsdet
 
     # -- sampling --------------------------------------------------------------------------

@@ -1,1 +1,1 @@
-from . import functional, nets
+from . import functional, nde, nets

@@ -869,6 +869,195 @@ def _nonlinearity_backward_launch(inputs, temperature, grad_outputs, grad_logabs
     return g_in, g_t
 
 
+# K20: the learned base densities.
+MOG_MAX_COMPONENTS = 64
+
+
+def _row_stride(name, t, batch, n):
+    """Row stride in elements of a parameter operand of K20 "diag": 0 for one shared row ([n] / [1, n]-shaped), else the
+    stride of dimension 0 of a [batch, ...] tensor whose rows are n contiguous elements."""
+    if t.numel() == n and (t.dim() < 2 or t.shape[0] == 1):
+        if not t.is_contiguous():
+            raise ValueError("%s must be contiguous" % name)
+        return 0
+    if t.dim() < 2 or t.shape[0] != batch or t.numel() != batch * n:
+        raise ValueError("%s must hold one row of %d elements, or one per input row" % (name, n))
+    if not t[0].is_contiguous() or (batch > 1 and t.stride(0) < n):
+        raise ValueError("%s: a row must be %d contiguous elements" % (name, n))
+    return t.stride(0) if batch > 1 else n
+
+
+def _diag_operands(inputs, means, log_stds):
+    """(batch, n, means, log_stds, param_stride, packed) of ops.diag_normal_log_prob; `packed`: `means` is the encoder's
+    whole [batch, 2n] output and `log_stds` its second half."""
+    N.require_device_f32("inputs", inputs)
+    if inputs.dim() < 2:
+        raise ValueError("inputs must have a batch dimension and at least one more, got shape %s" % (tuple(inputs.shape),))
+    B = inputs.shape[0]
+    n = max(int(np.prod(inputs.shape[1:])), 1)
+    N.require_device_f32("means", means)
+    if means.device != inputs.device:
+        raise ValueError("means is on %s, inputs on %s" % (means.device, inputs.device))
+    if log_stds is None:
+        if means.dim() != 2 or tuple(means.shape) != (B, 2 * n) or not means.is_contiguous():
+            raise ValueError("with log_stds=None, means is the contiguous [batch, 2 n] tensor of both halves")
+        return B, n, means, means[:, n:], 2 * n, True
+    N.require_device_f32("log_stds", log_stds)
+    if log_stds.device != inputs.device:
+        raise ValueError("log_stds is on %s, inputs on %s" % (log_stds.device, inputs.device))
+    stride = _row_stride("means", means, B, n)
+    if _row_stride("log_stds", log_stds, B, n) != stride:
+        raise ValueError("means and log_stds must have the same row stride")
+    return B, n, means, log_stds, stride, False
+
+
+def diag_normal_log_prob(inputs, means, log_stds, log_z, logabsdet=None):
+    """K20 "diag" -- -0.5 sum(((x - m) exp(-ls))^2) - sum(ls) - log_z (+ logabsdet) per row, one launch (distributions/normal.py
+    :95-114, :155-174): float32 `inputs` [B, ...] (contiguous; everything but dimension 0 is summed), `means` / `log_stds`
+    either one shared row ([N] or [1, N]: DiagonalNormal) or one row per input row ([B, ...], same row stride for both).
+    `log_stds=None`: `means` is the encoder's contiguous [B, 2 N] output, both halves read in place -- no slice copy -- and
+    its gradient arrives as one [B, 2 N] tensor.  `log_z`: a number or the module's float64 buffer.  The row's terms are
+    summed in float64 in K18's fixed order, `logabsdet` [B] is added inside that sum, and the result is rounded once.
+    Differentiable in every tensor operand."""
+    B, n, means, log_stds_view, stride, packed = _diag_operands(inputs, means, log_stds)
+    if logabsdet is not None:
+        N.require_device_f32("logabsdet", logabsdet, 1)
+        if logabsdet.shape[0] != B:
+            raise ValueError("logabsdet must have one entry per input row")
+    log_z = float(log_z)
+    if AG.needs_grad(inputs, means, log_stds, logabsdet):
+        return AG.DiagNormalLogProb.apply(inputs.contiguous(), means, log_stds, log_z, logabsdet)
+    return _diag_normal_launch(inputs, means, log_stds, log_z, logabsdet)
+
+
+def _diag_normal_launch(inputs, means, log_stds, log_z, logabsdet):
+    B, n, m, ls, stride, _ = _diag_operands(inputs.detach(), means.detach(), None if log_stds is None else log_stds.detach())
+    dev = inputs.device
+    x = inputs.detach().contiguous()
+    add = None if logabsdet is None else logabsdet.detach().contiguous()
+    out = torch.empty(B, dtype=torch.float32, device=dev)
+    lib = N.load()
+    nbytes = lib.nfa_diag_normal_workspace_bytes(B, n)
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev) if nbytes else None
+    hook = _launch_hook
+    with torch.cuda.device(dev):
+        token = hook.begin("diag_normal") if hook is not None else None
+        rc = lib.nfa_diag_normal_log_prob_f32(N.ptr(x), N.ptr(m), N.ptr(ls), N.ptr(add), N.ptr(out), N.ptr(ws), B, n, stride,
+                                              log_z, N.stream_handle(dev))
+        if hook is not None:
+            hook.end(token, 4 * (B * n + 2 * n * (B if stride else 1) + B * (2 if add is not None else 1)))
+    N.check(rc)
+    return out
+
+
+def _diag_normal_backward_launch(inputs, means, log_stds, grad_log_prob, want_params):
+    """K20 "diag"-backward: (grad_inputs, grad_means, grad_log_stds); packed operands: grad_means is the [B, 2 N] gradient of
+    the encoder output and grad_log_stds None; a shared row: both [1-row shaped] float32 from K17's column reduction."""
+    B, n, m, ls, stride, packed = _diag_operands(inputs, means, log_stds)
+    dev = inputs.device
+    x = inputs.detach().contiguous()
+    g = grad_log_prob.detach().contiguous()
+    g_x = torch.empty_like(x)
+    g_m = g_ls = None
+    gstride = 0
+    if want_params and stride:
+        if packed:
+            g_m = torch.empty_like(m)
+            g_ls = g_m[:, n:]
+            gstride = 2 * n
+        else:
+            g_m = torch.empty(means.shape, dtype=torch.float32, device=dev)
+            g_ls = torch.empty(log_stds.shape, dtype=torch.float32, device=dev)
+            gstride = n
+    hook = _launch_hook
+    with torch.cuda.device(dev):
+        token = hook.begin("diag_normal_backward") if hook is not None else None
+        rc = N.load().nfa_diag_normal_backward_f32(N.ptr(x), N.ptr(m), N.ptr(ls), N.ptr(g), N.ptr(g_x), N.ptr(g_m), N.ptr(g_ls),
+                                                   B, n, stride, gstride, N.stream_handle(dev))
+        if hook is not None:
+            hook.end(token, 4 * (2 * B * n + (4 * B * n if stride else 2 * n) + B))
+    N.check(rc)
+    if want_params and not stride:
+        # the shared row: sum_b grad_means = -sum_b grad_x, sum_b grad_log_stds = -sum_b grad_x (x - m) - sum_b g, from K17's
+        # deterministic float64 column reduction (at most NORM_MAX_FEATURES columns a call), rounded once
+        gx2, x2 = g_x.view(B, n), x.view(B, n)
+        parts = []
+        for c0 in range(0, n, NORM_MAX_FEATURES):
+            c1 = min(n, c0 + NORM_MAX_FEATURES)
+            whole = c0 == 0 and c1 == n
+            parts.append(column_sums(gx2 if whole else gx2[:, c0:c1].contiguous(), x2 if whole else x2[:, c0:c1].contiguous()))
+        sums = parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
+        G1, Gu = sums[0], sums[1]
+        m64 = m.detach().reshape(n).to(torch.float64)
+        g_m = (-G1).to(torch.float32).reshape(means.shape)
+        g_ls = (-(Gu - m64 * G1) - g.to(torch.float64).sum()).to(torch.float32).reshape(log_stds.shape)
+    return g_x, g_m, g_ls
+
+
+def mog_log_prob(inputs, outputs, num_components, epsilon, logabsdet=None):
+    """K20 "mog" -- MixtureOfGaussiansMADE.log_prob behind the MADE's forward pass (nn/nde/made.py:328-353) in one launch:
+    float32 `inputs` [B, D], `outputs` the final layer's [B, D * K * 3] read in place in the reference's interleaving
+    (..., K, 3) = logit, mean, unconstrained std, 1 <= K <= 64.  Per element logsumexp_k(log_softmax(logits)_k + log N(x;
+    m_k, softplus(u_k) + epsilon)) in float64; the row's elements are summed in float64 in K18's fixed order, `logabsdet` [B]
+    inside that sum, rounded once.  Differentiable in `inputs`, `outputs` and `logabsdet`."""
+    N.require_device_f32("inputs", inputs, 2)
+    N.require_device_f32("outputs", outputs)
+    B, D = inputs.shape
+    K = int(num_components)
+    if not 1 <= K <= MOG_MAX_COMPONENTS:
+        raise ValueError("num_components must be in 1 .. %d, got %d" % (MOG_MAX_COMPONENTS, K))
+    if D < 1:
+        raise ValueError("inputs must have at least one feature")
+    if outputs.device != inputs.device:
+        raise ValueError("outputs is on %s, inputs on %s" % (outputs.device, inputs.device))
+    if outputs.dim() < 2 or outputs.shape[0] != B or outputs.numel() != B * D * K * 3:
+        raise ValueError("outputs must hold %d x %d x %d x 3 elements, got shape %s" % (B, D, K, tuple(outputs.shape)))
+    if logabsdet is not None:
+        N.require_device_f32("logabsdet", logabsdet, 1)
+        if logabsdet.shape[0] != B:
+            raise ValueError("logabsdet must have one entry per input row")
+    if AG.needs_grad(inputs, outputs, logabsdet):
+        return AG.MoGLogProb.apply(inputs.contiguous(), outputs.contiguous(), K, float(epsilon), logabsdet)
+    return _mog_launch(inputs, outputs, K, float(epsilon), logabsdet)
+
+
+def _mog_launch(inputs, outputs, K, epsilon, logabsdet):
+    dev = inputs.device
+    B, D = inputs.shape
+    x, o = inputs.detach().contiguous(), outputs.detach().contiguous()
+    add = None if logabsdet is None else logabsdet.detach().contiguous()
+    out = torch.empty(B, dtype=torch.float32, device=dev)
+    lib = N.load()
+    nbytes = lib.nfa_mog_workspace_bytes(B, D)
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev) if nbytes else None
+    hook = _launch_hook
+    with torch.cuda.device(dev):
+        token = hook.begin("mog") if hook is not None else None
+        rc = lib.nfa_mog_log_prob_f32(N.ptr(x), N.ptr(o), N.ptr(add), N.ptr(out), N.ptr(ws), B, D, K, epsilon,
+                                      N.stream_handle(dev))
+        if hook is not None:
+            hook.end(token, 4 * (B * D * (1 + 3 * K) + B * (2 if add is not None else 1)))
+    N.check(rc)
+    return out
+
+
+def _mog_backward_launch(inputs, outputs, grad_log_prob, K, epsilon):
+    """K20 "mog"-backward: (grad_inputs [B, D], grad_outputs like outputs) in one launch."""
+    dev = inputs.device
+    B, D = inputs.shape
+    x, o, g = inputs.detach().contiguous(), outputs.detach().contiguous(), grad_log_prob.detach().contiguous()
+    g_x, g_o = torch.empty_like(x), torch.empty_like(o)
+    hook = _launch_hook
+    with torch.cuda.device(dev):
+        token = hook.begin("mog_backward") if hook is not None else None
+        rc = N.load().nfa_mog_backward_f32(N.ptr(x), N.ptr(o), N.ptr(g), N.ptr(g_x), N.ptr(g_o), B, D, K, epsilon,
+                                           N.stream_handle(dev))
+        if hook is not None:
+            hook.end(token, 4 * (2 * B * D * (1 + 3 * K) + B))
+    N.check(rc)
+    return g_x, g_o
+
+
 def rowsum(x):
     """K3 -- torch.sum over everything but the batch dimension."""
     N.require_device_f32("x", x)
