@@ -22,6 +22,9 @@
 //     loads: f16x3_gemm.hpp, request_stage), four waves per
 //     workgroup, two workgroups per CU; fragments 0 .. 3 of every stage are read right behind the PREVIOUS stage's
 //     barrier (f16x3_gemm.hpp: Lead), the barrier stands in front of a stage's last MFMAs;
+//   * biases and tables: a layer's biases and the next layer's table are fetched a layer ahead into a bias area in LDS, as
+//     LDS-DMA pieces issued in front of a stage's weight requests (rqs_resnet_f16x3_kernel.hpp: bias_area_piece) -- the
+//     layer loop holds no per-lane global load and no vmcnt(0);
 //   * the final layer is tile-major with the spline evaluation (rqs_fused8.hpp: one walk over fp32 running knot
 //     sums, logits read at scale 1 / kappa straight from the accumulators) woven between its MFMAs: 32 time units per
 //     tile (an f16 MFMA one, a bf8 MFMA two).
@@ -47,10 +50,17 @@
 using namespace nfa;
 
 // The instance of a launch: 8 bins (the diagnostic instances beside), the other bin counts in their own translation units.
-static k8x::KernelFn f16x3_kernel(bool inverse, int init_ks, int K, bool dbg) {
+static k8x::KernelFn f16x3_kernel(bool inverse, int init_ks, int K, bool dbg, bool bias_lds) {
     if (K != 8) {
-        const k8x::KernelFn kern = k8x::bins_kernel_a(K, inverse, init_ks);
-        return kern ? kern : k8x::bins_kernel_b(K, inverse, init_ks);
+        const k8x::KernelFn kern = k8x::bins_kernel_a(K, inverse, init_ks, bias_lds);
+        return kern ? kern : k8x::bins_kernel_b(K, inverse, init_ks, bias_lds);
+    }
+    if (!bias_lds) {
+        if (init_ks == 4)
+            return dbg ? (inverse ? k8x::rqs_resnet_f16x3_global_bias_kernel<true, 4, true> : k8x::rqs_resnet_f16x3_global_bias_kernel<false, 4, true>)
+                       : (inverse ? k8x::rqs_resnet_f16x3_global_bias_kernel<true, 4> : k8x::rqs_resnet_f16x3_global_bias_kernel<false, 4>);
+        return dbg ? (inverse ? k8x::rqs_resnet_f16x3_global_bias_kernel<true, 2, true> : k8x::rqs_resnet_f16x3_global_bias_kernel<false, 2, true>)
+                   : (inverse ? k8x::rqs_resnet_f16x3_global_bias_kernel<true, 2> : k8x::rqs_resnet_f16x3_global_bias_kernel<false, 2>);
     }
     if (init_ks == 4)
         return dbg ? (inverse ? k8x::rqs_resnet_f16x3_kernel<true, 4, true> : k8x::rqs_resnet_f16x3_kernel<false, 4, true>)
@@ -82,16 +92,27 @@ static int launch_f16x3(const LayerCall& c, const float* scales, float act_scale
     const int rows_per_feature = spline_rows_per_feature(a.sp.K);
     a.num_stages = init_ks + 16 * c.num_blocks + 2 * (c.num_transform * rows_per_feature / 32);
     a.bias_per_layer = 128 + 256 * c.num_blocks + c.num_transform * rows_per_feature;
-    const size_t lds = (size_t)kRing * kStageVec4 * 16 + (size_t)(kBlock / kWave) * c.features * kRowPad * sizeof(float) +
-                       (size_t)c.num_transform * rows_per_feature * sizeof(float);
+    // dynamic LDS: ring, row tiles, then the bias area (a layer's hidden and final biases, the next layer's raw table) --
+    // or, where that area would take the launch from two workgroups per CU to one, the final layer's biases alone and the
+    // instance that reads the hidden ones from global memory.  (The diagnostic instances take the area whenever it fits the launch.)
+    const size_t lds_rows = (size_t)kRing * kStageVec4 * 16 + (size_t)(kBlock / kWave) * c.features * kRowPad * sizeof(float);
+    const int final_floats = c.num_transform * rows_per_feature;
+    const size_t lds_area = lds_rows + (size_t)k8x::bias_area_floats(c.num_blocks, final_floats) * sizeof(float);
+    const size_t lds_plain = lds_rows + (size_t)final_floats * sizeof(float);
+    const size_t two_per_cu = 80 * 1024 - 2048;
+    // (and the area must fit the launch at all: 64 blocks at D = 128 do not)
+    const size_t launch_limit = kCuLds - 2048;
+    const bool bias_lds = lds_area <= launch_limit && (dbg_logits || lds_area <= two_per_cu || lds_plain > two_per_cu);
+    const size_t lds = bias_lds ? lds_area : lds_plain;
     int64_t blocks = c.batch >> 7;
-    const int64_t per_cu = lds + 2048 <= 80 * 1024 ? 2 : 1;
+    const int64_t per_cu = lds <= two_per_cu ? 2 : 1;
     const int64_t cap = (int64_t)device_cu_count() * per_cu;
     if (blocks > cap) blocks = cap;
     const bool inv = (c.flags & NFA_FLAG_INVERSE) != 0;
-    const k8x::KernelFn kern = f16x3_kernel(inv, init_ks, a.sp.K, dbg_logits);
+    const k8x::KernelFn kern = f16x3_kernel(inv, init_ks, a.sp.K, dbg_logits, bias_lds);
     if (!kern) return NFA_ERR_UNSUPPORTED;
-    note_layer_kernel("k8x::rqs_resnet_f16x3_kernel<inverse=%d, init_ks=%d, K=%d, dbg=%d>", inv ? 1 : 0, init_ks, a.sp.K, dbg_logits ? 1 : 0);
+    note_layer_kernel("k8x::rqs_resnet_f16x3_kernel<inverse=%d, init_ks=%d, K=%d, dbg=%d, bias=%s>", inv ? 1 : 0, init_ks, a.sp.K,
+                      dbg_logits ? 1 : 0, bias_lds ? "lds" : "global");
     return launch_kernel(kern, dim3((unsigned)blocks), dim3(kBlock), lds, (hipStream_t)c.stream, a, kCuLds - 2048);
 }
 

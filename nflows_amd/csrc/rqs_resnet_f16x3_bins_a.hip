@@ -5,11 +5,14 @@
 namespace nfa {
 namespace k8x {
 
-#define NFA_K8X_PICK(KB_)                                                                                                  \
-    (init_ks == 4 ? (inverse ? rqs_resnet_f16x3_kernel<true, 4, false, KB_> : rqs_resnet_f16x3_kernel<false, 4, false, KB_>) \
-                  : (inverse ? rqs_resnet_f16x3_kernel<true, 2, false, KB_> : rqs_resnet_f16x3_kernel<false, 2, false, KB_>))
+#define NFA_K8X_PICK_(KERNEL_, ...)                                                            \
+    (init_ks == 4 ? (inverse ? KERNEL_<true, 4, __VA_ARGS__> : KERNEL_<false, 4, __VA_ARGS__>) \
+                  : (inverse ? KERNEL_<true, 2, __VA_ARGS__> : KERNEL_<false, 2, __VA_ARGS__>))
+// (bias_lds: with the bias area, or the instance that reads the hidden biases from global memory)
+#define NFA_K8X_PICK(KB_) \
+    (bias_lds ? NFA_K8X_PICK_(rqs_resnet_f16x3_kernel, false, KB_) : NFA_K8X_PICK_(rqs_resnet_f16x3_global_bias_kernel, false, KB_))
 
-KernelFn bins_kernel_a(int K, bool inverse, int init_ks) {
+KernelFn bins_kernel_a(int K, bool inverse, int init_ks, bool bias_lds) {
     switch (K) {
         case 2: return NFA_K8X_PICK(2);
         case 3: return NFA_K8X_PICK(3);

@@ -8,6 +8,7 @@
 
 #include <hip/hip_ext.h>
 #include <stdlib.h>
+#include <type_traits>
 
 namespace nfa {
 namespace k8x {
@@ -35,8 +36,9 @@ struct Args {
 // 64-bit VALU (the group loop spent 23 v_lshl_add_u64 / v_mad_*64 per iteration on five of them, and they were among the
 // values the layer loop kept in scratch)
 typedef __attribute__((address_space(3))) float lds_f32;
+typedef __attribute__((address_space(3))) int lds_i32;
 
-using nfa::load_bias_tile;   // (global biases; the overload below reads the final layer's from LDS)
+using nfa::load_bias_tile;   // (global biases: the instances without the bias area; the overload below reads LDS)
 
 __device__ __forceinline__ void load_bias_tile(f32x16& acc, const lds_f32* bias_tile_half) {
     typedef __attribute__((address_space(3))) const vec4f lds_vec4f;
@@ -49,6 +51,37 @@ __device__ __forceinline__ void load_bias_tile(f32x16& acc, const lds_f32* bias_
         acc[q4 * 4 + 2] = b.z;
         acc[q4 * 4 + 3] = b.w;
     }
+}
+
+// The bias area (BIAS_LDS instances): a layer's biases and the next layer's raw table in LDS, fetched ahead as LDS-DMA pieces
+// by the mechanism of the weight stream (f16x3_gemm.hpp: request_stage) -- a buffer resource over the source (scalar), the
+// piece's offset as soffset, the lane's as voffset.  A piece is one wave instruction: 64 lanes x BYTES contiguous bytes, 1 KB
+// (BYTES 16) or 256 B (BYTES 4).  Pieces are issued IN FRONT of a stage's request_stage: they are then older than the three
+// requests the stage's counted wait (stream_advance: vmcnt(3)) leaves in flight, so that wait covers them, whatever their
+// number and whichever waves issue them, and the stage's barrier publishes them -- the ring's invariants stay as they are.
+// The resource covers the PIECE: its base is the piece's first byte and its size what is left of the source from there (the
+// range check compares the lane's voffset with the size and does not see an soffset), so lanes past the source's end read
+// nothing; what they write, if anything, must be padding.
+//   [hidden: 128 + 256 num_blocks floats][raw table of the next layer: 128 ints][final: dt x kFinalRows floats, padded to 1 KB]
+template <int BYTES>
+__device__ __forceinline__ void bias_area_piece(const void* src, int src_bytes, int piece_off, lds_f32* dst) {
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<char*>(static_cast<const char*>(src) + piece_off), (short)0, src_bytes - piece_off, 0x00020000);
+    // (the lane index made afresh: carried from the kernel's entry it would hold a register through the whole layer)
+    unsigned all = ~0u;
+    asm volatile("" : "+s"(all));
+    const unsigned lane = __builtin_amdgcn_mbcnt_hi(all, __builtin_amdgcn_mbcnt_lo(all, 0u));
+    static_assert(BYTES == 16 || BYTES == 4, "dwordx4 or dword pieces");
+    // (the builtin takes its size as a literal)
+    if constexpr (BYTES == 16)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)dst, 16, lane * 16, 0, 0, 0);
+    else
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)dst, 4, lane * 4, 0, 0, 0);
+}
+__host__ __device__ constexpr int bias_area_hidden_floats(int num_blocks) { return 128 + 256 * num_blocks; }
+__host__ __device__ constexpr int bias_area_final_floats(int final_floats) { return (final_floats + 255) & ~255; }
+__host__ __device__ constexpr int bias_area_floats(int num_blocks, int final_floats) {
+    return bias_area_hidden_floats(num_blocks) + kTabLayer + bias_area_final_floats(final_floats);
 }
 
 // Two or four wave-uniform floats through the scalar cache.  The kernel stores to global memory, so the compiler cannot prove the
@@ -192,14 +225,18 @@ __device__ __forceinline__ void any_group_tiles(f32x16& acc, Steps& f, BiasPtr g
 
 __device__ __forceinline__ bool not_finite(float v) { return !(__builtin_fabsf(v) < INFINITY); }
 
-template <bool INVERSE, int INIT_KS, bool DBG = false, int KB = 8>
-__global__ void __launch_bounds__(kBlock, 2) rqs_resnet_f16x3_kernel(const Args a) {
+// BIAS_LDS: the layer's biases and tables come through the bias area (above); without it every hidden bias tile is read
+// from global memory in front of its GEMM and the final layer's are copied through registers, each with a vmcnt(0) that
+// drains the weight ring -- kept for the geometries whose launch the larger area would take from two workgroups per CU
+// to one (rqs_resnet_f16x3.hip: launch_f16x3).
+template <bool INVERSE, int INIT_KS, bool DBG, int KB, bool BIAS_LDS>
+__device__ __forceinline__ void rqs_resnet_f16x3_body(const Args& a) {
     static_assert(!DBG || KB == 8, "the diagnostic instances: 8 bins");
     // rows of the final layer per transformed feature: 8 bins: 23 logits padded to 24, two features share three 32-row tiles;
     // otherwise 3 K - 1 padded to whole 16-row lane-half shares (one feature per lane-half and group of T tiles)
     constexpr int kFinalRows = KB == 8 ? 24 : 16 * ((3 * KB - 1 + 15) / 16);
     constexpr int NW = kBlock / kWave;
-    // dynamic LDS: the weight ring, per wave a [D][33] row tile, the final layer's biases of the current layer
+    // dynamic LDS: the weight ring, per wave a [D][33] row tile, the bias area (without it: the final layer's biases)
     extern __shared__ __attribute__((aligned(16))) float lds_dyn[];
     __shared__ int s_tab[2][kTabLayer];   // tables of the current and the next layer
     __shared__ int s_final[128];
@@ -226,6 +263,16 @@ __global__ void __launch_bounds__(kBlock, 2) rqs_resnet_f16x3_kernel(const Args 
     sm.fetch = 0;
     sm.num_stages = a.num_stages * a.num_layers;
     sm.tid = tid;
+    lds_f32* s_area = (lds_f32*)lds_dyn + kRing * kStageVec4 * 4 + NW * D * kRowPad;
+    lds_f32* s_traw = s_area + bias_area_hidden_floats(a.num_blocks);
+    // hidden biases of a layer: the initial layer's 512 B as two 256 B pieces, a block's 1 KB as one piece
+    auto request_hidden = [&](int layer) {
+        const float* src = a.bias + (size_t)layer * a.bias_per_layer;
+        const int bytes = bias_area_hidden_floats(a.num_blocks) * 4;
+        if (wave >= 2) bias_area_piece<4>(src, bytes, (wave - 2) * 256, s_area + (wave - 2) * 64);
+        for (int j = wave; j < a.num_blocks; j += NW) bias_area_piece<16>(src, bytes, 512 + j * 1024, s_area + 128 + j * 256);
+    };
+    if constexpr (BIAS_LDS) request_hidden(0);
     request_stage(sm);  // stage 0 -> slot 0
     sm.slot = 2;
     request_stage(sm);  // stage 1 -> slot 1
@@ -233,8 +280,24 @@ __global__ void __launch_bounds__(kBlock, 2) rqs_resnet_f16x3_kernel(const Args 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
+#ifdef NFA_K8X_STAGGER   // (measurement builds: the upper half of the grid -- the partners of the lower half's workgroups on
+                         //  their CUs -- starts NFA_K8X_STAGGER x 8 128 cycles late; measured at 8, half a layer, and not
+                         //  kept: DESIGN.md section 4, K8x item 9, profiles/r8/k8x_bias_lds_timing.txt)
+    if (blockIdx.x >= (gridDim.x >> 1))
+        for (int i = 0; i < NFA_K8X_STAGGER; ++i) __builtin_amdgcn_s_sleep(127);
+#endif
     lds_f32* s_row = (lds_f32*)lds_dyn + kRing * kStageVec4 * 4 + wave * D * kRowPad;
-    lds_f32* s_fbias = (lds_f32*)lds_dyn + kRing * kStageVec4 * 4 + NW * D * kRowPad;
+    lds_f32* s_fbias = BIAS_LDS ? s_traw + kTabLayer : s_area;
+    // final-layer biases of a layer: 1 KB pieces, the last one's lanes past the end land in the area's padding
+    auto request_final = [&](int layer) {
+        const float* src = a.bias + (size_t)layer * a.bias_per_layer + bias_area_hidden_floats(a.num_blocks);
+        const int bytes = dt * kFinalRows * 4;
+        for (int j = wave; j * 1024 < bytes; j += NW) bias_area_piece<16>(src, bytes, j * 1024, s_fbias + j * 256);
+    };
+    // raw table of a layer: two 256 B pieces
+    auto request_table = [&](int layer) {
+        if (wave < 2) bias_area_piece<4>(a.tables + layer * kTabLayer, kTabLayer * 4, wave * 256, s_traw + wave * 64);
+    };
     const int groups = dt >> 2;
     const int64_t num_quads = a.batch >> 7;
     const int gemms = 2 + 2 * a.num_blocks;   // per layer
@@ -282,18 +345,27 @@ __global__ void __launch_bounds__(kBlock, 2) rqs_resnet_f16x3_kernel(const Args 
             if ((layer + (blockIdx.x >= (gridDim.x >> 1) ? 1 : 0)) & 1) __builtin_amdgcn_s_setprio(1);
             else __builtin_amdgcn_s_setprio(0);
             const int* tab = s_tab[tb];
-            // the next layer's table (the first one again after the last: next row block) goes to the other half
-            // now; it is read only after this layer's many stage barriers
-            {
+            const int nl = layer + 1 < a.num_layers ? layer + 1 : 0;   // (after the last layer: the next row block's first)
+            // the next layer's table goes to the other half now; it is read only after this layer's many stage barriers
+            if constexpr (!BIAS_LDS) {
                 // (te made afresh from the lane count: carried from the kernel's entry it held a register through the
                 //  whole layer, one of the values the layer loop kept in scratch)
                 unsigned all = ~0u;
                 asm volatile("" : "+s"(all));
                 const int te_l = (int)__builtin_amdgcn_mbcnt_hi(all, __builtin_amdgcn_mbcnt_lo(all, 0u)) + ((wave & 1) << 6);
-                const int nl = layer + 1 < a.num_layers ? layer + 1 : 0;
                 s_tab[tb ^ 1][te_l] = checked(a.tables[nl * kTabLayer + te_l], te_l < kTabTr ? te_l < a.di : te_l - kTabTr < dt);
             }
-            const float* bias = a.bias + (size_t)layer * a.bias_per_layer + half * 16;  // + 32 per tile
+            // this layer's final biases and the next layer's raw table, in front of the initial GEMM's first request: landed
+            // and published by that stage's barrier.  (Their last readers: the previous layer's last final tile, two stage
+            // barriers back; this layer's clamp below, a whole final layer back.)
+            if constexpr (BIAS_LDS) {
+                request_final(layer);
+                request_table(nl);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            std::conditional_t<BIAS_LDS, const lds_f32*, const float*> bias;   // + 32 per tile
+            if constexpr (BIAS_LDS) bias = s_area + half * 16;
+            else bias = a.bias + (size_t)layer * a.bias_per_layer + half * 16;
             const float* sc = a.scales + (size_t)layer * gemms * 2;   // {1 / T, T} per GEMM (uniform)
             Pieces p[8];   // f16 pieces at scale S: the identity features, then the final layer's input
 
@@ -328,7 +400,15 @@ __global__ void __launch_bounds__(kBlock, 2) rqs_resnet_f16x3_kernel(const Args 
             }
             bias += 128;
             sc += 2;
-            {
+            if constexpr (BIAS_LDS) {
+                // the raw table has landed (a stage barrier of this layer is behind every wave): clamped into the other half
+                // of s_tab, which the final layer's barriers publish.  (Every thread takes part, entry tid mod 128: see
+                // the kernel's head.)
+                unsigned all = ~0u;
+                asm volatile("" : "+s"(all));
+                const int te_l = (int)__builtin_amdgcn_mbcnt_hi(all, __builtin_amdgcn_mbcnt_lo(all, 0u)) + ((wave & 1) << 6);
+                s_tab[tb ^ 1][te_l] = checked(((const lds_i32*)s_traw)[te_l], te_l < kTabTr ? te_l < a.di : te_l - kTabTr < dt);
+            } else {
                 // (every wave has passed a stage barrier of this layer: nobody reads the previous layer's biases any
                 //  more; the blocks' barriers come before the first use)
                 const float* fbias = a.bias + (size_t)layer * a.bias_per_layer + 128 + 256 * a.num_blocks;
@@ -363,6 +443,12 @@ __global__ void __launch_bounds__(kBlock, 2) rqs_resnet_f16x3_kernel(const Args 
                 sc += 4;
             }
 
+            // the next layer's hidden biases, in front of the final layer's first request: every wave is past a stage barrier
+            // behind this layer's last hidden bias read (the last block's second Linear, or the initial GEMM)
+            if constexpr (BIAS_LDS) {
+                request_hidden(nl);
+                __builtin_amdgcn_sched_barrier(0);
+            }
             // the residual stream's pieces for the final layer's 24 tiles
 #pragma unroll
             for (int t = 0; t < 4; ++t) tile_to_pieces<false>(h[t], hs, p[2 * t], p[2 * t + 1]);
@@ -545,6 +631,16 @@ __global__ void __launch_bounds__(kBlock, 2) rqs_resnet_f16x3_kernel(const Args 
     if (my_status && a.status) atomicOr(a.status, my_status);
 }
 
+// (two kernel templates over one body, not a fifth template parameter: the instances keep their names)
+template <bool INVERSE, int INIT_KS, bool DBG = false, int KB = 8>
+__global__ void __launch_bounds__(kBlock, 2) rqs_resnet_f16x3_kernel(const Args a) {
+    rqs_resnet_f16x3_body<INVERSE, INIT_KS, DBG, KB, true>(a);
+}
+template <bool INVERSE, int INIT_KS, bool DBG = false, int KB = 8>
+__global__ void __launch_bounds__(kBlock, 2) rqs_resnet_f16x3_global_bias_kernel(const Args a) {
+    rqs_resnet_f16x3_body<INVERSE, INIT_KS, DBG, KB, false>(a);
+}
+
 }  // namespace k8x
 }  // namespace nfa
 
@@ -553,7 +649,7 @@ namespace nfa {
 namespace k8x {
 typedef void (*KernelFn)(const Args);
 // the instances of the other translation units: nullptr when the unit does not hold the combination
-KernelFn bins_kernel_a(int K, bool inverse, int init_ks);   // 2 .. 7, 9 .. 12 bins
-KernelFn bins_kernel_b(int K, bool inverse, int init_ks);   // 13 .. 16, 20, 24, 32 bins
+KernelFn bins_kernel_a(int K, bool inverse, int init_ks, bool bias_lds);   // 2 .. 7, 9 .. 12 bins
+KernelFn bins_kernel_b(int K, bool inverse, int init_ks, bool bias_lds);   // 13 .. 16, 20, 24, 32 bins
 }  // namespace k8x
 }  // namespace nfa
