@@ -41,7 +41,9 @@ extern "C" {
                               16: nfa_norm_* (K17);
                               17: nfa_nonlin_* (K18);
                               18: nfa_lu_conv1x1_f32, nfa_lu_conv1x1_backward_f32 (K19);
-                              19: nfa_diag_normal_*, nfa_mog_* (K20) */
+                              19: nfa_diag_normal_*, nfa_mog_* (K20);
+                              still 19: nfa_affine_flow_made_f32 (K22) is an ADDED entry point -- no existing entry point, flag set
+                              or packed layout changed, so libraries and bindings of 19 keep working with each other */
 
 /* return codes */
 #define NFA_OK 0
@@ -594,6 +596,47 @@ int nfa_affine_flow_mlp_f32(const float *inputs, const void *weights_packed, con
                             int32_t *status, int64_t batch, int32_t features, int32_t num_transform,
                             int32_t num_identity, int32_t hidden_features, int32_t num_hidden_layers,
                             int32_t scale_activation, int32_t flags, void *stream);
+
+/*
+ * K22.  The density pass of a run of masked autoregressive affine layers in ONE launch: per layer
+ *   MaskedAffineAutoregressiveTransform.forward (autoregressive.py:64-128) over a MADE (made.py:233-311, ReLU, no batch
+ *   norm, no active dropout) + the neighbouring column permutations + CompositeTransform._cascade's loop.  K11's kernel in
+ *   its autoregressive mode: with `weight * mask` formed at pack time a MADE is K11's conditioner with
+ *   d_i = d_t = features (residual blocks: NFA_FLAG_RESIDUAL_BLOCKS' form; feed-forward blocks: the MLP form with
+ *   num_hidden_layers = num_blocks); the scale is softplus(u) + 1e-3 (NFA_SCALE_SOFTPLUS), per element K2b's arithmetic.
+ *   inputs          [batch, row_length]: `features` real columns, then pad columns that pass through every layer
+ *                   (row_length % 4 == 0; the density epilogue is told about them through NFA_FLAG_PAD_COLUMNS).
+ *   context         [batch, context_features], or NULL with context_features == 0.
+ *   weights_packed  K11's stages (nfa_affine_flow_mlp_f32), every matrix being weight * mask, per layer in the order consumed:
+ *                     context_layer          (context)     ceil(context_features / 16) k-steps, laid out as the initial
+ *                                                          layer's: column = 16 ks + 8 (l >> 5) + j, columns >= ce zero
+ *                                                          (the kernel forms b_0 + relu(Wc ctx + bc) first and adds the
+ *                                                          initial layer's products to it)
+ *                     initial_layer                        2 k-steps for features <= 32, else 4 (columns >= features zero)
+ *                     per residual block                   linear_layers[0] (8 k-steps), blocks[i].context_layer (context;
+ *                                                          k-steps as above), linear_layers[1] (8 k-steps)
+ *                     per feed-forward block               linear (8 k-steps)
+ *                     final_layer                          tile-major, ceil(features / 16) tiles of two stages; the
+ *                                                          reference's rows are interleaved (row 2 f: unconstrained scale
+ *                                                          of feature f, row 2 f + 1: its shift, autoregressive.py:118-128)
+ *                                                          and are reordered into K11's [8 shifts | 8 unconstrained scales]
+ *                                                          per lane-half, rows of features >= `features` zero.
+ *   bias_packed     fp32 in accumulator order, per layer: initial_layer (128), context_layer (128; context), per hidden
+ *                   Linear 128 (a residual block's context_layer bias is added to its linear_layers[0] bias), final_layer
+ *                   (32 per tile).
+ *   tables          int32 [(num_layers + 1) * 128] as for K11; every layer lists its `features` columns' slots in BOTH
+ *                   halves ([0, 64) and [64, 128)).
+ *   flags           NFA_FLAG_RESIDUAL_BLOCKS | NFA_FLAG_ACCUMULATE_LOGABSDET | NFA_FLAG_STANDARD_NORMAL_LOG_PROB |
+ *                   NFA_FLAG_SKIP_OUTPUTS | NFA_FLAG_PAD_COLUMNS.  NFA_FLAG_INVERSE: NFA_ERR_UNSUPPORTED (the inverse is
+ *                   sequential in the features; callers run the column-wise loop).
+ * Supported: hidden_features = 128, features <= 64, context_features <= 64, row_length % 4 == 0, batch % 128 == 0;
+ * otherwise NFA_ERR_UNSUPPORTED (callers then run the MADE's GEMMs and K2b).  Added under ABI 19 (see NFA_ABI_VERSION).
+ */
+int nfa_affine_flow_made_f32(const float *inputs, const float *context, int32_t context_features,
+                             const void *weights_packed, const float *bias_packed, const int32_t *tables,
+                             int32_t num_layers, float *outputs, float *logabsdet, int32_t *status, int64_t batch,
+                             int32_t row_length, int32_t features, int32_t hidden_features, int32_t num_hidden_layers,
+                             int32_t flags, void *stream);
 
 /*
  * K12.  The sequential part of AutoregressiveTransform.inverse (autoregressive.py:43-52) for

@@ -108,3 +108,33 @@ def conditional_rq_nsf_flow(num_layers=3, features=16, num_bins=8, hidden_featur
             num_bins=num_bins, tails="linear", tail_bound=tail_bound))
     return Flow(CompositeTransform(layers), StandardNormal([features]),
                 embedding_net=torch.nn.Linear(raw_context, context_features))
+
+
+def masked_affine_flow(features, hidden_features, num_layers, num_blocks=2, use_residual_blocks=True,
+                       random_mask=False, permutation=None, context_features=None, seed=0, scale_final=1.0,
+                       scale_linear1=1.0):
+    """A stack of MaskedAffineAutoregressiveTransform layers (MAF) on a standard normal base: per layer an optional
+    permutation ("reverse" / "random" / None) and the layer, created in that order -- the order of the reference's
+    MaskedAutoregressiveFlow factory (flows/autoregressive.py:14-68), which has no context and no choice of leaving the
+    permutation out.  The conditioners take the context as it is (no embedding net).  After construction the weights are
+    moved off the near-identity initialisation, as after training: every `final_layer` parameter is multiplied by
+    `scale_final`, every residual block's second Linear (`linear_layers.1`, initialised within +-1e-3) by `scale_linear1`.
+    tests/golden/make_golden_maf.py builds the same flows with the reference's classes; the seed reproduces their weights,
+    masks and permutations."""
+    if seed is not None:
+        torch.manual_seed(seed)
+    layers = []
+    for _ in range(num_layers):
+        if permutation is not None:
+            layers.append({"reverse": ReversePermutation, "random": RandomPermutation}[permutation](features))
+        layers.append(MaskedAffineAutoregressiveTransform(
+            features=features, hidden_features=hidden_features, context_features=context_features,
+            num_blocks=num_blocks, use_residual_blocks=use_residual_blocks, random_mask=random_mask))
+    flow = Flow(CompositeTransform(layers), StandardNormal([features]))
+    with torch.no_grad():
+        for name, p in flow.named_parameters():
+            if "final_layer" in name:
+                p.mul_(scale_final)
+            elif "linear_layers.1" in name:
+                p.mul_(scale_linear1)
+    return flow

@@ -1947,19 +1947,49 @@ def _affine_row_order(num_transform, additive):
     return torch.where(feat < dt, row, torch.full_like(row, -1)).reshape(-1)
 
 
+class _MaskedLinear(tuple):
+    """(weight * mask, bias) of a MADE's masked layer, with the two attributes the packer reads."""
+    weight = property(lambda self: self[0])
+    bias = property(lambda self: self[1])
+
+
 def _conditioner_linears(net):
     """(input Linear, hidden Linears, output Linear) of a K11 conditioner: an MLP's layers, or (round 5) a ResidualNet's
     initial_layer, the blocks' linear_layers in order, final_layer (nn/nets/resnet.py:58-100) -- the same stream of
-    stages, told apart by NFA_FLAG_RESIDUAL_BLOCKS."""
+    stages, told apart by NFA_FLAG_RESIDUAL_BLOCKS --, or (K22) a MADE's (transforms/made.py): the same places, every
+    matrix being `weight * mask`; feed-forward blocks have one Linear each."""
     if hasattr(net, "_input_layer"):
         return net._input_layer, list(net._hidden_layers), net._output_layer
+    if hasattr(net, "use_residual_blocks"):   # MADE
+        def masked(lin):
+            return _MaskedLinear((lin.weight.detach() * lin.mask, lin.bias.detach()))
+        hidden = [lin for block in net.blocks for lin in (block.linear_layers if net.use_residual_blocks else [block.linear])]
+        return masked(net.initial_layer), [masked(lin) for lin in hidden], masked(net.final_layer)
     return net.initial_layer, [lin for block in net.blocks for lin in block.linear_layers], net.final_layer
 
 
-def pack_mlp_conditioner(net, num_transform, additive=False):
+def _made_row_order(features):
+    """`_affine_row_order` for a MADE's output layer, whose rows are interleaved per feature (row 2 f: unconstrained scale,
+    row 2 f + 1: shift; autoregressive.py:118-128) where a coupling conditioner has [shift block | scale block]."""
+    order = _affine_row_order(features, False)
+    row = torch.where(order >= features, 2 * (order - features), 2 * order + 1)
+    return torch.where(order < 0, order, row)
+
+
+def _context_linears(net):
+    """The context terms of a MADE (made.py:274-281, :187-198) for K22: (context_layer, [a residual block's context_layer
+    per block]); feed-forward blocks take no context of their own."""
+    blocks = [block.context_layer for block in net.blocks] if net.use_residual_blocks else []
+    return net.context_layer, blocks
+
+
+def pack_mlp_conditioner(net, num_transform, additive=False, row_order=None, context=None):
     """Packs an MLP conditioner (nn/nets/mlp.py: _input_layer, _hidden_layers[*], _output_layer; all
-    hidden widths 128) -- or a ResidualNet without a context (`_conditioner_linears`) -- for K11 (layout in
-    include/nflows_amd.h).  Returns (weights [stages, 768*8] bf16, biases fp32)."""
+    hidden widths 128) -- or a ResidualNet without a context, or a MADE (`_conditioner_linears`) -- for K11 / K22 (layout
+    in include/nflows_amd.h).  `row_order`: which conditioner output every packed output row is (default: K11's
+    `_affine_row_order`).  `context` = `_context_linears(net)`: the context stages join the stream where the kernel
+    consumes them -- in front of the initial layer's, and behind the first Linear's of every residual block, whose bias takes
+    the block's context bias.  Returns (weights [stages, 768*8] bf16, biases fp32)."""
     dt = num_transform
     input_layer, hidden_layers, output_layer = _conditioner_linears(net)
     dev = output_layer.weight.device
@@ -1975,11 +2005,26 @@ def pack_mlp_conditioner(net, num_transform, additive=False):
     wi = torch.cat((wi, wi.new_zeros(128, 16 * init_ks - di)), dim=1)  # k = ks*16 + hf*8 + j
     stages.append(pieces(wi).view(3, 4, 32, init_ks, 2, 8).permute(3, 1, 0, 4, 2, 5).reshape(init_ks, -1))
     biases.append(_bias_accumulator_order(_pad_to(input_layer.bias.detach().float(), rows=128)))
-    for lin in hidden_layers:
+
+    def context_stages(lin):   # laid out as the input layer's, ceil(ce / 16) k-steps
+        w = _pad_to(lin.weight.detach().float(), rows=128)
+        ks = (w.shape[1] + 15) // 16
+        w = torch.cat((w, w.new_zeros(128, 16 * ks - w.shape[1])), dim=1)
+        return pieces(w).view(3, 4, 32, ks, 2, 8).permute(3, 1, 0, 4, 2, 5).reshape(ks, -1)
+    block_context = []
+    if context is not None:
+        stages.insert(0, context_stages(context[0]))   # (consumed in front of the input layer's stages)
+        biases.append(_bias_accumulator_order(_pad_to(context[0].bias.detach().float(), rows=128)))
+        block_context = context[1]
+    for i, lin in enumerate(hidden_layers):
         w = _pad_to(lin.weight.detach().float(), rows=128, cols=128).index_select(1, order_k)
         stages.append(pieces(w).view(3, 4, 32, 8, 2, 8).permute(3, 1, 0, 4, 2, 5).reshape(8, -1))
-        biases.append(_bias_accumulator_order(_pad_to(lin.bias.detach().float(), rows=128)))
-    order_r = _affine_row_order(dt, additive).to(dev)
+        b = lin.bias.detach().float()
+        if block_context and i % 2 == 0:
+            stages.append(context_stages(block_context[i // 2]))
+            b = b + block_context[i // 2].bias.detach().float()
+        biases.append(_bias_accumulator_order(_pad_to(b, rows=128)))
+    order_r = (_affine_row_order(dt, additive) if row_order is None else row_order).to(dev)
     wo = _pad_to(output_layer.weight.detach().float(), cols=128)
     bo = output_layer.bias.detach().float()
     wo = torch.cat((wo, wo.new_zeros(1, 128)), dim=0)     # row -1 = zero padding
@@ -1991,6 +2036,15 @@ def pack_mlp_conditioner(net, num_transform, additive=False):
     stages.append(pieces(wf).view(3, tiles, 32, 2, 4, 2, 8).permute(1, 3, 0, 4, 5, 2, 6).reshape(tiles * 2, -1))
     biases.append(_bias_accumulator_order(bf))
     return torch.cat(stages, dim=0).contiguous(), torch.cat(biases).contiguous()
+
+
+def pack_made_conditioner(net):
+    """A MADE with two outputs per feature (the conditioner of MaskedAffineAutoregressiveTransform) for K22:
+    `pack_mlp_conditioner`'s stages of `weight * mask`, the interleaved output rows put into K11's order, the context
+    stages where the net has a context."""
+    features = net.initial_layer.weight.shape[1]
+    return pack_mlp_conditioner(net, features, row_order=_made_row_order(features),
+                                context=_context_linears(net) if hasattr(net, "context_layer") else None)
 
 
 def affine_flow_mlp(inputs, weights_packed, bias_packed, tables, num_transform, num_identity, num_hidden_layers,
@@ -2007,6 +2061,22 @@ def affine_flow_mlp(inputs, weights_packed, bias_packed, tables, num_transform, 
             status, x.shape[0], x.shape[1], num_transform, num_identity, 128, num_hidden_layers, scale_activation, flags,
             stream)
     return _whole_layer_launch(launch, inputs, inverse, accumulate_into, standard_normal_log_prob, pad,
+                               flags=N.FLAG_RESIDUAL_BLOCKS if residual_blocks else 0)
+
+
+def affine_flow_made(inputs, weights_packed, bias_packed, tables, features, num_hidden_layers, context=None,
+                     accumulate_into=None, num_layers=1, standard_normal_log_prob=False, pad=None, residual_blocks=True):
+    """K22 -- the density pass of a run of masked autoregressive affine layers with their MADE conditioners in one launch
+    (blobs of `pack_made_conditioner` concatenated in execution order, tables from `flow_layer_tables` with every feature
+    in both halves; rows padded to a multiple of four columns by `pad`).  `num_hidden_layers`: the hidden Linears (twice
+    the number of residual blocks, or the number of feed-forward blocks).  Forward only.  Returns (outputs, logabsdet),
+    or (None, log_prob) with `standard_normal_log_prob`; None when the shape is outside the fast path."""
+    def launch(x, ctx, out, lad, redo, flags, status, stream):
+        return N.load().nfa_affine_flow_made_f32(
+            N.ptr(x), N.ptr(ctx), 0 if ctx is None else ctx.shape[1], N.ptr(weights_packed), N.ptr(bias_packed),
+            N.ptr(tables), num_layers, N.ptr(out), N.ptr(lad), status, x.shape[0], x.shape[1], features, 128,
+            num_hidden_layers, flags, stream)
+    return _whole_layer_launch(launch, inputs, False, accumulate_into, standard_normal_log_prob, pad, context,
                                flags=N.FLAG_RESIDUAL_BLOCKS if residual_blocks else 0)
 
 

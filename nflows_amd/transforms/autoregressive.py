@@ -194,6 +194,114 @@ class MaskedAffineAutoregressiveTransform(AutoregressiveTransform):
     def _elementwise_forward(self, inputs, autoregressive_params):
         return ops.affine_autoregressive(inputs, autoregressive_params, inverse=False)
 
+    # ---- whole-layer kernel K22 (csrc/affine_made.hip): the MADE inside the layer kernel, runs of such layers in one
+    #      launch.  The density pass only -- the inverse is sequential in the features and keeps its column-wise loop.
+    #      What follows is the protocol the run planner reads (transforms/base.py), as the coupling layers have it.
+    fuse_conditioner = os.environ.get("NFA_K22", "1") != "0"   # class-level switch for A/B measurements
+    unconditional_transform = None
+    _forward_only_run = True
+    _HOOKS = ("forward", "_elementwise_forward", "_elementwise_inverse", "_output_dim_multiplier")
+
+    @property
+    def _user_hooks(self):
+        """True when a subclass (or an assignment to the class or the instance) replaced one of the functions the
+        kernel stands for: such a layer runs the sequence above with the user's function."""
+        cls = type(self)
+        return any(h in self.__dict__ or getattr(cls, h) is not getattr(MaskedAffineAutoregressiveTransform, h)
+                   for h in self._HOOKS)
+
+    def _conditioner(self):
+        return self._modules["autoregressive_net"]
+
+    def _conditioner_shape(self):
+        """(hidden Linears, residual blocks?) of a MADE that K22 runs inside the layer kernel -- plain MADE, hidden width
+        <= 128, at most 64 features and 64 context features, no batch norm --, or None.  Read once per cache epoch;
+        the activations and the dropouts are plain attributes and are read on every call."""
+        held = self.__dict__.get("_conditioner_shape_held")
+        net = self._conditioner()
+        if held is None or held[0] != _cache.epoch() or held[1] is not net:
+            shape = None
+            if type(net) is made_module.MADE and self.features <= 64:
+                hidden, features = net.initial_layer.weight.shape
+                ce = net.context_layer.weight.shape[1] if hasattr(net, "context_layer") else 0
+                if (hidden <= 128 and features == self.features and ce <= 64
+                        and net.final_layer.weight.shape[0] == 2 * features
+                        and not any(isinstance(m, torch.nn.BatchNorm1d) for m in net.modules())):
+                    residual = bool(net.use_residual_blocks)
+                    shape = (len(net.blocks) * (2 if residual else 1), residual)
+            held = (_cache.epoch(), net, shape)
+            self.__dict__["_conditioner_shape_held"] = held
+        shape = held[2]
+        if shape is not None:
+            relu = (F.relu, torch.relu)
+            if net.__dict__.get("activation") not in relu or not all(
+                    b.__dict__.get("activation") in relu and (not b.dropout.training or b.dropout.p == 0.0)
+                    for b in net.blocks):
+                return None
+        return shape
+
+    def _context_features(self):
+        net = self._conditioner()
+        return net.context_layer.weight.shape[1] if hasattr(net, "context_layer") else 0
+
+    def _run_kind(self, context):
+        if not self.fuse_conditioner or torch.is_grad_enabled() or self._conditioner_shape() is None:
+            return None
+        ce = self._context_features()
+        if context is None:
+            return "k22" if ce == 0 else None
+        ok = (ce > 0 and torch.is_tensor(context) and context.dim() == 2 and context.dtype == torch.float32
+              and context.is_cuda and context.shape[1] == ce)
+        return "k22" if ok else None
+
+    def _fused_geometry(self, others=()):
+        """(padded features, transformed features, identity features, pad value): the row length in multiples of four,
+        the pad columns pass through; every feature is both read by the conditioner and transformed."""
+        return (self.features + 3) // 4 * 4, self.features, self.features, 0.0
+
+    def _run_signature(self):
+        return ("k22", self.features, self._conditioner_shape(), self._context_features())
+
+    def _all_columns(self):
+        dev = self._conditioner().initial_layer.weight.device
+        held = self.__dict__.get("_columns_held")
+        if held is None or held.device != dev:
+            held = self.__dict__["_columns_held"] = torch.arange(self.features, device=dev)
+        return held
+
+    transform_features = property(_all_columns)   # (what the planner writes into the two halves of the layer's table)
+    identity_features = property(_all_columns)
+
+    def _packed_mlp(self):
+        from .coupling import _weights_key
+        net = self._conditioner()
+        key = _weights_key(self, net)   # (parameters and buffers: the masks are part of the key)
+        cached = self.__dict__.get("_packed_made_cache")
+        if cached is None or cached[0] != key:
+            cached = self.__dict__["_packed_made_cache"] = (key, ops.pack_made_conditioner(net))
+        return cached[1]
+
+    def forward(self, inputs, context=None):
+        if (torch.is_tensor(inputs) and inputs.dim() == 2 and inputs.dtype == torch.float32 and inputs.is_cuda
+                and inputs.shape[0] >= 1 and inputs.shape[1] == self.features and not self._user_hooks
+                and self._run_kind(context) is not None):
+            fused = self._whole_layer(inputs, context)   # a run of one
+            if fused is not None:
+                return fused
+        return super().forward(inputs, context)
+
+    def _whole_layer(self, inputs, context):
+        from .base import CompositeTransform, _Run
+        run = self.__dict__.get("_own_run")
+        if run is None:
+            run = self.__dict__["_own_run"] = _Run([(self, None)])
+        # (the planner's blob / table cache, kept in this layer's own __dict__: the function reads nothing else of `self`)
+        weights, biases, tables, _, _ = CompositeTransform._run_plan(self, run, False)
+        hidden_linears, residual_blocks = self._conditioner_shape()
+        geometry = self._fused_geometry()
+        return ops.affine_flow_made(inputs, weights, biases, tables, self.features, hidden_linears, context,
+                                    pad=(geometry[0], geometry[3]), residual_blocks=residual_blocks)
+
     def _elementwise_inverse(self, inputs, autoregressive_params):
         return ops.affine_autoregressive(inputs, autoregressive_params, inverse=True)
 

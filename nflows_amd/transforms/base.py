@@ -56,16 +56,18 @@ def _switch_state():
     """The class-level A/B switches a run plan depends on."""
     from .coupling import (AdditiveCouplingTransform, AffineCouplingTransform,
                            PiecewiseRationalQuadraticCouplingTransform as RQ)
+    from .autoregressive import MaskedAffineAutoregressiveTransform as MAF
     return (RQ.fuse_conditioner, RQ.fuse_final_linear, RQ.conditioner_engine, RQ.conditioner_act_scale,
-            RQ.resnet_log2e, AffineCouplingTransform.fuse_conditioner, AdditiveCouplingTransform.fuse_conditioner)
+            RQ.resnet_log2e, AffineCouplingTransform.fuse_conditioner, AdditiveCouplingTransform.fuse_conditioner,
+            MAF.fuse_conditioner)
 
 
 def _layer_state(units):
     """Per-layer attributes a run plan depends on, re-read on every call: the layers' signatures (bins, tails,
     box, minimum sizes, engine ...), whether their conditioners are in training mode (active dropout), their
     unconditional transforms, and the A/B switches once more (they may be set on an instance)."""
-    # (`_modules[...]`: the plain dict behind `c.transform_net`, without nn.Module's attribute fallback)
-    return [(c._run_signature(), c._modules["transform_net"].training, c._modules.get("unconditional_transform") is None,
+    # (`_conditioner()`: the layer's conditioner from the plain `_modules` dict, without nn.Module's attribute fallback)
+    return [(c._run_signature(), c._conditioner().training, c._modules.get("unconditional_transform") is None,
              c.fuse_conditioner, getattr(c, "fuse_final_linear", None)) for c, _ in units]
 
 
@@ -86,7 +88,7 @@ class _Run(list):
     #      object in its module's dict, version counters, storage pointers), read from lists made once per epoch.
     def _flatten(self, epoch):
         from .coupling import _held_parameters
-        nets = [c._modules["transform_net"] for c, _ in self]
+        nets = [c._conditioner() for c, _ in self]
         per_layer = [_held_parameters(net) for net in nets]
         entries = [e for held in per_layer for e in held]
         bounds, at = [], 0
@@ -106,7 +108,7 @@ class _Run(list):
             flat = self._flatten(epoch)
         else:
             for (c, _), net in zip(self, flat[1]):
-                if c._modules["transform_net"] is not net:
+                if c._conditioner() is not net:
                     flat = self._flatten(epoch)
                     break
             else:
@@ -195,7 +197,7 @@ def _run_weights_fingerprint(units):
     if isinstance(units, _Run):
         return units.weights_fingerprint()
     from .coupling import _weights_key
-    return tuple([_weights_key(c, c.transform_net) for c, _ in units])
+    return tuple([_weights_key(c, c._conditioner()) for c, _ in units])
 
 
 def _run_geometry(units):
@@ -245,7 +247,7 @@ class CompositeTransform(Transform):
         units, after = self._plan_run(layers, start, inputs, context, inverse)
         if units:   # (only runs are kept: "no run here" is decided afresh on every call)
             units = _Run(units)
-            if len(cache) > 16:
+            if len(cache) > 16 + len(layers):   # (layers that are runs of one: a run may start at every position)
                 cache.clear()
             cache[key] = (units, after, list(layers), self._watched_state(units, layers, after, inputs.shape[1], context))
         return units, after
@@ -273,8 +275,8 @@ class CompositeTransform(Transform):
                 and inputs.dtype == torch.float32):
             return units, start
 
-        def eligible(t):
-            return self._joinable(t, inputs.shape[1], context)
+        def eligible(t):   # (K22 serves the density pass only: `_forward_only_run`)
+            return self._joinable(t, inputs.shape[1], context) and not (inverse and getattr(t, "_forward_only_run", False))
         i, signature = start, None
         while i < len(layers):
             perm = None
@@ -297,7 +299,8 @@ class CompositeTransform(Transform):
             signature = sig
             units.append((coupling, perm))
             i += step
-        if len(units) < 2:
+        # (a coupling layer on its own has its whole-layer path in its own forward; a MAF layer is a run of one)
+        if len(units) < (1 if units and getattr(units[0][0], "_forward_only_run", False) else 2):
             return [], start
         geometry = _run_geometry(units)
         ce = getattr(getattr(units[0][0], "transform_net", None), "context_features", None) or 0
@@ -311,7 +314,7 @@ class CompositeTransform(Transform):
         `tile16`: the mode of the f16 stream (ops.use_tile16)."""
         from .. import ops
         first = units[0][0]
-        mlp = type(first).__name__ in ("AffineCouplingTransform", "AdditiveCouplingTransform")
+        mlp = first._run_signature()[0] in ("k11", "k22")
         geometry = _run_geometry(units)   # one padded geometry for the run
         engine = None if mlp else first._whole_layer_engine(geometry)   # "k8x", "k8h" (the two-piece family) or "k8"
         f16, x3 = engine == "k8h", engine == "k8x"
@@ -328,7 +331,9 @@ class CompositeTransform(Transform):
         cache = self.__dict__.setdefault("_run_plans", {})
         plan = cache.get(key)
         if plan is None:
-            if len(cache) > 4:
+            # (a composite whose layers are runs of one -- MAF layers with a BatchNorm between them -- holds one plan per
+            #  layer: with a fixed bound of 4 every call of an 8-layer flow rebuilt every plan, 0.9 ms each)
+            if len(cache) > 4 + len(getattr(self, "_transforms", ())):
                 cache.clear()
             if isinstance(units, _Run):
                 units.verify_before_packing()
@@ -364,7 +369,14 @@ class CompositeTransform(Transform):
             if p is not None:
                 p._check(inputs)
         geometry = _run_geometry(units)
-        if type(first).__name__ in ("AffineCouplingTransform", "AdditiveCouplingTransform"):
+        if first._run_signature()[0] == "k22":
+            weights, biases, tables, _, _ = self._run_plan(units, inverse)
+            hidden_linears, residual_blocks = first._conditioner_shape()
+            head = ops.affine_flow_made(
+                inputs, weights, biases, tables, first.features, hidden_linears, context, total, num_layers=len(units),
+                standard_normal_log_prob=standard_normal_log_prob, pad=(geometry[0], geometry[3]),
+                residual_blocks=residual_blocks)
+        elif first._run_signature()[0] == "k11":
             weights, biases, tables, _, _ = self._run_plan(units, inverse)
             hidden_linears, residual_blocks = first._conditioner_shape()
             head = ops.affine_flow_mlp(

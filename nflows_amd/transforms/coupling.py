@@ -217,6 +217,11 @@ class CouplingTransform(Transform):
         else:
             self.unconditional_transform = unconditional_transform(features=self.num_identity_features)
 
+    def _conditioner(self):
+        """The layer's conditioner as the run planner reads it (transforms/base.py): the plain `_modules` entry, without
+        nn.Module's attribute fallback."""
+        return self._modules["transform_net"]
+
     @property
     def num_identity_features(self):
         return len(self.identity_features)
