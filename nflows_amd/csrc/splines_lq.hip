@@ -130,6 +130,17 @@ __device__ __forceinline__ int linear_eval(float x, float* p, const LqArgs& a, f
     return 0;
 }
 
+// The inverse's root of qa s^2 + qb s + c_ = 0 (quadratic.py:141-144), r = sqrt(qb^2 - 4 qa c_).  The reference writes
+// (-qb + r) / (2 qa); qb = height x width > 0, so in a flat bin (qa -> 0) the numerator is a difference of two nearly
+// equal numbers divided by a tiny one, and an ulp in qb moves the result by 1e-5 .. 1e-4: there the reference's own fp32 is
+// 10 - 200 x further from float64 than the rounding of its inputs explains, and a second fp32 evaluation lands elsewhere.
+// -2 c_ / (qb + r) is the same root ((-qb + r)(-qb - r) = 4 qa c_) without the cancellation, for either sign of qa.
+// qa == 0 exactly keeps the reference's 0 / 0 (its NaN pattern is part of the contract).
+__device__ __forceinline__ float quadratic_inverse_root(float qa, float qb, float c_, float r) {
+#pragma clang fp contract(off)
+    return qa == 0.0f ? (-qb + r) / (2.0f * qa) : (-2.0f * c_) / (qb + r);
+}
+
 // splines/quadratic.py:55-159.  w: K width logits (overwritten by the widths); h: K+1 slots, the
 // nh height logits sit at h[1..nh] (nh = K-1) or h[0..K] (nh = K+1) and are overwritten by the heights.
 template <int KT, bool INVERSE>
@@ -197,7 +208,7 @@ __device__ __forceinline__ int quadratic_eval(float x, float* w, float* h, const
     float out;
     if (INVERSE) {
         const float c_ = qc - u;
-        const float alpha = (-qb + sqrtf(qb * qb - (4.0f * qa) * c_)) / (2.0f * qa);
+        const float alpha = quadratic_inverse_root(qa, qb, c_, sqrtf(qb * qb - (4.0f * qa) * c_));
         out = clamp01(alpha * bw + l0);
         lad = -log_normal(alpha * (hr - hl) + hl);
     } else {
@@ -221,6 +232,12 @@ __device__ __forceinline__ float sign_of(float v) { return v > 0.0f ? 1.0f : (v 
 // Root of ca s^3 + cb s^2 + cc s + cd = u reported as lcw + s, by the reference's case analysis
 // (cubic.py:151-226): one real root, three real roots (the one inside the bin, +- 1e-5), and the
 // "almost quadratic" override for |ca| < 1e-3.
+// Known quirk, kept because it is the reference's: when none of the three roots falls inside the window, the fallback is
+// r1 (the reference's argsort(masks, descending)[0], cubic.py:212-224), which can lie far outside the bin.  At the top
+// of the box (input exactly +tail_bound in the inverse) the roots sit within an ulp of the window's edge, and which
+// evaluation misses it is luck: the reference's own fp32 returns 11.9457 for an element whose float64 result is 3.0
+// (tests/golden/splines_lq_edges.npz, cubic_k5_s3, element 258), and up to 1e-4 outside the box for a third of such
+// inputs.
 __device__ __forceinline__ float cubic_inverse_root(float ca, float cb, float cc, float cd, float u, float lcw,
                                                     float rcw, bool& almost_quadratic) {
 #pragma clang fp contract(off)
@@ -688,7 +705,7 @@ __global__ void __launch_bounds__(kBlock) quadratic_spline_backward_kernel(const
             const float c_ = c0 - u;
             const float disc = qb * qb - (4.0f * qa) * c_;
             const float r = sqrtf(disc);
-            const float alpha = (-qb + r) / (2.0f * qa);
+            const float alpha = quadratic_inverse_root(qa, qb, c_, r);
             const float out = alpha * bw + l0;
             const float g_out = (out < 0.0f || out > 1.0f) ? 0.0f : gy * a.span_in;
             const float D = alpha * dH + hl;

@@ -696,6 +696,53 @@ def sibling_spline_grad_cases():
     print("sibling spline gradients:", len(meta), "cases")
 
 
+def sibling_spline_edge_cases():
+    """Linear / quadratic / cubic splines ON and NEXT TO the ends of the box [-3, 3] (splines_lq_edges.npz): at the box
+    ends the authority is the reference itself, not a restatement of it.  Per case 512 inputs: 64 at each end exactly,
+    64 one ulp inside each end, 128 in the outer 0.5 % of the box on either side; the same array is the input of the
+    forward and of the inverse direction.  K = 8 and 5, logit scales 1.5 and 3; fp32 and fp64.  The quadratic has K + 1
+    heights, which the reference's linear-tails wrapper does not take (quadratic.py:34): it goes through the
+    constrained functional on the box [-3, 3]^2, the same arithmetic for inputs inside the box."""
+    out = {}
+    meta = []
+    g = torch.Generator().manual_seed(778)
+    B = 3.0
+    one = np.float32(B)
+    inside = np.nextafter(one, np.float32(0.0))
+    for kind in ("linear", "quadratic", "cubic"):
+        for K in (8, 5):
+            for scale in (1.5, 3.0):
+                x = torch.empty(512)
+                x[0:64], x[64:128] = -float(one), float(one)
+                x[128:192], x[192:256] = -float(inside), float(inside)
+                x[256:384] = -B + 0.005 * 2 * B * torch.rand(128, generator=g)
+                x[384:512] = B - 0.005 * 2 * B * torch.rand(128, generator=g)
+                x = x[torch.randperm(512, generator=g)]
+                if kind == "linear":
+                    logits, fn, kw = [scale * torch.randn(512, K, generator=g)], splines.unconstrained_linear_spline, dict(tail_bound=B, tails="linear")
+                elif kind == "quadratic":
+                    logits = [scale * torch.randn(512, K, generator=g), scale * torch.randn(512, K + 1, generator=g)]
+                    fn, kw = splines.quadratic_spline, dict(left=-B, right=B, bottom=-B, top=B)
+                else:
+                    logits = [scale * torch.randn(512, K, generator=g), scale * torch.randn(512, K, generator=g),
+                              torch.randn(512, 1, generator=g), torch.randn(512, 1, generator=g)]
+                    fn, kw = splines.unconstrained_cubic_spline, dict(tail_bound=B, tails="linear")
+                name = "%s_k%d_s%g" % (kind, K, scale)
+                for dtp, suf in ((torch.float32, ""), (torch.float64, "64")):
+                    args = [t.to(dtp) for t in logits]
+                    for inverse in (False, True):
+                        y, lad = fn(x.to(dtp), *args, inverse=inverse, **kw)
+                        out["%s/%s%s" % (name, "inv_" if inverse else "", "y" + suf)] = npy(y)
+                        out["%s/%s%s" % (name, "inv_" if inverse else "", "lad" + suf)] = npy(lad)
+                out[name + "/x"] = npy(x)
+                for i, t in enumerate(logits):
+                    out["%s/logits%d" % (name, i)] = npy(t)
+                meta.append((name, kind, repr(kw)))
+    out["meta"] = np.array(meta, dtype=object).astype(str)
+    np.savez_compressed(os.path.join(HERE, "splines_lq_edges.npz"), **out)
+    print("sibling spline edges:", len(meta), "cases")
+
+
 def sibling_coupling_cases():
     """Coupling layers outside the fused kernels: linear / quadratic piecewise couplings on [B, D]
     and spline couplings on [B, C, H, W] images with a ConvResidualNet conditioner."""
@@ -1572,6 +1619,9 @@ if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "lqgrads":
         sibling_spline_grad_cases()
         sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "lqedges":
+        sibling_spline_edge_cases()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "lq":
         sibling_spline_cases()
         sibling_coupling_cases()
@@ -1620,6 +1670,7 @@ if __name__ == "__main__":
     flow_h128_case()
     sibling_spline_cases()
     sibling_spline_grad_cases()
+    sibling_spline_edge_cases()
     sibling_coupling_cases()
     cubic_spline_cases()
     cubic_coupling_cases()

@@ -10,7 +10,8 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import LAD_TOL, OUT_TOL, assert_fp32_parity, assert_sibling_spline_parity, conditioning, parse_kwargs
+from helpers import (LAD_TOL, OUT_TOL, assert_fp32_parity, assert_sibling_spline_parity, assert_sibling_truth_parity, conditioning,
+                     parse_kwargs)
 from oracle import capi
 
 pytestmark = pytest.mark.gpu
@@ -390,6 +391,24 @@ def test_linear_and_quadratic_splines_golden(ops, golden_dir):
                 assert np.all(host(lad)[outside] == 0), name
 
 
+def k9_rule(kind, K, x, logits, inverse, got, ref, what):
+    """The float64-truth rule of the K9 splines (helpers.assert_sibling_truth_parity; tests/test_gpu_k9.py runs the case
+    table under it) on fresh inputs with linear tails +-3: `ref` is the C oracle's float build, the truth and the
+    conditioning come from its float64 build.  Reads and clears the status word."""
+    import k9_cases
+    from nflows_amd import InputOutsideDomain, ops as o
+    try:
+        o.check_status()
+        status = 0
+    except InputOutsideDomain:
+        status = 1
+    except AssertionError:
+        status = 2
+    kw = dict(tails="linear", tail_bound=3.0)
+    t = k9_cases.value_truth(kind, K, kw, x, [np.ascontiguousarray(a) for a in logits], inverse)
+    assert_sibling_truth_parity((host(got[0]), host(got[1])), ref, t["truth"], t["cond"], x, status, inverse, 3.0, what=what)
+
+
 @pytest.mark.parametrize("K", [3, 8, 40])
 def test_linear_and_quadratic_splines_oracle(ops, K):
     """Fresh inputs, packed and strided logit layouts, against the C oracle (float build)."""
@@ -408,14 +427,12 @@ def test_linear_and_quadratic_splines_oracle(ops, K):
         packed = dev(np.ascontiguousarray(blob[:, :2 * K - 1]))
         y2, lad2 = splines.unconstrained_quadratic_spline(dev(x), packed[:, :K], packed[:, K:], inverse=inverse, tail_bound=3.0)
         assert torch.equal(y, y2) and torch.equal(lad, lad2)      # strided gather == packed tile path
-        assert np.mean(np.abs(host(y) - oy) <= OUT_TOL * (1 + np.abs(oy))) >= 0.97
-        assert np.mean(np.abs(host(lad) - ol) <= LAD_TOL * (1 + np.abs(ol))) >= 0.97
+        k9_rule("quadratic", K, x, [uw, uh], inverse, (y, lad), (oy, ol), "K9 quadratic K=%d inverse=%s" % (K, inverse))
         oy, ol, st = capi.linear_spline(x, uw, spec, inverse=inverse)
         y, lad = splines.unconstrained_linear_spline(dev(x), t[:, :K], inverse=inverse, tail_bound=3.0)
         y2, lad2 = splines.unconstrained_linear_spline(dev(x), dev(np.ascontiguousarray(uw)), inverse=inverse, tail_bound=3.0)
         assert torch.equal(y, y2) and torch.equal(lad, lad2)
-        assert np.mean(np.abs(host(y) - oy) <= OUT_TOL * (1 + np.abs(oy))) >= 0.97
-        assert np.mean(np.abs(host(lad) - ol) <= LAD_TOL * (1 + np.abs(ol))) >= 0.97
+        k9_rule("linear", K, x, [uw], inverse, (y, lad), (oy, ol), "K9 linear K=%d inverse=%s" % (K, inverse))
     ops.check_status()
     # round trip
     xs = dev(np.clip(x, -2.999, 2.999))
@@ -470,8 +487,7 @@ def test_cubic_spline_golden(ops, golden_dir):
     y, lad = splines.unconstrained_cubic_spline(x, *args, tail_bound=3.0)
     oy, ol, st = capi.cubic_spline(host(x), *[host(t) for t in args], capi.make_spec(K, tails="linear", tail_bound=3.0))
     assert st == 0
-    assert np.mean(np.abs(host(y) - oy) <= OUT_TOL * (1 + np.abs(oy))) >= 0.97
-    assert np.mean(np.abs(host(lad) - ol) <= LAD_TOL * (1 + np.abs(ol))) >= 0.97
+    k9_rule("cubic", K, host(x), [host(t) for t in args], False, (y, lad), (oy, ol), "K9 cubic K=6")
     xr, lad_inv = splines.unconstrained_cubic_spline(y, *args, inverse=True, tail_bound=3.0)
     ops.check_status()
     assert (xr - x).abs().median().item() < 1e-5 and (lad + lad_inv).abs().median().item() < 1e-4
