@@ -43,7 +43,10 @@ extern "C" {
                               18: nfa_lu_conv1x1_f32, nfa_lu_conv1x1_backward_f32 (K19);
                               19: nfa_diag_normal_*, nfa_mog_* (K20);
                               still 19: nfa_affine_flow_made_f32 (K22) is an ADDED entry point -- no existing entry point, flag set
-                              or packed layout changed, so libraries and bindings of 19 keep working with each other */
+                              or packed layout changed, so libraries and bindings of 19 keep working with each other;
+                              still 19: NFA_FLAG_K8X_FORM (bits 16-17, nfa_rqs_flow_resnet_f16x3_f32) is an ADDED field whose zero is
+                              the behaviour of every caller of 19: an older library rejects a non-zero value as an unknown flag,
+                              an older binding never sets one */
 
 /* return codes */
 #define NFA_OK 0
@@ -97,6 +100,12 @@ extern "C" {
 #define NFA_ACTIVATION_ELU 2              /* F.elu, alpha 1 */
 #define NFA_ACTIVATION_TANH 3             /* torch.tanh / F.tanh.  Other than ReLU: 8 or 10 bins (round 5: also with a context), not K8s. */
 #define NFA_FLAG_ACTIVATION(a) ((a) << NFA_FLAG_ACTIVATION_SHIFT)
+#define NFA_FLAG_K8X_FORM_SHIFT 16        /* nfa_rqs_flow_resnet_f16x3_f32 only: bits 16-17 = which form of K8x runs where both */
+#define NFA_FLAG_K8X_FORM_MASK 0x30000    /* exist (8 bins, the wide form's LDS fits): a measurement and test switch */
+#define NFA_K8X_FORM_AUTO 0               /* the launcher's choice: wide from two 128-row blocks per CU */
+#define NFA_K8X_FORM_NARROW 1             /* four-wave workgroups, two per CU, a weight ring each */
+#define NFA_K8X_FORM_WIDE 2               /* one eight-wave workgroup per CU on one ring: same results, bit for bit */
+#define NFA_FLAG_K8X_FORM(f) ((f) << NFA_FLAG_K8X_FORM_SHIFT)
 
 /* tails */
 #define NFA_TAILS_NONE 0   /* rational_quadratic_spline: K+1 derivative logits per element */

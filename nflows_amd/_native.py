@@ -30,6 +30,7 @@ FLAG_STANDARD_NORMAL_LOG_PROB, FLAG_SKIP_OUTPUTS = 16, 32
 FLAG_RESIDUAL_BLOCKS = 64    # nfa_affine_flow_mlp_f32: the conditioner is a ResidualNet (ABI 11)
 FLAG_PAD_COLUMNS_SHIFT = 8   # bits 8-10: trailing pad columns the density epilogue leaves out
 FLAG_ACTIVATION_SHIFT = 12   # bits 12-14: activation of the conditioner's residual blocks in the whole-layer kernels
+FLAG_K8X_FORM_SHIFT = 16     # bits 16-17: K8x's form (0 the launcher's choice, 1 narrow, 2 wide)
 ACTIVATION_RELU, ACTIVATION_LEAKY_RELU, ACTIVATION_ELU, ACTIVATION_TANH = 0, 1, 2, 3
 TAILS_NONE, TAILS_LINEAR = 0, 1
 NONLIN_EXP, NONLIN_TANH, NONLIN_LOG_TANH, NONLIN_LEAKY_RELU, NONLIN_SIGMOID, NONLIN_CAUCHY_CDF = 0, 1, 2, 3, 4, 5

@@ -65,6 +65,45 @@ __device__ __forceinline__ void request_stage(WeightStream& sm) {
     sm.fetch = (sm.fetch + 1 == sm.num_stages) ? 0 : sm.fetch + 1;
 }
 
+// The wide form (eight waves on one ring: rqs_resnet_f16x3_kernel.hpp): a ring slot holds a PAIR of consecutive stages, 24 KB,
+// and sm.slot counts 12 KB halves, 0 .. 2 kRing - 1 -- the stage functions address `sm.slot * kStageVec4` either way.  A pair
+// is requested at the start of its first stage, two pairs ahead: the same three buffer_load ... lds per wave, 8 KB each over
+// 512 threads (the packed stages are contiguous, so is the slot: one linear copy of 24 KB).  The pair's one barrier stands
+// where its SECOND stage's stood, behind the same counted wait -- vmcnt(3): the next pair has landed, the three requests of
+// the pair behind it may be in flight --; between the halves of a pair the wave only moves on: both halves were complete and
+// published at the previous pair's barrier.  SUB: which half of its pair a stage is -- the stages of a layer are even in
+// number (init_ks + 16 blocks + 2 tiles), a k-step pair's tiles 0, 1 / 2, 3 and a final tile's k-steps 0 .. 3 / 4 .. 7 are
+// the two halves.  WAVES = 4 is the ring as it was.
+template <int WAVES, int SUB>
+__device__ __forceinline__ void request_stage(WeightStream& sm) {
+    static_assert(WAVES == 4 || WAVES == 8, "narrow or wide");
+    if constexpr (WAVES == 4) {
+        request_stage(sm);
+    } else if constexpr (SUB == 0) {
+        const int dst_half = sm.slot >= 2 ? sm.slot - 2 : sm.slot + 2 * kRing - 2;  // ((slot / 2 + 2) % 3) * 2
+        const char* stage = reinterpret_cast<const char*>(sm.w) + (size_t)sm.fetch * (kStageVec4 * 16);
+        const __amdgpu_buffer_rsrc_t rsrc =
+            __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(stage), (short)0, 2 * kStageVec4 * 16, 0x00020000);
+        const int wave = __builtin_amdgcn_readfirstlane(sm.tid >> 6);
+        char* slot = reinterpret_cast<char*>(sm.ring) + dst_half * (kStageVec4 * 16) + wave * (kWave * 16);
+        const unsigned lane_off = (unsigned)sm.tid * 16u;
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)(slot + i * WAVES * kWave * 16),
+                                                     16, lane_off, i * WAVES * kWave * 16, 0, 0);
+        sm.fetch = (sm.fetch + 2 == sm.num_stages) ? 0 : sm.fetch + 2;
+    }
+}
+template <int WAVES, int SUB>
+__device__ __forceinline__ void stream_advance(WeightStream& sm) {
+    if constexpr (WAVES == 4) {
+        stream_advance(sm);
+    } else {
+        if constexpr (SUB == 1) asm volatile("s_waitcnt vmcnt(3)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        sm.slot = (sm.slot + 1 == 2 * kRing) ? 0 : sm.slot + 1;
+    }
+}
+
 // the pieces of a k-step: 8 values per lane and piece = one register quad each (r: the last piece x 2^8)
 struct Pieces {
     uvec4 h, l, r;
@@ -207,10 +246,10 @@ __device__ __forceinline__ Lead read_lead(const vec4f* stage) {
 // The three f16 products of a k-step share their srcB as far as they can (the matrix pipe's energy depends on how often
 // srcB changes between consecutive instructions, a new srcA costs nothing: fused_common.hpp, round 4); within a stage the
 // order of the additions is immaterial to the result's error.
-template <bool LAST>
+template <bool LAST, int WAVES = 4, int SUB = 0>
 __device__ __forceinline__ void stage_kmajor(f32x16& acc0, f32x16& acc1, const Pieces& b0, const Pieces& b1, const i32x8& bx,
                                              WeightStream& sm, int lane, Lead& lead) {
-    request_stage(sm);
+    request_stage<WAVES, SUB>(sm);
     const vec4f* cur = sm.ring + sm.slot * kStageVec4 + lane;
     const f16x8 bh0 = __builtin_bit_cast(f16x8, b0.h), bl0 = __builtin_bit_cast(f16x8, b0.l);
     const f16x8 bh1 = __builtin_bit_cast(f16x8, b1.h), bl1 = __builtin_bit_cast(f16x8, b1.l);
@@ -236,7 +275,7 @@ __device__ __forceinline__ void stage_kmajor(f32x16& acc0, f32x16& acc1, const P
     acc1 = NFA_K8X_F16(al0, bh0, acc1);
     acc1 = NFA_K8X_F16(ah0, bh0, acc1);
     NFA_K8X_FENCE();
-    stream_advance(sm);          // every read of this stage has landed in registers; the next stage is complete
+    stream_advance<WAVES, SUB>(sm);   // every read of this stage has landed in registers; the next stage is complete
     if constexpr (!LAST) lead = read_lead(sm.ring + sm.slot * kStageVec4 + lane);
     NFA_K8X_FENCE();
     acc1 = NFA_K8X_F16(ah1, bl1, acc1);
@@ -247,7 +286,7 @@ __device__ __forceinline__ void stage_kmajor(f32x16& acc0, f32x16& acc1, const P
 
 // k-major GEMM (all four output tiles accumulate together): out^T[128 x 32 samples] += W[128 x 16 NKS] x act^T; two
 // stages per pair of k-steps (tiles 0, 1 and tiles 2, 3).  pair(pr, b0, b1) makes the pieces of k-steps 2 pr, 2 pr + 1.
-template <int NKS, class PairFn>
+template <int NKS, int WAVES, class PairFn>
 __device__ __forceinline__ void gemm_kmajor_pairs(f32x16 (&acc)[4], WeightStream& sm, int lane, PairFn&& pair) {
     static_assert(NKS % 2 == 0, "pairs of k-steps");
     Lead lead = read_lead(sm.ring + sm.slot * kStageVec4 + lane);
@@ -256,16 +295,16 @@ __device__ __forceinline__ void gemm_kmajor_pairs(f32x16 (&acc)[4], WeightStream
         Pieces b0, b1;
         pair(pr, b0, b1);
         const i32x8 bx = bf8_operand(b0, b1);
-        stage_kmajor<false>(acc[0], acc[1], b0, b1, bx, sm, lane, lead);
-        if (pr + 1 < NKS / 2) stage_kmajor<false>(acc[2], acc[3], b0, b1, bx, sm, lane, lead);
-        else stage_kmajor<true>(acc[2], acc[3], b0, b1, bx, sm, lane, lead);
+        stage_kmajor<false, WAVES, 0>(acc[0], acc[1], b0, b1, bx, sm, lane, lead);
+        if (pr + 1 < NKS / 2) stage_kmajor<false, WAVES, 1>(acc[2], acc[3], b0, b1, bx, sm, lane, lead);
+        else stage_kmajor<true, WAVES, 1>(acc[2], acc[3], b0, b1, bx, sm, lane, lead);
     }
 }
 
 // ... on activations given as pieces
-template <int NKS>
+template <int NKS, int WAVES = 4>
 __device__ __forceinline__ void gemm_kmajor(f32x16 (&acc)[4], const Pieces (&p)[8], WeightStream& sm, int lane) {
-    gemm_kmajor_pairs<NKS>(acc, sm, lane, [&](int pr, Pieces& b0, Pieces& b1) {
+    gemm_kmajor_pairs<NKS, WAVES>(acc, sm, lane, [&](int pr, Pieces& b0, Pieces& b1) {
         b0 = p[2 * pr];
         b1 = p[2 * pr + 1];
     });
@@ -274,9 +313,10 @@ __device__ __forceinline__ void gemm_kmajor(f32x16 (&acc)[4], const Pieces (&p)[
 // ... on the previous GEMM's accumulator tiles: relu(src) x scale split into pieces on the fly, one pair of k-steps (= one
 // source tile: the accumulator layout is the B layout) at a time; src itself stays.  Only the first tile can have an MFMA
 // close in front (the previous GEMM's); the others are read behind at least one stage of this GEMM.
+template <int WAVES = 4>
 __device__ __forceinline__ void gemm_kmajor_relu(f32x16 (&acc)[4], const f32x16 (&src)[4], float scale, WeightStream& sm,
                                                  int lane) {
-    gemm_kmajor_pairs<8>(acc, sm, lane, [&](int pr, Pieces& b0, Pieces& b1) {
+    gemm_kmajor_pairs<8, WAVES>(acc, sm, lane, [&](int pr, Pieces& b0, Pieces& b1) {
         if (pr == 0) tile_to_pieces<true, true>(src[pr], scale, b0, b1);
         else tile_to_pieces<true, false>(src[pr], scale, b0, b1);
     });

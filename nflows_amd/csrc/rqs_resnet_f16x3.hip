@@ -22,6 +22,10 @@
 //     loads: f16x3_gemm.hpp, request_stage), four waves per
 //     workgroup, two workgroups per CU; fragments 0 .. 3 of every stage are read right behind the PREVIOUS stage's
 //     barrier (f16x3_gemm.hpp: Lead), the barrier stands in front of a stage's last MFMAs;
+//   * the wide form (8 bins, from two 128-row blocks per CU on: launch_f16x3): ONE workgroup of eight waves per CU on one
+//     ring of three 24 KB slots, a slot = a pair of stages, one barrier per pair -- the CU moves every stage from L2
+//     into LDS once, not once per workgroup (the narrow form's two rings move 64.5 GB per launch at the headline
+//     shape); waves 0 .. 3 and 4 .. 7 run two consecutive row blocks with the narrow form's program: same bits;
 //   * biases and tables: a layer's biases and the next layer's table are fetched a layer ahead into a bias area in LDS, as
 //     LDS-DMA pieces issued in front of a stage's weight requests (rqs_resnet_f16x3_kernel.hpp: bias_area_piece) -- the
 //     layer loop holds no per-lane global load and no vmcnt(0);
@@ -69,14 +73,22 @@ static k8x::KernelFn f16x3_kernel(bool inverse, int init_ks, int K, bool dbg, bo
                : (inverse ? k8x::rqs_resnet_f16x3_kernel<true, 2> : k8x::rqs_resnet_f16x3_kernel<false, 2>);
 }
 
+// The wide form's instance (rqs_resnet_f16x3_kernel.hpp: one eight-wave workgroup per CU on one ring): 8 bins, bias area
+static k8x::KernelFn f16x3_wide_kernel(bool inverse, int init_ks) {
+    if (init_ks == 4) return inverse ? k8x::rqs_resnet_f16x3_kernel_wide<true, 4> : k8x::rqs_resnet_f16x3_kernel_wide<false, 4>;
+    return inverse ? k8x::rqs_resnet_f16x3_kernel_wide<true, 2> : k8x::rqs_resnet_f16x3_kernel_wide<false, 2>;
+}
+
 static int launch_f16x3(const LayerCall& c, const float* scales, float act_scale, float* dbg_logits = nullptr) {
     // (a power of two: the pieces' scale must come out again exactly)
     int exponent = 0;
     if (!(act_scale > 0.0f) || frexpf(act_scale, &exponent) != 0.5f) return NFA_ERR_INVALID_ARGUMENT;
     k8x::Args a;
     int activation = 0;
-    int rc = check_layer_call(c, {NFA_FLAG_ACTIVATION_MASK, true, false, false}, &a.sp, &activation);
+    int rc = check_layer_call(c, {NFA_FLAG_ACTIVATION_MASK | NFA_FLAG_K8X_FORM_MASK, true, false, false}, &a.sp, &activation);
     if (rc != NFA_OK) return rc;
+    const int form = (c.flags & NFA_FLAG_K8X_FORM_MASK) >> NFA_FLAG_K8X_FORM_SHIFT;
+    if (form > NFA_K8X_FORM_WIDE) return NFA_ERR_INVALID_ARGUMENT;
     if (activation != NFA_ACTIVATION_RELU || (dbg_logits && a.sp.K != 8)) return NFA_ERR_UNSUPPORTED;
     if (c.batch == 0) return NFA_OK;
     if (!layer_buffers_given(c) || !c.bias || !scales || !c.redo) return NFA_ERR_INVALID_ARGUMENT;
@@ -105,10 +117,25 @@ static int launch_f16x3(const LayerCall& c, const float* scales, float act_scale
     const bool bias_lds = lds_area <= launch_limit && (dbg_logits || lds_area <= two_per_cu || lds_plain > two_per_cu);
     const size_t lds = bias_lds ? lds_area : lds_plain;
     int64_t blocks = c.batch >> 7;
+    const bool inv = (c.flags & NFA_FLAG_INVERSE) != 0;
+    // The wide form: where an instance exists (8 bins, no diagnostics), its LDS -- a ring of twice the size, eight row tiles,
+    // the bias area -- fits the launch, and every CU gets at least two row blocks (below that the narrow form keeps all CUs
+    // busy and the wide form would halve them).  NFA_FLAG_K8X_FORM forces either form where the first two hold.
+    const size_t lds_wide = 2 * lds_rows + (size_t)k8x::bias_area_floats(c.num_blocks, final_floats) * sizeof(float);
+    const bool wide_fits = a.sp.K == 8 && !dbg_logits && lds_wide <= launch_limit;
+    const bool wide = wide_fits && form != NFA_K8X_FORM_NARROW &&
+                      (form == NFA_K8X_FORM_WIDE || blocks >= (int64_t)k8x::kWideBlocksPerCu * device_cu_count());
+    if (wide) {
+        int64_t grid = (blocks + 1) >> 1;
+        if (grid > device_cu_count()) grid = device_cu_count();
+        note_layer_kernel("k8x::rqs_resnet_f16x3_kernel<inverse=%d, init_ks=%d, K=%d, dbg=0, waves=8, bias=lds>", inv ? 1 : 0, init_ks,
+                          a.sp.K);
+        return launch_kernel(f16x3_wide_kernel(inv, init_ks), dim3((unsigned)grid), dim3(2 * kBlock), lds_wide, (hipStream_t)c.stream,
+                             a, kCuLds - 2048);
+    }
     const int64_t per_cu = lds <= two_per_cu ? 2 : 1;
     const int64_t cap = (int64_t)device_cu_count() * per_cu;
     if (blocks > cap) blocks = cap;
-    const bool inv = (c.flags & NFA_FLAG_INVERSE) != 0;
     const k8x::KernelFn kern = f16x3_kernel(inv, init_ks, a.sp.K, dbg_logits, bias_lds);
     if (!kern) return NFA_ERR_UNSUPPORTED;
     note_layer_kernel("k8x::rqs_resnet_f16x3_kernel<inverse=%d, init_ks=%d, K=%d, dbg=%d, bias=%s>", inv ? 1 : 0, init_ks, a.sp.K,

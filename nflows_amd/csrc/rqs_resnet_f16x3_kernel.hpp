@@ -149,10 +149,10 @@ struct SeqWeave {
 // [X01 lo, X01 hi, X23 lo, X23 hi].  The first pair's f16 fragments arrive in `lead` (read behind the previous stage's
 // barrier), the second pair's are requested behind the MFMAs that free the first pair's registers, and the stage's own
 // barrier stands in front of its last bf8 instruction: the next stage's lead fragments land while that one runs.
-template <int HS, class W>
+template <int HS, int WAVES, class W>
 __device__ __forceinline__ void stage_pumped(f32x16& acc, const Pieces (&p)[8], const i32x8 (&bx)[4], WeightStream& sm, int lane,
                                              Lead& lead, W& w) {
-    request_stage(sm);
+    request_stage<WAVES, HS>(sm);
     const vec4f* cur = sm.ring + sm.slot * kStageVec4 + lane;
     vec4f xa = cur[8 * 64], xb = cur[9 * 64];
     vec4f fh0 = lead.h0, fl0 = lead.l0, fh1 = lead.h1, fl1 = lead.l1;
@@ -192,7 +192,7 @@ __device__ __forceinline__ void stage_pumped(f32x16& acc, const Pieces (&p)[8], 
         NFA_K8X_PUMP_F16(HS * 16 + 11, ah1, bl1);
         NFA_K8X_PUMP_F16(HS * 16 + 12, al1, bh1);
         NFA_K8X_PUMP_F16(HS * 16 + 13, ah1, bh1);
-        stream_advance(sm);      // every read of this stage has landed in registers; the next stage is complete
+        stream_advance<WAVES, HS>(sm);   // every read of this stage has landed in registers; the next stage is complete
         lead = read_lead(sm.ring + sm.slot * kStageVec4 + lane);
         __builtin_amdgcn_sched_barrier(0);
         NFA_K8X_PUMP_BF8(HS * 16 + 14, ax, bx[HS * 2 + 1]);
@@ -201,11 +201,12 @@ __device__ __forceinline__ void stage_pumped(f32x16& acc, const Pieces (&p)[8], 
 #undef NFA_K8X_PUMP_F16
 #undef NFA_K8X_PUMP_BF8
 
-template <class W>
+// (WAVES: the ring's form, f16x3_gemm.hpp -- a tile's two stages are the halves of a wide pair)
+template <int WAVES = 4, class W>
 __device__ __forceinline__ void gemm_tile_pumped(f32x16& acc, const Pieces (&p)[8], const i32x8 (&bx)[4], WeightStream& sm, int lane,
                                                  Lead& lead, W&& w) {
-    stage_pumped<0>(acc, p, bx, sm, lane, lead, w);
-    stage_pumped<1>(acc, p, bx, sm, lane, lead, w);
+    stage_pumped<0, WAVES>(acc, p, bx, sm, lane, lead, w);
+    stage_pumped<1, WAVES>(acc, p, bx, sm, lane, lead, w);
 }
 
 // tiles TI .. T - 1 of a group of the general final layer (K8h's any_group_tiles on this kernel's GEMM): biases, the tile's
@@ -229,13 +230,25 @@ __device__ __forceinline__ bool not_finite(float v) { return !(__builtin_fabsf(v
 // from global memory in front of its GEMM and the final layer's are copied through registers, each with a vmcnt(0) that
 // drains the weight ring -- kept for the geometries whose launch the larger area would take from two workgroups per CU
 // to one (rqs_resnet_f16x3.hip: launch_f16x3).
-template <bool INVERSE, int INIT_KS, bool DBG, int KB, bool BIAS_LDS>
+//
+// WAVES: 4 -- the narrow form: a workgroup of four waves owns one 128-row block per pass and a ring of its own, two workgroups
+// per CU, each streaming the layer's weights into LDS for itself.  8 -- the wide form: ONE workgroup of eight waves per CU
+// on ONE ring of three 24 KB slots (f16x3_gemm.hpp: a slot holds a pair of stages, one barrier per pair), so a CU moves
+// every stage from L2 into LDS once instead of twice.  The workgroup owns two consecutive row blocks per pass: waves 0 .. 3
+// run block 2 q, waves 4 .. 7 block 2 q + 1, each wave the narrow form's program on its 32 rows -- same fragments, same
+// order, same bits.  The redo flag, the vote on non-finite results and the status are kept per half (per 128 rows).  With
+// an odd number of row blocks the last workgroup's upper half has none: it computes the lower half's block again (every
+// request and every barrier is the workgroup's) and stores nothing.
+template <bool INVERSE, int INIT_KS, bool DBG, int KB, bool BIAS_LDS, int WAVES = 4>
 __device__ __forceinline__ void rqs_resnet_f16x3_body(const Args& a) {
     static_assert(!DBG || KB == 8, "the diagnostic instances: 8 bins");
+    constexpr bool WIDE = WAVES == 8;
+    static_assert(WAVES == 4 || (WIDE && KB == 8 && BIAS_LDS && !DBG), "the wide form: 8 bins, bias area, no diagnostics");
+    constexpr int kRingFloats = kRing * kStageVec4 * 4 * (WIDE ? 2 : 1);
     // rows of the final layer per transformed feature: 8 bins: 23 logits padded to 24, two features share three 32-row tiles;
     // otherwise 3 K - 1 padded to whole 16-row lane-half shares (one feature per lane-half and group of T tiles)
     constexpr int kFinalRows = KB == 8 ? 24 : 16 * ((3 * KB - 1 + 15) / 16);
-    constexpr int NW = kBlock / kWave;
+    constexpr int NW = WAVES;
     // dynamic LDS: the weight ring, per wave a [D][33] row tile, the bias area (without it: the final layer's biases)
     extern __shared__ __attribute__((aligned(16))) float lds_dyn[];
     __shared__ int s_tab[2][kTabLayer];   // tables of the current and the next layer
@@ -263,19 +276,26 @@ __device__ __forceinline__ void rqs_resnet_f16x3_body(const Args& a) {
     sm.fetch = 0;
     sm.num_stages = a.num_stages * a.num_layers;
     sm.tid = tid;
-    lds_f32* s_area = (lds_f32*)lds_dyn + kRing * kStageVec4 * 4 + NW * D * kRowPad;
+    lds_f32* s_area = (lds_f32*)lds_dyn + kRingFloats + NW * D * kRowPad;
     lds_f32* s_traw = s_area + bias_area_hidden_floats(a.num_blocks);
     // hidden biases of a layer: the initial layer's 512 B as two 256 B pieces, a block's 1 KB as one piece
     auto request_hidden = [&](int layer) {
         const float* src = a.bias + (size_t)layer * a.bias_per_layer;
         const int bytes = bias_area_hidden_floats(a.num_blocks) * 4;
-        if (wave >= 2) bias_area_piece<4>(src, bytes, (wave - 2) * 256, s_area + (wave - 2) * 64);
+        if (wave >= NW - 2) bias_area_piece<4>(src, bytes, (wave - (NW - 2)) * 256, s_area + (wave - (NW - 2)) * 64);
         for (int j = wave; j < a.num_blocks; j += NW) bias_area_piece<16>(src, bytes, 512 + j * 1024, s_area + 128 + j * 256);
     };
     if constexpr (BIAS_LDS) request_hidden(0);
-    request_stage(sm);  // stage 0 -> slot 0
-    sm.slot = 2;
-    request_stage(sm);  // stage 1 -> slot 1
+    if constexpr (WIDE) {
+        sm.slot = 2;
+        request_stage<WAVES, 0>(sm);  // stages 0, 1 -> slot 0 (halves 0, 1)
+        sm.slot = 4;
+        request_stage<WAVES, 0>(sm);  // stages 2, 3 -> slot 1 (halves 2, 3)
+    } else {
+        request_stage(sm);  // stage 0 -> slot 0
+        sm.slot = 2;
+        request_stage(sm);  // stage 1 -> slot 1
+    }
     sm.slot = 0;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -286,7 +306,7 @@ __device__ __forceinline__ void rqs_resnet_f16x3_body(const Args& a) {
     if (blockIdx.x >= (gridDim.x >> 1))
         for (int i = 0; i < NFA_K8X_STAGGER; ++i) __builtin_amdgcn_s_sleep(127);
 #endif
-    lds_f32* s_row = (lds_f32*)lds_dyn + kRing * kStageVec4 * 4 + wave * D * kRowPad;
+    lds_f32* s_row = (lds_f32*)lds_dyn + kRingFloats + wave * D * kRowPad;
     lds_f32* s_fbias = BIAS_LDS ? s_traw + kTabLayer : s_area;
     // final-layer biases of a layer: 1 KB pieces, the last one's lanes past the end land in the area's padding
     auto request_final = [&](int layer) {
@@ -304,8 +324,16 @@ __device__ __forceinline__ void rqs_resnet_f16x3_body(const Args& a) {
     const float S = a.act_scale;
     int tb = 0;  // which half of s_tab holds the current layer's table
 
-    for (int64_t quad = blockIdx.x; quad < num_quads; quad += gridDim.x) {
-        const int64_t row0 = (quad << 7) + (wave << 5);
+    const int64_t num_passes = WIDE ? (num_quads + 1) >> 1 : num_quads;
+    for (int64_t pass = blockIdx.x; pass < num_passes; pass += gridDim.x) {
+        // (wide: the upper half of the last workgroup of an odd number of row blocks runs the lower half's block and stores
+        //  nothing -- arithmetic, no branch: see the kernel's head)
+        const int64_t quad_mine = WIDE ? 2 * pass + (wave >> 2) : pass;
+        // (the sign of the wrapping difference, not a compare and a select: the instance keeps the narrow form's v_cndmask count)
+        const int live_bit = WIDE ? (int)(((uint64_t)quad_mine - (uint64_t)num_quads) >> 63) : 1;
+        const bool live = live_bit != 0;
+        const int64_t quad = quad_mine - 1 + live_bit;
+        const int64_t row0 = (quad << 7) + ((WIDE ? wave & 3 : wave) << 5);
         // (lane-derived values are made opaque per iteration: hoisted out of this loop they would stay live through
         //  the whole kernel and push the register allocation into scratch)
         int lane_here = lane, di = a.di;
@@ -342,8 +370,14 @@ __device__ __forceinline__ void rqs_resnet_f16x3_body(const Args& a) {
         int quad_status = 0;
         for (int layer = 0; layer < a.num_layers; ++layer) {
             // the two workgroups resident on a CU take turns at the higher issue priority (see rqs_resnet_kernel.hpp)
-            if ((layer + (blockIdx.x >= (gridDim.x >> 1) ? 1 : 0)) & 1) __builtin_amdgcn_s_setprio(1);
-            else __builtin_amdgcn_s_setprio(0);
+            // (wide: the two halves of the workgroup.  NFA_K8X_WIDE_NOPRIO, measurement builds: the wide form without it)
+#ifdef NFA_K8X_WIDE_NOPRIO
+            if constexpr (!WIDE)
+#endif
+            {
+                if ((layer + ((WIDE ? wave >= 4 : blockIdx.x >= (gridDim.x >> 1)) ? 1 : 0)) & 1) __builtin_amdgcn_s_setprio(1);
+                else __builtin_amdgcn_s_setprio(0);
+            }
             const int* tab = s_tab[tb];
             const int nl = layer + 1 < a.num_layers ? layer + 1 : 0;   // (after the last layer: the next row block's first)
             // the next layer's table goes to the other half now; it is read only after this layer's many stage barriers
@@ -393,7 +427,7 @@ __device__ __forceinline__ void rqs_resnet_f16x3_body(const Args& a) {
             {
 #pragma unroll
                 for (int t = 0; t < 4; ++t) load_bias_tile(h[t], bias + t * 32);
-                gemm_kmajor<INIT_KS>(h, p, sm, lane);
+                gemm_kmajor<INIT_KS, WAVES>(h, p, sm, lane);
                 float s0[2];
                 uniform_load(sc, s0);
                 hs = s0[0];
@@ -427,7 +461,7 @@ __device__ __forceinline__ void rqs_resnet_f16x3_body(const Args& a) {
                 f32x16 u[4];
 #pragma unroll
                 for (int t = 0; t < 4; ++t) load_bias_tile(u[t], bias + t * 32);
-                gemm_kmajor_relu(u, h, hs, sm, lane);
+                gemm_kmajor_relu<WAVES>(u, h, hs, sm, lane);
                 uniform_load(sc, sb);
                 const float skip = hs * sb[3];   // (powers of two: exact)
 #pragma unroll
@@ -437,7 +471,7 @@ __device__ __forceinline__ void rqs_resnet_f16x3_body(const Args& a) {
 #pragma unroll
                     for (int q_ = 0; q_ < 16; ++q_) h[t][q_] = __builtin_fmaf(h[t][q_], skip, b1[q_]);
                 }
-                gemm_kmajor_relu(h, u, sb[0], sm, lane);
+                gemm_kmajor_relu<WAVES>(h, u, sb[0], sm, lane);
                 hs = sb[2];
                 bias += 256;
                 sc += 4;
@@ -503,10 +537,10 @@ __device__ __forceinline__ void rqs_resnet_f16x3_body(const Args& a) {
                     lds_f32* slot1 = s_row + tab[kTabTr + g * 4 + half * 2 + 1] * kRowPad + r;
                     load_bias_tile(acc[0], fbias + (g * 3 + 0) * 32);
                     if (g > 0) {
-                        gemm_tile_pumped(acc[0], p, bx, sm, lane, lead, w2);
+                        gemm_tile_pumped<WAVES>(acc[0], p, bx, sm, lane, lead, w2);
                         commit(fb, slot_b);
                     } else {
-                        gemm_tile_pumped(acc[0], p, bx, sm, lane, lead, NoWeave{});
+                        gemm_tile_pumped<WAVES>(acc[0], p, bx, sm, lane, lead, NoWeave{});
                     }
                     store_logits(acc[0], g * 3 + 0);
                     fa.x = *slot0;
@@ -516,7 +550,7 @@ __device__ __forceinline__ void rqs_resnet_f16x3_body(const Args& a) {
                         fa.eh[j] = acc[0][8 + j];
                     }
                     load_bias_tile(acc[1], fbias + (g * 3 + 1) * 32);
-                    gemm_tile_pumped(acc[1], p, bx, sm, lane, lead, w0);
+                    gemm_tile_pumped<WAVES>(acc[1], p, bx, sm, lane, lead, w0);
                     store_logits(acc[1], g * 3 + 1);
                     fb.x = *slot1;
 #pragma unroll
@@ -525,7 +559,7 @@ __device__ __forceinline__ void rqs_resnet_f16x3_body(const Args& a) {
                         fb.ew[j] = acc[1][8 + j];
                     }
                     load_bias_tile(acc[2], fbias + (g * 3 + 2) * 32);
-                    gemm_tile_pumped(acc[2], p, bx, sm, lane, lead, w1);
+                    gemm_tile_pumped<WAVES>(acc[2], p, bx, sm, lane, lead, w1);
                     store_logits(acc[2], g * 3 + 2);
                     commit(fa, slot0);
 #pragma unroll
@@ -600,8 +634,8 @@ __device__ __forceinline__ void rqs_resnet_f16x3_body(const Args& a) {
         __syncthreads();
         int any_bad = 0;
 #pragma unroll
-        for (int w_ = 0; w_ < NW; ++w_) any_bad |= s_bad[w_];
-        if (!any_bad) {
+        for (int w_ = 0; w_ < 4; ++w_) any_bad |= s_bad[(WIDE ? wave & 4 : 0) + w_];   // (this wave's 128 rows)
+        if (!any_bad && live) {
             if (!a.skip_out) {
                 vec4f* ov = reinterpret_cast<vec4f*>(a.out + row0 * D);
                 const int nvec = D * 8;
@@ -623,7 +657,7 @@ __device__ __forceinline__ void rqs_resnet_f16x3_body(const Args& a) {
             }
             my_status |= quad_status;
         }
-        if (tid == 0) a.redo[quad] = any_bad ? 1 : 0;
+        if ((WIDE ? (tid & 255) == 0 && live : tid == 0)) a.redo[quad] = any_bad ? 1 : 0;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();  // s_bad is rewritten by the next row block
     }
@@ -639,6 +673,15 @@ __global__ void __launch_bounds__(kBlock, 2) rqs_resnet_f16x3_kernel(const Args 
 template <bool INVERSE, int INIT_KS, bool DBG = false, int KB = 8>
 __global__ void __launch_bounds__(kBlock, 2) rqs_resnet_f16x3_global_bias_kernel(const Args a) {
     rqs_resnet_f16x3_body<INVERSE, INIT_KS, DBG, KB, false>(a);
+}
+
+// row blocks per CU from which the launcher takes the wide form (rqs_resnet_f16x3.hip: launch_f16x3)
+constexpr int kWideBlocksPerCu = 2;
+
+// the wide form (8 bins, bias area): one workgroup of eight waves per CU
+template <bool INVERSE, int INIT_KS>
+__global__ void __launch_bounds__(2 * kBlock, 1) rqs_resnet_f16x3_kernel_wide(const Args a) {
+    rqs_resnet_f16x3_body<INVERSE, INIT_KS, false, 8, true, 8>(a);
 }
 
 }  // namespace k8x

@@ -2449,6 +2449,11 @@ K8S_ENABLED = os.environ.get("NFA_K8S", "1") != "0"
 K8S_ALWAYS = os.environ.get("NFA_K8S", "1") == "2"     # (measurements: the 16-sample-tile kernel at every batch size)
 K8C_ENABLED = os.environ.get("NFA_K8C", "1") != "0"    # the column-split form of K8s for batches of at most 64 rows per CU
 K8C_ALWAYS = os.environ.get("NFA_K8C", "1") == "2"
+# K8x's form where both exist (8 bins, the wide form's LDS fits): 0 -- the launcher's choice (wide from two 128-row blocks per
+# CU), 1 -- narrow (four-wave workgroups, two per CU, a weight ring each), 2 -- wide (one eight-wave workgroup per CU on one
+# ring).  Same results bit for bit; `NFA_K8X_FORM=narrow|wide` forces one (measurements, tests/test_gpu_k8x_wide.py).
+K8X_FORMS = {"auto": 0, "narrow": 1, "wide": 2}
+K8X_FORM = K8X_FORMS[os.environ.get("NFA_K8X_FORM", "auto")]
 _cu_counts = {}
 
 
@@ -2719,7 +2724,7 @@ def rqs_coupling_resnet_f16x3(inputs, packed_f16x3, packed_exact, tables, num_tr
         B, D = x.shape
         args = (N.ptr(x), N.ptr(weights), N.ptr(biases), N.ptr(scales), N.ptr(tables), num_layers, N.ptr(out),
                 N.ptr(lad), N.ptr(redo), status, B, D, num_transform, num_identity, 128, num_blocks,
-                float(act_scale), ctypes.byref(spec), flags, stream)
+                float(act_scale), ctypes.byref(spec), flags | K8X_FORM << N.FLAG_K8X_FORM_SHIFT, stream)
         capture = capture_last_layer_logits.active
         if capture is None:
             return lib.nfa_rqs_flow_resnet_f16x3_f32(*args)

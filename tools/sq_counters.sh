@@ -4,12 +4,14 @@
 ENGINE=$1; PATTERN=$2
 ROOTDIR=${GRAFT_REPO_ROOT:-$PWD}
 OUT=$ROOTDIR/gpurun_out/r6
+OUT=${SQ_OUT:-$OUT}   # (SQ_OUT: another directory; the last group: the L2's requests and hits -- what the weight stream asks of it)
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
 BENCH="python $ROOTDIR/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --skip-extra --skip-consistency --skip-mfma-ceiling --skip-graph --skip-k1-roofline --engine $ENGINE"
 : > $OUT/sq_$ENGINE.txt
-for grp in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_VALU_MFMA_COEXEC_CYCLES" "SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_MFMA SQ_WAIT_INST_ANY" "SQ_WAIT_ANY SQ_ACTIVE_INST_LDS SQ_INSTS_LDS SQ_WAIT_INST_LDS" "SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_MISC SQ_LDS_BANK_CONFLICT" "SQ_INSTS_SALU SQ_INSTS_VMEM SQ_ACTIVE_INST_ANY SQ_INST_CYCLES_VMEM_RD"; do
+for grp in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_VALU_MFMA_COEXEC_CYCLES" "SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_MFMA SQ_WAIT_INST_ANY" "SQ_WAIT_ANY SQ_ACTIVE_INST_LDS SQ_INSTS_LDS SQ_WAIT_INST_LDS" "SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_MISC SQ_LDS_BANK_CONFLICT" "SQ_INSTS_SALU SQ_INSTS_VMEM SQ_ACTIVE_INST_ANY SQ_INST_CYCLES_VMEM_RD" \
+           "TCC_REQ_sum TCC_HIT_sum TCP_TCC_READ_REQ_sum"; do
   rm -rf $OUT/sq_tmp
   timeout 300 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $OUT/sq_tmp -o p -- $BENCH > $OUT/sq_tmp.log 2>&1
   python - "$PATTERN" $OUT <<'PY' >> $OUT/sq_$ENGINE.txt
