@@ -44,6 +44,8 @@ extern "C" {
                               19: nfa_diag_normal_*, nfa_mog_* (K20);
                               still 19: nfa_affine_flow_made_f32 (K22) is an ADDED entry point -- no existing entry point, flag set
                               or packed layout changed, so libraries and bindings of 19 keep working with each other;
+                              still 19: nfa_made_affine_inverse_f32 (K23) is an ADDED entry point, for the same reason (the two
+                              words it reads in K12's step blocks were zero and unread);
                               still 19: NFA_FLAG_K8X_FORM (bits 16-17, nfa_rqs_flow_resnet_f16x3_f32) is an ADDED field whose zero is
                               the behaviour of every caller of 19: an older library rejects a non-zero value as an unknown flag,
                               an older binding never sets one */
@@ -679,6 +681,37 @@ int nfa_made_rqs_inverse_f32(const float *inputs, const float *step_blocks, cons
                              float *hidden_out, int32_t *status, int64_t batch, int32_t features,
                              int32_t hidden_features, int32_t sequential_steps, const nfa_rqs_spec *spec,
                              void *stream);
+
+/*
+ * K23.  AutoregressiveTransform.inverse (autoregressive.py:43-52) of MaskedAffineAutoregressiveTransform
+ *   (autoregressive.py:64-128) over a MADE conditioner, context included, as one persistent kernel: K12's step loop with
+ *   the affine element -- x_t = (z_t - shift_t) / (softplus(u_t) + 1e-3), logabsdet -= log of that scale -- in place of
+ *   the spline, and EVERY feature a step (steps beyond the largest hidden degree have no units), so `outputs` and
+ *   `logabsdet` are complete and there is no `hidden_out`.
+ *   step_blocks / block_starts / layout: ops.pack_made_schedule(net, features, 2, block_cap=..., context=True): K12's
+ *     format with P = 2 (row 0 of a feature: the unconstrained scale, row 1: the shift) and two additions, both zero in
+ *     every blob K12 reads:
+ *       header word 4   1: another block of the same step follows.  Such a continuation block carries units only (in layer
+ *                       order across the step's blocks); the step's last block carries the output rows.  Steps are cut
+ *                       where one block per step does not fit the LDS twice beside the state (`block_cap`).
+ *       unit word 7     the context vector the unit adds after `acc + bias`, before the residual add and the ReLU
+ *                       (1-based, 0 = none).
+ *     block_starts int32 [num_blocks + 2] in 1 KB grains; num_blocks >= features + 1 (the last block, behind the last
+ *     step, holds no output rows).
+ *   context_terms  [batch, context_vectors, Hp] (Hp = `layout[5]`): per sample what the context adds to the units --
+ *                  vector 0 relu(context_layer(ctx)) for the initial layer (made.py:274-281), vector 1 + i
+ *                  blocks[i].context_layer(ctx) for the first Linear of residual block i (made.py:187-198); feed-forward
+ *                  blocks take none.  The caller forms them (one GEMM); NULL with context_vectors = 0.
+ *   outputs     [batch, features], logabsdet [batch] (the inverse's sign).
+ * Supported: ReLU, no batch norm; the state of sixteen samples (padded features + one vector per hidden Linear and per
+ * context vector) + two blocks of `layout[7]` floats within the LDS, otherwise NFA_ERR_UNSUPPORTED (callers keep the
+ * column-wise host loop).  Added under ABI 19 (see NFA_ABI_VERSION): no existing entry point, flag set or packed layout
+ * changed.
+ */
+int nfa_made_affine_inverse_f32(const float *inputs, const float *context_terms, int32_t context_vectors,
+                                const float *step_blocks, const int32_t *block_starts, int32_t num_blocks,
+                                const int32_t *layout, int32_t layout_len, float *outputs, float *logabsdet,
+                                int64_t batch, int32_t features, int32_t hidden_features, void *stream);
 
 /*
  * K13.  The output layer of a MADE conditioner and the autoregressive spline layer behind it in one kernel:

@@ -49,8 +49,8 @@ namespace nfa {
 constexpr int kMadeMaxLinears = 12;
 constexpr int kMadeSamples = 16;     // per workgroup
 constexpr int kMadeWaves = 4;
-constexpr int kMadeHeader = 16;      // ints in front of a step block: {units, offset of the unit rows, of the output rows, of the output biases}
-constexpr int kMadeUnitWords = 8;    // per unit, right behind the header: {bias, index, columns, src vector, dst vector, add_stream, set_stream, 0}
+constexpr int kMadeHeader = 16;      // ints in front of a step block: {units, offset of the unit rows, of the output rows, of the output biases, K23: 1 = the step continues in the next block}
+constexpr int kMadeUnitWords = 8;    // per unit, right behind the header: {bias, index, columns, src vector, dst vector, add_stream, set_stream, K23: context vector + 1 (K12: 0)}
 #ifndef NFA_K12_ROWS_AHEAD
 #define NFA_K12_ROWS_AHEAD 4   // groups of the output rows' dot products requested ahead (dot_rows_64); measured 2: 5.2 k, 3: 4.6 k, 4: 4.0 k cycles per step
 #endif
@@ -63,7 +63,7 @@ struct MadeInvArgs {
     float* lad;              // [B]   sum of the log-derivatives of columns < T
     float* hidden;           // [B, H] the output layer's input once all hidden units are final
     const float* blocks;     // the step blocks, one after the other
-    const int32_t* block_at; // [T + 2] start of block t in grains
+    const int32_t* block_at; // [T + 2] start of block t in grains (K23: [num_blocks + 2])
     int32_t* status;
     int64_t batch;
     int D, H, Hp, Xp, T, num_linears, residual, final_src, stream_vec, num_vectors, max_block;  // max_block in floats
@@ -71,6 +71,9 @@ struct MadeInvArgs {
         set_stream[kMadeMaxLinears];
     RqsDev sp;
     unsigned long long* trace;   // debug (nfa_debug_k7_trace): cycle stamps of workgroup 0, wave 0 over the first steps
+    // K23 (the affine element): the context terms [B, num_ctx, Hp] and the number of blocks (a step may span several)
+    const float* ctx;
+    int num_ctx, num_blocks, group;   // group: units of one Linear in groups of eight (NFA_K23_GROUP)
 };
 
 // sum over the sixteen lanes of a sample (a DPP row), every lane gets it
@@ -188,14 +191,30 @@ __device__ __forceinline__ void request_block(const MadeInvArgs& a, int t, float
                                          (__attribute__((address_space(3))) void*)(d + g * (kMadeGrain * 4)), 16, 0, 0);
 }
 
+// K23: the same step loop with the affine element of MaskedAffineAutoregressiveTransform (autoregressive.py:96-128) in
+// place of the spline -- KT = 0: P = 2 output rows per feature, (unconstrained scale, shift), K2b's arithmetic -- and what
+// a MAF needs beside it:
+//   * all D features are steps (T = D): steps beyond the largest hidden degree have no units, only output rows, so the
+//     kernel writes the complete [B, D] result and there is no tail GEMM and no `hidden` output;
+//   * a context enters a MADE as per-sample constants (made.py:274-281 and :187-198): relu(context_layer(ctx)) on the initial
+//     layer, blocks[i].context_layer(ctx) on a residual block's first Linear.  The caller computes them with one GEMM,
+//     [B, num_ctx, Hp]; every sample's vectors are staged into LDS once, behind the state, and a unit entry's last word
+//     names the vector it adds (1-based, 0 = none) after `acc + bias` and before the residual add and the ReLU;
+//   * a MAF step is wide (H / (D - 1) units per Linear): a step whose block would not fit twice beside the state is cut
+//     into continuation blocks (header word 4 = 1: another block of this step follows; it carries units only, the step's
+//     last block the output rows).  The loop runs over blocks; t advances -- and the z prefetch with it -- on a step's
+//     last block only.  The hand-over of a block is K12's, unchanged.
+// The RQ instances compile to what they were (`if constexpr`): for them a block is a step.
+//
 // LPS = lanes per sample.  16: four waves x four samples (round 3).  32 (round 4): EIGHT waves x two samples -- the same
 // sixteen samples and the same LDS per workgroup, but two waves per SIMD: a batch that gives every CU at most one
 // workgroup (configs[4]: 4 096 samples = 256 workgroups) has nothing else to hide the chain's LDS round trips with.
 template <int KT, int LPS>
-__global__ void __launch_bounds__((LPS / 4) * kWave) made_rqs_inverse_kernel(const MadeInvArgs a) {
+__global__ void __launch_bounds__((LPS / 4) * kWave) made_inverse_kernel(const MadeInvArgs a) {
 #pragma clang fp contract(off)
-    constexpr int P = 3 * KT - 1;
-    constexpr int RB = 8;                                           // output rows per pass of dot_rows
+    constexpr bool AFFINE = KT == 0;
+    constexpr int P = AFFINE ? 2 : 3 * KT - 1;
+    constexpr int RB = AFFINE ? 2 : 8;                              // output rows per pass of dot_rows
     constexpr int NW = LPS / 4;                                     // waves per workgroup (16 samples)
     constexpr int SPW = kWave / LPS;                                // samples per wave
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -208,12 +227,26 @@ __global__ void __launch_bounds__((LPS / 4) * kWave) made_rqs_inverse_kernel(con
     const int state_floats = x_floats + a.num_vectors * vec_floats;
     float* xs = lds;                                                // [16][px][4]
     float* vecs = lds + x_floats;                                   // [num_vectors][16][ph][4]
-    float* buf0 = lds + state_floats;                               // two step blocks
+    const int ctx_floats = AFFINE ? a.num_ctx * vec_floats : 0;
+    float* ctxs = lds + state_floats;                               // [num_ctx][16][ph][4] (K23)
+    float* buf0 = lds + state_floats + ctx_floats;                  // two step blocks
     float* buf1 = buf0 + a.max_block;
     request_block<NW>(a, 0, buf0, lane, wave);
     for (int i = threadIdx.x; i < state_floats; i += NW * kWave) lds[i] = 0.0f;
+    if constexpr (AFFINE) {
+        // this sample's context terms, read by its own sixteen lanes only (a dead sample stages the last row's)
+        for (int c = 0; c < a.num_ctx; ++c) {
+            const float* from = a.ctx + ((size_t)rrow * a.num_ctx + c) * a.Hp;
+            float* to = ctxs + c * vec_floats + s * ph * 4;
+            for (int k = q; k < (a.Hp >> 2); k += LPS)
+                *reinterpret_cast<vec4f*>(to + k * 4) = *reinterpret_cast<const vec4f*>(from + k * 4);
+        }
+    }
 
     float lad_acc = 0.0f;
+    // (K23 adds D terms where K12 adds T: one after the other in fp32 the sum was 2.1 x as far from float64 as the
+    //  reference's pairwise torch.sum at D = 64, so the affine element keeps its total in float64 and rounds once)
+    double lad_wide = 0.0;
     int my_status = 0;
     const float* zrow = a.z + rrow * a.D;
     float* stream = a.residual ? vecs + a.stream_vec * vec_floats : nullptr;
@@ -221,18 +254,33 @@ __global__ void __launch_bounds__((LPS / 4) * kWave) made_rqs_inverse_kernel(con
     unsigned long long* tr = (a.trace && blockIdx.x == 0 && threadIdx.x == 0) ? a.trace : nullptr;
     int ti = 0;
 #define NFA_K12_STAMP() if (tr && ti < 250) tr[ti++] = __builtin_readcyclecounter();
-    for (int t = 0; t <= a.T; ++t) {
-        float* blk = (t & 1) ? buf1 : buf0;
+    // (RQ: block b is step b.  Affine: `t` advances on a step's last block, `fresh` = the block opens a step)
+    const int nb = AFFINE ? a.num_blocks : 0;
+    int t_affine = 0;
+    bool fresh = true;
+    float z_held = 0.0f;
+    for (int b = 0; AFFINE ? b < nb : b <= a.T; ++b) {
+        const int t = AFFINE ? t_affine : b;
+        float* blk = (b & 1) ? buf1 : buf0;
         NFA_K12_STAMP()
         // block t has landed (every wave's share, requested a whole step ago), every wave is done with the
         // other buffer half (and, at t = 0, the state is zeroed)
         asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
         __syncthreads();
         NFA_K12_STAMP()
-        const float z_t = z_next;
-        if (t < a.T) {
-            request_block<NW>(a, t + 1, (t & 1) ? buf0 : buf1, lane, wave);
-            if (t + 1 < a.T) z_next = zrow[t + 1];
+        if constexpr (AFFINE) {
+            if (b + 1 < nb) request_block<NW>(a, b + 1, (b & 1) ? buf0 : buf1, lane, wave);
+            if (fresh) {   // (the z prefetch follows t, not the block index)
+                z_held = z_next;
+                if (t + 1 < a.T) z_next = zrow[t + 1];
+            }
+        }
+        const float z_t = AFFINE ? z_held : z_next;
+        if constexpr (!AFFINE) {
+            if (t < a.T) {
+                request_block<NW>(a, t + 1, (t & 1) ? buf0 : buf1, lane, wave);
+                if (t + 1 < a.T) z_next = zrow[t + 1];
+            }
         }
         // ---- the step's control data in ONE round trip: header and the first unit entries (a dependent LDS
         //      read per field was most of the unit chain's time: five to six round trips per unit)
@@ -249,6 +297,8 @@ __global__ void __launch_bounds__((LPS / 4) * kWave) made_rqs_inverse_kernel(con
         const float* rows = blk + __builtin_amdgcn_readfirstlane(h0.y);
         const float* wf = blk + __builtin_amdgcn_readfirstlane(h0.z);
         const float* fbias = blk + __builtin_amdgcn_readfirstlane(h0.w);
+        bool continued = false;   // another block of this step follows
+        if constexpr (AFFINE) continued = __builtin_amdgcn_readfirstlane(bv[1].x) != 0;
         // ---- 1. hidden units of degree t in layer order (typically one unit per layer), for this wave's samples
         auto unit = [&](vec4i e0, vec4i e1) {
             const float bias = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(e0.x));
@@ -258,11 +308,20 @@ __global__ void __launch_bounds__((LPS / 4) * kWave) made_rqs_inverse_kernel(con
             const float* src = src_v < 0 ? xs + s * px * 4 : vecs + src_v * vec_floats + s * ph * 4;
             const int at = state_index(j, s, ph);
             const float carried = add_stream ? stream[at] : 0.0f;   // (in flight beside the dot product's reads)
+            int ctx_v = 0;
+            float ctx_term = 0.0f;
+            if constexpr (AFFINE) {
+                ctx_v = __builtin_amdgcn_readfirstlane(e1.w);
+                if (ctx_v) ctx_term = ctxs[(ctx_v - 1) * vec_floats + at];
+            }
             float acc[1];
             if (kp == 256) dot_rows_64<1, 4, LPS>(acc, rows, kp, src, q, 1);
             else dot_rows<1, 4, LPS>(acc, rows, kp, src, kp >> 2, q, 1);
             rows += kp;
             float v = acc[0] + bias;
+            if constexpr (AFFINE) {
+                if (ctx_v) v = v + ctx_term;                    // h + relu(context_layer(ctx)) / lower(h) + context_layer(ctx)
+            }
             if (add_stream) v = carried + v;                    // residual connection (made.py:128)
             if (q == 0) {
                 if (set_stream) stream[at] = v;
@@ -272,11 +331,70 @@ __global__ void __launch_bounds__((LPS / 4) * kWave) made_rqs_inverse_kernel(con
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         };
+        bool one_by_one = true;
+        if constexpr (AFFINE) {
+            // K23, NFA_K23_GROUP: a MAF step has many units per Linear -- consecutive in the block, the same source vector and
+            // width, independent of each other.  Up to eight of them per pass of dot_rows: the source vector is read once
+            // for the eight rows, one fence per group.  Every dot product keeps its summation order (dot_rows<R> sums row
+            // by row as dot_rows<1> does), so the results are the one-by-one path's bit for bit.
+            if (a.group) {
+                one_by_one = false;
+                constexpr int RG = 8;
+                const int* words = reinterpret_cast<const int*>(blk);
+                for (int u = 0; u < units;) {
+                    const vec4i f0 = bv[kMadeHeader / 4 + 2 * u];
+                    const int kp = __builtin_amdgcn_readfirstlane(f0.z), src_v = __builtin_amdgcn_readfirstlane(f0.w);
+                    // the run of units of this Linear from u on (at most RG).  (The seven entries behind u are read whether
+                    // they exist or not: 16 + 8 (units + 7) words are inside a block of >= 256 words that holds the units' rows.)
+                    int next_src[RG - 1];
 #pragma unroll
-        for (int u = 0; u < kMadeUnitsAhead; ++u)
-            if (u < units) unit(ue[u][0], ue[u][1]);
-        for (int u = kMadeUnitsAhead; u < units; ++u) unit(bv[kMadeHeader / 4 + 2 * u], bv[kMadeHeader / 4 + 2 * u + 1]);
+                    for (int i = 1; i < RG; ++i) next_src[i - 1] = words[kMadeHeader + kMadeUnitWords * (u + i) + 3];
+                    int g = 1;
+#pragma unroll
+                    for (int i = 1; i < RG; ++i)
+                        if (g == i && u + i < units && __builtin_amdgcn_readfirstlane(next_src[i - 1]) == src_v) g = i + 1;
+                    const float* src = src_v < 0 ? xs + s * px * 4 : vecs + src_v * vec_floats + s * ph * 4;
+                    float acc[RG];
+                    if (kp == 256) dot_rows_64<RG, NFA_K12_ROWS_AHEAD, LPS>(acc, rows, kp, src, q, g);
+                    else dot_rows<RG, 4, LPS>(acc, rows, kp, src, kp >> 2, q, g);
+                    rows += g * kp;
+#pragma unroll
+                    for (int i = 0; i < RG; ++i) {
+                        if (i < g) {
+                            const vec4i e0 = bv[kMadeHeader / 4 + 2 * (u + i)], e1 = bv[kMadeHeader / 4 + 2 * (u + i) + 1];
+                            const float bias = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(e0.x));
+                            const int j = __builtin_amdgcn_readfirstlane(e0.y), dst_v = __builtin_amdgcn_readfirstlane(e1.x);
+                            const bool add_stream = __builtin_amdgcn_readfirstlane(e1.y) != 0;
+                            const bool set_stream = __builtin_amdgcn_readfirstlane(e1.z) != 0;
+                            const int ctx_v = __builtin_amdgcn_readfirstlane(e1.w);
+                            const int at = state_index(j, s, ph);
+                            float v = acc[i] + bias;
+                            if (ctx_v) v = v + ctxs[(ctx_v - 1) * vec_floats + at];
+                            if (add_stream) v = stream[at] + v;
+                            if (q == 0) {
+                                if (set_stream) stream[at] = v;
+                                if (dst_v >= 0) vecs[dst_v * vec_floats + at] = v < 0.0f ? 0.0f : v;
+                            }
+                        }
+                    }
+                    // the group's units are inputs of the next Linear (same wave: LDS is in order)
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                    u += g;
+                }
+            }
+        }
+        if (one_by_one) {
+#pragma unroll
+            for (int u = 0; u < kMadeUnitsAhead; ++u)
+                if (u < units) unit(ue[u][0], ue[u][1]);
+            for (int u = kMadeUnitsAhead; u < units; ++u) unit(bv[kMadeHeader / 4 + 2 * u], bv[kMadeHeader / 4 + 2 * u + 1]);
+        }
         NFA_K12_STAMP()
+        if constexpr (AFFINE) {
+            fresh = !continued;
+            if (continued) continue;
+        }
         if (t == a.T) break;
         // ---- 2. feature t's P output rows on the hidden vector as it stands: all sums in every lane of the sample
         const float* fin = vecs + a.final_src * vec_floats + s * ph * 4;
@@ -295,8 +413,14 @@ __global__ void __launch_bounds__((LPS / 4) * kWave) made_rqs_inverse_kernel(con
         // ---- 3. invert feature t (rational_quadratic.py:66-181 through the same evaluation as K5); every
         //      lane of a sample does it, one records the result
         float y, l;
-        my_status |= rqs_eval<KT, true, true, true>(z_t, p, a.sp, y, l);
-        lad_acc += l;
+        if constexpr (AFFINE) {
+            affine_element<true>(z_t, p[1], scale_of(p[0], NFA_SCALE_SOFTPLUS), y, l);   // (K2b: autoregressive.py:96-121)
+            ++t_affine;
+        } else {
+            my_status |= rqs_eval<KT, true, true, true>(z_t, p, a.sp, y, l);
+        }
+        if constexpr (AFFINE) lad_wide += (double)l;
+        else lad_acc += l;
         // (kept in LDS only: a global store per step would sit in front of the next step's vmcnt(0))
         if (q == 0) xs[state_index(t, s, px)] = y;
         NFA_K12_STAMP()
@@ -307,31 +431,20 @@ __global__ void __launch_bounds__((LPS / 4) * kWave) made_rqs_inverse_kernel(con
     // input of the output layer for features >= T
     if (live) {
         for (int k = q; k < a.T; k += LPS) a.x[row * a.D + k] = xs[state_index(k, s, px)];
-        if (q == 0) a.lad[row] = lad_acc;
-        const float* fin = vecs + a.final_src * vec_floats;
-        for (int k = q; k < a.H; k += LPS) a.hidden[row * a.H + k] = fin[state_index(k, s, ph)];
+        if (q == 0) a.lad[row] = AFFINE ? (float)lad_wide : lad_acc;
+        if constexpr (!AFFINE) {
+            const float* fin = vecs + a.final_src * vec_floats;
+            for (int k = q; k < a.H; k += LPS) a.hidden[row * a.H + k] = fin[state_index(k, s, ph)];
+        }
     } else {
         my_status = 0;
     }
     if (my_status && a.status) atomicOr(a.status, my_status);
 }
 
-}  // namespace nfa
 
-using namespace nfa;
-
-extern "C" int nfa_made_rqs_inverse_f32(const float* inputs, const float* step_blocks, const int32_t* block_starts,
-                                        const int32_t* layout, int32_t layout_len, float* outputs,
-                                        float* logabsdet, float* hidden_out, int32_t* status, int64_t batch,
-                                        int32_t features, int32_t hidden_features, int32_t sequential_steps,
-                                        const nfa_rqs_spec* spec, void* stream) {
-    if (batch < 0 || features < 1 || hidden_features < 1 || sequential_steps < 0 || sequential_steps > features ||
-        !layout || layout_len < 8)
-        return NFA_ERR_INVALID_ARGUMENT;
-    MadeInvArgs a;
-    int rc = make_dev_spec(spec, &a.sp);
-    if (rc != NFA_OK) return rc;
-    if (a.sp.beta != 1.0f || !a.sp.linear || (a.sp.K != 8 && a.sp.K != 10)) return NFA_ERR_UNSUPPORTED;
+// the `layout` words of ops.pack_made_schedule -> `a`
+static int read_made_layout(const int32_t* layout, int32_t layout_len, int32_t hidden_features, MadeInvArgs& a) {
     // layout: [num_linears, residual, final_src, stream_vec, num_vectors, Hp, Xp, max_block,
     //          then per Linear: padded_columns, src, dst, add_stream, set_stream]
     const int n = layout[0];
@@ -357,8 +470,34 @@ extern "C" int nfa_made_rqs_inverse_f32(const float* inputs, const float* step_b
         a.final_src >= a.num_vectors || a.max_block < kMadeGrain || (a.max_block % kMadeGrain) != 0 ||
         (a.residual && (a.stream_vec < 0 || a.stream_vec >= a.num_vectors)))
         return NFA_ERR_INVALID_ARGUMENT;
+    return NFA_OK;
+}
+
+// bytes of LDS: the state of sixteen samples (the features, one vector per Linear, `extra_vectors` more) and two blocks
+static size_t made_lds_bytes(const MadeInvArgs& a, int extra_vectors) {
     const size_t px = (((size_t)a.Xp >> 2) + 15) & ~(size_t)15, ph = (((size_t)a.Hp >> 2) + 15) & ~(size_t)15;   // chunks per sample
-    const size_t lds = ((px + (size_t)a.num_vectors * ph) * 4 * kMadeSamples + 2 * (size_t)a.max_block) * sizeof(float);
+    return ((px + (size_t)(a.num_vectors + extra_vectors) * ph) * 4 * kMadeSamples + 2 * (size_t)a.max_block) * sizeof(float);
+}
+
+}  // namespace nfa
+
+using namespace nfa;
+
+extern "C" int nfa_made_rqs_inverse_f32(const float* inputs, const float* step_blocks, const int32_t* block_starts,
+                                        const int32_t* layout, int32_t layout_len, float* outputs,
+                                        float* logabsdet, float* hidden_out, int32_t* status, int64_t batch,
+                                        int32_t features, int32_t hidden_features, int32_t sequential_steps,
+                                        const nfa_rqs_spec* spec, void* stream) {
+    if (batch < 0 || features < 1 || hidden_features < 1 || sequential_steps < 0 || sequential_steps > features ||
+        !layout || layout_len < 8)
+        return NFA_ERR_INVALID_ARGUMENT;
+    MadeInvArgs a;
+    int rc = make_dev_spec(spec, &a.sp);
+    if (rc != NFA_OK) return rc;
+    if (a.sp.beta != 1.0f || !a.sp.linear || (a.sp.K != 8 && a.sp.K != 10)) return NFA_ERR_UNSUPPORTED;
+    rc = read_made_layout(layout, layout_len, hidden_features, a);
+    if (rc != NFA_OK) return rc;
+    const size_t lds = made_lds_bytes(a, 0);
     if (lds + 4096 > (size_t)kCuLds) return NFA_ERR_UNSUPPORTED;   // (+ the 2 KB of logits and alignment)
     if (batch == 0) return NFA_OK;
     if (!inputs || !step_blocks || !block_starts || !outputs || !logabsdet || !hidden_out) return NFA_ERR_INVALID_ARGUMENT;
@@ -374,15 +513,65 @@ extern "C" int nfa_made_rqs_inverse_f32(const float* inputs, const float* step_b
     a.H = hidden_features;
     a.T = sequential_steps;
     a.trace = g_k7_trace;
+    a.ctx = nullptr;
+    a.num_ctx = 0;
+    a.num_blocks = sequential_steps + 1;
+    a.group = 0;
     // 32 lanes per sample (eight waves per workgroup: two per SIMD) was built in round 4 on the theory that the step
     // is a chain of LDS round trips which a second wave on the SIMD would hide; it is slower (every lane of a sample
     // repeats the spline inversion, the DPP sum grows a ds_swizzle stage): NFA_K12_LPS=32 selects it, 16 is the default
     const int64_t blocks = (batch + kMadeSamples - 1) / kMadeSamples;
     const char* lps_env = getenv("NFA_K12_LPS");
     const int lps = lps_env && atoi(lps_env) == 32 ? 32 : 16;   // (measured: 32 is SLOWER, 2.15 vs 1.97 ms at configs[4] -- profiles/r4/k12_lanes_per_sample.txt)
-    void (*kern)(const MadeInvArgs) = a.sp.K == 8 ? (lps == 32 ? made_rqs_inverse_kernel<8, 32> : made_rqs_inverse_kernel<8, 16>)
-                                                  : (lps == 32 ? made_rqs_inverse_kernel<10, 32> : made_rqs_inverse_kernel<10, 16>);
+    void (*kern)(const MadeInvArgs) = a.sp.K == 8 ? (lps == 32 ? made_inverse_kernel<8, 32> : made_inverse_kernel<8, 16>)
+                                                  : (lps == 32 ? made_inverse_kernel<10, 32> : made_inverse_kernel<10, 16>);
     note_layer_kernel("made_rqs_inverse_kernel<K=%d, lanes_per_sample=%d>", a.sp.K, lps);
     return launch_kernel(kern, dim3((unsigned)blocks), dim3((lps / 4) * kWave), lds, (hipStream_t)stream, a,
+                         kCuLds - 4096, false);
+}
+
+// K23: AutoregressiveTransform.inverse of MaskedAffineAutoregressiveTransform, all features, context included
+extern "C" int nfa_made_affine_inverse_f32(const float* inputs, const float* context_terms, int32_t context_vectors,
+                                           const float* step_blocks, const int32_t* block_starts, int32_t num_blocks,
+                                           const int32_t* layout, int32_t layout_len, float* outputs, float* logabsdet,
+                                           int64_t batch, int32_t features, int32_t hidden_features, void* stream) {
+    if (batch < 0 || features < 1 || hidden_features < 1 || context_vectors < 0 || !layout || layout_len < 8)
+        return NFA_ERR_INVALID_ARGUMENT;
+    MadeInvArgs a = {};
+    int rc = read_made_layout(layout, layout_len, hidden_features, a);
+    if (rc != NFA_OK) return rc;
+    // one block per step at least, t = 0 .. features (the last one holds nothing); at most one context vector per Linear
+    if (a.Xp < features || num_blocks < features + 1 || context_vectors > a.num_linears) return NFA_ERR_INVALID_ARGUMENT;
+    const size_t lds = made_lds_bytes(a, context_vectors);
+    if (lds + 4096 > (size_t)kCuLds) return NFA_ERR_UNSUPPORTED;
+    if (batch == 0) return NFA_OK;
+    if (!inputs || !step_blocks || !block_starts || !outputs || !logabsdet || (context_vectors > 0 && !context_terms))
+        return NFA_ERR_INVALID_ARGUMENT;
+    const int64_t blocks = (batch + kMadeSamples - 1) / kMadeSamples;
+    if (blocks > 0x7fffffff) return NFA_ERR_UNSUPPORTED;
+    a.z = inputs;
+    a.x = outputs;
+    a.lad = logabsdet;
+    a.hidden = nullptr;
+    a.blocks = step_blocks;
+    a.block_at = block_starts;
+    a.status = nullptr;
+    a.batch = batch;
+    a.D = features;
+    a.H = hidden_features;
+    a.T = features;
+    a.trace = nullptr;
+    a.ctx = context_terms;
+    a.num_ctx = context_vectors;
+    a.num_blocks = num_blocks;
+    // units in groups of eight where a Linear has at least five units per step (hidden / (features - 1)): measured 1.2-1.3 x
+    // faster at 6.4, 8.5 and 18 units, 0.88 x and 0.70 x at 3 and 2 (profiles/maf_sample_time.json); NFA_K23_GROUP=0 / 1
+    // forces either (A/B: the same bits)
+    const char* group_env = getenv("NFA_K23_GROUP");
+    a.group = group_env && group_env[0] ? (atoi(group_env) != 0 ? 1 : 0)
+                                        : (hidden_features >= 5 * (features > 1 ? features - 1 : 1) ? 1 : 0);
+    note_layer_kernel("made_inverse_kernel<element=affine, context=%d, continuation_blocks=%d, group=%d>",
+                      context_vectors > 0 ? 1 : 0, num_blocks - (features + 1), a.group);
+    return launch_kernel(made_inverse_kernel<0, 16>, dim3((unsigned)blocks), dim3(4 * kWave), lds, (hipStream_t)stream, a,
                          kCuLds - 4096, false);
 }

@@ -1134,14 +1134,21 @@ def _standard_normal_log_prob_launch(z, logabsdet):
     return out
 
 
-def pack_made_schedule(net, sequential_steps, params_per_feature):
+def pack_made_schedule(net, sequential_steps, params_per_feature, block_cap=None, context=False):
     """Packs a MADE (transforms/made.py) for K12 (csrc/made_inverse.hip): one contiguous block per step
     t = 0 .. T holding everything the step reads -- header (16 ints: number of units of degree t, offsets of
     the unit rows / the output rows / the output biases), the unit table (8 words per unit in layer order:
     bias, unit index, padded columns, source vector (-1 = the features), destination vector (-1 = none),
     add_stream, set_stream, 0), the units' masked weight rows (zero-padded to multiples of 16 columns),
     feature t's P rows of the output layer and its P biases (t < T) -- padded to 1 KB.
-    Returns (blocks fp32, block starts int32 [T + 2] in 1 KB grains, layout list)."""
+    Returns (blocks fp32, block starts int32 [T + 2] in 1 KB grains, layout list).
+
+    K23 (the affine element, `made_affine_inverse`) asks for more through the keywords, see `_pack_made_blocks`:
+    `block_cap` (floats) cuts a step into continuation blocks, `context` names the context vector a unit adds in the unit
+    entry's last word.  Then the block starts have one entry per BLOCK (+ 2), and None is returned where one unit, or a
+    feature's output rows, do not fit a block.  Without them the result is what it always was, byte for byte."""
+    if block_cap is not None or context:
+        return _pack_made_blocks(net, int(sequential_steps), int(params_per_feature), block_cap, bool(context))
     T, P = int(sequential_steps), int(params_per_feature)
     dev = net.final_layer.weight.device
     H = net.initial_layer.weight.shape[0]
@@ -1246,6 +1253,203 @@ def made_rqs_inverse(inputs, schedule, hidden_features, sequential_steps, spec):
     N.check(rc)
     _after_spline(spec, True, dev)
     return out, lad, hidden
+
+
+# ---- K23: the inverse of MaskedAffineAutoregressiveTransform in K12's step loop (csrc/made_inverse.hip) ----------------
+
+MADE_LDS_BYTES = 160 * 1024 - 4096     # what K12 / K23 may use of a CU's LDS (csrc/made_inverse.hip)
+MADE_MAX_LINEARS = 12                  # kMadeMaxLinears
+
+
+def _made_linears(net):
+    linears = [net.initial_layer]
+    for block in net.blocks:
+        linears += list(block.linear_layers) if net.use_residual_blocks else [block.linear]
+    return linears
+
+
+def made_context_layers(net):
+    """The Linears whose result enters a MADE as a per-sample constant, in the order of K23's context vectors:
+    context_layer (made.py:274-281), then every residual block's (made.py:187-198; feed-forward blocks ignore the context)."""
+    if not hasattr(net, "context_layer"):
+        return []
+    layers = [net.context_layer]
+    if net.use_residual_blocks:
+        layers += [block.context_layer for block in net.blocks]
+    return layers
+
+
+def made_state_bytes(features, hidden_features, num_linears, context_vectors=0):
+    """LDS of K12 / K23's per-sample state: sixteen samples x (the features + one vector per Linear and per context
+    vector), every vector padded to a multiple of 64 floats."""
+    Hp = (hidden_features + 15) // 16 * 16
+    Xp = max(16, (features + 15) // 16 * 16)
+    px, ph = (Xp // 4 + 15) // 16 * 16, (Hp // 4 + 15) // 16 * 16    # 16-byte chunks per sample
+    return (px + (num_linears + context_vectors) * ph) * 4 * 16 * 4
+
+
+def made_block_cap(features, hidden_features, num_linears, context_vectors=0):
+    """Floats a step block of K23 may have: what the LDS has left beside the state and the context vectors, halved (the
+    double buffer), rounded down to the 1 KB grain.  <= 0: the state alone does not fit."""
+    left = MADE_LDS_BYTES - made_state_bytes(features, hidden_features, num_linears, context_vectors)
+    return (left // 2 // 1024) * 256 if left > 0 else 0
+
+
+def _pack_made_blocks(net, T, P, block_cap, context):
+    """`pack_made_schedule` with a block cap and context vectors, whole slices of units at a time (the units of one degree
+    are consecutive once a Linear's rows are sorted by degree).  Block header: [units, offset of the unit rows, of the
+    output rows, of the output biases, 1 = another block of this step follows]; a continuation block carries units
+    only, in layer order, and the step's last block the output rows."""
+    dev = net.final_layer.weight.device
+    H = net.initial_layer.weight.shape[0]
+    Hp = (H + 15) // 16 * 16
+    Xp = max(16, (T + 15) // 16 * 16)
+    residual = bool(net.use_residual_blocks)
+    linears = _made_linears(net)
+    n = len(linears)
+    with_context = context and hasattr(net, "context_layer")
+    HDR, GRAIN, UNIT = 16, 256, 8
+    cap = None if block_cap is None else int(block_cap)
+    per_layer, tables, sorted_rows, starts = [], [], [], []
+    for l, lin in enumerate(linears):
+        w = (lin.weight.detach() * lin.mask).float().cpu().numpy()
+        deg = lin.degrees.to(torch.int64).cpu().numpy()
+        order = np.argsort(deg, kind="stable")
+        counts = np.bincount(deg, minlength=T + 2)[:T + 2]
+        starts.append(np.concatenate(([0], np.cumsum(counts))).tolist())   # starts[d] = #units of degree < d
+        kp = Xp if l == 0 else Hp
+        if l == 0:
+            w = w[:, :min(Xp, w.shape[1])]      # features >= T meet zero masks in every hidden unit
+        rows = np.zeros((w.shape[0], kp), dtype=np.float32)
+        rows[:, :w.shape[1]] = w
+        bias = lin.bias.detach().float().cpu().numpy() if lin.bias is not None else np.zeros(w.shape[0], dtype=np.float32)
+        sorted_rows.append(rows[order])
+        is_upper = residual and l > 0 and l % 2 == 0          # second Linear of a residual block
+        dst = -1 if (residual and l == n - 1) else l          # (the residual stream itself feeds the output layer)
+        entry = [kp, l - 1, dst, 1 if is_upper else 0, 1 if residual and (l == 0 or is_upper) else 0]
+        per_layer.append(entry)
+        ctx_v = 0                                             # 1-based index into made_context_layers(net)
+        if with_context:
+            ctx_v = 1 if l == 0 else (1 + (l + 1) // 2 if residual and l % 2 == 1 else 0)
+        table = np.zeros((w.shape[0], UNIT), dtype=np.int32)
+        table[:, 0] = np.ascontiguousarray(bias[order]).view(np.int32)
+        table[:, 1] = order
+        table[:, 2:7] = entry
+        table[:, 7] = ctx_v
+        tables.append(table)
+    final = net.final_layer
+    D = final.weight.shape[0] // P
+    wf = np.zeros((T, P, Hp), dtype=np.float32)
+    wf[:, :, :H] = (final.weight.detach() * final.mask).float().cpu().numpy().reshape(D, P, H)[:T]
+    bf = final.bias.detach().float().cpu().numpy().reshape(D, P)[:T]
+    tail = P * Hp + P
+    blocks, block_at, at = [], [], 0
+
+    def emit(slices, t, continued):
+        nonlocal at
+        units = sum(u1 - u0 for _, u0, u1 in slices)
+        rows_len = sum((u1 - u0) * per_layer[l][0] for l, u0, u1 in slices)
+        header = np.zeros(HDR, dtype=np.int32)
+        header[0] = units
+        header[1] = HDR + UNIT * units                      # unit rows
+        header[2] = header[1] + rows_len                    # output rows
+        parts = [header.view(np.float32)]
+        parts += [tables[l][u0:u1].reshape(-1).view(np.float32) for l, u0, u1 in slices]
+        parts += [sorted_rows[l][u0:u1].reshape(-1) for l, u0, u1 in slices]
+        if continued:
+            header[4] = 1
+        elif t < T:
+            header[3] = header[2] + P * Hp                  # output biases
+            parts += [wf[t].reshape(-1), bf[t]]
+        size = sum(p.size for p in parts)
+        parts.append(np.zeros((-size) % GRAIN, dtype=np.float32))
+        block_at.append(at)
+        at += (size + GRAIN - 1) // GRAIN
+        blocks.append(np.concatenate(parts))
+
+    for t in range(T + 1):
+        slices, used = [], HDR
+        for l in range(n):
+            u, u1 = starts[l][t], starts[l][t + 1]
+            cost = UNIT + per_layer[l][0]
+            while u < u1:
+                fit = u1 - u if cap is None else (cap - used) // cost
+                if fit <= 0:
+                    if not slices:
+                        return None                         # one unit is more than a block may hold
+                    emit(slices, t, True)
+                    slices, used = [], HDR
+                    continue
+                k = min(fit, u1 - u)
+                slices.append((l, u, u + k))
+                used += k * cost
+                u += k
+        if cap is not None and t < T and used + tail > cap:
+            if not slices:
+                return None                                 # a feature's output rows are more than a block may hold
+            emit(slices, t, True)
+            slices = []
+        emit(slices, t, False)
+    block_at += [at, at]
+    max_block = max(b.size for b in blocks)
+    layout = [n, int(residual), n - 1, n - 1 if residual else -1, n, Hp, Xp, max_block]
+    for e in per_layer:
+        layout += e
+    return (torch.from_numpy(np.concatenate(blocks)).to(dev), torch.tensor(block_at, dtype=torch.int32, device=dev), layout)
+
+
+def pack_made_context(net):
+    """The context Linears of a MADE (`made_context_layers`) as ONE weight [C * Hp, context_features] and bias [C * Hp]:
+    vector c's rows at c * Hp, rows beyond the hidden width zero.  None for a net without a context."""
+    layers = made_context_layers(net)
+    if not layers:
+        return None
+    H, ce = layers[0].weight.shape
+    Hp = (H + 15) // 16 * 16
+    with torch.no_grad():
+        w = layers[0].weight.new_zeros(len(layers), Hp, ce, dtype=torch.float32)
+        b = layers[0].weight.new_zeros(len(layers), Hp, dtype=torch.float32)
+        for c, lin in enumerate(layers):
+            w[c, :H] = lin.weight.detach()
+            b[c, :H] = lin.bias.detach()
+    return w.view(len(layers) * Hp, ce), b.view(-1), len(layers), Hp
+
+
+def made_context_terms(context, packed):
+    """[B, C, Hp]: what the context adds to a MADE's units -- relu(context_layer(ctx)) and every residual block's
+    context_layer(ctx) -- by one GEMM and one in-place ReLU, whatever the number of features."""
+    w, b, vectors, Hp = packed
+    terms = torch.addmm(b, context.detach(), w.t()).view(context.shape[0], vectors, Hp)
+    terms[:, 0].relu_()
+    return terms
+
+
+def made_affine_inverse(inputs, schedule, hidden_features, context_terms=None):
+    """K23 -- AutoregressiveTransform.inverse of a MaskedAffineAutoregressiveTransform over a MADE in one persistent
+    kernel: (outputs [B, D], logabsdet [B]), or None outside the kernel's family (NFA_ERR_UNSUPPORTED)."""
+    N.require_device_f32("inputs", inputs, 2)
+    dev = inputs.device
+    B, D = inputs.shape
+    z = inputs.detach().contiguous()
+    out = torch.empty_like(z)
+    lad = torch.empty(B, dtype=torch.float32, device=dev)
+    floats, ints, layout = schedule
+    vectors = 0
+    if context_terms is not None:
+        N.require_device_f32("context_terms", context_terms, 3)
+        context_terms = context_terms.contiguous()
+        vectors = context_terms.shape[1]
+        if context_terms.shape[0] != B or context_terms.shape[2] != layout[5]:
+            raise ValueError("context_terms is %s, expected [%d, C, %d]" % (tuple(context_terms.shape), B, layout[5]))
+    arr = (ctypes.c_int32 * len(layout))(*layout)
+    with torch.cuda.device(dev):
+        rc = N.load().nfa_made_affine_inverse_f32(
+            N.ptr(z), N.ptr(context_terms), vectors, N.ptr(floats), N.ptr(ints), ints.numel() - 2, arr, len(layout),
+            N.ptr(out), N.ptr(lad), B, D, hidden_features, N.stream_handle(dev))
+    if rc == N.ERR_UNSUPPORTED:
+        return None
+    N.check(rc)
+    return out, lad
 
 
 _sum_workspaces = {}

@@ -310,6 +310,76 @@ class MaskedAffineAutoregressiveTransform(AutoregressiveTransform):
         out, lad = ops.affine_autoregressive(column.reshape(-1, 1), params, inverse=True)
         return out.reshape(-1), lad
 
+    # ---- persistent kernel K23 (csrc/made_inverse.hip): the whole inverse of the layer -- every feature, the context
+    #      included -- in one launch: K12's step loop with the affine element.  Its own switch, independent of K22's.
+    fuse_sequential_inverse = os.environ.get("NFA_K23", "1") != "0"
+    _INVERSE_HOOKS = ("inverse", "_elementwise_inverse", "_inverse_column", "_output_dim_multiplier")
+    # Size rule from profiles/maf_sample_time.json: the kernel does one MADE pass per sample whatever the number of
+    # features, sixteen samples per workgroup; the host loop does one pass of GEMMs per FEATURE at full-device rates.  At
+    # 262 144 rows the loop is 2.1 x faster with 8 features and 1.15 x with 16, and 1.6-3.1 x slower with 21-64; at
+    # 16 384 rows the kernel is 1.7 x faster or better for every shape.
+    _INVERSE_KERNEL_ROW_LIMIT = (16, 65536)   # (features <=, rows >): such a call takes the host loop
+
+    def _inverse_kernel_serves_rows(self, rows):
+        few, many = self._INVERSE_KERNEL_ROW_LIMIT
+        return not (self.features <= few and rows > many)
+
+    def _inverse_kernel_net(self):
+        """The MADE when K23 can run it -- plain MADE, ReLU, no batch norm, no active dropout, at most 12 Linears --, else
+        None.  The structure is read once per cache epoch; activations and dropouts are plain attributes, read per call."""
+        held = self.__dict__.get("_inverse_net_held")
+        net = self._conditioner()
+        if held is None or held[0] != _cache.epoch() or held[1] is not net:
+            ok = (type(net) is made_module.MADE and self.features >= 2
+                  and net.initial_layer.weight.shape[1] == self.features
+                  and net.final_layer.weight.shape[0] == 2 * self.features
+                  and len(ops._made_linears(net)) <= ops.MADE_MAX_LINEARS
+                  and not any(isinstance(m, torch.nn.BatchNorm1d) for m in net.modules()))
+            held = self.__dict__["_inverse_net_held"] = (_cache.epoch(), net, ok)
+        if not held[2]:
+            return None
+        relu = (F.relu, torch.relu)
+        if net.__dict__.get("activation") not in relu or not all(
+                b.__dict__.get("activation") in relu and (not b.dropout.training or b.dropout.p == 0.0) for b in net.blocks):
+            return None
+        return net
+
+    def _inverse_kernel_plan(self, net):
+        """(step blocks of `ops.pack_made_schedule` or None where the shape does not fit the LDS, packed context Linears
+        or None), kept until a parameter, a mask or a write through `.data` changes (`coupling._weights_key`)."""
+        from .coupling import _weights_key
+        key = _weights_key(self, net)
+        cached = self.__dict__.get("_made_affine_cache")
+        if cached is None or cached[0] != key:
+            hidden = net.initial_layer.weight.shape[0]
+            linears = len(ops._made_linears(net))
+            vectors = len(ops.made_context_layers(net))
+            cap = ops.made_block_cap(self.features, hidden, linears, vectors)
+            schedule = ops.pack_made_schedule(net, self.features, 2, block_cap=cap, context=True) if cap > 0 else None
+            cached = self.__dict__["_made_affine_cache"] = (key, schedule, ops.pack_made_context(net) if schedule else None)
+        return cached[1], cached[2]
+
+    def inverse(self, inputs, context=None):
+        cls = type(self)
+        if (self.fuse_sequential_inverse and not torch.is_grad_enabled() and torch.is_tensor(inputs) and inputs.dim() == 2
+                and inputs.dtype == torch.float32 and inputs.is_cuda and inputs.shape[0] >= 1
+                and inputs.shape[1] == self.features and self._inverse_kernel_serves_rows(inputs.shape[0])
+                and not any(h in self.__dict__ or getattr(cls, h) is not getattr(MaskedAffineAutoregressiveTransform, h)
+                            for h in self._INVERSE_HOOKS)):
+            net = self._inverse_kernel_net()
+            ce = self._context_features() if net is not None else 0
+            if net is not None and (
+                    (context is None and ce == 0)
+                    or (ce > 0 and torch.is_tensor(context) and context.dim() == 2 and context.dtype == torch.float32
+                        and context.is_cuda and context.shape == (inputs.shape[0], ce))):
+                schedule, packed_context = self._inverse_kernel_plan(net)
+                if schedule is not None:
+                    terms = ops.made_context_terms(context, packed_context) if ce else None
+                    fused = ops.made_affine_inverse(inputs, schedule, net.initial_layer.weight.shape[0], terms)
+                    if fused is not None:
+                        return fused
+        return super().inverse(inputs, context)
+
 
 class MaskedPiecewiseRationalQuadraticAutoregressiveTransform(AutoregressiveTransform):
     """Autoregressive neural spline layer (autoregressive.py:404-495): per feature 3K-1 / 3K+1
