@@ -46,6 +46,8 @@ extern "C" {
                               or packed layout changed, so libraries and bindings of 19 keep working with each other;
                               still 19: nfa_made_affine_inverse_f32 (K23) is an ADDED entry point, for the same reason (the two
                               words it reads in K12's step blocks were zero and unread);
+                              still 19: nfa_householder_f32, nfa_householder_backward_f32, nfa_householder_backward_slabs (K24)
+                              are ADDED entry points, for the same reason;
                               still 19: NFA_FLAG_K8X_FORM (bits 16-17, nfa_rqs_flow_resnet_f16x3_f32) is an ADDED field whose zero is
                               the behaviour of every caller of 19: an older library rejects a non-zero value as an unknown flag,
                               an older binding never sets one */
@@ -1021,6 +1023,68 @@ int nfa_lu_conv1x1_backward_f32(const float *grad_outputs, const float *lower_en
                                 const float *unconstrained_upper_diag, const int64_t *channel_perm, float *grad_inputs,
                                 int32_t *status, int64_t batch, int32_t channels, int32_t height, int32_t width,
                                 double eps, int32_t flags, void *stream);
+
+/*
+ * K24.  A stage program over the rows of a float32 [batch, features] tensor, one launch per layer call:
+ *   HouseholderSequence   transforms/orthogonal.py      SVDLinear   transforms/svd.py      QRLinear   transforms/qr.py
+ * The stages, each optional, in this order (NFA_FLAG_INVERSE selects the right-hand forms):
+ *   1  - bias                    (inverse, bias given)
+ *   2  reflect by q_first        for each vector v_k, first to last (inverse: last to first):
+ *                                t = x . v_k,  x <- x - t (c_k v_k),  c_k = 2 / (v_k . v_k)
+ *   3  triangular                x <- R x (inverse: x <- R^-1 x by substitution), upper_entries / log_upper_diag given
+ *   4  diagonal                  x <- d x (inverse: x <- x / d), unconstrained_diagonal given
+ *   5  reflect by q_second       as 2
+ *   6  + bias                    (forward, bias given)
+ * and the classes' calls:
+ *   HouseholderSequence.forward / inverse   q_first = q_vectors
+ *   SVDLinear.forward   q_first = orthogonal_2.q_vectors, diagonal, q_second = orthogonal_1.q_vectors, bias
+ *   SVDLinear.inverse   q_first = orthogonal_1.q_vectors, diagonal, q_second = orthogonal_2.q_vectors, bias
+ *   QRLinear.forward    triangular, q_second = orthogonal.q_vectors, bias
+ *   QRLinear.inverse    q_first = orthogonal.q_vectors, triangular, bias
+ *
+ *   q_first, q_second        [num_first, features], [num_second, features], or NULL with a count of 0.  A zero vector
+ *                            gives non-finite outputs (2 / 0), as the reference does; no status is raised
+ *   unconstrained_diagonal   [features] or NULL: d_i = eps + softplus(.) (F.softplus: beta 1, threshold 20)
+ *   upper_entries            [features (features-1) / 2] or NULL: R's strict upper triangle, np.triu_indices(features, 1) order
+ *   log_upper_diag           [features], given with upper_entries: R_ii = exp(.)
+ *   bias                     [features] or NULL
+ *   logabsdet                [batch] or NULL (not written); every row receives the same value, 0 without a middle stage,
+ *                            +- sum_i log d_i, +- sum_i log_upper_diag_i (added with NFA_FLAG_ACCUMULATE_LOGABSDET)
+ * c_k, d_i, R_ii and the log-determinant are evaluated in float64 and rounded once; dot products are summed in blocks
+ * of 16.  The parameters are read as the modules hold them: nothing is packed, a changed parameter is seen by the next
+ * call.  A row's result depends on that row and the parameters only (not on batch, tile or grid).
+ * NFA_ERR_INVALID_ARGUMENT: batch < 0, features < 1, a negative count, eps < 0, unknown flags, both middle stages, one of
+ * upper_entries / log_upper_diag without the other, a NULL data pointer with rows to process.
+ * NFA_ERR_UNSUPPORTED: features < 2 or > 128, a count > 128.  batch == 0 is a no-op.  All of these before any launch.
+ */
+int nfa_householder_f32(const float *inputs, const float *q_first, int32_t num_first, const float *q_second,
+                        int32_t num_second, const float *unconstrained_diagonal, const float *upper_entries,
+                        const float *log_upper_diag, const float *bias, float *outputs, float *logabsdet,
+                        int64_t batch, int32_t features, double eps, int32_t flags, void *stream);
+
+/*
+ * K24-backward, with the parameters and flags & NFA_FLAG_INVERSE of the forward call.
+ *
+ * inputs == NULL (partials NULL too): the input gradient alone -- the stages transposed, last to first: the reflections
+ * (symmetric) in the opposite order, the diagonal as it is, R^T or R^-T (lower triangular, from the transposed image).
+ *
+ * inputs != NULL (the inputs of the forward call): programs without a triangular stage.  The input gradient and, in the
+ * same pass, one slab of float64 partial sums per workgroup, partials [slabs][(num_first + num_second + 1) features],
+ * zeroed by the caller, slabs = nfa_householder_backward_slabs(batch, features, num_first, num_second):
+ *   row k of the first num_first + num_second    sum over the workgroup's rows of  b x + a g   for reflection k, where x
+ *           is the reflection's input row, g the gradient at its input side, a = x . v_k, b = (gradient at its output) . v_k;
+ *           dL/dv_k = - c_k (sum over the slabs)
+ *   last row    the diagonal stage: sum g_out x_in (forward) or sum g_in y (inverse: dL/dd_i is minus this)
+ * The caller adds the slabs in index order in float64.  The stage inputs are recomputed in the kernel (a reflection is
+ * its own inverse), not stored.  Same (batch, features, counts, device) -> same bits.  NFA_ERR_UNSUPPORTED with
+ * upper_entries: QRLinear runs its triangular step as a launch of its own on either side (nflows_amd/autograd.py).
+ */
+int nfa_householder_backward_slabs(int64_t batch, int32_t features, int32_t num_first, int32_t num_second);
+int nfa_householder_backward_f32(const float *inputs, const float *grad_outputs, const float *q_first, int32_t num_first,
+                                 const float *q_second, int32_t num_second, const float *unconstrained_diagonal,
+                                 const float *upper_entries, const float *log_upper_diag, const float *bias,
+                                 float *grad_inputs, double *partials, int64_t batch, int32_t features, double eps,
+                                 int32_t flags, void *stream);
 
 /*
  * K17.  The normalisation transforms (transforms/normalization.py: BatchNorm :72-141, ActNorm :144-218), float32

@@ -88,6 +88,9 @@ EXPORTS = (
     "nfa_lu_linear_backward_f32",
     "nfa_lu_conv1x1_f32",
     "nfa_lu_conv1x1_backward_f32",
+    "nfa_householder_f32",
+    "nfa_householder_backward_slabs",
+    "nfa_householder_backward_f32",
     "nfa_norm_workspace_bytes",
     "nfa_norm_slab_count",
     "nfa_norm_column_stats_f32",
@@ -258,6 +261,12 @@ def _declare(lib):
     lib.nfa_lu_conv1x1_f32.argtypes = [vp] * 9 + [i64, i32, i32, i32, ctypes.c_double, i32, vp]
     lib.nfa_lu_conv1x1_backward_f32.restype = ctypes.c_int
     lib.nfa_lu_conv1x1_backward_f32.argtypes = [vp] * 7 + [i64, i32, i32, i32, ctypes.c_double, i32, vp]
+    lib.nfa_householder_f32.restype = ctypes.c_int
+    lib.nfa_householder_f32.argtypes = [vp, vp, i32, vp, i32] + [vp] * 6 + [i64, i32, ctypes.c_double, i32, vp]
+    lib.nfa_householder_backward_slabs.restype = ctypes.c_int
+    lib.nfa_householder_backward_slabs.argtypes = [i64, i32, i32, i32]
+    lib.nfa_householder_backward_f32.restype = ctypes.c_int
+    lib.nfa_householder_backward_f32.argtypes = [vp, vp, vp, i32, vp, i32] + [vp] * 6 + [i64, i32, ctypes.c_double, i32, vp]
     lib.nfa_norm_workspace_bytes.restype = ctypes.c_size_t
     lib.nfa_norm_workspace_bytes.argtypes = [i64, i32]
     lib.nfa_norm_slab_count.restype = ctypes.c_int

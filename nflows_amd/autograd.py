@@ -423,6 +423,99 @@ class LUConv1x1(torch.autograd.Function):
         return tuple(grads) + (None, None, None)
 
 
+def _rows_outer_f64(g, x, chunk=1024):
+    """g^T x of two float32 [B, D] tensors in float64, [D, D].  The library's GEMM gets no parallelism out of a
+    [D, B] x [B, D] product with a small D and a long B (28 ms at 262 144 x 16, DESIGN.md section 4 "K24"), so the rows
+    go in chunks as one batched product whose [D, D] results are added up; the same shape gives the same bits."""
+    B, D = g.shape
+    full = (B // chunk) * chunk
+    total = g.new_zeros(D, D, dtype=torch.float64)
+    if full:
+        gb = g[:full].view(-1, chunk, D).to(torch.float64)
+        xb = x[:full].view(-1, chunk, D).to(torch.float64)
+        total = total + torch.bmm(gb.transpose(1, 2), xb).sum(0)
+    if full < B:
+        total = total + g[full:].to(torch.float64).t() @ x[full:].to(torch.float64)
+    return total
+
+
+class Householder(torch.autograd.Function):
+    """K24 forward + K24-backward (ops.householder).  The backward kernel gives the input gradient and, per reflection k,
+    S_k = sum_rows [b x + a g] (ops._householder_backward_launch), so dL/dv_k = - c_k S_k with c_k = 2 / (v_k . v_k) in
+    float64; the diagonal logits receive the diagonal stage's sum and the log-determinant's +- sum(grad_logabsdet) / d_i
+    through softplus'; the bias the float64 column sum of the gradient where the bias is applied.
+
+    With a triangular stage (QRLinear) the reflections' part is the same kernel on the rows next to the reflections, and
+    the triangular step is a launch of its own on either side of it:
+        forward  y = Q (R x) + b:   h = R x,  (g_h, dQ) from the kernel at (h, g_y),  g_x = R^T g_h,   dR = triu(g_h^T x)
+        inverse  x = R^-1 Q^T (y - b):   g_u = R^-T g_x,  (g_y, dQ) from the kernel at (y, g_u),       dR = -triu(g_u^T x)
+    dR is a [D, D] reduction over the batch on the device's library GEMM in float64, as LULinear's; log_upper_diag
+    receives dR_ii R_ii and +- sum(grad_logabsdet)."""
+
+    @staticmethod
+    def forward(ctx, inputs, qa, qb, diag, upper, logd, bias, eps, inverse):
+        from . import ops
+        out, lad = ops._householder_launch(inputs, (qa, qb, diag, upper, logd, bias), eps, inverse, None)
+        ctx.save_for_backward(inputs, out, qa, qb, diag, upper, logd, bias)
+        ctx.eps, ctx.inverse = eps, inverse
+        return out, lad
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out, g_lad):
+        from . import ops
+        inputs, out, qa, qb, diag, upper, logd, bias = ctx.saved_tensors
+        eps, inverse = ctx.eps, ctx.inverse
+        f64 = torch.float64
+        sign = -1.0 if inverse else 1.0
+        g_out = torch.zeros_like(inputs) if g_out is None else g_out.contiguous()
+        lad_weight = None if g_lad is None else g_lad.to(f64).sum()
+        grads = [None] * 7
+        if not any(ctx.needs_input_grad[1:7]):
+            grads[0], _ = ops._householder_backward_launch(None, g_out, (qa, qb, diag, upper, logd, bias), eps, inverse)
+            return tuple(grads) + (None, None)
+        if upper is None:
+            g_in, sums = ops._householder_backward_launch(inputs, g_out, (qa, qb, diag, None, None, bias), eps, inverse)
+            g_at_bias = g_in if inverse else g_out
+        else:
+            tri = (None, None, None, upper, logd, None)
+            if not inverse:
+                h, _ = ops._householder_launch(inputs, tri, eps, False, None, want_logabsdet=False)
+                g_h, sums = ops._householder_backward_launch(h, g_out, (qa, qb, None, None, None, None), eps, False)
+                g_in, _ = ops._householder_backward_launch(None, g_h, tri, eps, False)
+                g_r, x_r, g_at_bias = g_h, inputs, g_out
+            else:
+                g_u, _ = ops._householder_backward_launch(None, g_out, tri, eps, True)
+                g_in, sums = ops._householder_backward_launch(inputs, g_u, (qa, qb, None, None, None, bias), eps, True)
+                g_r, x_r, g_at_bias = g_u, out, g_in
+            D = inputs.shape[1]
+            d_r = sign * _rows_outer_f64(g_r, x_r)
+            rows, cols = torch.triu_indices(D, D, 1, device=inputs.device)
+            grads[4] = d_r[rows, cols].to(upper.dtype)
+            d_logd = torch.diagonal(d_r) * torch.exp(logd.to(f64))
+            if lad_weight is not None:
+                d_logd = d_logd + sign * lad_weight
+            grads[5] = d_logd.to(logd.dtype)
+        grads[0] = g_in
+        row = 0
+        for slot, q in ((1, qa), (2, qb)):
+            if q is not None:
+                q64 = q.to(f64)
+                c = 2.0 / (q64 * q64).sum(1, keepdim=True)
+                grads[slot] = (-c * sums[row:row + q.shape[0]]).to(q.dtype)
+                row += q.shape[0]
+        if diag is not None:
+            logits = diag.to(f64)
+            d = torch.nn.functional.softplus(logits) + eps
+            d_d = sign * sums[row]
+            if lad_weight is not None:
+                d_d = d_d + sign * lad_weight / d
+            grads[3] = (d_d * torch.where(logits > 20.0, torch.ones_like(logits), torch.sigmoid(logits))).to(diag.dtype)
+        if bias is not None:
+            grads[6] = (sign * g_at_bias.to(f64).sum(0)).to(bias.dtype)
+        return tuple(grads) + (None, None)
+
+
 class Nonlinearity(torch.autograd.Function):
     """K18 forward + K18-backward (ops.nonlinearity): the input gradient from the saved inputs in one launch, Sigmoid's
     temperature gradient from per-workgroup float64 partials folded in a fixed order."""

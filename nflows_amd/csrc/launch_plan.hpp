@@ -88,6 +88,53 @@ inline int64_t persistent_grid(int cus, size_t lds, int cap, int64_t tiles) {
 }
 
 // ------------------------------------------------------------------------------------------
+// K24 (householder.hip): a lane owns a row, the workgroup has R lanes (64, 128 or 256), the tile sits column-major in
+// LDS with the odd row stride R + 1.  LDS image, in floats:
+//   double logd[DP] | d[DP] | bias[DP] | c[chunk] | a[R] b[R] double cd[chunk] (backward only) | lad[4] | region |
+//   tiles x DP (R + 1)
+// DP = features rounded up to 16.  The region is shared by everything that is staged for one stage at a time: `chunk`
+// reflection vectors, or the dense [DP, DP] image of the triangular factor.  tiles = 1 (forward) or 3 (backward: the
+// rows in float64, two tiles' worth, and their gradients).
+inline int hh_region_floats(int DP, int max_transforms, bool tri, int chunk) {
+    const int k = max_transforms < chunk ? max_transforms : chunk;
+    const int r = k * DP;
+    return tri && DP * DP > r ? DP * DP : r;
+}
+inline size_t hh_lds_bytes(int DP, int region, int R, int tiles, int chunk) {
+    return (size_t)4 * (4 * DP + chunk + (tiles > 1 ? 2 * R + 2 * chunk : 0) + 4 + region + tiles * DP * (R + 1));
+}
+
+struct HhTile {
+    int R = 0;         // rows per workgroup = its lanes; 0: nothing fits
+    size_t lds = 0;
+    int64_t grid = 0;  // workgroups resident together, at most one per tile
+};
+
+// R: the most waves a CU can hold under its LDS (at most 8 workgroups, 16 waves), fewer lanes per workgroup on a tie
+// (more workgroups: their load / compute / store phases overlap), then small enough that every CU gets a tile.
+inline HhTile plan_hh_tile(int DP, int region, int tiles, int chunk, int max_R, int64_t batch, int cus) {
+    HhTile t;
+    int best = 0;
+    for (int r = max_R; r >= kWave; r >>= 1) {
+        const size_t lds = hh_lds_bytes(DP, region, r, tiles, chunk);
+        if (lds + 256 > (size_t)kCuLds) continue;
+        int blocks = (int)((size_t)kCuLds / (lds + 256));
+        if (blocks > 8) blocks = 8;
+        int waves = blocks * (r / kWave);
+        if (waves > 16) waves = 16;
+        if (waves > best || (waves == best && r < t.R)) {
+            best = waves;
+            t.R = r;
+        }
+    }
+    if (best == 0) return t;
+    while (t.R > kWave && (batch + t.R - 1) / t.R < (int64_t)cus) t.R >>= 1;
+    t.lds = hh_lds_bytes(DP, region, t.R, tiles, chunk);
+    t.grid = persistent_grid(cus, t.lds, 8, (batch + t.R - 1) / t.R);
+    return t;
+}
+
+// ------------------------------------------------------------------------------------------
 // Row sums of an elementwise map over [batch, n] rows (K18): who visits which element, and in which order a row's terms are
 // added.  A function of (batch, n) only -- not of the device --, so the same shape gives the same bits everywhere.
 //   n <= kRowSumTile  "rows": a workgroup takes `rows` whole rows, one contiguous range of rows * n <= kRowSumTile elements

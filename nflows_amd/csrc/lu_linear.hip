@@ -29,11 +29,11 @@
 // permutation is "read plane perm[c]".  logabsdet is one value per image, +- HW sum_i log U_ii (float64, rounded once),
 // written by the lane that owns the image's pixel 0.  Everything between load and store is K16's code.
 #include "common.hpp"
+#include "lu_tri.hpp"   // tri_apply, expand_tri_image, softplus_f64, kLuBlk (shared with K24)
 
 namespace nfa {
 namespace {
 
-constexpr int kLuBlk = 16;        // register block
 constexpr int kLuMaxFeatures = 128;
 
 enum LuMode { kLuForward = 0, kLuInverse = 1, kLuForwardGrad = 2, kLuInverseGrad = 3 };
@@ -61,71 +61,6 @@ struct LuArgs {
 //   double logd[DP] | float M[DP*DP] | float bias[DP] | int perm[DP] | int scatter[DP] | float lad | float tile[DP*RS]
 inline size_t lu_lds_bytes(int DP, int R) {
     return (size_t)4 * (2 * DP + DP * DP + 3 * DP + 4 + DP * (R + 1));
-}
-
-__device__ __forceinline__ double softplus_f64(double u) {
-    return u > 20.0 ? u : log1p(exp(u));   // F.softplus, beta = 1, threshold = 20
-}
-
-// v <- T v (SOLVE = false) or v <- T^-1 v (SOLVE = true) for one row, in place.  T is the UPPER or the lower triangle
-// of the LDS image M (row stride DP) with its diagonal, or a unit diagonal (UNIT).  `col` points at the lane's row in
-// the column-major tile (element j at col[j * RS]).  nb = DP / 16.
-template <bool UPPER, bool UNIT, bool SOLVE>
-__device__ __forceinline__ void tri_apply(const float* __restrict__ M, int DP, int nb, float* col, int RS) {
-    constexpr bool kAscending = (UPPER != SOLVE);   // the order in which a block's inputs are still (or already) valid
-    for (int step = 0; step < nb; ++step) {
-        const int I = kAscending ? step : nb - 1 - step;
-        float v[kLuBlk], acc[kLuBlk], o[kLuBlk];
-#pragma unroll
-        for (int i = 0; i < kLuBlk; ++i) {
-            v[i] = col[(I * kLuBlk + i) * RS];
-            acc[i] = 0.f;
-        }
-        const int j0 = UPPER ? I + 1 : 0, j1 = UPPER ? nb : I;
-        for (int J = j0; J < j1; ++J) {
-            float xj[kLuBlk];
-#pragma unroll
-            for (int j = 0; j < kLuBlk; ++j) xj[j] = col[(J * kLuBlk + j) * RS];
-            const float* Mb = M + (I * kLuBlk) * DP + J * kLuBlk;
-#pragma unroll
-            for (int i = 0; i < kLuBlk; ++i) {
-                const float4* row = reinterpret_cast<const float4*>(Mb + i * DP);
-                float p = 0.f;
-#pragma unroll
-                for (int q = 0; q < kLuBlk / 4; ++q) {
-                    const float4 m = row[q];
-                    p = (q == 0) ? m.x * xj[0] : fmaf(m.x, xj[4 * q], p);
-                    p = fmaf(m.y, xj[4 * q + 1], p);
-                    p = fmaf(m.z, xj[4 * q + 2], p);
-                    p = fmaf(m.w, xj[4 * q + 3], p);
-                }
-                acc[i] += p;
-            }
-        }
-        const float* Md = M + (I * kLuBlk) * DP + I * kLuBlk;
-        if (!SOLVE) {
-#pragma unroll
-            for (int i = 0; i < kLuBlk; ++i) {
-                float p = UNIT ? v[i] : Md[i * DP + i] * v[i];
-#pragma unroll
-                for (int j = 0; j < kLuBlk; ++j)
-                    if (UPPER ? j > i : j < i) p = fmaf(Md[i * DP + j], v[j], p);
-                o[i] = p + acc[i];
-            }
-        } else {
-#pragma unroll
-            for (int s = 0; s < kLuBlk; ++s) {
-                const int i = UPPER ? kLuBlk - 1 - s : s;
-                float t = v[i] - acc[i];
-#pragma unroll
-                for (int j = 0; j < kLuBlk; ++j)
-                    if (UPPER ? j > i : j < i) t = fmaf(-Md[i * DP + j], o[j], t);
-                o[i] = UNIT ? t : t / Md[i * DP + i];
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < kLuBlk; ++i) col[(I * kLuBlk + i) * RS] = o[i];
-    }
 }
 
 template <int MODE, bool NCHW>
@@ -165,16 +100,7 @@ __global__ void __launch_bounds__(kBlock) lu_linear_kernel(const LuArgs a) {
         s_perm[c] = p;
         s_scat[c] = s;
     }
-    for (int e = tid; e < DP * DP; e += R) {
-        const int i = (int)fastdiv((uint32_t)e, a.div_DP);
-        const int j = e - i * DP;
-        if (i == j) continue;
-        const int si = kTransposed ? j : i, sj = kTransposed ? i : j;   // the element of L / U this image element is
-        float m = 0.f;
-        if (si < D && sj < D)
-            m = si > sj ? a.lower[(si * (si - 1)) / 2 + sj] : a.upper[si * D - (si * (si + 1)) / 2 + (sj - si - 1)];
-        s_M[e] = m;
-    }
+    expand_tri_image(s_M, a.lower, a.upper, D, DP, a.div_DP, kTransposed, tid, R);
     __syncthreads();
     if (tid == 0) {   // one fixed order, whatever the grid
         double s = 0.0;

@@ -574,6 +574,94 @@ def _lu_linear_backward_launch(grad_outputs, params, eps, inverse, perm, scat):
     return g_in
 
 
+HOUSEHOLDER_PARAMS = ("q_first", "q_second", "unconstrained_diagonal", "upper_entries", "log_upper_diag", "bias")
+
+
+def householder(inputs, q_first=None, q_second=None, unconstrained_diagonal=None, upper_entries=None,
+                log_upper_diag=None, bias=None, eps=1e-3, inverse=False, accumulate_into=None):
+    """K24 -- a stage program over the rows of a float32 [B, D] tensor, 2 <= D <= 128, from the modules' own parameter
+    tensors (transforms/orthogonal.py, svd.py, qr.py); each stage optional, in this order (inverse: the right-hand forms):
+      - bias (inverse) | reflect by q_first [K, D], K <= 128 | R x or R^-1 x (upper_entries, log_upper_diag) |
+      d x or x / d, d = eps + softplus(unconstrained_diagonal) | reflect by q_second | + bias (forward)
+    A set's reflections run first to last, with `inverse` last to first.  Returns (outputs [B, D], logabsdet [B]);
+    `accumulate_into` as `lu_linear`.  Differentiable in the inputs and every parameter given (K24-backward; the
+    triangular factor's gradients on the device's GEMM in float64) when one requires grad."""
+    N.require_device_f32("inputs", inputs, 2)
+    dev = inputs.device
+    B, D = inputs.shape
+    params = (q_first, q_second, unconstrained_diagonal, upper_entries, log_upper_diag, bias)
+    for name, t in zip(HOUSEHOLDER_PARAMS, params):
+        if t is None:
+            continue
+        N.require_device_f32(name, t, 2 if name.startswith("q_") else 1)
+        if t.device != dev:
+            raise ValueError("%s is on %s, inputs on %s" % (name, t.device, dev))
+        want = D * (D - 1) // 2 if name == "upper_entries" else D
+        if t.shape[-1] != want:
+            raise ValueError("%s must have %d entries per row for %d features, got shape %s"
+                             % (name, want, D, tuple(t.shape)))
+    if (upper_entries is None) != (log_upper_diag is None):
+        raise ValueError("upper_entries and log_upper_diag are given together")
+    if upper_entries is not None and unconstrained_diagonal is not None:
+        raise ValueError("a program has a triangular or a diagonal stage, not both")
+    if AG.needs_grad(inputs, *params):
+        out, lad = AG.Householder.apply(inputs.contiguous(), *params, float(eps), bool(inverse))
+        if accumulate_into is not None:
+            accumulate_into += lad
+            lad = accumulate_into
+        return out, lad
+    return _householder_launch(inputs, params, float(eps), inverse, accumulate_into)
+
+
+def _householder_pointers(params):
+    """The six parameter arguments of the C entry points (contiguous detached tensors, kept alive by the caller)."""
+    held = [None if t is None else t.detach().contiguous() for t in params]
+    qa, qb, diag, upper, logd, bias = held
+    args = (N.ptr(qa), 0 if qa is None else qa.shape[0], N.ptr(qb), 0 if qb is None else qb.shape[0], N.ptr(diag),
+            N.ptr(upper), N.ptr(logd), N.ptr(bias))
+    return held, args
+
+
+def _householder_launch(inputs, params, eps, inverse, accumulate_into, want_logabsdet=True):
+    dev = inputs.device
+    B, D = inputs.shape
+    x = inputs.detach().contiguous()
+    held, args = _householder_pointers(params)
+    out = torch.empty_like(x)
+    lad, flags = _lad_buffer(accumulate_into, B, dev, inverse) if want_logabsdet else (None, N.FLAG_INVERSE if inverse else 0)
+    hook = _launch_hook
+    with torch.cuda.device(dev):
+        token = hook.begin("householder") if hook is not None else None
+        rc = N.load().nfa_householder_f32(N.ptr(x), *args, N.ptr(out), N.ptr(lad), B, D, eps, flags, N.stream_handle(dev))
+        if hook is not None:
+            hook.end(token, 4 * (2 * B * D + B))
+    N.check(rc)   # (a shape the kernel does not serve is an error here: the classes route those to their generic path)
+    return out, lad
+
+
+def _householder_backward_launch(inputs, grad_outputs, params, eps, inverse):
+    """K24-backward.  inputs None: the input gradient alone (any program).  Otherwise (programs without a triangular
+    stage) also the float64 sums over the batch, [num_first + num_second + 1, D]: the slabs of the workgroups added
+    up by one float64 device reduction over a fixed shape (the same bits on every run)."""
+    dev = grad_outputs.device
+    B, D = grad_outputs.shape
+    g = grad_outputs.detach().contiguous()
+    held, args = _householder_pointers(params)
+    g_in = torch.empty_like(g)
+    x = partials = None
+    lib = N.load()
+    with torch.cuda.device(dev):
+        if inputs is not None:
+            x = inputs.detach().contiguous()
+            rows = args[1] + args[3] + 1
+            slabs = lib.nfa_householder_backward_slabs(B, D, args[1], args[3])
+            partials = torch.zeros(max(slabs, 1), rows, D, dtype=torch.float64, device=dev)
+        rc = lib.nfa_householder_backward_f32(N.ptr(x), N.ptr(g), *args, N.ptr(g_in), N.ptr(partials), B, D, eps,
+                                              N.FLAG_INVERSE if inverse else 0, N.stream_handle(dev))
+    N.check(rc)
+    return g_in, (None if partials is None else partials.sum(0))
+
+
 def lu_conv1x1(inputs, lower_entries, upper_entries, unconstrained_upper_diag, bias, eps=1e-3, inverse=False,
                channel_perm=None, accumulate_into=None):
     """K19 -- the invertible 1x1 convolution (transforms/conv.py): K16's layer over the channels of a float32

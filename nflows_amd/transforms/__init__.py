@@ -6,8 +6,11 @@ from .coupling import (AdditiveCouplingTransform, AffineCouplingTransform, Coupl
                        PiecewiseQuadraticCouplingTransform,
                        PiecewiseRationalQuadraticCouplingTransform)
 from .permutations import Permutation, RandomPermutation, ReversePermutation
-from .linear import Linear
+from .linear import Linear, NaiveLinear
 from .lu import LULinear
+from .orthogonal import HouseholderSequence
+from .svd import SVDLinear
+from .qr import QRLinear
 from .conv import OneByOneConvolution
 from .reshape import SqueezeTransform
 from .normalization import ActNorm, BatchNorm

@@ -5,11 +5,18 @@ API of nflows/transforms/linear.py: `Linear(features, using_cache=False)` owns `
 training mode; subclasses provide `forward_no_cache` / `inverse_no_cache`, `weight()`, `weight_inverse()` and
 `logabsdet()`.  The cached path multiplies by the cached matrices with the device's GEMM; a subclass with a kernel of
 its own (LULinear) overrides `forward` / `inverse`.
+
+`NaiveLinear(features, orthogonal_initialization=True, using_cache=False)` holds the weight matrix itself (`_weight`) and
+runs on stock device ops: `F.linear` going forward, an LU factorisation with `lu_solve` going back (both in float64,
+rounded once), the log-determinant from the factor's diagonal.  It has no kernel of its own: a dense [B, D] x [D, D] float32 product is the vendor
+library's ground (DESIGN.md section 4, K16's timings).
 """
+import numpy as np
 import torch
 from torch import nn
 from torch.nn import functional as F
 
+from ..utils import torchutils
 from ..utils import typechecks as check
 from .base import Transform
 
@@ -121,3 +128,46 @@ class Linear(Transform):
 
     def logabsdet(self):
         raise NotImplementedError()
+
+
+class NaiveLinear(Linear):
+    """y = W x + b with an unconstrained W: O(D^3) per call for the determinant or the factorisation."""
+
+    def __init__(self, features, orthogonal_initialization=True, using_cache=False):
+        super().__init__(features, using_cache)
+        if orthogonal_initialization:
+            self._weight = nn.Parameter(torchutils.random_orthogonal(features))
+        else:
+            bound = 1.0 / np.sqrt(features)
+            self._weight = nn.Parameter(torch.empty(features, features).uniform_(-bound, bound))
+
+    def _factor(self):
+        """(LU, pivots, log |det W|) from one factorisation, in float64: the factor serves every row of a call and the
+        determinant is one number, so nothing averages a float32 factorisation's error out; results are rounded once."""
+        lu, pivots = torch.linalg.lu_factor(self._weight.double())
+        return lu, pivots, torch.sum(torch.log(torch.abs(torch.diagonal(lu)))).to(self._weight.dtype)
+
+    def forward_no_cache(self, inputs):
+        _require_device(inputs)
+        outputs = F.linear(inputs, self._weight, self.bias)
+        return outputs, self.logabsdet() * outputs.new_ones(inputs.shape[0])
+
+    def inverse_no_cache(self, inputs):
+        _require_device(inputs)
+        lu, pivots, logabsdet = self._factor()
+        outputs = torch.linalg.lu_solve(lu, pivots, (inputs - self.bias).double().t()).t().to(inputs.dtype)
+        return outputs, (-logabsdet) * outputs.new_ones(inputs.shape[0])
+
+    def weight(self):
+        return self._weight
+
+    def weight_inverse(self):
+        return torch.inverse(self._weight.double()).to(self._weight.dtype)
+
+    def weight_inverse_and_logabsdet(self):
+        lu, pivots, logabsdet = self._factor()
+        identity = torch.eye(self.features, dtype=self._weight.dtype, device=self._weight.device)
+        return torch.linalg.lu_solve(lu, pivots, identity.double()).to(self._weight.dtype), logabsdet
+
+    def logabsdet(self):
+        return torchutils.logabsdet(self._weight.double()).to(self._weight.dtype)

@@ -40,6 +40,16 @@ def repeat_rows(x, num_reps):
     return torch.repeat_interleave(x, num_reps, dim=0)
 
 
+def logabsdet(x):
+    """log |det x| of a square matrix (torch.logdet serves positive determinants only)."""
+    return torch.linalg.slogdet(x)[1]
+
+
+def random_orthogonal(size):
+    """A random orthogonal [size, size] matrix: the Q factor of a standard normal matrix."""
+    return torch.linalg.qr(torch.randn(size, size))[0]
+
+
 def create_alternating_binary_mask(features, even=True):
     """uint8 mask 1,0,1,0,... (even=True) or 0,1,0,1,... (torchutils.py:89-100)."""
     mask = torch.zeros(features, dtype=torch.uint8)
