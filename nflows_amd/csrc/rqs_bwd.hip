@@ -14,8 +14,8 @@
 // Reverse mode through that expression gives adjoints of (x, a, b, c, e, d0, d1); knots are affine
 // in the prefix sums of min + (1-min K) softmax(logits / sqrt(H)) (:91-98), derivatives are
 // min_d + softplus(logit) (:104), so the adjoints of the 3K-1 (3K+1) logits follow in closed form.
-// The inverse direction (x = f^-1(y), lad = -log f'(x)) uses the same partials at the solution x
-// through the implicit-function theorem.
+// The inverse direction (x = f^-1(y), lad = -log f'(x)) differentiates the root th of the bin's quadratic
+// implicitly in (y - c, h, delta, d0, d1): `inverse_map_adjoint`.
 //
 // Same tile scheme as the generic forward kernel: R whole samples per workgroup, conditioner
 // output staged through LDS with 16-byte accesses; each lane overwrites its own P logits in LDS
@@ -103,20 +103,53 @@ __device__ __forceinline__ BinAdj forward_map_adjoint(float x, float a, float b,
     return g;
 }
 
-// d lad / d x of the forward map (needed by the inverse direction before the full adjoint)
-__device__ __forceinline__ float forward_lad_dx(float x, float a, float b, float c, float e, float d0, float d1) {
-    const float w = b - a, h = e - c;
-    const float rw = 1.0f / w;
-    const float delta = h * rw;
-    const float th = (x - a) * rw;
+// Adjoints of (a, b, c, e, d0, d1) and of the layer input y (returned in .x) for upstream (gout, gl) on the outputs of
+// the INVERSE map, xs = a + w th and lad = -L, at the root th of  c + h B(th; delta, d0, d1) = y:
+//     B = (delta th^2 + d0 t) / (delta + s t),    L = 2 log delta + log A - 2 log(delta + s t)
+// B and L depend on the knots through delta = h / w alone, so th is differentiated implicitly in (y - c, h, delta, d0, d1)
+//     d th = (d(y - c) - B dh - h (B_delta d delta + B_d0 d d0 + B_d1 d d1)) / (h B_th)
+// and a, w enter once more through xs.  (Differentiating f(x; a, b, ..) = y at fixed x instead, with the forward map's
+// partials, is the same in exact arithmetic; but at fixed x the partials of L with respect to a and b carry L_th / w,
+// which the term (gl L_x / f') f_a has to cancel: where the log-derivative is steep -- d lad / d x of several hundred --
+// the width-logit gradients came out of a difference of two numbers 1e3 times their size, up to 0.6 off on a scale of
+// 10 where the reference's own fp32 is within 3e-4.)
+__device__ __forceinline__ BinAdj inverse_map_adjoint(float th, float w, float h, float delta, float s, float d0,
+                                                      float d1, float gout, float gl) {
     const float omt = 1.0f - th;
     const float t = th * omt;
-    const float s = d0 + d1 - 2.0f * delta;
+    const float tp = 1.0f - 2.0f * th;
     const float den = delta + s * t;
+    const float rden = 1.0f / den;
+    const float B = (delta * th * th + d0 * t) * rden;
     const float A = d1 * th * th + 2.0f * delta * t + d0 * omt * omt;
-    const float dA = 2.0f * d1 * th - 2.0f * d0 * omt + 2.0f * delta * (1.0f - 2.0f * th);
-    const float dden = s * (1.0f - 2.0f * th);
-    return (dA / A - 2.0f * dden / den) * rw;
+    const float rA = 1.0f / A;
+    const float den_th = s * tp, den_dl = 1.0f - 2.0f * t;
+    const float B_th = ((2.0f * delta * th + d0 * tp) - B * den_th) * rden;
+    const float B_dl = (th * th - B * den_dl) * rden;
+    const float B_d0 = (t - B * t) * rden;
+    const float B_d1 = (-B * t) * rden;
+    const float L_th = (2.0f * d1 * th - 2.0f * d0 * omt + 2.0f * delta * tp) * rA - 2.0f * den_th * rden;
+    const float L_dl = 2.0f / delta + 2.0f * t * rA - 2.0f * den_dl * rden;
+    const float L_d0 = omt * omt * rA - 2.0f * t * rden;
+    const float L_d1 = th * th * rA - 2.0f * t * rden;
+
+    BinAdj g;
+    const float th_b = gout * w - gl * L_th;
+    const float lam = th_b / (h * B_th);  // adjoint of (y - c)
+    g.x = lam;
+    float h_b = -lam * B;
+    const float delta_b = -lam * h * B_dl - gl * L_dl;
+    g.d0 = -lam * h * B_d0 - gl * L_d0;
+    g.d1 = -lam * h * B_d1 - gl * L_d1;
+    float w_b = gout * th;
+    const float rw = 1.0f / w;
+    h_b += delta_b * rw;
+    w_b -= delta_b * delta * rw;
+    g.a = gout - w_b;
+    g.b = w_b;
+    g.e = h_b;
+    g.c = -lam - h_b;
+    return g;
 }
 
 __device__ __forceinline__ float sigmoid_beta(float u, float beta) {
@@ -195,16 +228,9 @@ __device__ __forceinline__ float rqs_backward(float x, float* sl, const RqsDev& 
         const float disc = qb * qb - (4.0f * qa) * qc;
         if (!(disc >= 0.0f)) status |= NFA_STATUS_NEG_DISCRIMINANT;
         const float root = (2.0f * qc) / ((-qb) - sqrtf(disc));
-        const float xs = root * in_w + cw0;
-        // f'(xs) = exp(lad_fwd(xs))
-        const float t1 = root * (1.0f - root), omr = 1.0f - root;
-        const float den = delta + s * t1;
-        const float fprime = (delta * delta) * ((d1 * root * root + 2.0f * delta * t1) + d0 * omr * omr) / (den * den);
-        // outputs: xs (adjoint g_out) and lad_inv = -log f'(xs) (adjoint gl)
-        const float Lx = forward_lad_dx(xs, cw0, cw1, ch0, ch1, d0, d1);
-        const float xbar = g_out - gl * Lx;
-        g_in = xbar / fprime;
-        g = forward_map_adjoint(xs, cw0, cw1, ch0, ch1, d0, d1, -g_in, -gl);
+        // outputs: xs = cw0 + in_w root (adjoint g_out) and lad_inv = -log f'(xs) (adjoint gl)
+        g = inverse_map_adjoint(root, in_w, in_h, delta, s, d0, d1, g_out, gl);
+        g_in = g.x;
     }
 
     // ---- knots -> logits.  p_j = softmax numerators / denominator (ew, eh hold the numerators)

@@ -265,6 +265,14 @@ def assert_gradient_rows(got, truth, cond, keep, cap, outside=None, gy=None, tol
     return share
 
 
+def close_to_truth(got, ref32, ref64, what, tol=2e-5):
+    got = got.detach().cpu().numpy().astype(np.float64)
+    scale = 1.0 + np.abs(ref64).max()
+    e_got = np.abs(got - ref64).max()
+    e_ref = np.abs(ref32.astype(np.float64) - ref64).max()
+    assert e_got <= 4 * e_ref + tol * scale, "%s: err %.3e (reference fp32 %.3e, scale %.2e)" % (what, e_got, e_ref, scale)
+
+
 def eager_oracle(flow_cpu, x, noise=None, context=None, fp64_device=None):
     """The two evaluations every whole-flow parity test needs, both through oracle/eager.py (the op-for-op PyTorch port of
     the reference's path; tests/test_oracle_golden.py pins it bit for bit to the real reference on the CPU):

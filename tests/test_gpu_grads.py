@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import parse_kwargs
+from helpers import close_to_truth, parse_kwargs
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -18,14 +18,6 @@ DEV = "cuda:0"
 
 def dev(a):
     return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def close_to_truth(got, ref32, ref64, what, tol=2e-5):
-    got = got.detach().cpu().numpy().astype(np.float64)
-    scale = 1.0 + np.abs(ref64).max()
-    e_got = np.abs(got - ref64).max()
-    e_ref = np.abs(ref32.astype(np.float64) - ref64).max()
-    assert e_got <= 4 * e_ref + tol * scale, "%s: err %.3e (reference fp32 %.3e, scale %.2e)" % (what, e_got, e_ref, scale)
 
 
 @pytest.fixture(scope="module")

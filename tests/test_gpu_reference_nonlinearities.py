@@ -1,6 +1,7 @@
 """The scenarios of the reference's tests/transforms/nonlinearities_test.py for the elementwise nonlinearities, restated against
 the drop-in classes on the device (in the manner of tests/test_gpu_reference_suite.py): same scenarios, sizes and tolerances,
-cited by file:line.  (Its piecewise-CDF classes, :33-91, are covered by tests/test_gpu_reference_suite.py.)"""
+cited by file:line.  (Its piecewise-CDF classes, :33-91, are restated in tests/test_gpu_cdf_shared.py: `test_raises_domain_exception`
+and `test_reference_scenarios`, for all four classes.)"""
 import pytest
 import torch
 
