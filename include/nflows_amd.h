@@ -851,6 +851,20 @@ int nfa_pack_resnet_hidden_train_f32(const float *initial_weight, const float *i
                                      int32_t hidden_features, int32_t num_blocks, void *forward_stages,
                                      float *forward_bias, float *final_bias_packed, void *backward_stages,
                                      void *stream);
+/* K25.  The same packer for a MADE with residual blocks (made.py: the same network with 0/1 masks multiplied into the
+ * weights): every weight element is multiplied by its mask before the bf16 split, so the streams are the bytes of
+ * nfa_pack_resnet_hidden_train_f32 on the products mask * weight.  masks: HOST array of 2 + 2 num_blocks device
+ * pointers -- the masks of W_in, of (W_0, W_1) per block and of W_f, fp32 in their weight's shape, each entry NULL for
+ * a Linear without one; masks == NULL: no masks at all.  initial_weight (and its mask) is [H, features] with
+ * features <= num_identity, final_weight [out_rows, H] and final_bias [out_rows] with out_rows <= out_features: the
+ * streams are laid out for num_identity identity columns and out_features outputs (both multiples of 4, what the two
+ * kernels take) and hold zeros past the arrays' own extents, so odd feature counts need no padded copies of the
+ * weights.  Added under ABI 19 (see NFA_ABI_VERSION): no existing entry point, flag set or packed layout changes. */
+int nfa_pack_made_train_f32(const float *initial_weight, const float *initial_bias, const float *const *block_params,
+                            const float *final_weight, const float *final_bias, const float *const *masks,
+                            int32_t features, int32_t out_rows, int32_t out_features, int32_t num_identity,
+                            int32_t hidden_features, int32_t num_blocks, void *forward_stages, float *forward_bias,
+                            float *final_bias_packed, void *backward_stages, void *stream);
 int nfa_resnet_hidden_forward_f32(const float *identity_inputs, const void *weights_packed,
                                   const float *bias_packed, float *saved, float *hidden,
                                   const float *final_bias_packed, float *params, int32_t out_features, int64_t batch,
@@ -940,6 +954,16 @@ int nfa_affine_coupling_f32(const float *inputs, const float *params, const floa
 int nfa_affine_autoregressive_f32(const float *inputs, const float *params, float *outputs,
                                   float *logabsdet, int64_t batch, int32_t features,
                                   int32_t inverse, void *stream);
+/* K25.  Its backward pass in one launch: given grad_outputs [batch, features] and grad_logabsdet [batch] (either may
+ * be NULL: zeros), writes grad_inputs [batch, features] and grad_params [batch, features, 2].  With s = softplus(u) +
+ * 1e-3 and ds = sigmoid(u) (exactly 1 where softplus returns u, u > 20) -- forward: g_x = g_y s, g_shift = g_y,
+ * g_u = (g_y x + g_l / s) ds; inverse: g_x = g_y / s, g_shift = -g_x, g_u = (-g_x out - g_l / s) ds.  `inputs` is read
+ * in the forward direction only, `outputs` (what nfa_affine_autoregressive_f32 produced) in the inverse direction
+ * only; the other may be NULL.  Deterministic (no reduction).  Added under ABI 19. */
+int nfa_affine_autoregressive_backward_f32(const float *inputs, const float *params, const float *outputs,
+                                           const float *grad_outputs, const float *grad_logabsdet,
+                                           float *grad_inputs, float *grad_params, int64_t batch, int32_t features,
+                                           int32_t inverse, void *stream);
 
 /*
  * K4.  Column permutation, bit-exact for any 4-byte element type:

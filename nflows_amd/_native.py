@@ -58,6 +58,7 @@ EXPORTS = (
     "nfa_made_affine_inverse_f32",
     "nfa_rqs_made_output_f32",
     "nfa_pack_resnet_hidden_train_f32",
+    "nfa_pack_made_train_f32",
     "nfa_resnet_hidden_forward_f32",
     "nfa_resnet_hidden_backward_f32",
     "nfa_resnet_backward_f32",
@@ -83,6 +84,7 @@ EXPORTS = (
     "nfa_rqs_shared_f32",
     "nfa_affine_coupling_f32",
     "nfa_affine_autoregressive_f32",
+    "nfa_affine_autoregressive_backward_f32",
     "nfa_permute_cols_b32",
     "nfa_lu_linear_f32",
     "nfa_lu_linear_backward_f32",
@@ -196,6 +198,8 @@ def _declare(lib):
     lib.nfa_pack_resnet_hidden_train_f32.restype = ctypes.c_int
     lib.nfa_pack_resnet_hidden_train_f32.argtypes = [vp, vp, ctypes.POINTER(vp), vp, vp, i32, i32, i32, i32, vp, vp, vp,
                                                      vp, vp]
+    lib.nfa_pack_made_train_f32.restype = ctypes.c_int
+    lib.nfa_pack_made_train_f32.argtypes = [vp, vp, ctypes.POINTER(vp), vp, vp, ctypes.POINTER(vp)] + [i32] * 6 + [vp] * 5
     lib.nfa_resnet_hidden_forward_f32.restype = ctypes.c_int
     lib.nfa_resnet_hidden_forward_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i64, i32, i32, i32, vp]
     lib.nfa_resnet_hidden_backward_f32.restype = ctypes.c_int
@@ -251,6 +255,8 @@ def _declare(lib):
     lib.nfa_affine_coupling_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp]
     lib.nfa_affine_autoregressive_f32.restype = ctypes.c_int
     lib.nfa_affine_autoregressive_f32.argtypes = [vp, vp, vp, vp, i64, i32, i32, vp]
+    lib.nfa_affine_autoregressive_backward_f32.restype = ctypes.c_int
+    lib.nfa_affine_autoregressive_backward_f32.argtypes = [vp] * 7 + [i64, i32, i32, vp]
     lib.nfa_permute_cols_b32.restype = ctypes.c_int
     lib.nfa_permute_cols_b32.argtypes = [vp, vp, vp, vp, i64, i32, vp]
     lib.nfa_lu_linear_f32.restype = ctypes.c_int

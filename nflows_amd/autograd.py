@@ -4,8 +4,8 @@ The reference is trained by autograd through eager ops (`loss = -flow.log_prob(x
 loss.backward()`, examples/moons.ipynb cell 3).  These `torch.autograd.Function`s make the same
 call pattern work on the fused kernels: forward = the forward kernel, backward = ONE HIP kernel
 for the spline layers (`nfa_rqs_coupling_backward_f32`, which recomputes the layer from its
-inputs) and a few elementwise device ops for the cheap affine layers.  Everything stays on the
-GPU; there is no CPU path here either.
+inputs) and for the affine autoregressive element (K25), a few elementwise device ops for the affine
+coupling layer.  Everything stays on the GPU; there is no CPU path here either.
 """
 import ctypes
 
@@ -216,34 +216,27 @@ class AffineCoupling(torch.autograd.Function):
 
 
 class AffineAutoregressive(torch.autograd.Function):
-    """K2b forward; elementwise device ops backward (params interleaved [B, D, 2])."""
+    """K2b forward; K25's element kernel backward (`nfa_affine_autoregressive_backward_f32`: one launch, params
+    interleaved [B, D, 2])."""
 
     @staticmethod
     def forward(ctx, inputs, params, inverse):
         from . import ops
         out, lad = ops._affine_autoregressive_launch(inputs, params, inverse)
-        ctx.save_for_backward(inputs, params, out)
         ctx.inverse = bool(inverse)
+        ctx.save_for_backward(out if ctx.inverse else inputs, params)   # (what the backward kernel reads)
+        ctx.set_materialize_grads(False)   # an unused output's gradient arrives as None: the kernel's null pointer
         return out, lad
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g_out, g_lad):
-        inputs, params, out = ctx.saved_tensors
-        B, D = inputs.shape
-        p = params.reshape(B, D, 2)
-        s, ds = _scale_and_grad(p[..., 0], N.SCALE_SOFTPLUS)
-        g_out = torch.zeros_like(inputs) if g_out is None else g_out
-        gl = (torch.zeros(B, device=inputs.device) if g_lad is None else g_lad)[:, None]
-        if not ctx.inverse:
-            g_in = g_out * s
-            g_shift = g_out
-            g_s = g_out * inputs + gl / s
-        else:
-            g_in = g_out / s
-            g_shift = -g_in
-            g_s = -g_in * out - gl / s
-        g_params = torch.stack((g_s * ds, g_shift), dim=-1).reshape(params.shape)
+        from . import ops
+        if g_out is None and g_lad is None:
+            return None, None, None
+        seen, params = ctx.saved_tensors
+        g_in, g_params = ops.affine_autoregressive_backward(None if ctx.inverse else seen, params,
+                                                            seen if ctx.inverse else None, g_out, g_lad, ctx.inverse)
         return g_in, g_params, None
 
 
@@ -725,66 +718,123 @@ class ResidualNetHidden(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, g_out):
-        from . import ops
-        nb, H = ctx.nb, ctx.H
-        need = ctx.needs_input_grad[2:]   # per parameter
-        g_out = g_out.contiguous()
+        return _resnet_hidden_backward(ctx, g_out, ctx.saved_tensors)
 
-        def wgrad(inputs, grad_outputs, need_w, need_b, rows=None, cols=None):
-            """(grad_weight, grad_bias) of a Linear; rows / cols: the net's own width inside the 128-wide arrays"""
-            if not (need_w or need_b):
-                return None, None
-            got = ops.linear_wgrad(inputs, grad_outputs, need_bias=need_b)
-            if got is None:   # widths K10 does not take
-                got = (grad_outputs.t() @ inputs if need_w else None), (grad_outputs.sum(0) if need_b else None)
-            g_w, g_b = (got[0] if need_w else None), got[1]
-            if g_w is not None and (rows is not None or cols is not None):
-                g_w = g_w[:rows, :cols].contiguous()
-            if g_b is not None and rows is not None:
-                g_b = g_b[:rows].contiguous()
-            return g_w, g_b
 
-        narrow = H if H != 128 else None
-        tail = ()
-        fused = None
-        if ctx.with_final:
-            x, saved, bwd_w, hidden, w_f = ctx.saved_tensors
-            tail = wgrad(hidden, g_out, need[-2], need[-1], cols=narrow)
-            # the final Linear's input gradient inside the backward kernel (round 4; its W_f^T stages are in `bwd_w`)
-            if ops.FUSED_FINAL_DGRAD:
-                fused = ops.resnet_backward(g_out, bwd_w, saved, x.shape[1])
-            if fused is None:
-                g_hidden = g_out @ w_f        # ... or one library GEMM
-        else:
-            x, saved, bwd_w = ctx.saved_tensors
-            g_hidden = g_out
-        if fused is not None:
-            g_x, grads, g_hidden = fused      # (g_hidden [B, 128]: zero columns past a narrower net's width)
-        else:
+def _resnet_hidden_backward(ctx, g_out, saved_tensors):
+    """K14's backward pass for ResidualNetHidden and MadeNet: (grad of x, None, then one gradient per parameter).
+    `saved_tensors`: (x, saved, bwd_w) or, with the final Linear, (x, saved, bwd_w, hidden, W_f -- or a function
+    that returns it, called only where the backward kernel does not take the width)."""
+    from . import ops
+    nb, H = ctx.nb, ctx.H
+    need = ctx.needs_input_grad[2:]   # per parameter
+    g_out = g_out.contiguous()
+
+    def wgrad(inputs, grad_outputs, need_w, need_b, rows=None, cols=None):
+        """(grad_weight, grad_bias) of a Linear; rows / cols: the net's own width inside the 128-wide arrays"""
+        if not (need_w or need_b):
+            return None, None
+        got = ops.linear_wgrad(inputs, grad_outputs, need_bias=need_b)
+        if got is None:   # widths K10 does not take
+            got = (grad_outputs.t() @ inputs if need_w else None), (grad_outputs.sum(0) if need_b else None)
+        g_w, g_b = (got[0] if need_w else None), got[1]
+        if g_w is not None and (rows is not None or cols is not None):
+            g_w = g_w[:rows, :cols].contiguous()
+        if g_b is not None and rows is not None:
+            g_b = g_b[:rows].contiguous()
+        return g_w, g_b
+
+    narrow = H if H != 128 else None
+    tail = ()
+    fused = None
+    if ctx.with_final:
+        x, saved, bwd_w, hidden, w_f = saved_tensors
+        tail = wgrad(hidden, g_out, need[-2], need[-1], cols=narrow)
+        # the final Linear's input gradient inside the backward kernel (round 4; its W_f^T stages are in `bwd_w`)
+        if ops.FUSED_FINAL_DGRAD:
+            fused = ops.resnet_backward(g_out, bwd_w, saved, x.shape[1])
+        if fused is None:
+            g_hidden = g_out @ (w_f() if callable(w_f) else w_f)        # ... or one library GEMM
+    else:
+        x, saved, bwd_w = saved_tensors
+        g_hidden = g_out
+    if fused is not None:
+        g_x, grads, g_hidden = fused      # (g_hidden [B, 128]: zero columns past a narrower net's width)
+    else:
+        if narrow is not None:
+            g_hidden = torch.nn.functional.pad(g_hidden, (0, 128 - H))
+        g_x, grads = ops.resnet_hidden_backward(g_hidden, bwd_w, saved, x.shape[1])
+    di = ctx.di if ctx.di != x.shape[1] else None      # (x was saved with its pad columns)
+    out = [(g_x if di is None else g_x[:, :di]) if ctx.needs_input_grad[0] else None, None]
+    out += wgrad(x, grads[0] if nb else g_hidden, need[0], need[1], rows=narrow, cols=di)
+    # the 2 nb hidden Linears (all 128 -> 128 inside the padded arrays): ONE launch pair of K10 when every gradient
+    # is wanted (a training step), layer by layer otherwise
+    hidden_problems = []
+    for k in range(nb):
+        hidden_problems.append((saved[2 * k], grads[2 * k + 1]))
+        hidden_problems.append((saved[2 * k + 1], grads[2 * k + 2] if k + 1 < nb else g_hidden))
+    batched = None
+    if nb and all(need[2:2 + 4 * nb]) and 2 * nb <= 8 and BATCHED_WGRAD:
+        batched = ops.linear_wgrad_batched(hidden_problems, need_bias=True)
+    if batched is not None:
+        for g_w, g_b in batched:
             if narrow is not None:
-                g_hidden = torch.nn.functional.pad(g_hidden, (0, 128 - H))
-            g_x, grads = ops.resnet_hidden_backward(g_hidden, bwd_w, saved, x.shape[1])
-        di = ctx.di if ctx.di != x.shape[1] else None      # (x was saved with its pad columns)
-        out = [(g_x if di is None else g_x[:, :di]) if ctx.needs_input_grad[0] else None, None]
-        out += wgrad(x, grads[0] if nb else g_hidden, need[0], need[1], rows=narrow, cols=di)
-        # the 2 nb hidden Linears (all 128 -> 128 inside the padded arrays): ONE launch pair of K10 when every gradient
-        # is wanted (a training step), layer by layer otherwise
-        hidden_problems = []
-        for k in range(nb):
-            hidden_problems.append((saved[2 * k], grads[2 * k + 1]))
-            hidden_problems.append((saved[2 * k + 1], grads[2 * k + 2] if k + 1 < nb else g_hidden))
-        batched = None
-        if nb and all(need[2:2 + 4 * nb]) and 2 * nb <= 8 and BATCHED_WGRAD:
-            batched = ops.linear_wgrad_batched(hidden_problems, need_bias=True)
-        if batched is not None:
-            for g_w, g_b in batched:
-                if narrow is not None:
-                    g_w, g_b = g_w[:narrow, :narrow].contiguous(), g_b[:narrow].contiguous()
-                out += (g_w, g_b)
-        else:
-            for q, (inp, g_o) in enumerate(hidden_problems):
-                out += wgrad(inp, g_o, need[2 + 2 * q], need[3 + 2 * q], rows=narrow, cols=narrow)
-        return tuple(out) + tuple(tail)
+                g_w, g_b = g_w[:narrow, :narrow].contiguous(), g_b[:narrow].contiguous()
+            out += (g_w, g_b)
+    else:
+        for q, (inp, g_o) in enumerate(hidden_problems):
+            out += wgrad(inp, g_o, need[2 + 2 * q], need[3 + 2 * q], rows=narrow, cols=narrow)
+    return tuple(out) + tuple(tail)
+
+
+class MadeNet(torch.autograd.Function):
+    """K25: a MADE with residual blocks and no context (made.py: initial masked Linear, `h += L1(relu(L0(relu(h))))`
+    per block, final masked Linear) under autograd on K14 and K10 -- the ResidualNet of `ResidualNetHidden` with its
+    0/1 masks multiplied into the weights by the packer (`nfa_pack_made_train_f32`: no `mask * weight` tensors), and
+    into K10's weight gradients on the way out (a masked-out weight's gradient is exactly zero, as autograd through
+    `mask * weight` gives).  Arguments: inputs [B, D], masks = (mask of W_in, of W_0 and W_1 per block, of W_f), then
+    W_in, b_in, (W_0, b_0, W_1, b_1) per block, W_f, b_f.  Feature counts and output widths that are no multiples
+    of four run with zero pad columns on the inputs and zero pad rows of the final Linear, which exist only in the
+    packed streams.  Deterministic: every kernel in it sums in a fixed order."""
+
+    @staticmethod
+    def forward(ctx, x, masks, *params):
+        from . import ops
+        nb = (len(params) - 4) // 4
+        blocks = [params[2 + 4 * k: 6 + 4 * k] for k in range(nb)]
+        final = params[-2:]
+        ctx.di, ctx.rows = x.shape[1], final[0].shape[0]
+        ctx.nb, ctx.with_final, ctx.H = nb, True, params[0].shape[0]
+        x = x.detach()
+        if ctx.di % 4:
+            x = torch.nn.functional.pad(x, (0, 4 - ctx.di % 4))
+        out4 = (ctx.rows + 3) // 4 * 4
+        fwd_w, fwd_b, bwd_w, fbias = ops.pack_made_train(params[0], params[1], blocks, final, masks)
+        hidden, saved, out = ops.resnet_hidden_forward(x, fwd_w, fwd_b, nb, fbias, out4)
+        ctx.save_for_backward(x.contiguous(), saved, bwd_w, hidden, final[0], *masks)
+        return out if out4 == ctx.rows else out[:, :ctx.rows]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out):
+        x, saved, bwd_w, hidden, w_f = ctx.saved_tensors[:5]
+        masks = ctx.saved_tensors[5:]
+        rows, pad = ctx.rows, -ctx.rows % 4
+        if pad:
+            g_out = torch.nn.functional.pad(g_out, (0, pad))
+
+        def masked_final():   # (only where the backward kernel leaves the final Linear's input gradient to a GEMM)
+            w = w_f if masks[-1] is None else w_f * masks[-1]
+            return torch.nn.functional.pad(w, (0, 0, 0, pad)) if pad else w
+
+        grads = list(_resnet_hidden_backward(ctx, g_out, (x, saved, bwd_w, hidden, masked_final)))
+        if pad:   # the final Linear's gradients without the pad rows
+            grads[-2] = None if grads[-2] is None else grads[-2][:rows].contiguous()
+            grads[-1] = None if grads[-1] is None else grads[-1][:rows].contiguous()
+        pairs = [(g, m) for g, m in zip(grads[2::2], masks) if g is not None and m is not None]
+        if pairs:
+            torch._foreach_mul_([g for g, _ in pairs], [m for _, m in pairs])
+        return tuple(grads)
 
 
 def _dense_rows(t, n, width):

@@ -45,4 +45,26 @@ __device__ __forceinline__ void affine_element(float xin, float shift, float sc,
     }
 }
 
+// gradients of one element of the affine autoregressive layer (K25, `affine_ar_backward_kernel`) given the incoming
+// gradients g_y of its output and g_l of its row's logabsdet: scale = softplus(u) + 1e-3 with d scale / d u =
+// sigmoid(u), exactly 1 where softplus1 returns u.  `other` is the layer's input x in the forward direction and
+// its OUTPUT in the inverse direction (x = (y - shift) / scale: d x / d scale = -x / scale).
+template <bool INVERSE>
+__device__ __forceinline__ void affine_element_grad(float other, float u, float g_y, float g_l, float& g_x, float& g_u,
+                                                    float& g_shift) {
+#pragma clang fp contract(off)
+    const float s = scale_of(u, NFA_SCALE_SOFTPLUS);
+    const float e = expf(u);
+    const float ds = u > 20.0f ? 1.0f : e / (1.0f + e);
+    if (INVERSE) {
+        g_x = g_y / s;
+        g_shift = -g_x;
+        g_u = (-g_x * other - g_l / s) * ds;
+    } else {
+        g_x = g_y * s;
+        g_shift = g_y;
+        g_u = (g_y * other + g_l / s) * ds;
+    }
+}
+
 }  // namespace nfa

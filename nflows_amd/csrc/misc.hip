@@ -149,6 +149,75 @@ __global__ void __launch_bounds__(kBlock) affine_ar_kernel(const float* __restri
 }
 
 // ------------------------------------------------------------------------------------------
+// K25: backward of K2b.  No row reduction: flat over the B * D elements in chunks of 4 * kBlock, four elements per lane
+// (16-byte accesses: one float4 of x or of the output, one of g_y and of g_x, two of the interleaved (u, shift) pairs
+// in and out), a scalar tail for B * D % 4 and for buffers that are not 16-byte aligned.  The row of an element -- for
+// g_l, one value per row -- is the chunk's first row (one uniform division per chunk) plus the fast divide of the
+// element's offset from that row's start, which stays below 2^16 for D <= kArBwdFastDivD.  28 B per element forward,
+// 32 B inverse.
+constexpr int kArBwdChunk = 4 * kBlock;
+constexpr int kArBwdFastDivD = 65535 - kArBwdChunk;
+
+struct AffineArBwdArgs {
+    const float* other;   // the layer's input (forward) or its output (inverse)
+    const float* params;
+    const float* g_y;     // null: zeros
+    const float* g_l;     // null: zeros
+    float* g_x;
+    float* g_params;
+    int64_t total;
+    int D, vec;
+    FastDiv div_D;
+};
+
+template <bool INVERSE>
+__global__ void __launch_bounds__(kBlock) affine_ar_backward_kernel(const AffineArBwdArgs a) {
+#pragma clang fp contract(off)
+    const int64_t nchunks = (a.total + kArBwdChunk - 1) / kArBwdChunk;
+    const uint32_t D = (uint32_t)a.D;
+    for (int64_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
+        const int64_t e0 = chunk * kArBwdChunk;
+        const int64_t row0 = e0 / a.D;
+        const uint32_t n0 = (uint32_t)(e0 - row0 * a.D) + 4u * threadIdx.x;   // offset from the start of row0
+        const int64_t e = e0 + 4 * (int64_t)threadIdx.x;
+        if (e >= a.total) continue;
+        float gl[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const uint32_t n = n0 + c;
+            const int64_t r = row0 + (a.D <= kArBwdFastDivD ? fastdiv(n, a.div_D) : n / D);
+            gl[c] = (a.g_l && e + c < a.total) ? a.g_l[r] : 0.0f;
+        }
+        if (a.vec && e + 4 <= a.total) {
+            const float4 o = *reinterpret_cast<const float4*>(a.other + e);
+            const float4 p0 = *reinterpret_cast<const float4*>(a.params + 2 * e);
+            const float4 p1 = *reinterpret_cast<const float4*>(a.params + 2 * e + 4);
+            float4 gy = {0.0f, 0.0f, 0.0f, 0.0f};
+            if (a.g_y) gy = *reinterpret_cast<const float4*>(a.g_y + e);
+            float4 gx, q0, q1;
+            affine_element_grad<INVERSE>(o.x, p0.x, gy.x, gl[0], gx.x, q0.x, q0.y);
+            affine_element_grad<INVERSE>(o.y, p0.z, gy.y, gl[1], gx.y, q0.z, q0.w);
+            affine_element_grad<INVERSE>(o.z, p1.x, gy.z, gl[2], gx.z, q1.x, q1.y);
+            affine_element_grad<INVERSE>(o.w, p1.z, gy.w, gl[3], gx.w, q1.z, q1.w);
+            *reinterpret_cast<float4*>(a.g_x + e) = gx;
+            *reinterpret_cast<float4*>(a.g_params + 2 * e) = q0;
+            *reinterpret_cast<float4*>(a.g_params + 2 * e + 4) = q1;
+        } else {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const int64_t i = e + c;
+                if (i >= a.total) break;
+                float gx, gu, gs;
+                affine_element_grad<INVERSE>(a.other[i], a.params[2 * i], a.g_y ? a.g_y[i] : 0.0f, gl[c], gx, gu, gs);
+                a.g_x[i] = gx;
+                a.g_params[2 * i] = gu;
+                a.g_params[2 * i + 1] = gs;
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // K4: out[b, c] = in[b, perm[c]] on 4-byte words.  R rows per workgroup through LDS so that both
 // the global read and the global write are fully coalesced 16-byte accesses.
 struct PermArgs {
@@ -308,6 +377,32 @@ extern "C" int nfa_affine_autoregressive_f32(const float* inputs, const float* p
     if (!inputs || !params || !outputs || !logabsdet) return NFA_ERR_INVALID_ARGUMENT;
     return launch_kernel_args(affine_ar_kernel, wave_per_row_grid(batch), dim3(kBlock), 0, (hipStream_t)stream, 0, false,
                               inputs, params, outputs, logabsdet, batch, features, inverse);
+}
+
+extern "C" int nfa_affine_autoregressive_backward_f32(const float* inputs, const float* params, const float* outputs,
+                                                      const float* grad_outputs, const float* grad_logabsdet,
+                                                      float* grad_inputs, float* grad_params, int64_t batch,
+                                                      int32_t features, int32_t inverse, void* stream) {
+    if (batch < 0 || features < 1) return NFA_ERR_INVALID_ARGUMENT;
+    if (batch == 0) return NFA_OK;
+    if (!params || !grad_inputs || !grad_params || (inverse ? !outputs : !inputs)) return NFA_ERR_INVALID_ARGUMENT;
+    AffineArBwdArgs a;
+    a.other = inverse ? outputs : inputs;
+    a.params = params;
+    a.g_y = grad_outputs;
+    a.g_l = grad_logabsdet;
+    a.g_x = grad_inputs;
+    a.g_params = grad_params;
+    a.total = batch * features;
+    a.D = features;
+    a.div_D = make_fastdiv((uint32_t)(features <= kArBwdFastDivD ? features : 1));
+    const uintptr_t bits = reinterpret_cast<uintptr_t>(a.other) | reinterpret_cast<uintptr_t>(params) |
+                           reinterpret_cast<uintptr_t>(grad_outputs) | reinterpret_cast<uintptr_t>(grad_inputs) |
+                           reinterpret_cast<uintptr_t>(grad_params);
+    a.vec = (bits & 15) == 0;
+    const int64_t g = persistent_grid(device_cu_count(), 8, (a.total + kArBwdChunk - 1) / kArBwdChunk);
+    return inverse ? launch_kernel(affine_ar_backward_kernel<true>, dim3((unsigned)g), dim3(kBlock), 0, (hipStream_t)stream, a, 0, false)
+                   : launch_kernel(affine_ar_backward_kernel<false>, dim3((unsigned)g), dim3(kBlock), 0, (hipStream_t)stream, a, 0, false);
 }
 
 extern "C" int nfa_permute_cols_b32(const void* inputs, const int64_t* perm, void* outputs,

@@ -697,7 +697,19 @@ struct PackArgs {
     __bf16* bwd;
     int di, nb, init_ks, out_features, final_tiles;
     int H;   // the net's hidden width (<= 128): rows / columns past it are zero in the streams (units that stay 0)
+    // K25 (a MADE's masked Linears): optional 0/1 masks in the weights' own shapes, multiplied in before the split
+    // (null: the weight as it is); d_i / out_features columns and rows the SOURCE arrays have (<= di / out_features:
+    // the streams' pad columns and rows are zero)
+    const float* m_in;
+    const float* m_blk[3][2];   // masks of W_0, W_1 per block
+    const float* m_f;
+    int di_src, out_src;
 };
+
+// weight element `idx`, times its mask where the Linear has one
+__device__ __forceinline__ float pack_weight(const float* w, const float* m, int idx) {
+    return m ? w[idx] * m[idx] : w[idx];
+}
 
 // input feature consumed at (k-step ks, lane-half hf, element j) when the GEMM's input is the previous layer's
 // accumulator tiles (ops._k8_column_order)
@@ -722,7 +734,7 @@ __global__ void __launch_bounds__(kBlock) pack_resnet_hidden_kernel(const PackAr
         for (int e = tid; e < 32 * a.final_tiles; e += kBlock) {
             const int tile = e >> 5, half = (e >> 4) & 1, q = e & 15;
             const int src = 32 * tile + 8 * (q >> 2) + 4 * half + (q & 3);
-            a.final_bias[e] = src < a.out_features ? a.b_f[src] : 0.0f;
+            a.final_bias[e] = src < a.out_src ? a.b_f[src] : 0.0f;
         }
         return;
     }
@@ -737,7 +749,7 @@ __global__ void __launch_bounds__(kBlock) pack_resnet_hidden_kernel(const PackAr
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int col = acc_col(ks, hf, j);
-            v[j] = (row < a.out_features && col < a.H) ? a.w_f[row * a.H + col] : 0.0f;
+            v[j] = (row < a.out_src && col < a.H) ? pack_weight(a.w_f, a.m_f, row * a.H + col) : 0.0f;
         }
     } else if (s < n_hid) {
         dst = a.fwd + (size_t)s * 6144;
@@ -746,15 +758,16 @@ __global__ void __launch_bounds__(kBlock) pack_resnet_hidden_kernel(const PackAr
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int col = s * 16 + hf * 8 + j;
-                v[j] = (col < a.di && row < a.H) ? a.w_in[row * a.di + col] : 0.0f;
+                v[j] = (col < a.di_src && row < a.H) ? pack_weight(a.w_in, a.m_in, row * a.di_src + col) : 0.0f;
             }
         } else {
             const int lin = (s - a.init_ks) >> 3, ks = (s - a.init_ks) & 7;
             const float* w = a.blk[lin >> 1][(lin & 1) ? 2 : 0];
+            const float* m = a.m_blk[lin >> 1][lin & 1];
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int col = acc_col(ks, hf, j);
-                v[j] = (row < a.H && col < a.H) ? w[row * a.H + col] : 0.0f;
+                v[j] = (row < a.H && col < a.H) ? pack_weight(w, m, row * a.H + col) : 0.0f;
             }
         }
     } else if (s < n_fwd + n_bwd_k) {   // W_1^T, W_0^T per block, last block first
@@ -762,11 +775,12 @@ __global__ void __launch_bounds__(kBlock) pack_resnet_hidden_kernel(const PackAr
         dst = a.bwd + (size_t)s * 6144;
         const int lin = s >> 3, ks = s & 7;
         const float* w = a.blk[a.nb - 1 - (lin >> 1)][(lin & 1) ? 0 : 2];
+        const float* m = a.m_blk[a.nb - 1 - (lin >> 1)][(lin & 1) ? 0 : 1];
         const int row = 32 * grp + i;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int col = acc_col(ks, hf, j);
-            v[j] = (row < a.H && col < a.H) ? w[col * a.H + row] : 0.0f;
+            v[j] = (row < a.H && col < a.H) ? pack_weight(w, m, col * a.H + row) : 0.0f;
         }
     } else if (s >= n_fwd + n_bwd_k + 2 * tiles_x) {   // W_f^T (round 4: the final Linear's input gradient inside the
         // backward kernel), k-major over the out_features columns of g_params in their natural order: A[h][c] = W_f[c][h]
@@ -777,7 +791,7 @@ __global__ void __launch_bounds__(kBlock) pack_resnet_hidden_kernel(const PackAr
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int col = ks * 16 + hf * 8 + j;
-            v[j] = (col < a.out_features && row < a.H) ? a.w_f[col * a.H + row] : 0.0f;
+            v[j] = (col < a.out_src && row < a.H) ? pack_weight(a.w_f, a.m_f, col * a.H + row) : 0.0f;
         }
     } else {                            // W_in^T, tile-major: [piece][k4][lane], rows past d_i are zero
         s -= n_fwd;
@@ -788,7 +802,7 @@ __global__ void __launch_bounds__(kBlock) pack_resnet_hidden_kernel(const PackAr
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int col = acc_col(ks, hf, j);
-            v[j] = (row < a.di && col < a.H) ? a.w_in[col * a.di + row] : 0.0f;
+            v[j] = (row < a.di_src && col < a.H) ? pack_weight(a.w_in, a.m_in, col * a.di_src + row) : 0.0f;
         }
     }
     bf16x2 hh[4], mm[4], ll[4];
@@ -942,16 +956,20 @@ extern "C" int nfa_resnet_backward_f32(const float* grad_params, int32_t out_fea
                                  grad_identity_inputs, batch, num_identity, hidden_features, num_blocks, stream);
 }
 
-extern "C" int nfa_pack_resnet_hidden_train_f32(const float* initial_weight, const float* initial_bias,
-                                                const float* const* block_params, const float* final_weight,
-                                                const float* final_bias, int32_t out_features, int32_t num_identity,
-                                                int32_t hidden_features, int32_t num_blocks, void* forward_stages,
-                                                float* forward_bias, float* final_bias_packed, void* backward_stages,
-                                                void* stream) {
+// the packer's launch; `masks` (K25) null or [2 + 2 num_blocks] pointers: the masks of W_in, (W_0, W_1) per block and W_f,
+// each null or in its weight's shape; src_identity / src_out: columns of W_in and rows of W_f / b_f in memory
+static int launch_pack(const float* initial_weight, const float* initial_bias, const float* const* block_params,
+                       const float* final_weight, const float* final_bias, const float* const* masks, int32_t src_identity,
+                       int32_t src_out, int32_t out_features, int32_t num_identity, int32_t hidden_features,
+                       int32_t num_blocks, void* forward_stages, float* forward_bias, float* final_bias_packed,
+                       void* backward_stages, void* stream) {
     const int rc = check_train(0, num_identity, hidden_features, num_blocks, true);
     if (rc != NFA_OK) return rc;
     if (out_features < 0) return NFA_ERR_INVALID_ARGUMENT;
     if ((out_features & 3) != 0 || out_features > 32 * 1024) return NFA_ERR_UNSUPPORTED;
+    if (src_identity < 1 || src_identity > num_identity || src_out < 0 || src_out > out_features ||
+        (out_features > 0 && src_out < 1))
+        return NFA_ERR_INVALID_ARGUMENT;
     if (!initial_weight || !initial_bias || !forward_stages || !forward_bias || !backward_stages ||
         (num_blocks > 0 && !block_params) || (out_features > 0 && (!final_weight || !final_bias || !final_bias_packed)))
         return NFA_ERR_INVALID_ARGUMENT;
@@ -963,6 +981,12 @@ extern "C" int nfa_pack_resnet_hidden_train_f32(const float* initial_weight, con
             a.blk[k][q] = k < num_blocks ? block_params[4 * k + q] : nullptr;
             if (k < num_blocks && !a.blk[k][q]) return NFA_ERR_INVALID_ARGUMENT;
         }
+    a.m_in = masks ? masks[0] : nullptr;
+    for (int k = 0; k < 3; ++k)
+        for (int q = 0; q < 2; ++q) a.m_blk[k][q] = (masks && k < num_blocks) ? masks[1 + 2 * k + q] : nullptr;
+    a.m_f = (masks && out_features > 0) ? masks[1 + 2 * num_blocks] : nullptr;
+    a.di_src = src_identity;
+    a.out_src = src_out;
     a.fwd = reinterpret_cast<__bf16*>(forward_stages);
     a.fwd_bias = forward_bias;
     a.bwd = reinterpret_cast<__bf16*>(backward_stages);
@@ -977,4 +1001,27 @@ extern "C" int nfa_pack_resnet_hidden_train_f32(const float* initial_weight, con
     a.final_tiles = (out_features + 31) / 32;
     const int stages = a.init_ks + 32 * num_blocks + 2 * a.final_tiles + 2 * ((num_identity + 31) / 32) + (out_features + 15) / 16;
     return launch_kernel(pack_resnet_hidden_kernel, dim3(stages + 1), dim3(kBlock), 0, (hipStream_t)stream, a, 0, false);
+}
+
+extern "C" int nfa_pack_resnet_hidden_train_f32(const float* initial_weight, const float* initial_bias,
+                                                const float* const* block_params, const float* final_weight,
+                                                const float* final_bias, int32_t out_features, int32_t num_identity,
+                                                int32_t hidden_features, int32_t num_blocks, void* forward_stages,
+                                                float* forward_bias, float* final_bias_packed, void* backward_stages,
+                                                void* stream) {
+    return launch_pack(initial_weight, initial_bias, block_params, final_weight, final_bias, nullptr, num_identity,
+                       out_features, out_features, num_identity, hidden_features, num_blocks, forward_stages,
+                       forward_bias, final_bias_packed, backward_stages, stream);
+}
+
+extern "C" int nfa_pack_made_train_f32(const float* initial_weight, const float* initial_bias,
+                                       const float* const* block_params, const float* final_weight,
+                                       const float* final_bias, const float* const* masks, int32_t features,
+                                       int32_t out_rows, int32_t out_features, int32_t num_identity,
+                                       int32_t hidden_features, int32_t num_blocks, void* forward_stages,
+                                       float* forward_bias, float* final_bias_packed, void* backward_stages,
+                                       void* stream) {
+    return launch_pack(initial_weight, initial_bias, block_params, final_weight, final_bias, masks, features, out_rows,
+                       out_features, num_identity, hidden_features, num_blocks, forward_stages, forward_bias,
+                       final_bias_packed, backward_stages, stream);
 }

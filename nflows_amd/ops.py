@@ -493,6 +493,39 @@ def _affine_autoregressive_launch(inputs, params, inverse):
     return out, lad
 
 
+def affine_autoregressive_backward(inputs, params, outputs, grad_outputs, grad_logabsdet, inverse=False):
+    """K25 -- the backward pass of K2b in one launch (nfa_affine_autoregressive_backward_f32): (grad_inputs [B, D],
+    grad_params in the shape of `params`).  `grad_outputs` [B, D] / `grad_logabsdet` [B] may be None (zeros); `outputs`
+    (what the forward call returned) is read in the inverse direction only, `inputs` in the forward direction only."""
+    seen = outputs if inverse else inputs
+    N.require_device_f32("outputs" if inverse else "inputs", seen, 2)
+    N.require_device_f32("autoregressive_params", params)
+    B, D = seen.shape
+    if params.numel() != B * D * 2:
+        raise ValueError("autoregressive_params must hold %d values" % (B * D * 2))
+    dev = seen.device
+    seen = seen.detach().contiguous()
+    p = params.detach().contiguous()
+    if grad_outputs is not None:
+        N.require_device_f32("grad_outputs", grad_outputs, 2)
+        if grad_outputs.shape != seen.shape:
+            raise ValueError("grad_outputs must be [%d, %d]" % (B, D))
+        grad_outputs = grad_outputs.detach().contiguous()
+    if grad_logabsdet is not None:
+        N.require_device_f32("grad_logabsdet", grad_logabsdet)
+        if grad_logabsdet.numel() != B:
+            raise ValueError("grad_logabsdet must hold %d values" % B)
+        grad_logabsdet = grad_logabsdet.detach().contiguous()
+    g_in = torch.empty_like(seen)
+    g_p = torch.empty(params.shape, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = N.load().nfa_affine_autoregressive_backward_f32(
+            None if inverse else N.ptr(seen), N.ptr(p), N.ptr(seen) if inverse else None, N.ptr(grad_outputs),
+            N.ptr(grad_logabsdet), N.ptr(g_in), N.ptr(g_p), B, D, int(bool(inverse)), N.stream_handle(dev))
+    N.check(rc)
+    return g_in, g_p
+
+
 def permute_cols(inputs, permutation):
     """K4 -- torch.index_select(inputs, 1, permutation) for 2-D tensors of 4-byte elements."""
     if not torch.is_tensor(inputs) or not inputs.is_cuda:
@@ -2066,6 +2099,49 @@ def pack_resnet_hidden_train(w_in, b_in, block_params, final=None):
         rc = N.load().nfa_pack_resnet_hidden_train_f32(
             N.ptr(flat[0]), N.ptr(flat[1]), ptrs, N.ptr(fin[0]) if fin else None, N.ptr(fin[1]) if fin else None, out,
             di, w_in.shape[0], nb, N.ptr(fwd), N.ptr(bias), N.ptr(fbias), N.ptr(bwd), N.stream_handle(dev))
+    N.check(rc)
+    return fwd, bias, bwd, fbias
+
+
+def pack_made_train(w_in, b_in, block_params, final, masks):
+    """K25: K14's packer for a MADE with residual blocks, ONE launch (nfa_pack_made_train_f32) -- every weight times its
+    0/1 mask before the bf16 split, so the result is `pack_resnet_hidden_train_reference` on the products
+    `mask * weight`, bit for bit, with no product tensor in between.  `masks` = [mask of W_in, (of W_0, of W_1) per
+    block, and with `final` of W_f]; an entry may be None.  Odd sizes need no padded copies: the streams are laid
+    out for ceil4(features) identity columns and ceil4(out) outputs and hold zeros past the arrays' own extents (what
+    `pack_resnet_hidden_train_reference` writes for zero-padded weights).  Returns (forward stages, forward biases,
+    backward stages, final-layer bias or None)."""
+    dev = w_in.device
+    D, H, nb = w_in.shape[1], w_in.shape[0], len(block_params)
+    di = (D + 3) // 4 * 4
+    flat = [w_in.detach().contiguous(), b_in.detach().contiguous()]
+    for group in block_params:
+        flat += [t.detach().contiguous() for t in group]
+    fin = [t.detach().contiguous() for t in final] if final is not None else []
+    masks = [None if m is None else m.detach().contiguous() for m in masks]
+    if len(masks) != 1 + 2 * nb + (1 if fin else 0):
+        raise ValueError("nflows_amd: one mask (or None) per weight: %d expected" % (1 + 2 * nb + (1 if fin else 0)))
+    weights = [flat[0]] + [flat[2 + 2 * q] for q in range(2 * nb)] + fin[:1]
+    for t in flat + fin + [m for m in masks if m is not None]:
+        if t.dtype != torch.float32 or not t.is_cuda or t.device != dev:
+            raise TypeError("nflows_amd: the conditioner's parameters and masks must be float32 tensors on one device")
+    for w, m in zip(weights, masks):
+        if m is not None and m.shape != w.shape:
+            raise ValueError("nflows_amd: a mask has its weight's shape")
+    rows = fin[0].shape[0] if fin else 0
+    out = (rows + 3) // 4 * 4
+    init_ks = 4 if di > 32 else 2
+    tiles, ft = (di + 31) // 32, (out + 31) // 32
+    fwd = torch.empty(init_ks + 16 * nb + 2 * ft, 6144, dtype=torch.bfloat16, device=dev)
+    bias = torch.empty(128 * (1 + 2 * nb), dtype=torch.float32, device=dev)
+    fbias = torch.empty(32 * ft, dtype=torch.float32, device=dev) if fin else None
+    bwd = torch.empty(16 * nb + 2 * tiles + (out + 15) // 16, 6144, dtype=torch.bfloat16, device=dev)
+    ptrs = (ctypes.c_void_p * max(1, 4 * nb))(*[t.data_ptr() for t in flat[2:]])
+    mptrs = (ctypes.c_void_p * (2 + 2 * nb))(*[None if m is None else m.data_ptr() for m in masks])
+    with torch.cuda.device(dev):
+        rc = N.load().nfa_pack_made_train_f32(
+            N.ptr(flat[0]), N.ptr(flat[1]), ptrs, N.ptr(fin[0]) if fin else None, N.ptr(fin[1]) if fin else None, mptrs,
+            D, rows, out, di, H, nb, N.ptr(fwd), N.ptr(bias), N.ptr(fbias), N.ptr(bwd), N.stream_handle(dev))
     N.check(rc)
     return fwd, bias, bwd, fbias
 

@@ -6,12 +6,15 @@ Checkpoint-compatible with nflows/transforms/made.py: modules `initial_layer`,
 the same rules (made.py:42-69).  MADE has no `hidden_features` attribute on purpose: the
 autoregressive spline transform then applies no 1/sqrt(hidden) scaling (autoregressive.py:464-466).
 """
+import os
+
 import torch
 from torch import nn
 from torch.nn import functional as F
 
 from .. import _cache
 from ..nn.functional import linear
+from ..nn.nets.resnet import _has_inner_hooks
 
 
 # ---- degrees and masks ------------------------------------------------------------------------
@@ -206,7 +209,58 @@ class MADE(nn.Module):
             h = block(h, context)
         return h
 
+    # K25: the whole net under autograd on K14 / K10 (autograd.MadeNet).  Class-level default from NFA_K25 (0 = the
+    # eager masked Linears); `net.fuse_training = False` on an instance switches it at run time.  Like K14 on a
+    # ResidualNet the fused path is once-differentiable, computes in fp32 and runs no forward hooks of the inner
+    # layers, so it steps aside by itself under autocast or when an inner module carries a hook.
+    fuse_training = os.environ.get("NFA_K25", "1") != "0"
+
+    def _fusable(self, batch, features, context=None):
+        """The net and the shape are K25's (whatever device the tensors are on): the switch is on, a plain MADE with
+        residual blocks, ReLU throughout, no context / batch norm / active dropout, no autocast, no hook on an inner
+        module, and a shape K14 takes (`ops.resnet_hidden_train_supported`: hidden width 4 .. 128 in multiples of 4, at
+        most 64 features and 3 blocks, rows in multiples of 128)."""
+        if not (self.fuse_training and type(self) is MADE and self.use_residual_blocks and context is None):
+            return False
+        if self.activation is not F.relu or getattr(self, "context_layer", None) is not None:
+            return False
+        if torch.is_autocast_enabled() or torch.is_autocast_enabled("cpu") or _has_inner_hooks(self):
+            return False
+        first, final = self.initial_layer, self.final_layer
+        from .. import ops
+        if not ops.resnet_hidden_train_supported(batch, features, first.out_features, len(self.blocks)):
+            return False
+        if features != first.in_features or final.in_features != first.out_features or final.out_features > 32768:
+            return False
+        for b in self.blocks:
+            if (type(b) is not MaskedResidualBlock or b.activation is not F.relu or b.use_batch_norm
+                    or (b.training and b.dropout.p != 0.0) or getattr(b, "context_layer", None) is not None):
+                return False
+        return True
+
+    def _fused_training(self, inputs, context=None):
+        """K25 applies: `_fusable`, under autograd, float32 inputs, parameters and masks on one HIP device."""
+        if not (torch.is_grad_enabled() and torch.is_tensor(inputs) and inputs.is_cuda and inputs.dtype == torch.float32
+                and inputs.dim() == 2 and self._fusable(inputs.shape[0], inputs.shape[1], context)):
+            return False
+        layers = [self.initial_layer, self.final_layer] + [l for b in self.blocks for l in b.linear_layers]
+        for l in layers:
+            if (type(l) is not MaskedLinear or l.bias is None or l._frozen_weight is not None
+                    or l.weight.dtype != torch.float32 or l.weight.device != inputs.device
+                    or l.mask.dtype != torch.float32 or l.mask.device != inputs.device):
+                return False   # (half-precision or misplaced parameters: the eager modules report it their own way)
+        return any(p.requires_grad for p in self.parameters()) or inputs.requires_grad
+
     def forward(self, inputs, context=None):
+        if self._fused_training(inputs, context):
+            from .. import autograd as AG
+            masks, params = [self.initial_layer.mask], [self.initial_layer.weight, self.initial_layer.bias]
+            for b in self.blocks:
+                for l in b.linear_layers:
+                    masks.append(l.mask)
+                    params += [l.weight, l.bias]
+            masks.append(self.final_layer.mask)
+            return AG.MadeNet.apply(inputs, tuple(masks), *params, self.final_layer.weight, self.final_layer.bias)
         return self.final_layer(self.hidden(inputs, context))
 
     def is_deterministic(self):
