@@ -1,6 +1,6 @@
 // The split-f16 GEMM machinery of K8x (rqs_resnet_f16x3.hip): every fp32 operand as THREE f16 pieces
 //
-//   x s = hi + lo + r' 2^-8,   hi = RN16(x s),  lo = RN16(x s - hi),  r' = RN16((x s - hi - lo) 2^8)      (s: a power of two)
+//   x s = hi + lo + r' 2^-8,   hi = RN16(x s),  lo = RN16(x s - hi),  r' = RN8((x s - hi - lo) 2^8)       (s: a power of two)
 //
 // 11 + 11 + 11 significand bits with a sign each: the three pieces hold ANY fp32 value exactly while the last one stays
 // above f16's smallest subnormal (2^-24), i.e. -- the last piece being kept at 2^8 times its value -- for |x s| >= 2^-9;
@@ -19,7 +19,12 @@
 // build took 5 and the three-piece bf16 scheme (bf16x3_gemm.hpp) takes 6.
 // A bf8 operand of a lane (32 bytes, two k-steps ks0, ks1; the lane's eight k values each):
 //   A (weights)      [bf8(hi_w) ks0 | bf8(r'_w) ks0 | bf8(hi_w) ks1 | bf8(r'_w) ks1]     packed by the host
-//   B (activations)  [bf8(r'_x) ks0 | bf8(hi_x) ks0 | bf8(r'_x) ks1 | bf8(hi_x) ks1]     the high bytes of the f16 pieces
+//   B (activations)  [r'_x ks0 | bf8(hi_x) ks0 | r'_x ks1 | bf8(hi_x) ks1]               hi: the high bytes of the f16 piece
+// The activations' last piece is read by nothing but this operand and is made as bf8 in the first place (round 10: RN8 =
+// v_cvt_scalef32_pk_bf8_f32, round to nearest even e5m2 of its input DIVIDED by the scale operand's power of two, infinity on
+// overflow, two values per instruction into either half-word: tools/cvt_bf8_probe.hip, profiles/r10/cvt_bf8_probe.txt).  It
+// is one bit (or zero) wherever lo is a normal f16, so rounding it to three bits loses nothing there; below that it is
+// within 2^-3 of a 2^-22-level term, like the truncated hi factor.
 // (which k the hardware gives byte e of lane-half h is immaterial: A and B use the same map.)
 // The LDS-DMA ring, its counted waits and its barriers are bf16x3_gemm.hpp's; a 12 KB stage holds twelve 1 KB fragments
 // ([64 lanes] x 16 B): k-major stages cover TWO k-steps of TWO output tiles, [2 tiles][H0, L0, H1, L1, X lo, X hi]; a
@@ -104,9 +109,11 @@ __device__ __forceinline__ void stream_advance(WeightStream& sm) {
     }
 }
 
-// the pieces of a k-step: 8 values per lane and piece = one register quad each (r: the last piece x 2^8)
+// the pieces of a k-step: 8 values per lane; hi and lo as f16 = one register quad each, the last piece x 2^8 as bf8 = two
+// registers, in the order the bf8 operand takes them (values 0 .. 3, values 4 .. 7)
 struct Pieces {
-    uvec4 h, l, r;
+    uvec4 h, l;
+    unsigned r[2];
 };
 
 // The conversions are `asm volatile`: a plain asm statement is free to move, and hipcc's scheduler moved these across the
@@ -125,20 +132,36 @@ struct Pieces {
 //   t  = v s - hi                          v_fma_mix_f32 with the f16 `hi` as negated addend: exact (<= 13 bits)
 //   lo = RN16(t)
 //   d  = t - lo                            exact in fp32
-//   r' = RN16(256 d)                       one bit (or zero) where lo is a normal f16; all of d's bits while 256 d >= 2^-24
+//   r' = RN8(256 d)                        v_cvt_scalef32_pk_bf8_f32 with 2^-8 as its scale: the two bytes of the pair into
+//                                          the lower (UPPER = false: the upper one is undefined) or the upper half-word of
+//                                          `rr`; one bit (or zero) where lo is a normal f16
 // |v s| >= 65520 gives hi = inf, t = -inf, lo = -inf, d = NaN: the overflow poisons every sum it enters, the row block is
 // flagged and redone by the exact kernel.  (One asm block: hipcc puts an `s_nop 0` between two adjacent asm statements;
-// early-clobber everywhere: every output is written before the last input is read.)
+// early-clobber everywhere: every output is written before the last input is read.  The s_nop behind the conversion: an
+// instruction that writes half a register needs one wait state in front of a VALU instruction that reads the register,
+// and the compiler does not see the one in here.)
 // ReLU before the split gives the pieces the sign mask on the pieces gave (K8x up to round 6): a negative v, -0 included,
 // has a negative or -0 `hi`, and all three pieces were cleared; NaN and +inf pass both ways.
 #define NFA_K8X_SPLIT_REST                                                  \
     "v_fma_mixlo_f16 %1, %3, 1.0, 0 op_sel_hi:[0,0,0]\n\t"                  \
     "v_fma_mixhi_f16 %1, %4, 1.0, 0 op_sel_hi:[0,0,0]\n\t"                  \
     "v_fma_mix_f32 %3, %3, 1.0, -%1 op_sel_hi:[0,0,1]\n\t"                  \
-    "v_fma_mix_f32 %4, %4, 1.0, -%1 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"   \
-    "v_fma_mixlo_f16 %2, %3, %8, 0 op_sel_hi:[0,0,0]\n\t"                   \
-    "v_fma_mixhi_f16 %2, %4, %8, 0 op_sel_hi:[0,0,0]"
-template <bool RELU = false>
+    "v_fma_mix_f32 %4, %4, 1.0, -%1 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
+#define NFA_K8X_SPLIT_LOWER "v_cvt_scalef32_pk_bf8_f32 %2, %3, %4, %8\n\ts_nop 0"
+#define NFA_K8X_SPLIT_UPPER "v_cvt_scalef32_pk_bf8_f32 %2, %3, %4, %8 op_sel:[0,0,0,1]\n\ts_nop 0"
+#define NFA_K8X_SPLIT_RELU                                                  \
+    "v_maximum3_f32 %3, %5, 0, 0\n\t"                                       \
+    "v_maximum3_f32 %4, %6, 0, 0\n\t"                                       \
+    "v_fma_mixlo_f16 %0, %3, %7, 0 op_sel_hi:[0,0,0]\n\t"                   \
+    "v_fma_mixhi_f16 %0, %4, %7, 0 op_sel_hi:[0,0,0]\n\t"                   \
+    "v_fma_mix_f32 %3, %3, %7, -%0 op_sel_hi:[0,0,1]\n\t"                   \
+    "v_fma_mix_f32 %4, %4, %7, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
+#define NFA_K8X_SPLIT_PLAIN                                                 \
+    "v_fma_mixlo_f16 %0, %5, %7, 0 op_sel_hi:[0,0,0]\n\t"                   \
+    "v_fma_mixhi_f16 %0, %6, %7, 0 op_sel_hi:[0,0,0]\n\t"                   \
+    "v_fma_mix_f32 %3, %5, %7, -%0 op_sel_hi:[0,0,1]\n\t"                   \
+    "v_fma_mix_f32 %4, %6, %7, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
+template <bool RELU = false, bool UPPER = false>
 __device__ __forceinline__ void split3_scaled(float v0, float v1, float scale, unsigned& hi, unsigned& lo, unsigned& rr) {
 #if defined(NFA_K8X_NO_ASM)
     typedef _Float16 h2 __attribute__((ext_vector_type(2)));
@@ -150,51 +173,55 @@ __device__ __forceinline__ void split3_scaled(float v0, float v1, float scale, u
     const h2 h = {(_Float16)x0, (_Float16)x1};
     const float t0 = x0 - (float)h[0], t1 = x1 - (float)h[1];
     const h2 l = {(_Float16)t0, (_Float16)t1};
-    const h2 r = {(_Float16)((t0 - (float)l[0]) * 256.0f), (_Float16)((t1 - (float)l[1]) * 256.0f)};
+    typedef short s2 __attribute__((ext_vector_type(2)));
+    const s2 r = __builtin_amdgcn_cvt_scalef32_pk_bf8_f32(__builtin_bit_cast(s2, UPPER ? rr : 0u), t0 - (float)l[0], t1 - (float)l[1],
+                                                          0.00390625f, UPPER);
     hi = __builtin_bit_cast(unsigned, h);
     lo = __builtin_bit_cast(unsigned, l);
     rr = __builtin_bit_cast(unsigned, r);
 #else
     unsigned h, l, r;
+    if constexpr (UPPER) r = rr;
     float t0, t1;
-    if constexpr (RELU)
-        NFA_K8X_ASM(
-            "v_maximum3_f32 %3, %5, 0, 0\n\t"
-            "v_maximum3_f32 %4, %6, 0, 0\n\t"
-            "v_fma_mixlo_f16 %0, %3, %7, 0 op_sel_hi:[0,0,0]\n\t"
-            "v_fma_mixhi_f16 %0, %4, %7, 0 op_sel_hi:[0,0,0]\n\t"
-            "v_fma_mix_f32 %3, %3, %7, -%0 op_sel_hi:[0,0,1]\n\t"
-            "v_fma_mix_f32 %4, %4, %7, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
-            NFA_K8X_SPLIT_REST
-            : "=&v"(h), "=&v"(l), "=&v"(r), "=&v"(t0), "=&v"(t1)
-            : "v"(v0), "v"(v1), "v"(scale), "s"(256.0f));
+    // (the lower form's `r` is an output only: nothing of the register's old contents survives the upper form)
+    if constexpr (RELU && UPPER)
+        NFA_K8X_ASM(NFA_K8X_SPLIT_RELU NFA_K8X_SPLIT_REST NFA_K8X_SPLIT_UPPER
+                    : "=&v"(h), "=&v"(l), "+v"(r), "=&v"(t0), "=&v"(t1)
+                    : "v"(v0), "v"(v1), "v"(scale), "s"(0.00390625f));
+    else if constexpr (RELU)
+        NFA_K8X_ASM(NFA_K8X_SPLIT_RELU NFA_K8X_SPLIT_REST NFA_K8X_SPLIT_LOWER
+                    : "=&v"(h), "=&v"(l), "=&v"(r), "=&v"(t0), "=&v"(t1)
+                    : "v"(v0), "v"(v1), "v"(scale), "s"(0.00390625f));
+    else if constexpr (UPPER)
+        NFA_K8X_ASM(NFA_K8X_SPLIT_PLAIN NFA_K8X_SPLIT_REST NFA_K8X_SPLIT_UPPER
+                    : "=&v"(h), "=&v"(l), "+v"(r), "=&v"(t0), "=&v"(t1)
+                    : "v"(v0), "v"(v1), "v"(scale), "s"(0.00390625f));
     else
-        NFA_K8X_ASM(
-            "v_fma_mixlo_f16 %0, %5, %7, 0 op_sel_hi:[0,0,0]\n\t"
-            "v_fma_mixhi_f16 %0, %6, %7, 0 op_sel_hi:[0,0,0]\n\t"
-            "v_fma_mix_f32 %3, %5, %7, -%0 op_sel_hi:[0,0,1]\n\t"
-            "v_fma_mix_f32 %4, %6, %7, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
-            NFA_K8X_SPLIT_REST
-            : "=&v"(h), "=&v"(l), "=&v"(r), "=&v"(t0), "=&v"(t1)
-            : "v"(v0), "v"(v1), "v"(scale), "s"(256.0f));
+        NFA_K8X_ASM(NFA_K8X_SPLIT_PLAIN NFA_K8X_SPLIT_REST NFA_K8X_SPLIT_LOWER
+                    : "=&v"(h), "=&v"(l), "=&v"(r), "=&v"(t0), "=&v"(t1)
+                    : "v"(v0), "v"(v1), "v"(scale), "s"(0.00390625f));
     hi = h;
     lo = l;
     rr = r;
 #endif
 }
 #undef NFA_K8X_SPLIT_REST
+#undef NFA_K8X_SPLIT_LOWER
+#undef NFA_K8X_SPLIT_UPPER
+#undef NFA_K8X_SPLIT_RELU
+#undef NFA_K8X_SPLIT_PLAIN
 
-// the bf8 B operand of two k-steps: the high bytes of the r' and hi pieces (an f16's high byte IS its bf8 truncation: same
-// sign, same five exponent bits, the two leading fraction bits; infinities and NaNs stay what they are)
+// the bf8 B operand of two k-steps: the r' pieces as they are and the high bytes of the hi pieces (an f16's high byte IS its
+// bf8 truncation: same sign, same five exponent bits, the two leading fraction bits; infinities and NaNs stay what they are)
 __device__ __forceinline__ i32x8 bf8_operand(const Pieces& p0, const Pieces& p1) {
     constexpr unsigned kHigh = 0x07050301u;   // bytes 1, 3 of the second argument, then bytes 1, 3 of the first
     i32x8 b;
-    b[0] = (int)__builtin_amdgcn_perm(p0.r[1], p0.r[0], kHigh);
-    b[1] = (int)__builtin_amdgcn_perm(p0.r[3], p0.r[2], kHigh);
+    b[0] = (int)p0.r[0];
+    b[1] = (int)p0.r[1];
     b[2] = (int)__builtin_amdgcn_perm(p0.h[1], p0.h[0], kHigh);
     b[3] = (int)__builtin_amdgcn_perm(p0.h[3], p0.h[2], kHigh);
-    b[4] = (int)__builtin_amdgcn_perm(p1.r[1], p1.r[0], kHigh);
-    b[5] = (int)__builtin_amdgcn_perm(p1.r[3], p1.r[2], kHigh);
+    b[4] = (int)p1.r[0];
+    b[5] = (int)p1.r[1];
     b[6] = (int)__builtin_amdgcn_perm(p1.h[1], p1.h[0], kHigh);
     b[7] = (int)__builtin_amdgcn_perm(p1.h[3], p1.h[2], kHigh);
     return b;
@@ -206,18 +233,16 @@ template <bool RELU, bool WB = true>
 __device__ __forceinline__ void tile_to_pieces(const f32x16& a, float scale, Pieces& p0, Pieces& p1) {
     if constexpr (WB) asm volatile("s_nop 7\n\ts_nop 3" : : "v"(a));   // (the tile's last MFMA has written back)
 #pragma unroll
-    for (int q2 = 0; q2 < 8; ++q2) {
-        unsigned h, l, r;
-        split3_scaled<RELU>(a[q2 * 2], a[q2 * 2 + 1], scale, h, l, r);
-        if (q2 < 4) {
-            p0.h[q2] = h;
-            p0.l[q2] = l;
-            p0.r[q2] = r;
-        } else {
-            p1.h[q2 - 4] = h;
-            p1.l[q2 - 4] = l;
-            p1.r[q2 - 4] = r;
-        }
+    for (int q2 = 0; q2 < 8; q2 += 2) {
+        Pieces& p = q2 < 4 ? p0 : p1;
+        unsigned h0, l0, h1, l1, r;
+        split3_scaled<RELU, false>(a[q2 * 2], a[q2 * 2 + 1], scale, h0, l0, r);
+        split3_scaled<RELU, true>(a[q2 * 2 + 2], a[q2 * 2 + 3], scale, h1, l1, r);
+        p.h[q2 & 3] = h0;
+        p.l[q2 & 3] = l0;
+        p.h[(q2 & 3) + 1] = h1;
+        p.l[(q2 & 3) + 1] = l1;
+        p.r[(q2 & 3) >> 1] = r;
     }
 }
 

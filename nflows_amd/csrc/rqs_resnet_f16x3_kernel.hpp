@@ -239,6 +239,42 @@ __device__ __forceinline__ bool not_finite(float v) { return !(__builtin_fabsf(v
 // order, same bits.  The redo flag, the vote on non-finite results and the status are kept per half (per 128 rows).  With
 // an odd number of row blocks the last workgroup's upper half has none: it computes the lower half's block again (every
 // request and every barrier is the workgroup's) and stores nothing.
+// The skip connection on eight values of a residual tile, IN PLACE: h = fma(h, skip, b1).  Written as asm for the register
+// it names, not for the instruction: left to the compiler the result took the freshly loaded bias tile's registers (a
+// two-address v_fmac_f32 onto its addend), the second Linear accumulated there, and the last k-step pair of every block
+// copied the four tiles back to the registers the block loop carries h in -- 32 v_mov_b64 behind four waits for the
+// matrix pipe's write-back.  Volatile keeps the blocks in front of the second Linear's first piece split, far from the
+// first MFMA that reads the tile (the compiler does not see a VALU write inside an asm statement as one).
+template <int B0>
+__device__ __forceinline__ void skip_half(f32x16& h, const f32x16& b1, float skip) {
+#if defined(NFA_K8X_NO_ASM)
+#pragma unroll
+    for (int q = B0; q < B0 + 8; ++q) h[q] = __builtin_fmaf(h[q], skip, b1[q]);
+#else
+    float e0 = h[B0], e1 = h[B0 + 1], e2 = h[B0 + 2], e3 = h[B0 + 3], e4 = h[B0 + 4], e5 = h[B0 + 5], e6 = h[B0 + 6], e7 = h[B0 + 7];
+    NFA_K8X_ASM(
+        "v_fma_f32 %0, %0, %8, %9\n\t"
+        "v_fma_f32 %1, %1, %8, %10\n\t"
+        "v_fma_f32 %2, %2, %8, %11\n\t"
+        "v_fma_f32 %3, %3, %8, %12\n\t"
+        "v_fma_f32 %4, %4, %8, %13\n\t"
+        "v_fma_f32 %5, %5, %8, %14\n\t"
+        "v_fma_f32 %6, %6, %8, %15\n\t"
+        "v_fma_f32 %7, %7, %8, %16"
+        : "+v"(e0), "+v"(e1), "+v"(e2), "+v"(e3), "+v"(e4), "+v"(e5), "+v"(e6), "+v"(e7)
+        : "v"(skip), "v"(b1[B0]), "v"(b1[B0 + 1]), "v"(b1[B0 + 2]), "v"(b1[B0 + 3]), "v"(b1[B0 + 4]), "v"(b1[B0 + 5]),
+          "v"(b1[B0 + 6]), "v"(b1[B0 + 7]));
+    h[B0] = e0;
+    h[B0 + 1] = e1;
+    h[B0 + 2] = e2;
+    h[B0 + 3] = e3;
+    h[B0 + 4] = e4;
+    h[B0 + 5] = e5;
+    h[B0 + 6] = e6;
+    h[B0 + 7] = e7;
+#endif
+}
+
 template <bool INVERSE, int INIT_KS, bool DBG, int KB, bool BIAS_LDS, int WAVES = 4>
 __device__ __forceinline__ void rqs_resnet_f16x3_body(const Args& a) {
     static_assert(!DBG || KB == 8, "the diagnostic instances: 8 bins");
@@ -412,11 +448,11 @@ __device__ __forceinline__ void rqs_resnet_f16x3_body(const Args& a) {
                     float v0 = s_row[tab[kTabId + i0] * kRowPad + r], v1 = s_row[tab[kTabId + i0 + 1] * kRowPad + r];
                     v0 = i0 < di ? v0 : 0.0f;
                     v1 = i0 + 1 < di ? v1 : 0.0f;
-                    unsigned hi, lo, rr;
-                    split3_scaled(v0, v1, S, hi, lo, rr);
+                    unsigned hi, lo;   // (the pair's last pieces: two bytes, one half-word of r[j2 / 2])
+                    if (j2 & 1) split3_scaled<false, true>(v0, v1, S, hi, lo, p[ks].r[j2 >> 1]);
+                    else split3_scaled<false, false>(v0, v1, S, hi, lo, p[ks].r[j2 >> 1]);
                     p[ks].h[j2] = hi;
                     p[ks].l[j2] = lo;
-                    p[ks].r[j2] = rr;
                 }
             }
 
@@ -468,8 +504,8 @@ __device__ __forceinline__ void rqs_resnet_f16x3_body(const Args& a) {
                 for (int t = 0; t < 4; ++t) {
                     f32x16 b1;
                     load_bias_tile(b1, bias + 128 + t * 32);
-#pragma unroll
-                    for (int q_ = 0; q_ < 16; ++q_) h[t][q_] = __builtin_fmaf(h[t][q_], skip, b1[q_]);
+                    skip_half<0>(h[t], b1, skip);
+                    skip_half<8>(h[t], b1, skip);
                 }
                 gemm_kmajor_relu<WAVES>(h, u, sb[0], sm, lane);
                 hs = sb[2];
