@@ -154,7 +154,11 @@ __device__ __forceinline__ BinAdj inverse_map_adjoint(float th, float w, float h
 
 __device__ __forceinline__ float sigmoid_beta(float u, float beta) {
     const float z = u * beta;
-    return z > 20.0f ? 1.0f : 1.0f / (1.0f + exp_noclamp(-z));  // d/du [softplus(u; beta)]
+    // d/du [softplus(u; beta)].  Below -87 the sigmoid IS exp(z) to fp32 precision, and exp_noclamp(-z) must not be
+    // asked: past 88.7 its exp2 is inf and its correction term inf * 0 or inf - inf, a NaN where the reference has 0.
+    // (Results below 2^-126 are flushed to 0 on the device and may be denormal in a host build of this function.)
+    if (z < -87.0f) return exp_noclamp(z);
+    return z > 20.0f ? 1.0f : 1.0f / (1.0f + exp_noclamp(-z));
 }
 
 // One spline: overwrites the lane's P logits in `sl` with their gradients; returns d loss / d input.
