@@ -255,6 +255,19 @@ __device__ __forceinline__ void kstep(f32x16 (&acc)[4], const bf16x8& bh, const 
 // point at about the same time, the burst of 33 MB per array waited for itself in the next counted vmcnt (stores share
 // the counter with the ring's requests) and nothing overlapped it: 26 of the forward kernel's 78 us at 65 536 rows
 // (profiles/r4/k14_ablations.txt).
+__device__ __forceinline__ void zero_tile(f32x16& acc) {
+#pragma unroll
+    for (int q = 0; q < 16; ++q) acc[q] = 0.0f;
+}
+
+// acc += the bias of its tile (after the products: a block's second Linear, whose accumulator starts at zero)
+__device__ __forceinline__ void add_bias_tile(f32x16& acc, const float* bias_tile_half) {
+    f32x16 b;
+    load_bias_tile(b, bias_tile_half);
+#pragma unroll
+    for (int q = 0; q < 16; ++q) acc[q] += b[q];
+}
+
 // 64 ReLU masks of a lane (4 tiles x 16 accumulator registers) as two words: bit 16 t + q of the pair
 struct Mask64 {
     unsigned lo, hi;   // tiles 0-1, tiles 2-3
@@ -407,16 +420,39 @@ __global__ void __launch_bounds__(kBlock, 2) resnet_hidden_forward_kernel(const 
 #ifdef NFA_K14_BURST_STORES
                 store_tile<true>(in1, row, t, half, u[t]);
 #endif
-                f32x16 b1;
-                load_bias_tile(b1, bias + 128 + t * 32);
-#pragma unroll
-                for (int q = 0; q < 16; ++q) hs[t][q] += b1[q];   // skip connection: accumulate onto h
             }
             {
-                // (the second GEMM accumulates INTO hs while it reads u: relu(a), the second Linear's input, is stored
-                //  from u on the way)
-                gemm_from_tiles<true>(hs, u, sm, lane, in1, row, half, stage, &ma);
+                // The second Linear sums into an accumulator of its OWN and joins the residual stream with one addition,
+                // h += (W_1 u + b_1).  (Until the table of tests/train_kernel_cases.py the GEMM accumulated INTO hs: every one
+                // of its 48 MFMAs then rounded the accumulator at the size of h, not of the product -- 2 u |h| per block
+                // where eager fp32 adds 0.3 u |h|, DESIGN.md section 4 "K14 / K10: how they are tested".)  relu(a), the
+                // second Linear's input, is stored from u on the way.
+                // (h, u and the accumulator are 192 registers: the last tile of h waits in the wave's 4 KB of LDS behind the
+                //  store images, so that nothing spills -- scratch traffic may not share the counter of the ring)
+                vec4f* park = reinterpret_cast<vec4f*>(lds_dyn + kTrainRing * kStageVec4 * 4 + (kBlock / kWave) * kTrainTileFloats) +
+                              wave * (4 * kWave) + lane_here;
+#pragma unroll
+                for (int q4 = 0; q4 < 4; ++q4)
+                    park[q4 * kWave] = vec4f{hs[3][4 * q4], hs[3][4 * q4 + 1], hs[3][4 * q4 + 2], hs[3][4 * q4 + 3]};
+                f32x16 v[4];
+#pragma unroll
+                for (int t = 0; t < 4; ++t) zero_tile(v[t]);
+                gemm_from_tiles<true>(v, u, sm, lane, in1, row, half, stage, &ma);
                 pm[(int64_t)(2 * blk + 1) * (a.batch << 1)] = ((unsigned long long)ma.hi << 32) | ma.lo;
+#pragma unroll
+                for (int q4 = 0; q4 < 4; ++q4) {
+                    const vec4f w = park[q4 * kWave];
+                    hs[3][4 * q4] = w.x;
+                    hs[3][4 * q4 + 1] = w.y;
+                    hs[3][4 * q4 + 2] = w.z;
+                    hs[3][4 * q4 + 3] = w.w;
+                }
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    add_bias_tile(v[t], bias + 128 + t * 32);
+#pragma unroll
+                    for (int q = 0; q < 16; ++q) hs[t][q] += v[t][q];   // the skip connection
+                }
             }
             bias += 256;
         }
@@ -531,11 +567,6 @@ __device__ __forceinline__ void apply_mask(f32x16& acc, const Mask64& m, int t) 
     const unsigned w = (t < 2 ? m.lo : m.hi) >> (16 * (t & 1));
 #pragma unroll
     for (int q = 0; q < 16; ++q) acc[q] = ((w >> q) & 1u) ? acc[q] : 0.0f;
-}
-
-__device__ __forceinline__ void zero_tile(f32x16& acc) {
-#pragma unroll
-    for (int q = 0; q < 16; ++q) acc[q] = 0.0f;
 }
 
 template <int NB, bool FINAL = false>   // number of blocks (their masks live in registers): 0 .. 3 (four would spill: no
@@ -876,7 +907,9 @@ extern "C" int nfa_resnet_hidden_forward_f32(const float* identity_inputs, const
     a.grad_hidden = nullptr;
     a.final_ksteps = a.final_first = 0;
     a.num_stages = init_ks + 16 * num_blocks + 2 * a.final_tiles;
-    const size_t lds = (size_t)kTrainRing * kStageVec4 * 16 + (size_t)(kBlock / kWave) * kTrainTileFloats * sizeof(float);
+    // the ring, every wave's store image and every wave's parked tile of h (4 KB): 70 KB, two workgroups per CU
+    const size_t lds = (size_t)kTrainRing * kStageVec4 * 16 + (size_t)(kBlock / kWave) * kTrainTileFloats * sizeof(float) +
+                       (size_t)(kBlock / kWave) * 4 * kWave * 16;
     hipStream_t st = (hipStream_t)stream;
     void (*kern)(const TrainArgs) = init_ks == 2 ? resnet_hidden_forward_kernel<2> : resnet_hidden_forward_kernel<4>;
     return launch_kernel(kern, train_grid(batch), dim3(kBlock), lds, st, a, 0, false);
