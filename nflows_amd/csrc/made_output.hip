@@ -11,7 +11,8 @@
 // any number of features.  A wave owns 32 samples, hidden^T (split into three bf16 pieces once) is the MFMA B
 // operand and stays in registers, the weights -- masked, re-tiled and split by the host (ops.pack_made_output) --
 // are the A operand, shared by the four waves of a workgroup through a double-buffered LDS tile; six bf16 products
-// per fp32 multiply-add (hi*hi, hi*mid, mid*hi, hi*lo, lo*hi, mid*mid: fp32 accuracy, full fp32 range).  The rows
+// per fp32 multiply-add (hi*hi, hi*mid, mid*hi, hi*lo, lo*hi, mid*mid: fp32 accuracy, full fp32 range; the five small
+// ones on an accumulator of their own, added once per tile).  The rows
 // of a group of four features are ordered so that the 48 accumulator values of a lane are the 24 + 24 logits of
 // its two features (ops._k7_row_order): the spline is evaluated straight from the accumulators.
 //
@@ -165,7 +166,7 @@ __global__ void __launch_bounds__(kBlock, 1) rqs_made_output_kernel(const MadeOu
             const int f = (g0 + g + 2 + (j >> 1)) * 4 + half * 2 + (j & 1);
             xnext[j] = xrow[f < last ? f : last];
         }
-        f32x16 acc[3];
+        f32x16 acc[3], small[3];
 #pragma unroll
         for (int u = 0; u < 6; ++u) {   // six tiles = two groups: the LDS buffers alternate statically
             const int t = u % 3;
@@ -176,6 +177,13 @@ __global__ void __launch_bounds__(kBlock, 1) rqs_made_output_kernel(const MadeOu
             bf16x8 ah = __builtin_bit_cast(bf16x8, cur[(0 * 16) * 64]);
             bf16x8 am = __builtin_bit_cast(bf16x8, cur[(1 * 16) * 64]);
             bf16x8 al = __builtin_bit_cast(bf16x8, cur[(2 * 16) * 64]);
+            // the five small products of a k-step accumulate in `small`, the leading one alone onto the bias (K11's
+            // NFA_MFMA6_SPLIT): with all six on one accumulator a 256-column logit took 96 roundings at the sum's own
+            // magnitude -- twice that on the hardware, which rounds the two lane halves' eight columns one after the
+            // other -- and sat 1.8 - 2.5 x as far from float64 as a plain fp32 product (tests/ar_spline_cases.py)
+            // (one `small` per tile, added where the group's accumulators are consumed: an add behind every tile's last MFMA
+            //  would wait for it in front of the next tile's first)
+            small[t] = f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #ifdef NFA_K13_ABL_NO_MFMA
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
@@ -188,8 +196,8 @@ __global__ void __launch_bounds__(kBlock, 1) rqs_made_output_kernel(const MadeOu
                 const bf16x8 nh = __builtin_bit_cast(bf16x8, cur[(0 * 16 + kn) * 64]);
                 const bf16x8 nm = __builtin_bit_cast(bf16x8, cur[(1 * 16 + kn) * 64]);
                 const bf16x8 nl = __builtin_bit_cast(bf16x8, cur[(2 * 16 + kn) * 64]);
-                // smallest products first
-                NFA_MFMA6(acc[t], ah, am, al, bh[ks], bm[ks], bl[ks]);   // (bf16x3_gemm.hpp: product order)
+                // the leading product onto `acc`, the five small ones (smallest first) onto `small`
+                NFA_MFMA6_SPLIT(acc[t], small[t], ah, am, al, bh[ks], bm[ks], bl[ks]);   // (fused_common.hpp: product order)
                 ah = nh;
                 am = nm;
                 al = nl;
@@ -200,6 +208,10 @@ __global__ void __launch_bounds__(kBlock, 1) rqs_made_output_kernel(const MadeOu
                 const int gg = g + u / 3;
                 const int f0 = (g0 + gg) * 4 + half * 2;
                 const bool has0 = f0 < a.nf, has1 = f0 + 1 < a.nf;
+#pragma unroll
+                for (int tt = 0; tt < 3; ++tt)
+#pragma unroll
+                    for (int q = 0; q < 16; ++q) acc[tt][q] += small[tt][q];
                 NFA_K7_FEATURE_A(pa, acc[0], acc[1]);
                 NFA_K7_FEATURE_B(pb, acc[1], acc[2]);
                 float y0, l0, y1, l1;

@@ -1351,15 +1351,19 @@ def pack_made_schedule(net, sequential_steps, params_per_feature, block_cap=None
     return (torch.cat(blocks).contiguous().to(dev), torch.tensor(block_at, dtype=torch.int32, device=dev), layout)
 
 
-def made_rqs_inverse(inputs, schedule, hidden_features, sequential_steps, spec):
+def made_rqs_inverse(inputs, schedule, hidden_features, sequential_steps, spec, out=None):
     """K12 -- the sequential features of the autoregressive spline inverse in one persistent kernel.
     Returns (outputs [B, D] with columns < sequential_steps filled, their logabsdet [B], hidden [B, H]),
-    or None outside the kernel's shape family."""
+    or None outside the kernel's shape family.  `out`: the [B, D] buffer to fill (the other columns are left as
+    they are)."""
     N.require_device_f32("inputs", inputs, 2)
     dev = inputs.device
     B, D = inputs.shape
     z = inputs.detach().contiguous()
-    out = torch.empty_like(z)
+    if out is None:
+        out = torch.empty_like(z)
+    elif (out.dtype != torch.float32 or out.device != dev or tuple(out.shape) != (B, D) or not out.is_contiguous()):
+        raise ValueError("out must be a contiguous float32 [batch, features] tensor on the inputs' device")
     lad = torch.empty(B, dtype=torch.float32, device=dev)
     hidden = torch.empty(B, hidden_features, dtype=torch.float32, device=dev)
     floats, ints, layout = schedule
