@@ -2827,6 +2827,7 @@ K8C_ALWAYS = os.environ.get("NFA_K8C", "1") == "2"
 K8X_FORMS = {"auto": 0, "narrow": 1, "wide": 2}
 K8X_FORM = K8X_FORMS[os.environ.get("NFA_K8X_FORM", "auto")]
 _cu_counts = {}
+TILE16 = {"k8h": 0, "k8s": 1, "k8c": 2}   # the two-piece engines by their use_tile16 mode
 
 
 def use_tile16(batch, num_bins, context, device, activation=0):

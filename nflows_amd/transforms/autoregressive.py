@@ -153,13 +153,11 @@ class AutoregressiveTransform(Transform):
         degree <= d, i.e. features 0 .. d - 1)."""
         # (one device read per cache epoch: `degrees` / `mask` are registered buffers, a load_state_dict from a
         #  checkpoint with other random masks replaces them and advances the epoch)
-        cached = self.__dict__.get("_sequential_steps_cache")
-        if cached is None or cached[0] != _cache.epoch():
+        def read():
             net = self.autoregressive_net
             degrees = [net.initial_layer.degrees] + [b.degrees for b in net.blocks]
-            cached = (_cache.epoch(), int(max(int(d.max()) for d in degrees)))
-            self.__dict__["_sequential_steps_cache"] = cached
-        return cached[1]
+            return int(max(int(d.max()) for d in degrees))
+        return _cache.keyed(self, "_sequential_steps_cache", (_cache.epoch(),), read)
 
     def _output_dim_multiplier(self):
         raise NotImplementedError()
@@ -217,10 +215,9 @@ class MaskedAffineAutoregressiveTransform(AutoregressiveTransform):
         """(hidden Linears, residual blocks?) of a MADE that K22 runs inside the layer kernel -- plain MADE, hidden width
         <= 128, at most 64 features and 64 context features, no batch norm --, or None.  Read once per cache epoch;
         the activations and the dropouts are plain attributes and are read on every call."""
-        held = self.__dict__.get("_conditioner_shape_held")
         net = self._conditioner()
-        if held is None or held[0] != _cache.epoch() or held[1] is not net:
-            shape = None
+
+        def read():
             if type(net) is made_module.MADE and self.features <= 64:
                 hidden, features = net.initial_layer.weight.shape
                 ce = net.context_layer.weight.shape[1] if hasattr(net, "context_layer") else 0
@@ -228,10 +225,9 @@ class MaskedAffineAutoregressiveTransform(AutoregressiveTransform):
                         and net.final_layer.weight.shape[0] == 2 * features
                         and not any(isinstance(m, torch.nn.BatchNorm1d) for m in net.modules())):
                     residual = bool(net.use_residual_blocks)
-                    shape = (len(net.blocks) * (2 if residual else 1), residual)
-            held = (_cache.epoch(), net, shape)
-            self.__dict__["_conditioner_shape_held"] = held
-        shape = held[2]
+                    return len(net.blocks) * (2 if residual else 1), residual
+            return None
+        shape = _cache.keyed(self, "_conditioner_shape_held", (_cache.epoch(), net), read)
         if shape is not None:
             relu = (F.relu, torch.relu)
             if net.__dict__.get("activation") not in relu or not all(
@@ -273,13 +269,9 @@ class MaskedAffineAutoregressiveTransform(AutoregressiveTransform):
     identity_features = property(_all_columns)
 
     def _packed_mlp(self):
-        from .coupling import _weights_key
         net = self._conditioner()
-        key = _weights_key(self, net)   # (parameters and buffers: the masks are part of the key)
-        cached = self.__dict__.get("_packed_made_cache")
-        if cached is None or cached[0] != key:
-            cached = self.__dict__["_packed_made_cache"] = (key, ops.pack_made_conditioner(net))
-        return cached[1]
+        key = _cache.weights_key(self, net)   # (parameters and buffers: the masks are part of the key)
+        return _cache.keyed(self, "_packed_made_cache", key, lambda: ops.pack_made_conditioner(net))
 
     def forward(self, inputs, context=None):
         if (torch.is_tensor(inputs) and inputs.dim() == 2 and inputs.dtype == torch.float32 and inputs.is_cuda
@@ -327,16 +319,13 @@ class MaskedAffineAutoregressiveTransform(AutoregressiveTransform):
     def _inverse_kernel_net(self):
         """The MADE when K23 can run it -- plain MADE, ReLU, no batch norm, no active dropout, at most 12 Linears --, else
         None.  The structure is read once per cache epoch; activations and dropouts are plain attributes, read per call."""
-        held = self.__dict__.get("_inverse_net_held")
         net = self._conditioner()
-        if held is None or held[0] != _cache.epoch() or held[1] is not net:
-            ok = (type(net) is made_module.MADE and self.features >= 2
-                  and net.initial_layer.weight.shape[1] == self.features
-                  and net.final_layer.weight.shape[0] == 2 * self.features
-                  and len(ops._made_linears(net)) <= ops.MADE_MAX_LINEARS
-                  and not any(isinstance(m, torch.nn.BatchNorm1d) for m in net.modules()))
-            held = self.__dict__["_inverse_net_held"] = (_cache.epoch(), net, ok)
-        if not held[2]:
+        if not _cache.keyed(self, "_inverse_net_held", (_cache.epoch(), net), lambda: (
+                type(net) is made_module.MADE and self.features >= 2
+                and net.initial_layer.weight.shape[1] == self.features
+                and net.final_layer.weight.shape[0] == 2 * self.features
+                and len(ops._made_linears(net)) <= ops.MADE_MAX_LINEARS
+                and not any(isinstance(m, torch.nn.BatchNorm1d) for m in net.modules()))):
             return None
         relu = (F.relu, torch.relu)
         if net.__dict__.get("activation") not in relu or not all(
@@ -346,18 +335,15 @@ class MaskedAffineAutoregressiveTransform(AutoregressiveTransform):
 
     def _inverse_kernel_plan(self, net):
         """(step blocks of `ops.pack_made_schedule` or None where the shape does not fit the LDS, packed context Linears
-        or None), kept until a parameter, a mask or a write through `.data` changes (`coupling._weights_key`)."""
-        from .coupling import _weights_key
-        key = _weights_key(self, net)
-        cached = self.__dict__.get("_made_affine_cache")
-        if cached is None or cached[0] != key:
+        or None), kept until a parameter, a mask or a write through `.data` changes (`_cache.weights_key`)."""
+        def pack():
             hidden = net.initial_layer.weight.shape[0]
             linears = len(ops._made_linears(net))
             vectors = len(ops.made_context_layers(net))
             cap = ops.made_block_cap(self.features, hidden, linears, vectors)
             schedule = ops.pack_made_schedule(net, self.features, 2, block_cap=cap, context=True) if cap > 0 else None
-            cached = self.__dict__["_made_affine_cache"] = (key, schedule, ops.pack_made_context(net) if schedule else None)
-        return cached[1], cached[2]
+            return schedule, ops.pack_made_context(net) if schedule else None
+        return _cache.keyed(self, "_made_affine_cache", _cache.weights_key(self, net), pack)
 
     def inverse(self, inputs, context=None):
         cls = type(self)
@@ -494,16 +480,14 @@ class MaskedPiecewiseRationalQuadraticAutoregressiveTransform(AutoregressiveTran
                 and not any(isinstance(m, torch.nn.BatchNorm1d) for m in net.modules())):
             return None
         key = (_cache.epoch(), sequential) + tuple((p.data_ptr(), p._version) for p in net.parameters())
-        cached = self.__dict__.get("_made_schedule_cache")
-        if cached is None or cached[0] != key:
-            cached = (key, ops.pack_made_schedule(net, sequential, self._output_dim_multiplier()))
-            self.__dict__["_made_schedule_cache"] = cached
+        schedule = _cache.keyed(self, "_made_schedule_cache", key,
+                                lambda: ops.pack_made_schedule(net, sequential, self._output_dim_multiplier()))
         spec = ops.make_rqs_spec(self.num_bins, self.tails, tail_bound=self.tail_bound,
                                  min_bin_width=self.min_bin_width, min_bin_height=self.min_bin_height,
                                  min_derivative=self.min_derivative,
                                  wh_divisor=float(np.sqrt(net.hidden_features)) if hasattr(net, "hidden_features") else 0.0)
         hidden_features = net.initial_layer.weight.shape[0]
-        return ops.made_rqs_inverse(inputs, cached[1], hidden_features, sequential, spec)
+        return ops.made_rqs_inverse(inputs, schedule, hidden_features, sequential, spec)
 
     def _inverse_column(self, column, params):
         """One feature: params [B, P]; the spline layer kernel with a single (transformed) feature."""

@@ -20,6 +20,7 @@ import torch
 from torch import nn
 
 from .. import _cache
+from .. import ops
 from ..errors import InputOutsideDomain, InverseNotAvailable  # noqa: F401  (re-exported)
 
 
@@ -73,7 +74,12 @@ def _layer_state(units):
 
 class _Run(list):
     """The units [(coupling, permutation or None)] of a run, with what is the same on every call kept beside
-    them: the run's padded geometry (ops.fused_geometry over its layers)."""
+    them: the run's padded geometry (ops.fused_geometry over its layers) and how its weights are followed
+    (_cache.RunWeights)."""
+
+    def __init__(self, units):
+        super().__init__(units)
+        self._weights = _cache.RunWeights([c for c, _ in self])
 
     def geometry(self):
         held = self.__dict__.get("_geometry")
@@ -82,108 +88,11 @@ class _Run(list):
             self.__dict__["_geometry"] = held
         return held
 
-    # ---- the weights of the whole run in one flat pass (round 4).  coupling._weights_key layer by layer cost ~10 us per
-    #      layer and call -- 0.3-0.4 ms per `log_prob` of a 32-layer flow, more than the kernel takes on 8 192 rows: the
-    #      small-batch figures of bench.py were the HOST's.  Same signs as _weights_key (epoch, identity of every held
-    #      object in its module's dict, version counters, storage pointers), read from lists made once per epoch.
-    def _flatten(self, epoch):
-        from .coupling import _held_parameters
-        nets = [c._conditioner() for c, _ in self]
-        per_layer = [_held_parameters(net) for net in nets]
-        entries = [e for held in per_layer for e in held]
-        bounds, at = [], 0
-        for held in per_layer:
-            bounds.append((at, at + len(held)))
-            at += len(held)
-        flat = (epoch, nets, entries, [p for _, _, p in entries], bounds)
-        self.__dict__["_flat"] = flat
-        return flat
-
     def weights_fingerprint(self):
-        from .. import _cache
-        from . import coupling
-        epoch = _cache.epoch()
-        flat = self.__dict__.get("_flat")
-        if flat is None or flat[0] != epoch or not _cache.HOOKED:
-            flat = self._flatten(epoch)
-        else:
-            for (c, _), net in zip(self, flat[1]):
-                if c._conditioner() is not net:
-                    flat = self._flatten(epoch)
-                    break
-            else:
-                for d, name, p in flat[2]:
-                    if d.get(name) is not p:
-                        flat = self._flatten(epoch)
-                        break
-        params = flat[3]
-        key = (epoch, tuple([p._version for p in params]), tuple([p.data_ptr() for p in params]))
-        every = coupling.VERIFY_WEIGHTS_EVERY
-        de = _cache.data_epoch()
-        if self.__dict__.get("_data_seen") != de:
-            # the `.data` of a watched parameter was touched since the run last looked (or this is its first use): every
-            # layer's record is brought up to date -- ONE checksum over all parameters of the run, one synchronising
-            # comparison; layers whose contents changed under an unchanged visible key get a new `_data_salt`
-            if not coupling._capturing(params):
-                self.__dict__["_data_seen"] = de
-                self._recheck_run(flat, key, de)
-        elif every and params and not coupling._capturing(params):
-            # the periodic check: one layer at a time, every layer once per `every` calls (no call pays for all of them)
-            n = self.__dict__["_verify_calls"] = self.__dict__.get("_verify_calls", 0) + 1
-            stride = max(1, every // len(self))
-            if n % stride == 0:
-                i = (n // stride) % len(self)
-                lo, hi = flat[4][i]
-                coupling._track_contents(self[i][0], "_contents_run", (epoch, key[1][lo:hi], key[2][lo:hi]), params[lo:hi],
-                                         periodic=False, compare_now=True)
-        return key + (tuple([c.__dict__.get("_data_salt", 0) for c, _ in self]),)
-
-    def _recheck_run(self, flat, key, de):
-        """A `.data` event (or the run's first use): per layer, contents on record under the layer's current visible key are
-        compared with the contents now -- a difference, or no such record (the key moved since: nothing to compare with),
-        advances the layer's `_data_salt`, i.e. its packs are rebuilt from the current values --, and the records are renewed."""
-        from . import coupling
-        params, bounds = flat[3], flat[4]
-        now = coupling._checksum(params)
-        verdicts, rows = [], []
-        for i, ((c, _), (lo, hi)) in enumerate(zip(self, bounds)):
-            sub = (flat[0], key[1][lo:hi], key[2][lo:hi])
-            state = c.__dict__.get("_contents_run")
-            if state is not None and state[0] == sub and state[1].shape[0] == hi - lo:
-                verdicts.append((state[1] == now[lo:hi]).all())
-                rows.append(i)
-            else:
-                c.__dict__["_data_salt"] = c.__dict__.get("_data_salt", 0) + 1
-            c.__dict__["_contents_run"] = [sub, now[lo:hi], 0, de]
-            layer_record = c.__dict__.get("_contents")      # (the layer's own record, coupling._weights_key: same event,
-            if layer_record is not None:                     #  same contents -- it must not answer it a second time)
-                layer_record[1], layer_record[3] = now[lo:hi], de
-        if rows:
-            for same, i in zip(torch.stack(verdicts).cpu().tolist(), rows):    # (the one synchronisation)
-                if not same:
-                    c = self[i][0]
-                    c.__dict__["_data_salt"] = c.__dict__.get("_data_salt", 0) + 1
+        return self._weights.fingerprint()
 
     def verify_before_packing(self):
-        """Called on every plan-cache miss, before the layers' packed weights are looked up.  A miss does not mean the
-        weights changed visibly -- the first inverse call, a batch that crosses the 16-sample-tile threshold, an evicted
-        plan -- and the per-layer packs are keyed on version counters, storage pointers and the `.data` salt: a write that
-        announced itself through none of them since the last pack would be packed into the NEW plan from the OLD blobs.
-        So: a layer whose key is the one its checksum was recorded under is COMPARED now (StalePackedWeights on a
-        difference); a layer with a new key gets its checksum recorded."""
-        from . import coupling
-        if not coupling.VERIFY_WEIGHTS_EVERY:
-            return
-        flat = self.__dict__.get("_flat")
-        if flat is None:
-            return
-        params = flat[3]
-        if coupling._capturing(params):
-            return
-        versions, ptrs = tuple([p._version for p in params]), tuple([p.data_ptr() for p in params])
-        for (c, _), (lo, hi) in zip(self, flat[4]):
-            coupling._track_contents(c, "_contents_run", (flat[0], versions[lo:hi], ptrs[lo:hi]), params[lo:hi],
-                                     periodic=False, compare_now=True)
+        self._weights.verify_before_packing()
 
 
 def _permutation_key(p):
@@ -192,12 +101,11 @@ def _permutation_key(p):
 
 
 def _run_weights_fingerprint(units):
-    """What `_run_plan` keys the run's packed weights on: `_Run.weights_fingerprint()` -- one flat pass over the run --
-    or, for a plain list of units, the per-layer keys."""
+    """What `_run_plan` keys the run's packed weights on: `_Run.weights_fingerprint()` -- one flat pass over the run
+    (_cache.RunWeights) -- or, for a plain list of units, the per-layer keys."""
     if isinstance(units, _Run):
         return units.weights_fingerprint()
-    from .coupling import _weights_key
-    return tuple([_weights_key(c, c._conditioner()) for c, _ in units])
+    return tuple([_cache.weights_key(c, c._conditioner()) for c, _ in units])
 
 
 def _run_geometry(units):
@@ -312,7 +220,6 @@ class CompositeTransform(Transform):
         """Concatenated weight / bias blobs and the composed tables of a run, cached until a weight or a
         permutation changes.  (weights, biases, tables, f16 stream or None, K8x's (weights, biases, scales) or None);
         `tile16`: the mode of the f16 stream (ops.use_tile16)."""
-        from .. import ops
         first = units[0][0]
         mlp = first._run_signature()[0] in ("k11", "k22")
         geometry = _run_geometry(units)   # one padded geometry for the run
@@ -362,8 +269,6 @@ class CompositeTransform(Transform):
     def _run_fused(self, units, inputs, total, context, inverse, standard_normal_log_prob=False):
         """One launch for the run (ragged batches are padded to full 128-row blocks inside `ops`).  Returns
         the outputs (or log_prob with `standard_normal_log_prob`), or None when the kernel declines."""
-        from .. import ops
-        from .coupling import _TILE16
         first = units[0][0]
         for _, p in units:
             if p is not None:
@@ -386,7 +291,7 @@ class CompositeTransform(Transform):
                 residual_blocks=residual_blocks)
         else:
             # (batches that give a CU at most one 128-row block: the 16-sample-tile kernels K8s / K8c and their own stream)
-            head = first._whole_layer_cascade(lambda engine: self._run_plan(units, inverse, _TILE16.get(engine, 0)), geometry,
+            head = first._whole_layer_cascade(lambda engine: self._run_plan(units, inverse, ops.TILE16.get(engine, 0)), geometry,
                                               inputs, context, inverse, total, len(units), standard_normal_log_prob)
         if head is None:
             return None

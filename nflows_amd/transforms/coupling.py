@@ -26,140 +26,11 @@ from .. import _cache
 from .. import autograd as _autograd
 from .. import _native as N
 from .. import ops
+from .._cache import StalePackedWeights  # noqa: F401  (re-exported: the path users catch it by)
 from ..utils import torchutils
 from .base import Transform
 from . import splines
 from .splines import rational_quadratic
-
-
-def _held_parameters(net):
-    """[(the `_parameters` / `_buffers` dict of a leaf module, name, tensor)] of every parameter and buffer of `net`
-    (buffers: the running statistics of batch-norm layers, folded into the packed weights).  The parameters are re-classed
-    as _cache.WatchedParameter on the way: their `.data` then reports its use (writes through it reach no version counter)."""
-    params = [(m._parameters, name, p) for m in net.modules() for name, p in m._parameters.items() if p is not None]
-    for _, _, p in params:
-        _cache.watch(p)
-    return params + [(m._buffers, name, b) for m in net.modules() for name, b in m._buffers.items() if b is not None]
-
-
-class StalePackedWeights(RuntimeError):
-    """NFA_VERIFY_WEIGHTS: a conditioner's weights changed without any of the signs the packed-weight caches look at --
-    version counters, storage pointers, registrations, and (round 6) the `.data` of its Parameters (_cache.WatchedParameter):
-    a write into raw storage, through a view's `.data`, by a foreign kernel.  The fused kernels have been using the OLD
-    weights; `nflows_amd.invalidate_packed_weights()` after such writes is the remedy."""
-
-
-# How the packed weights follow the parameters (round 6).
-#   visible changes   in-place updates (version counters), rebound storage (data_ptr), (re)registered objects,
-#                     load_state_dict / .to() (cache epoch): part of every weight key, the packs are rebuilt.
-#   `.data`           reading or assigning the `.data` of a conditioner Parameter advances _cache.data_epoch(); the next
-#                     use of a weight key compares the parameters' CONTENTS with the checksum recorded when the key was new
-#                     (one synchronising comparison per layer, or one for a whole run) and, on a difference, advances the
-#                     layer's `_data_salt` -- part of the key: repacked from the new values, nothing raised, and no call
-#                     without such an event pays anything.
-#   everything else   NFA_VERIFY_WEIGHTS=N (default 256; 0 = off, 1 = every use): every N-th use of a key repeats the
-#                     comparison, staggered over the layers, and raises StalePackedWeights; also on every plan-cache miss of
-#                     a run (_Run.verify_before_packing).  Skipped while a stream is being captured into a HIP graph.
-VERIFY_WEIGHTS_EVERY = int(os.environ.get("NFA_VERIFY_WEIGHTS", "256") or 0)
-
-_CHECKSUM_LAYOUTS = {}
-
-
-def _checksum(params):
-    """int64 [len(params)] on the parameters' device: per parameter the sum over its elements of (bit pattern as int32) x (an
-    odd multiplier that depends on the position), modulo 2^64 -- exact, sensitive to the sign and the position of every
-    element (round 5's fp32 norms were blind to a sign flip of a small entry), NaNs included (a bit pattern like any
-    other).  fp32 parameters on one device: one concatenation, one multiply, one segmented sum; no synchronisation."""
-    with torch.no_grad():
-        params = [p.detach() for p in params]
-        if not params:
-            return torch.zeros(0, dtype=torch.int64)
-        if not (all(p.dtype == torch.float32 for p in params) and len({p.device for p in params}) == 1):
-            return torch.stack([(p.double().reshape(-1).view(torch.int64) >> 7).sum().cpu() + p.numel() for p in params])
-        dev = params[0].device
-        sizes = tuple(p.numel() for p in params)
-        layout = _CHECKSUM_LAYOUTS.get((dev, sizes))
-        if layout is None:
-            if len(_CHECKSUM_LAYOUTS) > 64:
-                _CHECKSUM_LAYOUTS.clear()
-            sz = torch.tensor(sizes, device=dev)
-            seg = torch.repeat_interleave(torch.arange(len(sizes), device=dev), sz)
-            # (the position INSIDE the parameter: a parameter's checksum does not depend on what it is concatenated with)
-            at = torch.arange(sum(sizes), dtype=torch.int64, device=dev) - (torch.cumsum(sz, 0) - sz)[seg]
-            mult = ((at * 2654435761) % 2147483647) * 2 + 1
-            layout = _CHECKSUM_LAYOUTS[(dev, sizes)] = (mult, seg)
-        mult, seg = layout
-        bits = torch.cat([p.reshape(-1) for p in params]).view(torch.int32).to(torch.int64)
-        return torch.zeros(len(sizes), dtype=torch.int64, device=dev).index_add_(0, seg, bits * mult)
-
-
-def _same_checksum(a, b):
-    return a.shape == b.shape and bool(torch.equal(a, b))    # (synchronises)
-
-
-def _capturing(params):
-    return bool(params) and params[0].is_cuda and torch.cuda.is_current_stream_capturing()
-
-
-def _stale(owner):
-    return StalePackedWeights(
-        "the parameters of %s changed through a write the packed-weight caches cannot see (raw storage, a view's `.data`, a "
-        "foreign kernel): call nflows_amd.invalidate_packed_weights() after such writes" % type(owner).__name__)
-
-
-def _track_contents(owner, slot, key, params, periodic=True, compare_now=False):
-    """The record `owner.__dict__[slot]` = [visible key, checksum of the contents when the key was new, use count, data epoch]
-    and what is done with it: a new key records (no synchronisation); a `.data` event since the record compares and, on a
-    difference, advances `_data_salt` (repack, no exception); `periodic` counts uses and compares every
-    NFA_VERIFY_WEIGHTS-th (`compare_now`: at once) -- a difference there is a write nothing announced: StalePackedWeights."""
-    de = _cache.data_epoch()
-    state = owner.__dict__.get(slot)
-    if state is None or state[0] != key:
-        # (the count starts at a per-layer offset: the layers of a flow are used once per call each, and 32 synchronising
-        #  comparisons landing in ONE call were a 3 ms spike every 256th step)
-        owner.__dict__[slot] = [key, _checksum(params), (id(owner) >> 6) % max(1, VERIFY_WEIGHTS_EVERY), de]
-        return
-    if state[3] != de:
-        if _capturing(params):
-            return
-        state[3] = de
-        now = _checksum(params)
-        if not _same_checksum(now, state[1]):
-            state[1] = now
-            owner.__dict__["_data_salt"] = owner.__dict__.get("_data_salt", 0) + 1
-        return
-    if not VERIFY_WEIGHTS_EVERY or _capturing(params):
-        return
-    if periodic:
-        state[2] += 1
-    if (compare_now or (periodic and state[2] % VERIFY_WEIGHTS_EVERY == 0)) and not _same_checksum(_checksum(params), state[1]):
-        owner.__dict__.pop(slot, None)
-        raise _stale(owner)
-
-
-def _weights_key(owner, net):
-    """Fingerprint of a conditioner's weights for the packed-weight caches: storage pointers and version counters of its
-    parameters, read from a list made once per cache epoch (walking `net.parameters()` costs ~10 us per call and layer: a
-    millisecond per `log_prob` of a 32-layer flow), and the layer's `_data_salt` (see above: writes through `.data`).
-    In-place updates advance the counters; moves, `load_state_dict` and (re)registered Parameter objects advance the epoch
-    (_cache.py).  Swaps that bypass the registration hooks -- `torch.func.functional_call`,
-    `stateless._reparametrize_module`, a direct `module._parameters[name] = other` -- are caught by checking on every
-    call that each held object still IS the entry of its module's `_parameters` dict."""
-    epoch = _cache.epoch()
-    held = owner.__dict__.get("_weights_list")
-    if held is None or held[0] != epoch or held[1] is not net or not _cache.HOOKED:
-        held = (epoch, net, _held_parameters(net))
-        owner.__dict__["_weights_list"] = held
-    else:
-        for d, name, p in held[2]:
-            if d.get(name) is not p:
-                held = (epoch, net, _held_parameters(net))
-                owner.__dict__["_weights_list"] = held
-                break
-    # (data_ptr as well: `p.data = other` rebinds the storage without touching the counter)
-    key = (epoch,) + tuple([(p.data_ptr(), p._version) for _, _, p in held[2]])
-    _track_contents(owner, "_contents", key, [p for _, _, p in held[2]])
-    return key + (owner.__dict__.get("_data_salt", 0),)
 
 
 class CouplingTransform(Transform):
@@ -248,11 +119,7 @@ class CouplingTransform(Transform):
             return self.identity_features
         key = (perm.data_ptr(), perm._version, self.identity_features.data_ptr(),
                self.identity_features._version)
-        cached = getattr(self, "_id_cols_cache", None)
-        if cached is None or cached[0] != key:
-            cached = (key, perm[self.identity_features])
-            self._id_cols_cache = cached
-        return cached[1]
+        return _cache.keyed(self, "_id_cols_cache", key, lambda: perm[self.identity_features])
 
     def forward(self, inputs, context=None, in_perm=None, logabsdet_accumulator=None):
         """outputs[:, identity] = inputs[:, identity]; outputs[:, transform] = f(inputs[:, transform];
@@ -496,22 +363,20 @@ class AffineCouplingTransform(CouplingTransform):
         layers (nn/nets/mlp.py:47-68), or (round 5) a ResidualNet of width <= 128 with ReLU blocks, no context and no batch
         norm (nn/nets/resnet.py:55-100: the conditioner of the reference's own SimpleRealNVP, flows/realnvp.py:44-71) --,
         or None.  Read once per cache epoch (a swapped conditioner registers Parameters, which advances it)."""
-        held = self.__dict__.get("_conditioner_shape_held")
-        if held is None or held[0] != _cache.epoch():
+        def read():
             from ..nn.nets.mlp import MLP
             from ..nn.nets.resnet import ResidualNet
-            net, shape = self.transform_net, None
+            net = self.transform_net
             if type(net) is MLP:
                 if (net._activation is torch.nn.functional.relu and not net._activate_output
                         and all(h <= 128 for h in net._hidden_sizes)):
-                    shape = (len(net._hidden_layers), False)
+                    return len(net._hidden_layers), False
             elif type(net) is ResidualNet:
                 if (net.context_features is None and net.hidden_features <= 128
                         and not any(b.use_batch_norm for b in net.blocks)):
-                    shape = (2 * len(net.blocks), True)
-            held = (_cache.epoch(), shape)
-            self.__dict__["_conditioner_shape_held"] = held
-        shape = held[1]
+                    return 2 * len(net.blocks), True
+            return None
+        shape = _cache.keyed(self, "_conditioner_shape_held", (_cache.epoch(),), read)
         if shape is not None and shape[1]:   # (a block's activation is a plain attribute: read on every call)
             relu = (torch.nn.functional.relu, torch.relu)
             if not all(b.__dict__.get("activation") in relu for b in self.transform_net.blocks):
@@ -529,13 +394,9 @@ class AffineCouplingTransform(CouplingTransform):
 
     def _packed_mlp(self):
         net = self.transform_net
-        key = _weights_key(self, net)
-        cached = getattr(self, "_packed_mlp_cache", None)
-        if cached is None or cached[0] != key:
-            cached = (key, ops.pack_mlp_conditioner(net, self.num_transform_features,
-                                                    additive=self._activation_code() == N.SCALE_ADDITIVE))
-            self._packed_mlp_cache = cached
-        return cached[1]
+        return _cache.keyed(self, "_packed_mlp_cache", _cache.weights_key(self, net),
+                            lambda: ops.pack_mlp_conditioner(net, self.num_transform_features,
+                                                             additive=self._activation_code() == N.SCALE_ADDITIVE))
 
     def _generic_float64(self, inputs, context, inverse, logabsdet_accumulator):
         """float64 vectors: the reference's expressions (coupling.py:73-130, :228-252) as tensor operations on
@@ -645,16 +506,7 @@ class PiecewiseCouplingTransform(CouplingTransform):
         return self._piecewise_cdf(inputs, transform_params, inverse)
 
 
-_TILE16 = {"k8h": 0, "k8s": 1, "k8c": 2}   # the two-piece engines by their ops.use_tile16 mode
 _F16_PACK_SLOTS = ("_packed_resnet_f16_cache", "_packed_resnet_f16s_cache", "_packed_resnet_f16c_cache")   # K8h, K8s, K8c
-
-
-def _cached_pack(owner, slot, key, pack):
-    """`pack()`, kept in `owner.__dict__[slot]` with `key` and made again when the key changes"""
-    cached = owner.__dict__.get(slot)
-    if cached is None or cached[0] != key:
-        cached = owner.__dict__[slot] = (key, pack())
-    return cached[1]
 
 
 class PiecewiseRationalQuadraticCouplingTransform(PiecewiseCouplingTransform):
@@ -731,12 +583,8 @@ class PiecewiseRationalQuadraticCouplingTransform(PiecewiseCouplingTransform):
         """(padded features, transformed features, identity features, pad value) the whole-layer kernels are
         given for this layer -- or for the run of this layer and `others` (ops.fused_geometry)."""
         if not others:   # (asked several times per call and layer: kept per tail bound)
-            held = self.__dict__.get("_own_geometry")
-            if held is None or held[0] != self.tail_bound:
-                held = (self.tail_bound, ops.fused_geometry(
-                    self.features, [(self.num_transform_features, self.num_identity_features)], self.tail_bound))
-                self.__dict__["_own_geometry"] = held
-            return held[1]
+            return _cache.keyed(self, "_own_geometry", self.tail_bound, lambda: ops.fused_geometry(
+                self.features, [(self.num_transform_features, self.num_identity_features)], self.tail_bound))
         layers = [(c.num_transform_features, c.num_identity_features) for c in (self,) + tuple(others)]
         return ops.fused_geometry(self.features, layers, self.tail_bound)
 
@@ -775,12 +623,10 @@ class PiecewiseRationalQuadraticCouplingTransform(PiecewiseCouplingTransform):
     def _static_signature(self):
         """(features, residual blocks, context features) of the layer's conditioner: read once per cache epoch
         (a conditioner swapped for another one registers its Parameters, which advances the epoch)."""
-        held = self.__dict__.get("_static_sig")
-        if held is None or held[0] != _cache.epoch():
+        def read():
             net = self.transform_net
-            held = (_cache.epoch(), (self.features, len(getattr(net, "blocks", ())), getattr(net, "context_features", None)))
-            self.__dict__["_static_sig"] = held
-        return held[1]
+            return self.features, len(getattr(net, "blocks", ())), getattr(net, "context_features", None)
+        return _cache.keyed(self, "_static_sig", (_cache.epoch(),), read)
 
     def _resnet_eligible(self, context):
         net = self.transform_net
@@ -826,13 +672,11 @@ class PiecewiseRationalQuadraticCouplingTransform(PiecewiseCouplingTransform):
         net = self.transform_net
         if not any(b.use_batch_norm for b in net.blocks):
             return net
-        key = (tuple(b.training for b in net.blocks),) + _weights_key(self, net)
-        cached = self.__dict__.get("_folded_net_cache")
-        if cached is None or cached[0] != key:
+        key = (tuple(b.training for b in net.blocks),) + _cache.weights_key(self, net)
+        def fold():
             with torch.no_grad():
-                cached = (key, ops.fold_batch_norm(net))
-            self.__dict__["_folded_net_cache"] = cached
-        return cached[1]
+                return ops.fold_batch_norm(net)
+        return _cache.keyed(self, "_folded_net_cache", key, fold)
 
     # experiment switch: fold log2(e) into the width / height logits as well (one v_exp_f32 per
     # softmax numerator)
@@ -900,7 +744,7 @@ class PiecewiseRationalQuadraticCouplingTransform(PiecewiseCouplingTransform):
                 return res
         elif stream is not None:
             res = ops.rqs_coupling_resnet_f16(inputs, stream, (weights, biases), tables, dt4, di_u, nb, spec, inverse,
-                                              accumulate_into, context=context, tile16=_TILE16[engine], activation=act, **run)
+                                              accumulate_into, context=context, tile16=ops.TILE16[engine], activation=act, **run)
             if res is None and engine != "k8h":
                 stream = plan("k8h")[3]
                 if stream is not None:
@@ -913,8 +757,8 @@ class PiecewiseRationalQuadraticCouplingTransform(PiecewiseCouplingTransform):
     def _packed_resnet_f16x3(self, geometry=None):
         """(weights, biases, scales) for K8x (ops.pack_resnet_conditioner_f16x3), per weight key"""
         _, dt4, di_u, _ = geometry or self._fused_geometry()
-        key = (ops.K8X_ACT_SCALE, dt4, di_u) + _weights_key(self, self.transform_net)
-        return _cached_pack(self, "_packed_resnet_f16x3_cache", key,
+        key = (ops.K8X_ACT_SCALE, dt4, di_u) + _cache.weights_key(self, self.transform_net)
+        return _cache.keyed(self, "_packed_resnet_f16x3_cache", key,
                             lambda: ops.pack_resnet_conditioner_f16x3(self._folded_net(), self.num_transform_features,
                                                                       self._transform_dim_multiplier(),
                                                                       pad_transform_to=dt4, pad_identity_to=di_u))
@@ -923,8 +767,8 @@ class PiecewiseRationalQuadraticCouplingTransform(PiecewiseCouplingTransform):
         """(weights, parameter words) for K8h, or -- `tile16` = 1 / 2 (ops.use_tile16) -- for K8s / K8c (the 16-sample-tile
         kernels of small batches)."""
         _, dt4, di_u, _ = geometry or self._fused_geometry()
-        key = (self.conditioner_act_scale, dt4, di_u, tile16) + _weights_key(self, self.transform_net)
-        return _cached_pack(self, _F16_PACK_SLOTS[tile16], key,
+        key = (self.conditioner_act_scale, dt4, di_u, tile16) + _cache.weights_key(self, self.transform_net)
+        return _cache.keyed(self, _F16_PACK_SLOTS[tile16], key,
                             lambda: ops.pack_resnet_conditioner_f16(self._folded_net(), self.num_transform_features,
                                                                     self._transform_dim_multiplier(),
                                                                     act_scale=self.conditioner_act_scale,
@@ -947,8 +791,8 @@ class PiecewiseRationalQuadraticCouplingTransform(PiecewiseCouplingTransform):
 
     def _packed_resnet(self, geometry=None):
         _, dt4, di_u, _ = geometry or self._fused_geometry()
-        key = (dt4, di_u, self._log2e()) + _weights_key(self, self.transform_net)
-        return _cached_pack(self, "_packed_resnet_cache", key,
+        key = (dt4, di_u, self._log2e()) + _cache.weights_key(self, self.transform_net)
+        return _cache.keyed(self, "_packed_resnet_cache", key,
                             lambda: ops.pack_resnet_conditioner(self._folded_net(), self.num_transform_features,
                                                                 self._transform_dim_multiplier(), log2e=self._log2e(),
                                                                 pad_transform_to=dt4, pad_identity_to=di_u))
@@ -975,7 +819,7 @@ class PiecewiseRationalQuadraticCouplingTransform(PiecewiseCouplingTransform):
 
         def plan(engine):
             return (*self._packed_resnet(), tables,
-                    self._f16_stream(tables, _TILE16[engine]) if engine in _TILE16 else None,
+                    self._f16_stream(tables, ops.TILE16[engine]) if engine in ops.TILE16 else None,
                     self._packed_resnet_f16x3() if engine == "k8x" else None)
         # (ragged batches are padded to full 128-row blocks, odd shapes to multiples of four columns, in `ops`)
         return self._whole_layer_cascade(plan, self._fused_geometry(), inputs, context, inverse, accumulate_into)
@@ -984,12 +828,9 @@ class PiecewiseRationalQuadraticCouplingTransform(PiecewiseCouplingTransform):
         split = self.final_linear_engine == "bf16x3"
         key = (_cache.epoch(), layer.weight.data_ptr(), layer.weight._version, layer.bias.data_ptr(),
                layer.bias._version, split)
-        cached = getattr(self, "_packed_cache", None)
-        if cached is None or cached[0] != key:
-            cached = (key, ops.pack_final_linear(layer.weight, layer.bias, self.num_transform_features,
-                                                 self._transform_dim_multiplier(), split_bf16=split))
-            self._packed_cache = cached
-        return cached[1]
+        return _cache.keyed(self, "_packed_cache", key,
+                            lambda: ops.pack_final_linear(layer.weight, layer.bias, self.num_transform_features,
+                                                          self._transform_dim_multiplier(), split_bf16=split))
 
     def _condition_and_transform(self, inputs, identity_split, context, inverse, in_perm=None,
                                  out_scatter=None, accumulate_into=None):

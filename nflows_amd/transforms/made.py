@@ -70,11 +70,7 @@ class MaskedLinear(nn.Linear):
         # and call otherwise -- 18 MB of traffic for the output layer of the D = 784 model); keyed like the
         # packed-weight caches (_cache.py: writes through `.data` need invalidate_packed_weights())
         key = (_cache.epoch(), self.weight.data_ptr(), self.weight._version, self.mask.data_ptr())
-        hit = self.__dict__.get("_masked_weight_cache")
-        if hit is None or hit[0] != key:
-            hit = (key, self.mask * self.weight)
-            self.__dict__["_masked_weight_cache"] = hit
-        return hit[1]
+        return _cache.keyed(self, "_masked_weight_cache", key, lambda: self.mask * self.weight)
 
     def forward(self, x):
         return linear(x, self.masked_weight(), self.bias)

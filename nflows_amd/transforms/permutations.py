@@ -11,6 +11,7 @@ next to a coupling layer inside `CompositeTransform` the permutation is not laun
 """
 import torch
 
+from .. import _cache
 from .. import ops
 from ..utils import typechecks as check
 from .base import Transform
@@ -30,15 +31,12 @@ class Permutation(Transform):
         super().__init__()
         self.register_buffer("_permutation", permutation)
         self._dim = dim
-        self._argsort_cache = None  # (key, tensor): argsort is recomputed only if the buffer changes
 
     @property
     def _inverse_permutation(self):
         buf = self._permutation
         key = (buf.data_ptr(), buf._version, buf.device)
-        if self._argsort_cache is None or self._argsort_cache[0] != key:
-            self._argsort_cache = (key, torch.argsort(buf))
-        return self._argsort_cache[1]
+        return _cache.keyed(self, "_argsort_cache", key, lambda: torch.argsort(buf))   # (made again only if the buffer changes)
 
     def _check(self, inputs):
         dim, size = self._dim, self._buffers["_permutation"].shape[0]

@@ -217,3 +217,74 @@ def test_k12_one_log_derivative_per_row(monkeypatch, name):
     A.assert_one_lad(dict(col=p["col"], ref=t["ref"], truth=t["truth"], cond=t["cond"]), x[:, :T], lad, status, True, name + " one lad")
     outside = np.abs(p["z"][:, :T]) > A.TAIL_BOUND
     assert np.array_equal(x[:, :T].view(np.uint32)[outside], p["z"][:, :T].view(np.uint32)[outside])
+
+
+def test_k12_k13_packs_follow_the_parameters_and_the_masks(monkeypatch):
+    """The K12 schedule and the K13 output pack of the class are rebuilt when a parameter changes in place, after
+    `invalidate_packed_weights()` when it changed through `.data`, and when `load_state_dict` brings other masks: every
+    result bit for bit a fresh copy's, one K12 and one K13 launch per `inverse`, one K13 launch per `forward`."""
+    import nflows_amd
+    from nflows_amd import ops
+    from nflows_amd.transforms import MaskedPiecewiseRationalQuadraticAutoregressiveTransform as AR
+
+    def build(seed):
+        torch.manual_seed(seed)
+        return AR(features=12, hidden_features=48, num_bins=8, tails="linear", tail_bound=3.0, use_residual_blocks=False,
+                  random_mask=True).eval()
+    layer = build(60).to(DEV)
+    assert layer._sequential_steps() == 11
+    x = torch.randn(64, 12, device=DEV, generator=torch.Generator(DEV).manual_seed(1))
+    calls = {"k12": 0, "k13": 0}
+    real12, real13 = ops.made_rqs_inverse, ops.made_output_spline
+
+    def count12(*a, **k):
+        r = real12(*a, **k)
+        calls["k12"] += r is not None
+        return r
+
+    def count13(*a, **k):
+        r = real13(*a, **k)
+        calls["k13"] += r is not None
+        return r
+    monkeypatch.setattr(ops, "made_rqs_inverse", count12)
+    monkeypatch.setattr(ops, "made_output_spline", count13)
+
+    def both(t):
+        with torch.no_grad():
+            calls.update(k12=0, k13=0)
+            forward = t(x)
+            assert calls == {"k12": 0, "k13": 1}, calls
+            calls.update(k12=0, k13=0)
+            inverse = t.inverse(x)
+            assert calls == {"k12": 1, "k13": 1}, calls
+        assert _status() in (0, 2)
+        return forward + inverse
+
+    def fresh():
+        return both(copy.deepcopy(layer))
+
+    def same(a, b):
+        return all(torch.equal(p, q) for p, q in zip(a, b))
+
+    def different(a, b):   # (the forward pass and the inverse pass, each on its own)
+        return not same(a[:2], b[:2]) and not same(a[2:], b[2:])
+    net = layer.autoregressive_net
+    written = list(net.final_layer.parameters()) + [net.initial_layer.weight]
+    first = both(layer)
+    assert same(first, fresh())
+    with torch.no_grad():
+        for p in written:
+            p.mul_(2)
+    doubled = both(layer)
+    assert same(doubled, fresh()) and different(doubled, first)
+    for p in written:
+        p.data.mul_(0.5)
+    nflows_amd.invalidate_packed_weights()
+    halved = both(layer)
+    assert same(halved, fresh()) and same(halved, first)
+    other = build(61)
+    masks = [k for k in other.state_dict() if k.endswith(".mask")]
+    assert any(not torch.equal(other.state_dict()[k], layer.state_dict()[k].cpu()) for k in masks)
+    layer.load_state_dict(other.state_dict())
+    loaded = both(layer)
+    assert same(loaded, both(other.to(DEV))) and different(loaded, halved)

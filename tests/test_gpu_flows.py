@@ -807,7 +807,7 @@ def test_a_write_through_data_is_served_on_the_next_call(monkeypatch, engine):
     import copy
     import nflows_amd
     from nflows_amd import configs
-    from nflows_amd.transforms import coupling as C
+    from nflows_amd import _cache as C
     from nflows_amd.transforms import PiecewiseRationalQuadraticCouplingTransform as RQ
     assert C.VERIFY_WEIGHTS_EVERY == int(os.environ.get("NFA_VERIFY_WEIGHTS", "256") or 0)
     if engine == "k11":

@@ -1233,7 +1233,7 @@ def test_run_plans_are_cached_and_follow_changes(monkeypatch):
     a Parameter object replaced."""
     from nflows_amd import _cache, configs
     from nflows_amd.transforms import PiecewiseRationalQuadraticCouplingTransform as RQ
-    from nflows_amd.transforms.coupling import _weights_key
+    from nflows_amd._cache import weights_key
     flow = configs.rq_nsf_flow(num_layers=4, features=16, num_bins=8, hidden_features=64, seed=0).eval()
     comp = flow._transform
     x = torch.randn(8, 16)
@@ -1271,20 +1271,20 @@ def test_run_plans_are_cached_and_follow_changes(monkeypatch):
     assert len(plan()[0]) == 4
     # weights: version counters of a list made once per epoch; a replaced Parameter advances the epoch
     first = units[0][0]
-    k0 = _weights_key(first, first.transform_net)
-    assert _weights_key(first, first.transform_net) == k0
+    k0 = weights_key(first, first.transform_net)
+    assert weights_key(first, first.transform_net) == k0
     with torch.no_grad():
         first.transform_net.final_layer.bias.add_(1.0)
-    k1 = _weights_key(first, first.transform_net)
+    k1 = weights_key(first, first.transform_net)
     assert k1 != k0
     bias = first.transform_net.final_layer.bias
     bias.data = bias.data.clone()                  # storage rebound, counter untouched: the pointer is in the key
-    assert _weights_key(first, first.transform_net) != k1
-    k1 = _weights_key(first, first.transform_net)
+    assert weights_key(first, first.transform_net) != k1
+    k1 = weights_key(first, first.transform_net)
     epoch = _cache.epoch()
     first.transform_net.final_layer.bias = torch.nn.Parameter(torch.zeros_like(first.transform_net.final_layer.bias))
     assert _cache.epoch() > epoch
-    k2 = _weights_key(first, first.transform_net)
+    k2 = weights_key(first, first.transform_net)
     assert k2 != k1 and first.__dict__["_weights_list"][2][-1][2] is first.transform_net.final_layer.bias
     # swaps that bypass the registration hooks (torch.func.functional_call / stateless._reparametrize_module):
     # the held objects are checked against the modules' `_parameters` entries on every call
@@ -1293,10 +1293,10 @@ def test_run_plans_are_cached_and_follow_changes(monkeypatch):
     other = {n: p.detach().clone() + 1.0 for n, p in net.named_parameters()}
     epoch = _cache.epoch()
     with stateless._reparametrize_module(net, other):
-        inside = _weights_key(first, net)
+        inside = weights_key(first, net)
         assert _cache.epoch() == epoch and inside != k2
         assert inside[1:-1] == tuple((p.data_ptr(), p._version) for p in net.parameters()) and inside[-1] == 0   # (+ the `.data` salt)
-    assert _weights_key(first, net) == k2
+    assert weights_key(first, net) == k2
     w_before = first._packed_resnet()[1].clone()
     with torch.no_grad():
         first.transform_net.final_layer.bias.add_(2.0)
@@ -1490,52 +1490,52 @@ def test_verify_weights_mode_detects_writes_through_data(monkeypatch):
     the base class's descriptor): the periodic comparison raises."""
     import nflows_amd
     from nflows_amd import _cache, configs
-    from nflows_amd.transforms import coupling as C
+    from nflows_amd import _cache as C
     raw = torch._C.TensorBase.data.__get__
     default_period = C.VERIFY_WEIGHTS_EVERY
     flow = configs.rq_nsf_flow(num_layers=2, features=8, num_bins=8, hidden_features=16, seed=0)
     layer = flow._transform._transforms[1]
     net = layer.transform_net
     monkeypatch.setattr(C, "VERIFY_WEIGHTS_EVERY", 1)
-    k0 = C._weights_key(layer, net)
+    k0 = C.weights_key(layer, net)
     assert type(net.final_layer.bias) is _cache.WatchedParameter and isinstance(net.final_layer.bias, torch.nn.Parameter)
-    assert C._weights_key(layer, net) == k0                 # unchanged weights: passes, same key
+    assert C.weights_key(layer, net) == k0                 # unchanged weights: passes, same key
     with torch.no_grad():
         net.final_layer.bias.add_(1.0)                      # a visible update: new key, new checksum
-    k1 = C._weights_key(layer, net)
-    assert k1 != k0 and C._weights_key(layer, net) == k1
+    k1 = C.weights_key(layer, net)
+    assert k1 != k0 and C.weights_key(layer, net) == k1
     net.final_layer.bias.data.mul_(0.5)                     # invisible to the counters, reported by the Parameter
-    k1b = C._weights_key(layer, net)
+    k1b = C.weights_key(layer, net)
     assert k1b != k1 and k1b[:-1] == k1[:-1] and k1b[-1] == k1[-1] + 1    # only the salt moved: repack, no exception
-    assert C._weights_key(layer, net) == k1b
+    assert C.weights_key(layer, net) == k1b
     assert float(net.final_layer.bias.data.abs().sum()) > 0               # a READ of `.data`: compared, nothing changes
-    assert C._weights_key(layer, net) == k1b
+    assert C.weights_key(layer, net) == k1b
     for p_ in net.parameters():
         p_.data.mul_(1.0)                                                  # writes that change nothing
-    assert C._weights_key(layer, net) == k1b
+    assert C.weights_key(layer, net) == k1b
     raw(net.final_layer.bias).mul_(0.5)                     # announced by nothing ...
     with pytest.raises(C.StalePackedWeights):
-        C._weights_key(layer, net)                          # ... but not invisible to the periodic comparison
+        C.weights_key(layer, net)                          # ... but not invisible to the periodic comparison
     nflows_amd.invalidate_packed_weights()
-    k2 = C._weights_key(layer, net)
-    assert k2 != k1b and C._weights_key(layer, net) == k2
+    k2 = C.weights_key(layer, net)
+    assert k2 != k1b and C.weights_key(layer, net) == k2
     # a sign flip of one small entry (round 5's fp32 norms could not see it): the checksum is exact
     b = net.final_layer.bias
     with torch.no_grad():
         b.copy_(torch.linspace(-1.0, 2.0, b.numel()))
         b[3] = 1e-3
-    k2 = C._weights_key(layer, net)
+    k2 = C.weights_key(layer, net)
     raw(b)[3] = -1e-3
     with pytest.raises(C.StalePackedWeights):
-        C._weights_key(layer, net)
+        C.weights_key(layer, net)
     nflows_amd.invalidate_packed_weights()
-    k2 = C._weights_key(layer, net)
+    k2 = C.weights_key(layer, net)
     monkeypatch.setattr(C, "VERIFY_WEIGHTS_EVERY", 3)       # every third use of the key only
     raw(net.final_layer.bias).mul_(2.0)
     raised_at = None
     for use in range(1, 5):
         try:
-            assert C._weights_key(layer, net) == k2
+            assert C.weights_key(layer, net) == k2
         except C.StalePackedWeights:
             raised_at = use
             break
@@ -1546,12 +1546,12 @@ def test_verify_weights_mode_detects_writes_through_data(monkeypatch):
     assert "NFA_VERIFY_WEIGHTS" in os.environ or default_period == 256
     monkeypatch.setattr(C, "VERIFY_WEIGHTS_EVERY", 256)
     nflows_amd.invalidate_packed_weights()
-    k3 = C._weights_key(layer, net)
+    k3 = C.weights_key(layer, net)
     raw(net.final_layer.bias).add_(0.125)
     raised_at = None
     for use in range(1, 300):
         try:
-            assert C._weights_key(layer, net) == k3
+            assert C.weights_key(layer, net) == k3
         except C.StalePackedWeights:
             raised_at = use
             break
@@ -1560,8 +1560,8 @@ def test_verify_weights_mode_detects_writes_through_data(monkeypatch):
     with torch.no_grad():
         net.final_layer.bias.fill_(float("nan"))
     monkeypatch.setattr(C, "VERIFY_WEIGHTS_EVERY", 1)
-    k4 = C._weights_key(layer, net)
-    assert C._weights_key(layer, net) == k4
+    k4 = C.weights_key(layer, net)
+    assert C.weights_key(layer, net) == k4
 
 
 def test_select_columns_backward_equals_index_select():
@@ -1997,14 +1997,14 @@ def test_output_gradient_images_are_swizzled_conflict_free():
 
 def test_run_level_weight_fingerprint_and_verification(monkeypatch):
     """transforms/base.py `_Run.weights_fingerprint` (round 4): the weights of a whole run of layers in one flat pass --
-    what `_run_plan` keys the run's packed weights on instead of one coupling._weights_key per layer (0.3-0.4 ms per call
+    what `_run_plan` keys the run's packed weights on instead of one _cache.weights_key per layer (0.3-0.4 ms per call
     of a 32-layer flow on the host).  It follows in-place updates (version counters), rebound storage (`p.data = ...`),
     swapped parameter objects and swapped conditioners like the per-layer key; and the staggered verification (one layer
     per few calls) turns a write through `.data` into StalePackedWeights within `NFA_VERIFY_WEIGHTS` calls."""
     import torch
     import nflows_amd
     from nflows_amd import configs
-    from nflows_amd.transforms import coupling as C
+    from nflows_amd import _cache as C
     flow = configs.rq_nsf_flow(4, 16, 8, 32, seed=3).eval()
     T = flow._transform
     layers = list(T._transforms)
@@ -2165,7 +2165,7 @@ def test_a_plan_miss_does_not_launder_a_data_write(monkeypatch):
     import torch
     import nflows_amd
     from nflows_amd import configs
-    from nflows_amd.transforms import coupling as C
+    from nflows_amd import _cache as C
     flow = configs.rq_nsf_flow(4, 16, 8, 32, seed=3).eval()
     T = flow._transform
     layers = list(T._transforms)
@@ -2205,7 +2205,7 @@ def test_a_plan_miss_does_not_launder_a_data_write(monkeypatch):
     plan(False)
     T.__dict__["_run_plans"].clear()
     raw(b).neg_()
-    with pytest.raises(C.StalePackedWeights):
+    with pytest.raises(nflows_amd.transforms.coupling.StalePackedWeights):
         plan(False)
     nflows_amd.invalidate_packed_weights()
     plan(False)
