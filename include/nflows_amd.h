@@ -50,7 +50,9 @@ extern "C" {
                               are ADDED entry points, for the same reason;
                               still 19: NFA_FLAG_K8X_FORM (bits 16-17, nfa_rqs_flow_resnet_f16x3_f32) is an ADDED field whose zero is
                               the behaviour of every caller of 19: an older library rejects a non-zero value as an unknown flag,
-                              an older binding never sets one */
+                              an older binding never sets one;
+                              still 19: nfa_pack_resnet_f64, nfa_rqs_resnet_layer_f64 (K26) are ADDED entry points, for the same
+                              reason */
 
 /* return codes */
 #define NFA_OK 0
@@ -804,6 +806,43 @@ int nfa_rqs_elementwise_backward_f64(const double *inputs, const double *unnorma
                                      const double *grad_logabsdet, double *grad_inputs, double *grad_widths,
                                      double *grad_heights, double *grad_derivatives, int64_t n,
                                      const nfa_rqs_spec *spec, int32_t inverse, void *stream);
+
+/*
+ * K26.  A whole rational-quadratic spline coupling layer in float64, one launch: what the reference does in
+ * coupling.py:73-130 (split, conditioner, spline, merge) with a ResidualNet conditioner (nn/nets/resnet.py:55-100:
+ * initial Linear, blocks h += W_1 relu(W_0 relu(h) + b_0) + b_1, final Linear; ReLU, no context, no batch norm, no
+ * dropout) and the functional of splines/rational_quadratic.py:13-181 on the [batch, num_transform * P] output of that
+ * net, P = 3 K - 1 (linear tails) or 3 K + 1 (tails = None), logits per feature [w_0..w_{K-1}, h_0..h_{K-1}, d...]
+ * (coupling.py:541-582).  The GEMMs run on v_mfma_f64_16x16x4_f64, the conditioner's output stays on the chip, the
+ * per-element arithmetic is nfa_rqs_elementwise_f64's.
+ *
+ * nfa_pack_resnet_f64: the module's tensors (float64, contiguous, on the device; initial_weight [H, num_identity],
+ * block_params a HOST array of 4 num_blocks device pointers W_0, b_0, W_1, b_1 of [H, H] / [H], final_weight
+ * [num_transform * P, H]) -> the packed stream of `packed_doubles` doubles the kernel reads: every matrix as the B
+ * fragments of the f64 MFMA, k-step major, the hidden width zero-padded to a multiple of 16, the identity features to
+ * a multiple of 4, W_f in chunks of whole features (at most 128 columns, a multiple of four features where four fit)
+ * padded to whole 16-column tiles, then the biases padded the same way (csrc/launch_plan.hpp: f64_layer_layout states
+ * the offsets; packed_doubles must be its total).
+ *
+ * nfa_rqs_resnet_layer_f64: outputs [batch, features]: the columns identity_idx [num_identity] (int64) pass through
+ * bit for bit, the columns transform_idx [num_transform] are transformed, every other column is left unwritten;
+ * logabsdet [batch] receives the row's sum of log-derivatives (added in float64 in an order the shape fixes), or is
+ * increased by it under NFA_FLAG_ACCUMULATE_LOGABSDET; NFA_FLAG_INVERSE selects the inverse spline; spec->wh_divisor
+ * is the / sqrt(hidden_features) of coupling.py:554-559.  status as nfa_rqs_elementwise_f64 (plus NFA_STATUS_BAD_INDEX
+ * for a column index outside [0, features): that element is skipped).  Rows beyond `batch` in the last 16-row tile
+ * are neither read nor written; a row's result does not depend on the other rows or on its place in the batch.
+ * NFA_ERR_UNSUPPORTED: hidden_features > 128, more than 64 identity or transformed features, more than 32 bins.
+ * Added under ABI 19 (see NFA_ABI_VERSION): no existing entry point, flag set or packed layout changes.
+ */
+int nfa_pack_resnet_f64(const double *initial_weight, const double *initial_bias, const double *const *block_params,
+                        const double *final_weight, const double *final_bias, int32_t num_identity,
+                        int32_t hidden_features, int32_t num_blocks, int32_t num_transform,
+                        int32_t params_per_feature, double *packed, int64_t packed_doubles, void *stream);
+int nfa_rqs_resnet_layer_f64(const double *inputs, const double *packed, int64_t packed_doubles,
+                             const int64_t *identity_idx, const int64_t *transform_idx, double *outputs,
+                             double *logabsdet, int32_t *status, int64_t batch, int32_t features,
+                             int32_t num_identity, int32_t num_transform, int32_t hidden_features, int32_t num_blocks,
+                             const nfa_rqs_spec *spec, int32_t flags, void *stream);
 
 /*
  * K14.  The hidden part of a ResidualNet conditioner under TRAINING (nn/nets/resnet.py:92-100 without the final

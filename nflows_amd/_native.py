@@ -52,6 +52,8 @@ EXPORTS = (
     "nfa_rqs_flow_resnet_context_f32",
     "nfa_rqs_elementwise_f64",
     "nfa_rqs_elementwise_backward_f64",
+    "nfa_pack_resnet_f64",
+    "nfa_rqs_resnet_layer_f64",
     "nfa_affine_flow_mlp_f32",
     "nfa_affine_flow_made_f32",
     "nfa_made_rqs_inverse_f32",
@@ -195,6 +197,10 @@ def _declare(lib):
                                                     i32, sp, i32, vp]
     lib.nfa_rqs_elementwise_f64.restype = ctypes.c_int
     lib.nfa_rqs_elementwise_f64.argtypes = [vp, vp, i64, vp, i64, vp, i64, i32, vp, vp, vp, vp, i64, sp, i32, vp]
+    lib.nfa_pack_resnet_f64.restype = ctypes.c_int
+    lib.nfa_pack_resnet_f64.argtypes = [vp, vp, ctypes.POINTER(vp), vp, vp, i32, i32, i32, i32, i32, vp, i64, vp]
+    lib.nfa_rqs_resnet_layer_f64.restype = ctypes.c_int
+    lib.nfa_rqs_resnet_layer_f64.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, sp, i32, vp]
     lib.nfa_pack_resnet_hidden_train_f32.restype = ctypes.c_int
     lib.nfa_pack_resnet_hidden_train_f32.argtypes = [vp, vp, ctypes.POINTER(vp), vp, vp, i32, i32, i32, i32, vp, vp, vp,
                                                      vp, vp]

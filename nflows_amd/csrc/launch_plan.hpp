@@ -197,4 +197,78 @@ inline int plan_mog_tile(int K) {
     return plan_element_tile(1, (size_t)(kDefaultDynLds - kMogStaticLds), [K](int T) { return mog_tile_bytes(T, K); });
 }
 
+// ------------------------------------------------------------------------------------------
+// K26 (rqs_resnet_f64.hip): a whole spline coupling layer in float64 on v_mfma_f64_16x16x4_f64.  A wave owns 16 rows,
+// a workgroup's four waves a block of kF64Rows rows; the workgroups walk the row blocks persistently.
+//
+// The packed stream (doubles).  A matrix W [out, in] is held as the B fragments of its k-steps: k-step kk (4 values of
+// `in`), column tile t (16 values of `out`), lane l hold W[16 t + (l & 15)][4 kk + (l >> 4)] at ((kk * nt + t) * 64 + l),
+// zero past the matrix's own extents.  In order:
+//   w_in      W_in  [H, di]           ks0 = ceil(di / 4) k-steps x NT = ceil(H / 16) tiles
+//   w_blocks  per block W_0, W_1      ksh = HP / 4 k-steps x NT tiles each (HP = 16 NT)
+//   w_final   W_f in chunks of F whole features (F P <= 128 columns; a multiple of four features where four fit, so
+//             that 16 rows x F features fill whole waves): chunk c holds the rows [c F P, (c F + F_c) P) of W_f as ksh
+//             k-steps x NTF = ceil(F P / 16) tiles -- the last chunk (F_last features) NTL = ceil(F_last P / 16) tiles
+//   b_in      HP                      biases, zero-padded like the columns they belong to
+//   b_blocks  per block b_0, b_1      HP each
+//   b_final   per chunk 16 NTF (the last: 16 NTL)
+constexpr int kF64Rows = 64;
+
+struct F64LayerLayout {
+    int HP = 0, NT = 0, ks0 = 0, ksh = 0;   // hidden width padded to 16, its tiles, k-steps of the initial / hidden Linears
+    int F = 0, chunks = 0, NTF = 0, NTL = 0;
+    int64_t w_in = 0, w_blocks = 0, w_final = 0, b_in = 0, b_blocks = 0, b_final = 0, total = 0;
+};
+
+inline F64LayerLayout f64_layer_layout(int di, int H, int num_blocks, int dt, int P) {
+    F64LayerLayout l;
+    l.NT = (H + 15) / 16;
+    l.HP = 16 * l.NT;
+    l.ks0 = (di + 3) / 4;
+    l.ksh = l.HP / 4;
+    int F = 128 / P;
+    if (F >= 4) F &= ~3;
+    if (F > dt) F = dt;
+    l.F = F;
+    l.chunks = (dt + F - 1) / F;
+    const int last = dt - (l.chunks - 1) * F;
+    l.NTF = (F * P + 15) / 16;
+    l.NTL = (last * P + 15) / 16;
+    const int64_t hidden = (int64_t)l.ksh * l.NT * 64;
+    l.w_in = 0;
+    l.w_blocks = (int64_t)l.ks0 * l.NT * 64;
+    l.w_final = l.w_blocks + 2 * (int64_t)num_blocks * hidden;
+    l.b_in = l.w_final + (int64_t)l.ksh * 64 * ((int64_t)(l.chunks - 1) * l.NTF + l.NTL);
+    l.b_blocks = l.b_in + l.HP;
+    l.b_final = l.b_blocks + 2 * (int64_t)num_blocks * l.HP;
+    l.total = l.b_final + 16 * ((int64_t)(l.chunks - 1) * l.NTF + l.NTL);
+    return l;
+}
+
+// LDS image of a workgroup, in doubles: per wave the activations [16][AS] (the next GEMM's A operand: AS = the widest k
+// extent + 2, so that the 32 lanes of a ds_read_b64 pass fall into 32 different bank pairs) and a chunk's logits
+// [16][LS], then two buffers of kc k-steps of the widest matrix.  kc: the most k-steps per buffer (8, 4, 2, 1) that fit
+// the CU.  One workgroup per CU: the kernel's registers (two sets of accumulator tiles) leave room for one wave per SIMD.
+struct F64LayerPlan {
+    int AS = 0, LS = 0, kc = 0, max_nt = 0;
+    size_t lds = 0;
+    int64_t tiles = 0, grid = 0;
+};
+
+inline F64LayerPlan plan_f64_layer(const F64LayerLayout& l, int di, int64_t batch, int cus) {
+    F64LayerPlan p;
+    const int dip = 4 * l.ks0;
+    p.AS = (l.HP > dip ? l.HP : dip) + 2;
+    const int ntf = l.chunks > 1 && l.NTF > l.NTL ? l.NTF : l.NTL;
+    p.LS = 16 * ntf + 1;
+    p.max_nt = l.NT > ntf ? l.NT : ntf;
+    const size_t fixed = (size_t)(kBlock / kWave) * 16 * (p.AS + p.LS) * 8;
+    for (p.kc = 8; p.kc > 1; p.kc >>= 1)
+        if (fixed + (size_t)2 * p.kc * p.max_nt * 64 * 8 + 256 <= (size_t)kCuLds) break;
+    p.lds = fixed + (size_t)2 * p.kc * p.max_nt * 64 * 8;
+    p.tiles = (batch + kF64Rows - 1) / kF64Rows;
+    p.grid = persistent_grid(cus, p.lds, 1, p.tiles);
+    return p;
+}
+
 }  // namespace nfa

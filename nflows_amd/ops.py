@@ -3138,6 +3138,146 @@ def rqs_coupling_fused_linear(inputs, hidden, weight_packed, bias_padded, transf
     return out, lad
 
 
+# ---------------------------------------------------------------------------------------------------------
+# K26: a whole spline coupling layer in float64 (csrc/rqs_resnet_f64.hip)
+
+F64_LAYER_ROWS = 64    # rows of a workgroup's row block: 16 per wave
+F64_LAYER_MAX_HIDDEN, F64_LAYER_MAX_FEATURES, F64_LAYER_MAX_BINS = 128, 64, 32
+
+
+def resnet_f64_layout(num_identity, hidden_features, num_blocks, num_transform, params_per_feature):
+    """Offsets (in doubles) of K26's packed stream -- csrc/launch_plan.hpp: f64_layer_layout, which documents it."""
+    di, H, nb, dt, P = num_identity, hidden_features, num_blocks, num_transform, params_per_feature
+    NT = (H + 15) // 16
+    HP, ks0 = 16 * NT, (di + 3) // 4
+    ksh = HP // 4
+    F = 128 // P
+    if F >= 4:
+        F &= ~3
+    F = min(F, dt)
+    chunks = (dt + F - 1) // F
+    last = dt - (chunks - 1) * F
+    NTF, NTL = (F * P + 15) // 16, (last * P + 15) // 16
+    hidden = ksh * NT * 64
+    w_blocks = ks0 * NT * 64
+    w_final = w_blocks + 2 * nb * hidden
+    b_in = w_final + ksh * 64 * ((chunks - 1) * NTF + NTL)
+    b_blocks = b_in + HP
+    b_final = b_blocks + 2 * nb * HP
+    total = b_final + 16 * ((chunks - 1) * NTF + NTL)
+    return dict(HP=HP, NT=NT, ks0=ks0, ksh=ksh, F=F, chunks=chunks, NTF=NTF, NTL=NTL, last=last, w_in=0, w_blocks=w_blocks,
+                w_final=w_final, b_in=b_in, b_blocks=b_blocks, b_final=b_final, total=total)
+
+
+def f64_layer_plan(batch, cus):
+    """(row blocks, workgroups) of a K26 launch: one persistent workgroup per CU, at most one per row block.  The LDS
+    bytes and the k-steps per weight buffer are csrc/launch_plan.hpp's alone (plan_f64_layer); `last_layer_kernel()`
+    names what a launch took."""
+    tiles = (batch + F64_LAYER_ROWS - 1) // F64_LAYER_ROWS
+    return dict(tiles=tiles, grid=min(cus, tiles))
+
+
+def _resnet_f64_tensors(net):
+    """(W_in, b_in, [W_0, b_0, W_1, b_1 per block], W_f, b_f) of a ResidualNet"""
+    blocks = []
+    for b in net.blocks:
+        first, second = b.linear_layers
+        blocks += [first.weight, first.bias, second.weight, second.bias]
+    return net.initial_layer.weight, net.initial_layer.bias, blocks, net.final_layer.weight, net.final_layer.bias
+
+
+def _fragments_f64(w, ks, nt):
+    """W [out, in] -> its ks x nt B fragments: [kk][t][lane] = W[16 t + (lane & 15)][4 kk + (lane >> 4)], zero-padded"""
+    padded = w.new_zeros(16 * nt, 4 * ks)
+    padded[:w.shape[0], :w.shape[1]] = w
+    return padded.reshape(nt, 16, ks, 4).permute(2, 0, 3, 1).reshape(-1)
+
+
+def pack_resnet_f64_reference(net, num_transform, params_per_feature):
+    """K26's packed stream by tensor operations (any device, CPU included: the tests' statement of the layout)."""
+    w_in, b_in, blocks, w_f, b_f = [t.detach() if torch.is_tensor(t) else [u.detach() for u in t]
+                                    for t in _resnet_f64_tensors(net)]
+    H, di = w_in.shape
+    P, dt = params_per_feature, num_transform
+    lay = resnet_f64_layout(di, H, len(blocks) // 4, dt, P)
+
+    def bias(b, padded):
+        out = b.new_zeros(padded)
+        out[:b.numel()] = b
+        return out
+    parts = [_fragments_f64(w_in, lay["ks0"], lay["NT"])]
+    parts += [_fragments_f64(w, lay["ksh"], lay["NT"]) for w in blocks[0::2]]
+    rows = [(c * lay["F"] * P, min((c + 1) * lay["F"], dt) * P, lay["NTL"] if c == lay["chunks"] - 1 else lay["NTF"])
+            for c in range(lay["chunks"])]
+    parts += [_fragments_f64(w_f[lo:hi], lay["ksh"], nt) for lo, hi, nt in rows]
+    parts += [bias(b_in, lay["HP"])] + [bias(b, lay["HP"]) for b in blocks[1::2]]
+    parts += [bias(b_f[lo:hi], 16 * nt) for lo, hi, nt in rows]
+    packed = torch.cat(parts).to(torch.float64)
+    assert packed.numel() == lay["total"]
+    return packed
+
+
+def pack_resnet_f64(net, num_transform, params_per_feature):
+    """K26's packed stream from a float64 ResidualNet on the device (nfa_pack_resnet_f64: a launch per matrix and bias)."""
+    w_in, b_in, blocks, w_f, b_f = _resnet_f64_tensors(net)
+    flat = [t.detach().contiguous() for t in [w_in, b_in] + blocks + [w_f, b_f]]
+    for t in flat:
+        if t.dtype != torch.float64 or not t.is_cuda:
+            raise TypeError("nflows_amd: K26 packs float64 parameters on the device")
+    dev = w_in.device
+    H, di = w_in.shape
+    nb = len(blocks) // 4
+    lay = resnet_f64_layout(di, H, nb, num_transform, params_per_feature)
+    if tuple(w_f.shape) != (num_transform * params_per_feature, H):
+        raise ValueError("final_layer.weight must be [%d, %d], got %s" % (num_transform * params_per_feature, H, tuple(w_f.shape)))
+    packed = torch.empty(lay["total"], dtype=torch.float64, device=dev)
+    ptrs = (ctypes.c_void_p * max(1, 4 * nb))(*[t.data_ptr() for t in flat[2:-2]])
+    with torch.cuda.device(dev):
+        rc = N.load().nfa_pack_resnet_f64(N.ptr(flat[0]), N.ptr(flat[1]), ptrs, N.ptr(flat[-2]), N.ptr(flat[-1]), di, H, nb,
+                                          num_transform, params_per_feature, N.ptr(packed), lay["total"],
+                                          N.stream_handle(dev))
+    N.check(rc)
+    return packed
+
+
+def rqs_resnet_layer_f64(inputs, packed, identity_idx, transform_idx, hidden_features, num_blocks, spec, inverse=False,
+                         accumulate_into=None):
+    """K26 -- one spline coupling layer with its ResidualNet conditioner on float64 [B, D] rows, one launch.  `packed`:
+    pack_resnet_f64 of the conditioner.  Returns (outputs [B, D], logabsdet [B]); with `accumulate_into` (a contiguous
+    float64 [B] tensor) the layer's sum is added to it and it is returned."""
+    N.require_device_real("inputs", inputs, torch.float64, 2)
+    if inputs.dtype != torch.float64 or packed.dtype != torch.float64 or not packed.is_cuda:
+        raise TypeError("nflows_amd: K26 takes float64 tensors on the device")
+    dev = inputs.device
+    B, D = inputs.shape
+    idf = _idx("identity_features", identity_idx, dev)
+    tf = _idx("transform_features", transform_idx, dev)
+    x = inputs.detach().contiguous()
+    out = torch.empty_like(x)
+    flags = N.FLAG_INVERSE if inverse else 0
+    if accumulate_into is None:
+        lad = torch.empty(B, dtype=torch.float64, device=dev)
+    else:
+        lad = accumulate_into
+        if lad.dtype != torch.float64 or lad.device != dev or tuple(lad.shape) != (B,) or not lad.is_contiguous():
+            raise ValueError("accumulate_into must be a contiguous float64 [batch] tensor on the inputs' device")
+        flags |= N.FLAG_ACCUMULATE_LOGABSDET
+    if idf.numel() + tf.numel() < D:   # (columns of neither half: the kernel leaves them unwritten)
+        out.copy_(x)
+    hook = _launch_hook
+    with torch.cuda.device(dev):
+        token = hook.begin("k26") if hook is not None else None
+        rc = N.load().nfa_rqs_resnet_layer_f64(N.ptr(x), N.ptr(packed), packed.numel(), N.ptr(idf), N.ptr(tf), N.ptr(out),
+                                               N.ptr(lad), N.ptr(_status_word(dev)), B, D, idf.numel(), tf.numel(),
+                                               hidden_features, num_blocks, ctypes.byref(spec), flags,
+                                               N.stream_handle(dev))
+        if hook is not None:
+            hook.end(token, 8 * (2 * B * D + B) + 8 * packed.numel())
+    N.check(rc)
+    _after_spline(spec, inverse, dev)
+    return out, lad
+
+
 def last_layer_kernel():
     """Name of the layer kernel this thread launched last (`nfa_last_layer_kernel`): the launchers pick the instance
     from the batch, the CU count and the LDS budget."""

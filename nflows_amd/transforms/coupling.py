@@ -824,6 +824,72 @@ class PiecewiseRationalQuadraticCouplingTransform(PiecewiseCouplingTransform):
         # (ragged batches are padded to full 128-row blocks, odd shapes to multiples of four columns, in `ops`)
         return self._whole_layer_cascade(plan, self._fused_geometry(), inputs, context, inverse, accumulate_into)
 
+    # K26: the whole layer in float64 in one launch (conditioner on the f64 matrix instruction, K5d's spline arithmetic);
+    # class-level switch, NFA_K26=0 = off: float64 inputs then take `_generic` as before
+    fuse_float64 = os.environ.get("NFA_K26", "1") != "0"
+    # K26's size rule (measured, DESIGN.md section 4 "K26"): a workgroup takes 64 rows through the whole layer, about 0.28 ms
+    # at width 128 however few rows there are, so conditioners wider than 32 keep the generic path below this many rows
+    fuse_float64_min_rows = int(os.environ.get("NFA_K26_MIN_ROWS", "8192"))
+
+    def _float64_module_ok(self, context):
+        """What K26 asks of the layer itself (the inputs: `_float64_layer_eligible`): no grad, a plain ResidualNet of
+        float64 parameters without context, batch norm or active dropout, ReLU blocks, width <= 128, 1 .. 64 features in
+        either half, <= 32 bins, linear tails or none, no unconditional transform, no user hooks."""
+        net = self._modules["transform_net"]
+        from ..nn.nets.resnet import ResidualNet
+        if not (self.fuse_float64 and not torch.is_grad_enabled() and context is None and type(net) is ResidualNet
+                and self.unconditional_transform is None and not self._user_hooks
+                and (self.tails == "linear" or self.tails is None)
+                and 1 <= self.num_bins <= ops.F64_LAYER_MAX_BINS
+                and 1 <= self.num_identity_features <= ops.F64_LAYER_MAX_FEATURES
+                and 1 <= self.num_transform_features <= ops.F64_LAYER_MAX_FEATURES
+                and self._block_activation() == N.ACTIVATION_RELU):
+            return False
+
+        def read():   # (shapes and dtypes: once per cache epoch -- `.double()`, `.to()`, a swapped layer advance it)
+            first, final = net.initial_layer, net.final_layer
+            return (net.context_features is None and 1 <= net.hidden_features <= ops.F64_LAYER_MAX_HIDDEN
+                    and not any(b.use_batch_norm for b in net.blocks)
+                    and type(first) is torch.nn.Linear and type(final) is torch.nn.Linear
+                    and first.bias is not None and final.bias is not None
+                    and tuple(first.weight.shape) == (net.hidden_features, self.num_identity_features)
+                    and tuple(final.weight.shape) == (self.num_transform_features * self._transform_dim_multiplier(),
+                                                      net.hidden_features)
+                    and all(type(layer) is torch.nn.Linear and layer.bias is not None
+                            and tuple(layer.weight.shape) == (net.hidden_features, net.hidden_features)
+                            for b in net.blocks for layer in b.linear_layers)
+                    and all(getattr(b, "context_layer", None) is None for b in net.blocks))
+        if not _cache.keyed(self, "_f64_static", (_cache.epoch(), net.initial_layer.weight.dtype), read):
+            return False
+        return (all(p.dtype == torch.float64 for p in net.parameters())
+                and all(not b.training or b.dropout.p == 0.0 for b in net.blocks))
+
+    def _float64_layer_eligible(self, inputs, context, accumulate_into=None):
+        if not (inputs.dim() == 2 and inputs.is_cuda and inputs.dtype == torch.float64 and inputs.is_contiguous()):
+            return False
+        if accumulate_into is not None and not (accumulate_into.dtype == torch.float64 and accumulate_into.is_contiguous()
+                                                and accumulate_into.device == inputs.device
+                                                and tuple(accumulate_into.shape) == (inputs.shape[0],)):
+            return False
+        if getattr(self._modules["transform_net"], "hidden_features", 0) > 32 and inputs.shape[0] < self.fuse_float64_min_rows:
+            return False
+        return (self._float64_module_ok(context)
+                and all(p.device == inputs.device for p in self._modules["transform_net"].parameters())
+                and self.identity_features.device == inputs.device)
+
+    def _packed_resnet_f64(self):
+        net = self.transform_net
+        return _cache.keyed(self, "_packed_f64_cache", _cache.weights_key(self, net),
+                            lambda: ops.pack_resnet_f64(net, self.num_transform_features, self._transform_dim_multiplier()))
+
+    def _generic(self, inputs, context, inverse, logabsdet_accumulator):
+        if self._float64_layer_eligible(inputs, context, logabsdet_accumulator):
+            net = self.transform_net
+            return ops.rqs_resnet_layer_f64(inputs, self._packed_resnet_f64(), self.identity_features,
+                                            self.transform_features, net.hidden_features, len(net.blocks), self._spec(),
+                                            inverse, logabsdet_accumulator)
+        return super()._generic(inputs, context, inverse, logabsdet_accumulator)
+
     def _packed_final_linear(self, layer):
         split = self.final_linear_engine == "bf16x3"
         key = (_cache.epoch(), layer.weight.data_ptr(), layer.weight._version, layer.bias.data_ptr(),
