@@ -924,6 +924,38 @@ int nfa_resnet_backward_f32(const float *grad_params, int32_t out_features, cons
                             const float *saved, float *grads, float *grad_hidden, float *grad_identity_inputs,
                             int64_t batch, int32_t num_identity, int32_t hidden_features, int32_t num_blocks,
                             void *stream);
+/* K27: the two kernels for a conditioner WITH a context, whose Linears stay the caller's: their outputs arrive as dense
+ * [batch, 128] float planes (exact zeros past the net's width), one per block in planes[num_blocks].
+ *   mode NFA_TRAIN_CTX_GLU (a ResidualNet, resnet.py:42-52): identity_inputs is [x | context] ([batch, num_identity], the
+ *     initial Linear is only wider); per block t_k = W_1 relu(a_k) + b_1 is written to pre [num_blocks, batch, 128] and
+ *     h_{k+1} = h_k + t_k sigmoid(planes[k]).  The sigmoid is evaluated from exp(-|c|): finite and monotone over the
+ *     whole float range, 0 / 1 at logits past -+104, NaN for NaN.  initial_plane must be null.
+ *   mode NFA_TRAIN_CTX_ADD (a MADE with residual blocks, made.py:129-137, :197-201): a_k = W_0 relu(h_k) + b_0 +
+ *     planes[k], and h_0 += initial_plane where that is not null.  pre is not used.
+ * saved (with the packed ReLU masks behind its planes), hidden, params and the streams are nfa_resnet_hidden_forward_f32's.
+ * The backward entry takes exactly one of grad_hidden [batch, 128] (out_features = 0: nfa_resnet_hidden_backward_f32's
+ * pass) and grad_params [batch, out_features] (nfa_resnet_backward_f32's pass, grad_hidden_out [batch, 128] written).
+ * GLU, per block from the last to the first with g the gradient of h_{k+1} and s = sigmoid(planes[k]):
+ *     plane_grads[k] [batch, 128] = g pre[k] s (1 - s)      (d loss / d planes[k])
+ *     gated_grads[k] (of [num_blocks, batch, 128]) = g s    (the grad_outputs of block k's SECOND Linear for
+ *                                                            nfa_linear_wgrad_f32 -- not grads[2 k + 2] / grad_hidden)
+ *     grads[2 k + 1] = (gated_grads[k] W_1) . [a_k > 0],  grads[2 k] = g + (grads[2 k + 1] W_0) . [h_k > 0]
+ * ADD: the pass of the entry points above, unchanged (planes, pre, plane_grads, gated_grads are ignored and may be
+ * null): d loss / d planes[k] IS grads[2 k + 1], d loss / d initial_plane IS grads[0] (grad_hidden without a block).
+ * NFA_ERR_UNSUPPORTED outside num_identity <= 64 and % 4 == 0, batch % 128 == 0, num_blocks <= 3, hidden_features ==
+ * 128.  Added under ABI 19 (see NFA_ABI_VERSION): no existing entry point, flag set or packed layout changes. */
+#define NFA_TRAIN_CTX_GLU 1
+#define NFA_TRAIN_CTX_ADD 2
+int nfa_resnet_hidden_forward_ctx_f32(int32_t mode, const float *identity_inputs, const float *const *planes,
+                                      const float *initial_plane, const void *weights_packed, const float *bias_packed,
+                                      float *saved, float *pre, float *hidden, const float *final_bias_packed,
+                                      float *params, int32_t out_features, int64_t batch, int32_t num_identity,
+                                      int32_t hidden_features, int32_t num_blocks, void *stream);
+int nfa_resnet_backward_ctx_f32(int32_t mode, const float *grad_hidden, const float *grad_params, int32_t out_features,
+                                const float *const *planes, const float *pre, const void *weights_packed,
+                                const float *saved, float *grads, float *const *plane_grads, float *gated_grads,
+                                float *grad_hidden_out, float *grad_identity_inputs, int64_t batch,
+                                int32_t num_identity, int32_t hidden_features, int32_t num_blocks, void *stream);
 
 /*
  * K9.  The spline's siblings as elementwise functionals (no row-sum), same calling convention as

@@ -64,6 +64,8 @@ EXPORTS = (
     "nfa_resnet_hidden_forward_f32",
     "nfa_resnet_hidden_backward_f32",
     "nfa_resnet_backward_f32",
+    "nfa_resnet_hidden_forward_ctx_f32",
+    "nfa_resnet_backward_ctx_f32",
     "nfa_rqs_flow_resnet_f16x2_f32",
     "nfa_rqs_flow_resnet_f16x2_tile16_f32",
     "nfa_rqs_flow_resnet_f16x2_colsplit_f32",
@@ -212,6 +214,12 @@ def _declare(lib):
     lib.nfa_resnet_hidden_backward_f32.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, i32, vp]
     lib.nfa_resnet_backward_f32.restype = ctypes.c_int
     lib.nfa_resnet_backward_f32.argtypes = [vp, i32, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp]
+    lib.nfa_resnet_hidden_forward_ctx_f32.restype = ctypes.c_int
+    lib.nfa_resnet_hidden_forward_ctx_f32.argtypes = [i32, vp, ctypes.POINTER(vp), vp, vp, vp, vp, vp, vp, vp, vp, i32, i64,
+                                                      i32, i32, i32, vp]
+    lib.nfa_resnet_backward_ctx_f32.restype = ctypes.c_int
+    lib.nfa_resnet_backward_ctx_f32.argtypes = [i32, vp, vp, i32, ctypes.POINTER(vp), vp, vp, vp, vp, ctypes.POINTER(vp), vp,
+                                                vp, vp, i64, i32, i32, i32, vp]
     lib.nfa_rqs_elementwise_backward_f64.restype = ctypes.c_int
     lib.nfa_rqs_elementwise_backward_f64.argtypes = [vp, vp, i64, vp, i64, vp, i64, i32, vp, vp, vp, vp, vp, vp,
                                                      i64, sp, i32, vp]

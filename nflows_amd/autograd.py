@@ -721,13 +721,16 @@ class ResidualNetHidden(torch.autograd.Function):
         return _resnet_hidden_backward(ctx, g_out, ctx.saved_tensors)
 
 
-def _resnet_hidden_backward(ctx, g_out, saved_tensors):
+def _resnet_hidden_backward(ctx, g_out, saved_tensors, context=None):
     """K14's backward pass for ResidualNetHidden and MadeNet: (grad of x, None, then one gradient per parameter).
     `saved_tensors`: (x, saved, bwd_w) or, with the final Linear, (x, saved, bwd_w, hidden, W_f -- or a function
-    that returns it, called only where the backward kernel does not take the width)."""
+    that returns it, called only where the backward kernel does not take the width).
+    `context` (K27, the Functions with a context): dict(mode, planes, pre, first_param) -- the pass goes through
+    `ops.resnet_backward_ctx`, the second Linears' grad_outputs are the GATED gradients in GLU mode, and the dict
+    receives `grads`, `g_hidden` and `plane_grads` (GLU) for the planes' gradients."""
     from . import ops
     nb, H = ctx.nb, ctx.H
-    need = ctx.needs_input_grad[2:]   # per parameter
+    need = ctx.needs_input_grad[context["first_param"] if context else 2:]   # per parameter
     g_out = g_out.contiguous()
 
     def wgrad(inputs, grad_outputs, need_w, need_b, rows=None, cols=None):
@@ -746,13 +749,18 @@ def _resnet_hidden_backward(ctx, g_out, saved_tensors):
 
     narrow = H if H != 128 else None
     tail = ()
-    fused = None
+    fused = gated = None
     if ctx.with_final:
         x, saved, bwd_w, hidden, w_f = saved_tensors
         tail = wgrad(hidden, g_out, need[-2], need[-1], cols=narrow)
         # the final Linear's input gradient inside the backward kernel (round 4; its W_f^T stages are in `bwd_w`)
-        if ops.FUSED_FINAL_DGRAD:
+        if ops.FUSED_FINAL_DGRAD and context is None:
             fused = ops.resnet_backward(g_out, bwd_w, saved, x.shape[1])
+        elif ops.FUSED_FINAL_DGRAD and g_out.shape[1] % 4 == 0:
+            got = ops.resnet_backward_ctx(context["mode"], g_out, bwd_w, saved, x.shape[1], context["planes"],
+                                          context["pre"], from_params=True)
+            fused, gated = (got[0], got[1], got[2]), got[4]
+            context.update(plane_grads=got[3])
         if fused is None:
             g_hidden = g_out @ (w_f() if callable(w_f) else w_f)        # ... or one library GEMM
     else:
@@ -763,7 +771,14 @@ def _resnet_hidden_backward(ctx, g_out, saved_tensors):
     else:
         if narrow is not None:
             g_hidden = torch.nn.functional.pad(g_hidden, (0, 128 - H))
-        g_x, grads = ops.resnet_hidden_backward(g_hidden, bwd_w, saved, x.shape[1])
+        if context is None:
+            g_x, grads = ops.resnet_hidden_backward(g_hidden, bwd_w, saved, x.shape[1])
+        else:
+            g_x, grads, g_hidden, plane_grads, gated = ops.resnet_backward_ctx(
+                context["mode"], g_hidden, bwd_w, saved, x.shape[1], context["planes"], context["pre"])
+            context.update(plane_grads=plane_grads)
+    if context is not None:
+        context.update(grads=grads, g_hidden=g_hidden)
     di = ctx.di if ctx.di != x.shape[1] else None      # (x was saved with its pad columns)
     out = [(g_x if di is None else g_x[:, :di]) if ctx.needs_input_grad[0] else None, None]
     out += wgrad(x, grads[0] if nb else g_hidden, need[0], need[1], rows=narrow, cols=di)
@@ -772,7 +787,10 @@ def _resnet_hidden_backward(ctx, g_out, saved_tensors):
     hidden_problems = []
     for k in range(nb):
         hidden_problems.append((saved[2 * k], grads[2 * k + 1]))
-        hidden_problems.append((saved[2 * k + 1], grads[2 * k + 2] if k + 1 < nb else g_hidden))
+        if context is not None and gated is not None:   # GLU: the second Linear saw g sigmoid(c_k), not g
+            hidden_problems.append((saved[2 * k + 1], gated[k]))
+        else:
+            hidden_problems.append((saved[2 * k + 1], grads[2 * k + 2] if k + 1 < nb else g_hidden))
     batched = None
     if nb and all(need[2:2 + 4 * nb]) and 2 * nb <= 8 and BATCHED_WGRAD:
         batched = ops.linear_wgrad_batched(hidden_problems, need_bias=True)
@@ -835,6 +853,105 @@ class MadeNet(torch.autograd.Function):
         if pairs:
             torch._foreach_mul_([g for g, _ in pairs], [m for _, m in pairs])
         return tuple(grads)
+
+
+class ResidualNetHiddenCtx(torch.autograd.Function):
+    """K27: `ResidualNetHidden` for a ResidualNet WITH a context (resnet.py:42-52, :92-100): the context is concatenated to
+    the inputs by the caller (under autograd), every block's `context_layer` stays a stock Linear whose output, zero-padded
+    to 128 columns, enters as a plane; the kernels gate t_k = W_1 relu(a_k) + b_1 with sigmoid(plane) and return the
+    planes' gradients, from which autograd reaches the context Linears, the context and whatever produced it.
+    Arguments: [inputs | context] [B, d_i + C], with_final, the number of blocks, one plane [B, 128] per block, then the
+    parameters as `ResidualNetHidden` takes them.  Once-differentiable and deterministic."""
+
+    @staticmethod
+    def forward(ctx, x, with_final, nb, *rest):
+        from . import ops
+        planes, params = rest[:nb], rest[nb:]
+        hidden_params = params[:-2] if with_final else params
+        assert (len(hidden_params) - 2) // 4 == nb
+        blocks = [hidden_params[2 + 4 * k: 6 + 4 * k] for k in range(nb)]
+        final = params[-2:] if with_final else None
+        w_in = params[0]
+        ctx.di = x.shape[1]
+        if ctx.di % 4:
+            pad = 4 - ctx.di % 4
+            x = torch.nn.functional.pad(x.detach(), (0, pad))
+            w_in = torch.nn.functional.pad(w_in.detach(), (0, pad))
+        fwd_w, fwd_b, bwd_w, fbias = ops.pack_resnet_hidden_train(w_in, params[1], blocks, final)
+        hidden, saved, out, pre = ops.resnet_hidden_forward_ctx(ops.TRAIN_CTX_GLU, x, planes, fwd_w, fwd_b, nb, fbias,
+                                                                final[0].shape[0] if with_final else 0)
+        ctx.nb, ctx.with_final, ctx.H = nb, with_final, params[0].shape[0]
+        planes = [p.detach() for p in planes]
+        if with_final:
+            ctx.save_for_backward(x.detach().contiguous(), saved, bwd_w, hidden, final[0], pre, *planes)
+            return out
+        ctx.save_for_backward(x.detach().contiguous(), saved, bwd_w, pre, *planes)
+        return hidden if ctx.H == 128 else hidden[:, :ctx.H]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out):
+        from . import ops
+        n = 5 if ctx.with_final else 3
+        pre, planes = ctx.saved_tensors[n], ctx.saved_tensors[n + 1:]
+        context = dict(mode=ops.TRAIN_CTX_GLU, planes=planes, pre=pre, first_param=3 + ctx.nb)
+        grads = _resnet_hidden_backward(ctx, g_out, ctx.saved_tensors[:n], context)
+        plane_grads = context["plane_grads"]
+        return (grads[0], None, None) + tuple(plane_grads[k] for k in range(ctx.nb)) + tuple(grads[2:])
+
+
+class MadeNetCtx(torch.autograd.Function):
+    """K27: `MadeNet` for a MADE with residual blocks AND a context (made.py:129-137, :197-201): the net's and the blocks'
+    `context_layer`s stay stock Linears; their outputs, zero-padded to 128 columns (the net's through its ReLU), enter as
+    planes that the forward kernel adds to h_0 and to every a_k.  The backward pass is `MadeNet`'s: the gradient of
+    block k's plane IS grads[2 k + 1], the initial plane's grads[0] (d loss / d hidden without a block) -- returned as
+    views.  Arguments: inputs [B, D], masks, the number of blocks, the initial plane, one plane per block, then the
+    parameters as `MadeNet` takes them."""
+
+    @staticmethod
+    def forward(ctx, x, masks, nb, initial_plane, *rest):
+        from . import ops
+        planes, params = rest[:nb], rest[nb:]
+        assert (len(params) - 4) // 4 == nb
+        blocks = [params[2 + 4 * k: 6 + 4 * k] for k in range(nb)]
+        final = params[-2:]
+        ctx.di, ctx.rows = x.shape[1], final[0].shape[0]
+        ctx.nb, ctx.with_final, ctx.H = nb, True, params[0].shape[0]
+        x = x.detach()
+        if ctx.di % 4:
+            x = torch.nn.functional.pad(x, (0, 4 - ctx.di % 4))
+        out4 = (ctx.rows + 3) // 4 * 4
+        fwd_w, fwd_b, bwd_w, fbias = ops.pack_made_train(params[0], params[1], blocks, final, masks)
+        hidden, saved, out, _ = ops.resnet_hidden_forward_ctx(ops.TRAIN_CTX_ADD, x, planes, fwd_w, fwd_b, nb, fbias, out4,
+                                                              initial_plane=initial_plane)
+        ctx.save_for_backward(x.contiguous(), saved, bwd_w, hidden, final[0], *masks)
+        return out if out4 == ctx.rows else out[:, :ctx.rows]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out):
+        from . import ops
+        x, saved, bwd_w, hidden, w_f = ctx.saved_tensors[:5]
+        masks = ctx.saved_tensors[5:]
+        rows, pad, nb = ctx.rows, -ctx.rows % 4, ctx.nb
+        if pad:
+            g_out = torch.nn.functional.pad(g_out, (0, pad))
+
+        def masked_final():
+            w = w_f if masks[-1] is None else w_f * masks[-1]
+            return torch.nn.functional.pad(w, (0, 0, 0, pad)) if pad else w
+
+        context = dict(mode=ops.TRAIN_CTX_ADD, planes=(), pre=None, first_param=4 + nb)
+        grads = list(_resnet_hidden_backward(ctx, g_out, (x, saved, bwd_w, hidden, masked_final), context))
+        if pad:
+            grads[-2] = None if grads[-2] is None else grads[-2][:rows].contiguous()
+            grads[-1] = None if grads[-1] is None else grads[-1][:rows].contiguous()
+        pairs = [(g, m) for g, m in zip(grads[2::2], masks) if g is not None and m is not None]
+        if pairs:
+            torch._foreach_mul_([g for g, _ in pairs], [m for _, m in pairs])
+        g_all = context["grads"]
+        g_initial = g_all[0] if nb else context["g_hidden"]
+        return (grads[0], None, None, g_initial) + tuple(g_all[2 * k + 1] for k in range(nb)) + tuple(grads[2:])
 
 
 def _dense_rows(t, n, width):

@@ -26,8 +26,13 @@
 // implies that at most the three youngest requests are pending).
 //
 // Restrictions (the host keeps the eager path otherwise): hidden width <= 128 and a multiple of 4 (narrower nets are
-// zero-padded into the 128-wide streams by the packer), ReLU, no context / batch norm / active dropout, at most three
+// zero-padded into the 128-wide streams by the packer), ReLU, no batch norm / active dropout, at most three
 // blocks, d_i <= 64 and d_i % 4 == 0, batch % 128 == 0.
+//
+// K27: a context.  The context Linears stay the caller's; their outputs arrive as dense [B, 128] planes and the kernels'
+// MODE says what they do with them (TrainMode below: the GLU gate of a ResidualNet, the additive terms of a MADE).  A
+// plane read in the middle of a row block is an ordinary load: the ring is drained in front of it (`s_waitcnt vmcnt(0)`)
+// and the load is awaited before the next ring request (nfa_resnet_hidden_forward_ctx_f32 / nfa_resnet_backward_ctx_f32).
 
 #include "bf16x3_gemm.hpp"
 
@@ -55,7 +60,27 @@ struct TrainArgs {
     const float* gparams;
     float* grad_hidden;
     int final_ksteps, final_first;
+    // K27 (a conditioner with a context, MODE != kModeNone; unused and unread otherwise): the context Linears' outputs
+    // arrive as dense [B, 128] planes (exact zeros past the net's width) that stock ops computed
+    const float* planes[3];     // per block: GLU: the gate's logits c_k;  ADD: the term added to a_k
+    const float* initial_plane; // ADD, optional: the term added to h_0
+    float* pre;                 // GLU: [nb][B][128], t_k = W_1 relu(a_k) + b_1 (forward: written, backward: read)
+    float* plane_grads[3];      // GLU backward: d loss / d planes[k], [B, 128]
+    float* gated_grads;         // GLU backward: [nb][B][128], g_t = g sigmoid(c_k): `grad_outputs` of block k's second Linear
 };
+
+// K27: how a context enters the blocks.  kModeGlu (ResidualNet): h_{k+1} = h_k + t_k sigmoid(planes[k]);  kModeAdd
+// (MADE): a_k = W_0 relu(h_k) + b_0 + planes[k], h_0 += initial_plane.  Every statement of a mode sits behind
+// `if constexpr (MODE ...)`: the kModeNone instances are the kernels of before.
+enum TrainMode : int { kModeNone = 0, kModeGlu = 1, kModeAdd = 2 };
+
+// sigmoid(c) from e = exp(-|c|) in [0, 1]: 1 / (1 + e) for c >= 0, e / (1 + e) below -- no overflow and no inf * 0
+// anywhere, monotone, exactly 0 and 1 at logits past -+104, NaN for NaN
+__device__ __forceinline__ float sigmoid_stable(float c) {
+    const float e = expf(-fabsf(c));
+    const float r = 1.0f / (1.0f + e);
+    return c >= 0.0f ? r : e * r;
+}
 
 // accumulator tile <-> rows of a [B, 128] array: element (row, 32 t + 8 q4 + 4 half + i) = acc[4 q4 + i]
 //
@@ -354,7 +379,16 @@ __device__ __forceinline__ void gemm_tile_pieces(f32x16& acc, const bf16x8 (&ph)
     }
 }
 
-template <int INIT_KS>
+// loads the lane's 64 values of a [B, 128] array (accumulator layout); the caller waits
+__device__ __forceinline__ void load_tiles_raw(vec4f (&v)[16], const float* base, int64_t row, int half) {
+    const vec4f* p = reinterpret_cast<const vec4f*>(base + row * 128 + 4 * half);
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int q4 = 0; q4 < 4; ++q4) v[t * 4 + q4] = p[8 * t + 2 * q4];
+}
+
+template <int INIT_KS, int MODE = kModeNone>
 __global__ void __launch_bounds__(kBlock, 2) resnet_hidden_forward_kernel(const TrainArgs a) {
 #pragma clang fp contract(off)
     extern __shared__ __attribute__((aligned(16))) float lds_dyn[];
@@ -365,7 +399,11 @@ __global__ void __launch_bounds__(kBlock, 2) resnet_hidden_forward_kernel(const 
     const int64_t num_quads = a.batch >> 7;
     const int64_t plane = a.batch * 128;   // one saved activation
     for (int64_t quad = blockIdx.x; quad < num_quads; quad += gridDim.x) {
-        const int64_t row0 = (quad << 7) + (wave << 5);
+        // (K27's instances: what depends on the wave is formed per row block like what depends on the lane -- hoisted out
+        //  of this loop, those addresses were spilled, and scratch traffic may not share the ring's counter)
+        int wave_here = wave;
+        if constexpr (MODE != kModeNone) asm volatile("" : "+v"(wave_here));
+        const int64_t row0 = (quad << 7) + (wave_here << 5);
         int lane_here = lane, di = a.di;
         asm volatile("" : "+v"(lane_here), "+s"(di));
         const int half = lane_here >> 5, r = lane_here & 31;
@@ -384,9 +422,33 @@ __global__ void __launch_bounds__(kBlock, 2) resnet_hidden_forward_kernel(const 
                     const int k0 = ks * 16 + half * 8 + g * 4;
                     xv[ks][g] = k0 < di ? *reinterpret_cast<const vec4f*>(xr + k0) : vec4f{0.0f, 0.0f, 0.0f, 0.0f};
                 }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if constexpr (MODE == kModeAdd) {
+                // the initial layer's context term, with x while the ring is drained: h_0 = b_in + plane (+ W_in x below)
+                if (a.initial_plane) {   // (wave-uniform)
+                    vec4f pv[16];
+                    load_tiles_raw(pv, a.initial_plane, row, half);
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
-            for (int t = 0; t < 4; ++t) load_bias_tile(hs[t], bias + t * 32);
+                    for (int t = 0; t < 4; ++t) {
+                        load_bias_tile(hs[t], bias + t * 32);
+#pragma unroll
+                        for (int q4 = 0; q4 < 4; ++q4) {
+                            hs[t][4 * q4] += pv[4 * t + q4].x;
+                            hs[t][4 * q4 + 1] += pv[4 * t + q4].y;
+                            hs[t][4 * q4 + 2] += pv[4 * t + q4].z;
+                            hs[t][4 * q4 + 3] += pv[4 * t + q4].w;
+                        }
+                    }
+                } else {
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) load_bias_tile(hs[t], bias + t * 32);
+                }
+            } else {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+                for (int t = 0; t < 4; ++t) load_bias_tile(hs[t], bias + t * 32);
+            }
 #pragma unroll
             for (int ks = 0; ks < INIT_KS; ++ks) {
                 bf16x2 hh[4], mm[4], ll[4];
@@ -411,6 +473,23 @@ __global__ void __launch_bounds__(kBlock, 2) resnet_hidden_forward_kernel(const 
 #endif
                 load_bias_tile(u[t], bias + t * 32);
             }
+            if constexpr (MODE == kModeAdd) {
+                // a_k's context term: ordinary loads in the middle of the stream, so the ring is drained first and the
+                // loads are awaited before the next ring request (u is not live yet: the plane lands in it)
+                vec4f pv[16];
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                load_tiles_raw(pv, a.planes[blk], row, half);
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+                for (int t = 0; t < 4; ++t)
+#pragma unroll
+                    for (int q4 = 0; q4 < 4; ++q4) {
+                        u[t][4 * q4] += pv[4 * t + q4].x;
+                        u[t][4 * q4 + 1] += pv[4 * t + q4].y;
+                        u[t][4 * q4 + 2] += pv[4 * t + q4].z;
+                        u[t][4 * q4 + 3] += pv[4 * t + q4].w;
+                    }
+            }
             unsigned long long* pm = packed_masks(a.saved, a.batch, a.num_blocks) + ((row0 >> 5) << 6) + lane_here;
             Mask64 mh = {0u, 0u}, ma = {0u, 0u};   // [h_k > 0], [a_k > 0]
             gemm_from_tiles<true>(u, hs, sm, lane, in0, row, half, stage, &mh);    // (stores relu(h), the first Linear's input, on the way)
@@ -430,14 +509,33 @@ __global__ void __launch_bounds__(kBlock, 2) resnet_hidden_forward_kernel(const 
                 // (h, u and the accumulator are 192 registers: the last tile of h waits in the wave's 4 KB of LDS behind the
                 //  store images, so that nothing spills -- scratch traffic may not share the counter of the ring)
                 vec4f* park = reinterpret_cast<vec4f*>(lds_dyn + kTrainRing * kStageVec4 * 4 + (kBlock / kWave) * kTrainTileFloats) +
-                              wave * (4 * kWave) + lane_here;
+                              wave_here * (4 * kWave) + lane_here;
 #pragma unroll
                 for (int q4 = 0; q4 < 4; ++q4)
                     park[q4 * kWave] = vec4f{hs[3][4 * q4], hs[3][4 * q4 + 1], hs[3][4 * q4 + 2], hs[3][4 * q4 + 3]};
+                // (K27's instances keep a few more addresses alive than the register file has room for: half of the tile
+                //  before it waits too, in 8 KB more of LDS per workgroup)
+                [[maybe_unused]] vec4f* park2 = reinterpret_cast<vec4f*>(lds_dyn + kTrainRing * kStageVec4 * 4 + (kBlock / kWave) * kTrainTileFloats) +
+                                                (kBlock / kWave) * (4 * kWave) + wave_here * (2 * kWave) + lane_here;
+                if constexpr (MODE != kModeNone) {
+#pragma unroll
+                    for (int q4 = 2; q4 < 4; ++q4)
+                        park2[(q4 - 2) * kWave] = vec4f{hs[2][4 * q4], hs[2][4 * q4 + 1], hs[2][4 * q4 + 2], hs[2][4 * q4 + 3]};
+                }
                 f32x16 v[4];
 #pragma unroll
                 for (int t = 0; t < 4; ++t) zero_tile(v[t]);
                 gemm_from_tiles<true>(v, u, sm, lane, in1, row, half, stage, &ma);
+                if constexpr (MODE != kModeNone) {
+#pragma unroll
+                    for (int q4 = 2; q4 < 4; ++q4) {
+                        const vec4f w = park2[(q4 - 2) * kWave];
+                        hs[2][4 * q4] = w.x;
+                        hs[2][4 * q4 + 1] = w.y;
+                        hs[2][4 * q4 + 2] = w.z;
+                        hs[2][4 * q4 + 3] = w.w;
+                    }
+                }
                 pm[(int64_t)(2 * blk + 1) * (a.batch << 1)] = ((unsigned long long)ma.hi << 32) | ma.lo;
 #pragma unroll
                 for (int q4 = 0; q4 < 4; ++q4) {
@@ -447,11 +545,36 @@ __global__ void __launch_bounds__(kBlock, 2) resnet_hidden_forward_kernel(const 
                     hs[3][4 * q4 + 2] = w.z;
                     hs[3][4 * q4 + 3] = w.w;
                 }
+                if constexpr (MODE == kModeGlu) {
+                    // t_k = W_1 relu(a_k) + b_1 leaves for the backward pass, then h += t_k sigmoid(c_k).  The logits are
+                    // ordinary loads: ring drained first, awaited before the next ring request; u is dead, they take its place
+                    float* pre = a.pre + blk * plane;
 #pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    add_bias_tile(v[t], bias + 128 + t * 32);
+                    for (int t = 0; t < 4; ++t) {
+                        add_bias_tile(v[t], bias + 128 + t * 32);
+                        store_tile<false>(pre, row, t, half, v[t], stage);
+                    }
+                    vec4f cv[16];
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    load_tiles_raw(cv, a.planes[blk], row, half);
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
-                    for (int q = 0; q < 16; ++q) hs[t][q] += v[t][q];   // the skip connection
+                    for (int t = 0; t < 4; ++t)
+#pragma unroll
+                        for (int q4 = 0; q4 < 4; ++q4) {
+                            const float c4[4] = {cv[4 * t + q4].x, cv[4 * t + q4].y, cv[4 * t + q4].z, cv[4 * t + q4].w};
+#pragma unroll
+                            for (int i = 0; i < 4; ++i) {
+                                hs[t][4 * q4 + i] += v[t][4 * q4 + i] * sigmoid_stable(c4[i]);   // the gated skip connection
+                            }
+                        }
+                } else {
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) {
+                        add_bias_tile(v[t], bias + 128 + t * 32);
+#pragma unroll
+                        for (int q = 0; q < 16; ++q) hs[t][q] += v[t][q];   // the skip connection
+                    }
                 }
             }
             bias += 256;
@@ -538,15 +661,6 @@ __device__ __forceinline__ void kstep_final(f32x16 (&acc)[4], TrainStream& sm, c
     sm.slot = (sm.slot + 1 == kTrainRing) ? 0 : sm.slot + 1;
 }
 
-// loads the lane's 64 values of a [B, 128] array (accumulator layout); the caller waits
-__device__ __forceinline__ void load_tiles_raw(vec4f (&v)[16], const float* base, int64_t row, int half) {
-    const vec4f* p = reinterpret_cast<const vec4f*>(base + row * 128 + 4 * half);
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int q4 = 0; q4 < 4; ++q4) v[t * 4 + q4] = p[8 * t + 2 * q4];
-}
-
 __device__ __forceinline__ Mask64 load_mask(const float* base, int64_t row, int half) {
     vec4f v[16];
     load_tiles_raw(v, base, row, half);
@@ -569,7 +683,7 @@ __device__ __forceinline__ void apply_mask(f32x16& acc, const Mask64& m, int t) 
     for (int q = 0; q < 16; ++q) acc[q] = ((w >> q) & 1u) ? acc[q] : 0.0f;
 }
 
-template <int NB, bool FINAL = false>   // number of blocks (their masks live in registers): 0 .. 3 (four would spill: no
+template <int NB, bool FINAL = false, int MODE = kModeNone>   // number of blocks (their masks live in registers): 0 .. 3 (four would spill: no
                                         // scratch traffic may share the counter of the LDS-DMA ring); FINAL: the incoming
                                         // gradient is g_params and the final Linear's input gradient is computed first
 __global__ void __launch_bounds__(kBlock, 2) resnet_hidden_backward_kernel(const TrainArgs a) {
@@ -648,6 +762,47 @@ __global__ void __launch_bounds__(kBlock, 2) resnet_hidden_backward_kernel(const
         // ---- blocks, last to first: g_a = (g_h W_1) . [a > 0];  g_h += (g_a W_0) . [h > 0]
 #pragma unroll
         for (int blk = NB - 1; blk >= 0; --blk) {
+            [[maybe_unused]] f32x16 gt[4];   // GLU: g_t = g sigmoid(c_k), what the second Linear saw of the incoming gradient
+            if constexpr (MODE == kModeGlu) {
+                // the gate: logits and t_k are ordinary loads (ring drained first, awaited before the next ring request),
+                // two tiles at a time so that g, g_t and the loads stay inside the register file; the gradient of the
+                // plane and g_t (K10's grad_outputs of W_1) leave at once
+                float* gc_out = a.plane_grads[blk];
+                float* gt_out = a.gated_grads + blk * plane;
+                const vec4f* cp = reinterpret_cast<const vec4f*>(a.planes[blk] + row * 128 + 4 * half);
+                const vec4f* pp = reinterpret_cast<const vec4f*>(a.pre + blk * plane + row * 128 + 4 * half);
+#pragma unroll
+                for (int pair = 0; pair < 2; ++pair) {
+                    vec4f cv[8], pv[8];
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) {
+                        cv[i] = cp[8 * (2 * pair + (i >> 2)) + 2 * (i & 3)];
+                        pv[i] = pp[8 * (2 * pair + (i >> 2)) + 2 * (i & 3)];
+                    }
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+                    for (int tt = 0; tt < 2; ++tt) {
+                        const int t = 2 * pair + tt;
+                        f32x16 gc;
+#pragma unroll
+                        for (int q4 = 0; q4 < 4; ++q4) {
+                            const vec4f c = cv[4 * tt + q4], p = pv[4 * tt + q4];
+                            const float c4[4] = {c.x, c.y, c.z, c.w}, p4[4] = {p.x, p.y, p.z, p.w};
+#pragma unroll
+                            for (int i = 0; i < 4; ++i) {
+                                const float s = sigmoid_stable(c4[i]);
+                                const float g = gs[t][4 * q4 + i];
+                                // (1 - s as eager's glu_backward forms it: exactly 0 once s rounds to 1)
+                                gc[4 * q4 + i] = ((g * p4[i]) * s) * (1.0f - s);
+                                gt[t][4 * q4 + i] = g * s;
+                            }
+                        }
+                        store_tile<false>(gc_out, row, t, half, gc);
+                        store_tile<false>(gt_out, row, t, half, gt[t]);
+                    }
+                }
+            }
             f32x16 u[4];
 #pragma unroll
             for (int t = 0; t < 4; ++t) zero_tile(u[t]);
@@ -657,7 +812,8 @@ __global__ void __launch_bounds__(kBlock, 2) resnet_hidden_backward_kernel(const
             if (blk < NB - 1) gemm_from_tiles<false, true>(u, gs, sm, lane, a.grads + (2 * (blk + 1)) * plane, row, half, stage);
             else gemm_from_tiles<false>(u, gs, sm, lane);
 #else
-            gemm_from_tiles<false>(u, gs, sm, lane);
+            if constexpr (MODE == kModeGlu) gemm_from_tiles<false>(u, gt, sm, lane);
+            else gemm_from_tiles<false>(u, gs, sm, lane);
 #endif
             float* ga = a.grads + (2 * blk + 1) * plane;
             // (three blocks: the interleaved form spills 12 bytes per lane -- scratch reloads share vmcnt with the ring --,
@@ -875,11 +1031,30 @@ static dim3 train_grid(int64_t batch) {
 
 using namespace nfa;
 
-extern "C" int nfa_resnet_hidden_forward_f32(const float* identity_inputs, const void* weights_packed,
-                                             const float* bias_packed, float* saved, float* hidden,
-                                             const float* final_bias_packed, float* params, int32_t out_features,
-                                             int64_t batch, int32_t num_identity, int32_t hidden_features,
-                                             int32_t num_blocks, void* stream) {
+// K27: the planes of a context and the arrays that go with them (TrainArgs' fields of the same names)
+struct TrainContext {
+    int mode = kModeNone;
+    const float* const* planes = nullptr;   // [num_blocks]
+    const float* initial_plane = nullptr;
+    float* pre = nullptr;
+    float* const* plane_grads = nullptr;    // [num_blocks]
+    float* gated_grads = nullptr;
+};
+
+static void set_context(TrainArgs& a, const TrainContext& c, int num_blocks) {
+    for (int k = 0; k < 3; ++k) {
+        a.planes[k] = (c.planes && k < num_blocks) ? c.planes[k] : nullptr;
+        a.plane_grads[k] = (c.plane_grads && k < num_blocks) ? c.plane_grads[k] : nullptr;
+    }
+    a.initial_plane = c.initial_plane;
+    a.pre = c.pre;
+    a.gated_grads = c.gated_grads;
+}
+
+static int launch_train_forward(const float* identity_inputs, const void* weights_packed, const float* bias_packed,
+                                float* saved, float* hidden, const float* final_bias_packed, float* params,
+                                int32_t out_features, int64_t batch, int32_t num_identity, int32_t hidden_features,
+                                int32_t num_blocks, const TrainContext& c, void* stream) {
     const int rc = check_train(batch, num_identity, hidden_features, num_blocks);
     if (rc != NFA_OK) return rc;
     if (out_features < 0) return NFA_ERR_INVALID_ARGUMENT;
@@ -889,6 +1064,7 @@ extern "C" int nfa_resnet_hidden_forward_f32(const float* identity_inputs, const
         (out_features > 0 && (!final_bias_packed || !params)))
         return NFA_ERR_INVALID_ARGUMENT;
     TrainArgs a;
+    set_context(a, c, num_blocks);
     a.x = identity_inputs;
     a.w = reinterpret_cast<const vec4f*>(weights_packed);
     a.bias = bias_packed;
@@ -909,16 +1085,68 @@ extern "C" int nfa_resnet_hidden_forward_f32(const float* identity_inputs, const
     a.num_stages = init_ks + 16 * num_blocks + 2 * a.final_tiles;
     // the ring, every wave's store image and every wave's parked tile of h (4 KB): 70 KB, two workgroups per CU
     const size_t lds = (size_t)kTrainRing * kStageVec4 * 16 + (size_t)(kBlock / kWave) * kTrainTileFloats * sizeof(float) +
-                       (size_t)(kBlock / kWave) * 4 * kWave * 16;
+                       (size_t)(kBlock / kWave) * 4 * kWave * 16 +
+                       (c.mode != kModeNone ? (size_t)(kBlock / kWave) * 2 * kWave * 16 : 0);   // (K27: half a tile more parked, 8 KB)
     hipStream_t st = (hipStream_t)stream;
     void (*kern)(const TrainArgs) = init_ks == 2 ? resnet_hidden_forward_kernel<2> : resnet_hidden_forward_kernel<4>;
+    if (c.mode == kModeGlu)
+        kern = init_ks == 2 ? resnet_hidden_forward_kernel<2, kModeGlu> : resnet_hidden_forward_kernel<4, kModeGlu>;
+    else if (c.mode == kModeAdd)
+        kern = init_ks == 2 ? resnet_hidden_forward_kernel<2, kModeAdd> : resnet_hidden_forward_kernel<4, kModeAdd>;
     return launch_kernel(kern, train_grid(batch), dim3(kBlock), lds, st, a, 0, false);
+}
+
+extern "C" int nfa_resnet_hidden_forward_f32(const float* identity_inputs, const void* weights_packed,
+                                             const float* bias_packed, float* saved, float* hidden,
+                                             const float* final_bias_packed, float* params, int32_t out_features,
+                                             int64_t batch, int32_t num_identity, int32_t hidden_features,
+                                             int32_t num_blocks, void* stream) {
+    return launch_train_forward(identity_inputs, weights_packed, bias_packed, saved, hidden, final_bias_packed, params,
+                                out_features, batch, num_identity, hidden_features, num_blocks, TrainContext(), stream);
+}
+
+// mode and pointer checks shared by the two K27 entry points; `backward`: the arrays of the backward pass are wanted too
+static int check_context(int32_t mode, const TrainContext& c, int32_t num_blocks, int64_t batch, bool backward) {
+    if (mode != kModeGlu && mode != kModeAdd) return NFA_ERR_INVALID_ARGUMENT;
+    if (batch <= 0 || num_blocks <= 0 || num_blocks > 3) return NFA_OK;   // (check_train judges these)
+    if (mode == kModeAdd && backward) return NFA_OK;                       // (ADD: the backward pass reads no plane)
+    if (!c.planes) return NFA_ERR_INVALID_ARGUMENT;
+    for (int k = 0; k < num_blocks; ++k)
+        if (!c.planes[k]) return NFA_ERR_INVALID_ARGUMENT;
+    if (mode == kModeGlu) {
+        if (!c.pre) return NFA_ERR_INVALID_ARGUMENT;
+        if (backward) {
+            if (!c.plane_grads || !c.gated_grads) return NFA_ERR_INVALID_ARGUMENT;
+            for (int k = 0; k < num_blocks; ++k)
+                if (!c.plane_grads[k]) return NFA_ERR_INVALID_ARGUMENT;
+        }
+    }
+    return NFA_OK;
+}
+
+extern "C" int nfa_resnet_hidden_forward_ctx_f32(int32_t mode, const float* identity_inputs, const float* const* planes,
+                                                 const float* initial_plane, const void* weights_packed,
+                                                 const float* bias_packed, float* saved, float* pre, float* hidden,
+                                                 const float* final_bias_packed, float* params, int32_t out_features,
+                                                 int64_t batch, int32_t num_identity, int32_t hidden_features,
+                                                 int32_t num_blocks, void* stream) {
+    TrainContext c;
+    c.mode = mode;
+    c.planes = planes;
+    c.initial_plane = mode == kModeAdd ? initial_plane : nullptr;
+    c.pre = pre;
+    if (mode == kModeGlu && initial_plane) return NFA_ERR_INVALID_ARGUMENT;
+    const int rc = check_context(mode, c, num_blocks, batch, false);
+    if (rc != NFA_OK) return rc;
+    return launch_train_forward(identity_inputs, weights_packed, bias_packed, saved, hidden, final_bias_packed, params,
+                                out_features, batch, num_identity, hidden_features, num_blocks, c, stream);
 }
 
 static int launch_train_backward(const float* grad_hidden, const float* grad_params, int32_t out_features,
                                  float* grad_hidden_out, const void* weights_packed, const float* saved, float* grads,
                                  float* grad_identity_inputs, int64_t batch, int32_t num_identity,
-                                 int32_t hidden_features, int32_t num_blocks, void* stream) {
+                                 int32_t hidden_features, int32_t num_blocks, void* stream,
+                                 const TrainContext& c = TrainContext()) {
     const int rc = check_train(batch, num_identity, hidden_features, num_blocks);
     if (rc != NFA_OK) return rc;
     const bool with_final = grad_params != nullptr || out_features != 0;
@@ -929,6 +1157,7 @@ static int launch_train_backward(const float* grad_hidden, const float* grad_par
         !grad_identity_inputs || (num_blocks > 0 && (!saved || !grads)))
         return NFA_ERR_INVALID_ARGUMENT;
     TrainArgs a;
+    set_context(a, c, num_blocks);
     a.x = grad_hidden;
     a.w = reinterpret_cast<const vec4f*>(weights_packed);
     a.bias = nullptr;
@@ -967,6 +1196,14 @@ static int launch_train_backward(const float* grad_hidden, const float* grad_par
     else
         kern = num_blocks == 0 ? resnet_hidden_backward_kernel<0> : num_blocks == 1 ? resnet_hidden_backward_kernel<1>
                : num_blocks == 2 ? resnet_hidden_backward_kernel<2> : resnet_hidden_backward_kernel<3>;
+    if (c.mode == kModeGlu && num_blocks > 0) {   // (ADD and a net without blocks: the kernels of before)
+        if (with_final)
+            kern = num_blocks == 1 ? resnet_hidden_backward_kernel<1, true, kModeGlu>
+                   : num_blocks == 2 ? resnet_hidden_backward_kernel<2, true, kModeGlu> : resnet_hidden_backward_kernel<3, true, kModeGlu>;
+        else
+            kern = num_blocks == 1 ? resnet_hidden_backward_kernel<1, false, kModeGlu>
+                   : num_blocks == 2 ? resnet_hidden_backward_kernel<2, false, kModeGlu> : resnet_hidden_backward_kernel<3, false, kModeGlu>;
+    }
     return launch_kernel(kern, grid, block, lds, st, a, 0, false);
 }
 
@@ -987,6 +1224,30 @@ extern "C" int nfa_resnet_backward_f32(const float* grad_params, int32_t out_fea
     if (!grad_params && batch > 0) return NFA_ERR_INVALID_ARGUMENT;
     return launch_train_backward(nullptr, grad_params, out_features, grad_hidden, weights_packed, saved, grads,
                                  grad_identity_inputs, batch, num_identity, hidden_features, num_blocks, stream);
+}
+
+extern "C" int nfa_resnet_backward_ctx_f32(int32_t mode, const float* grad_hidden, const float* grad_params,
+                                           int32_t out_features, const float* const* planes, const float* pre,
+                                           const void* weights_packed, const float* saved, float* grads,
+                                           float* const* plane_grads, float* gated_grads, float* grad_hidden_out,
+                                           float* grad_identity_inputs, int64_t batch, int32_t num_identity,
+                                           int32_t hidden_features, int32_t num_blocks, void* stream) {
+    TrainContext c;
+    c.mode = mode;
+    c.planes = planes;
+    c.pre = const_cast<float*>(pre);
+    c.plane_grads = plane_grads;
+    c.gated_grads = gated_grads;
+    const int rc = check_context(mode, c, num_blocks, batch, true);
+    if (rc != NFA_OK) return rc;
+    if ((grad_hidden != nullptr) == (grad_params != nullptr) && batch > 0) return NFA_ERR_INVALID_ARGUMENT;   // exactly one
+    if (grad_params || out_features != 0) {
+        if (out_features < 4 || grad_hidden) return NFA_ERR_INVALID_ARGUMENT;
+        return launch_train_backward(nullptr, grad_params, out_features, grad_hidden_out, weights_packed, saved, grads,
+                                     grad_identity_inputs, batch, num_identity, hidden_features, num_blocks, stream, c);
+    }
+    return launch_train_backward(grad_hidden, nullptr, 0, nullptr, weights_packed, saved, grads, grad_identity_inputs, batch,
+                                 num_identity, hidden_features, num_blocks, stream, c);
 }
 
 // the packer's launch; `masks` (K25) null or [2 + 2 num_blocks] pointers: the masks of W_in, (W_0, W_1) per block and W_f,

@@ -92,16 +92,31 @@ class GraphedTrainStep:
     The warm-up runs `warmup` REAL optimisation steps on `example_inputs` (PyTorch's whole-network
     capture recipe needs the optimizer state and the gradient buffers to exist before capture).
     `loss_fn(flow, inputs) -> 0-dim tensor` replaces the default negative mean log-likelihood.
+
+    Conditional flows: `example_context` (same rows, same device) makes the step
+    `loss = -flow.log_prob(x, context=ctx).mean()`; call `step(x, ctx)`.  The context gets a static copy
+    like the inputs, and a `loss_fn` is then called as `loss_fn(flow, inputs, context)`.
     """
 
-    def __init__(self, flow, optimizer, example_inputs, loss_fn=None, warmup=3):
+    def __init__(self, flow, optimizer, example_inputs, loss_fn=None, warmup=3, example_context=None):
         if not example_inputs.is_cuda:
             raise NotImplementedError("nflows_amd: HIP graphs need inputs on a HIP device")
         if optimizer.defaults.get("capturable") is False:
             raise ValueError("GraphedTrainStep needs a capture-safe optimizer: construct it with capturable=True")
+        if example_context is not None:
+            if not torch.is_tensor(example_context) or example_context.device != example_inputs.device:
+                raise ValueError("GraphedTrainStep: example_context must be a tensor on the inputs' device")
+            if example_context.dim() < 1 or example_context.shape[0] != example_inputs.shape[0]:
+                raise ValueError("GraphedTrainStep: example_context needs one row per row of example_inputs")
         self.flow = flow
         self.optimizer = optimizer
-        self._loss_fn = loss_fn if loss_fn is not None else (lambda f, x: -f.log_prob(x).mean())
+        self._static_ctx = None if example_context is None else example_context.detach().clone()
+        if loss_fn is not None:
+            self._loss_fn = loss_fn if self._static_ctx is None else (lambda f, x: loss_fn(f, x, self._static_ctx))
+        elif self._static_ctx is None:
+            self._loss_fn = lambda f, x: -f.log_prob(x).mean()
+        else:
+            self._loss_fn = lambda f, x: -f.log_prob(x, context=self._static_ctx).mean()
         self._static_in = example_inputs.detach().clone()
         device = example_inputs.device
         side = torch.cuda.Stream(device=device)
@@ -124,9 +139,16 @@ class GraphedTrainStep:
         self.optimizer.step()
         return loss
 
-    def __call__(self, inputs):
+    def __call__(self, inputs, context=None):
         if inputs.shape != self._static_in.shape or inputs.dtype != self._static_in.dtype:
             raise ValueError("GraphedTrainStep was captured for %s %s" % (tuple(self._static_in.shape), self._static_in.dtype))
+        if (context is None) != (self._static_ctx is None):
+            raise ValueError("GraphedTrainStep was captured %s a context" % ("without" if self._static_ctx is None else "with"))
+        if context is not None:
+            if context.shape != self._static_ctx.shape or context.dtype != self._static_ctx.dtype:
+                raise ValueError("GraphedTrainStep was captured for a context %s %s" % (tuple(self._static_ctx.shape),
+                                                                                     self._static_ctx.dtype))
+            self._static_ctx.copy_(context)
         self._static_in.copy_(inputs)
         self._graph.replay()
         return self._static_loss

@@ -169,33 +169,69 @@ class _Net(nn.Module):
             for _ in range(num_blocks))
         self.final_layer = make(width, n_out)
 
+    def _fusable_with_context(self, inputs, context):
+        """K27's part of the gate (whatever device the tensors are on): the switch NFA_K27 is on, the context is a
+        float32 [B, C] tensor (C >= 1) on the inputs' device, inputs and context together are at most 64 columns
+        (K14 pads them to a multiple of 4), and every block gates through a `context_layer` that is an nn.Linear with a
+        bias from those C columns to the hidden width."""
+        from ... import ops
+        if not (ops.CTX_TRAINING and torch.is_tensor(context) and context.dtype == torch.float32 and context.dim() == 2
+                and inputs.dim() == 2 and context.device == inputs.device and context.shape[0] == inputs.shape[0]
+                and context.shape[1] >= 1 and (inputs.shape[1] + context.shape[1] + 3) // 4 * 4 <= 64):
+            return False
+        for b in self.blocks:
+            layer = getattr(b, "context_layer", None)
+            if (type(layer) is not nn.Linear or layer.bias is None or layer.in_features != context.shape[1]
+                    or layer.out_features != self.hidden_features or layer.weight.dtype != torch.float32
+                    or layer.weight.device != inputs.device):
+                return False
+        return True
+
     def _fused_training(self, inputs, context):
         """K14 (one kernel for the hidden part's forward pass, one for its input gradients) applies: plain
-        ResidualNet under autograd on the device, ReLU, no context / batch norm / active dropout, the shapes
-        `ops.resnet_hidden_train_supported` lists."""
-        if not (self.fuse_training and type(self) is ResidualNet and context is None and torch.is_grad_enabled()
+        ResidualNet under autograd on the device, ReLU, no batch norm / active dropout, the shapes
+        `ops.resnet_hidden_train_supported` lists; with a context (K27) what `_fusable_with_context` asks on top.  A net
+        built with `context_features` but called without a context keeps the eager modules."""
+        if not (self.fuse_training and type(self) is ResidualNet and torch.is_grad_enabled()
                 and inputs.is_cuda and inputs.dtype == torch.float32 and inputs.dim() == 2):
             return False
         if torch.is_autocast_enabled() or _has_inner_hooks(self):
             return False
+        if context is not None and not self._fusable_with_context(inputs, context):
+            return False
         from ... import ops
-        if not ops.resnet_hidden_train_supported(inputs.shape[0], inputs.shape[1], self.hidden_features, len(self.blocks)):
+        width = inputs.shape[1] + (context.shape[1] if context is not None else 0)
+        if not ops.resnet_hidden_train_supported(inputs.shape[0], width, self.hidden_features, len(self.blocks)):
             return False
         w = self.initial_layer.weight
-        if inputs.shape[1] != self.initial_layer.in_features or w.dtype != torch.float32 or w.device != inputs.device:
+        if width != self.initial_layer.in_features or w.dtype != torch.float32 or w.device != inputs.device:
             return False   # (half-precision or misplaced parameters: the eager modules report it their own way)
         for b in self.blocks:
             if (b.activation is not F.relu or b.use_batch_norm or (b.training and b.dropout.p != 0.0)
-                    or getattr(b, "context_layer", None) is not None):
+                    or (context is None and getattr(b, "context_layer", None) is not None)):
                 return False
-        return any(p.requires_grad for p in self.parameters()) or inputs.requires_grad
+        return (any(p.requires_grad for p in self.parameters()) or inputs.requires_grad
+                or (context is not None and context.requires_grad))
+
+    def _context_planes(self, context):
+        """every block's `context_layer(context)` as a dense [B, 128] plane: the stock Linear under autograd -- its own
+        GEMMs forward and backward, in the eager path's shapes --, a narrower net's output zero-padded to K14's width"""
+        pad = 128 - self.hidden_features
+        planes = [F.linear(context, b.context_layer.weight, b.context_layer.bias) for b in self.blocks]
+        return [F.pad(p, (0, pad)) for p in planes] if pad else planes
+
+    def _fused_apply(self, inputs, context, with_final, *tail):
+        from ... import autograd as AG
+        if context is None:
+            return AG.ResidualNetHidden.apply(inputs, with_final, *self._hidden_parameters(), *tail)
+        return AG.ResidualNetHiddenCtx.apply(torch.cat((inputs, context), dim=1), with_final, len(self.blocks),
+                                             *self._context_planes(context), *self._hidden_parameters(), *tail)
 
     def hidden(self, inputs, context=None):
         """Activations in front of `final_layer` (the fused spline kernels K7 / K7b consume these
         and apply `final_layer` themselves)."""
         if self._fused_training(inputs, context):
-            from ... import autograd as AG
-            return AG.ResidualNetHidden.apply(inputs, False, *self._hidden_parameters())
+            return self._fused_apply(inputs, context, False)
         h = inputs if context is None else torch.cat((inputs, context), dim=1)
         h = apply_layer(self.initial_layer, h)
         for block in self.blocks:
@@ -215,8 +251,7 @@ class _Net(nn.Module):
                 and final.out_features % 4 == 0 and final.out_features <= 32768   # (the packer's / kernel's limit)
                 and final.in_features == self.hidden_features):
             # the whole conditioner's forward pass in one kernel (K14 with the final Linear appended)
-            from ... import autograd as AG
-            return AG.ResidualNetHidden.apply(inputs, True, *self._hidden_parameters(), final.weight, final.bias)
+            return self._fused_apply(inputs, context, True, final.weight, final.bias)
         return apply_layer(final, self.hidden(inputs, context))
 
 

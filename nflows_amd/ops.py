@@ -2297,6 +2297,92 @@ def resnet_backward(grad_params, bwd_stages, saved, num_identity):
     return gx, grads, g_hidden
 
 
+# K27: K14 / K10 for conditioners with a context (A/B switch: NFA_K27=0 keeps the eager modules whenever one is passed)
+CTX_TRAINING = os.environ.get("NFA_K27", "1") != "0"
+TRAIN_CTX_GLU, TRAIN_CTX_ADD = 1, 2     # include/nflows_amd.h: NFA_TRAIN_CTX_GLU / _ADD
+
+
+def _train_planes(planes, batch, dev):
+    """the context Linears' outputs as the kernels read them: dense float32 [B, 128] on `dev`"""
+    out = []
+    for p in planes:
+        N.require_device_f32("planes", p, 2)
+        if p.shape != (batch, 128) or p.device != dev:
+            raise ValueError("nflows_amd: a context plane is a [batch, 128] tensor on the inputs' device")
+        out.append(p.detach().contiguous())
+    return out
+
+
+def resnet_hidden_forward_ctx(mode, x, planes, fwd_stages, fwd_bias, num_blocks, final_bias=None, out_features=0,
+                              initial_plane=None):
+    """K27 forward (`nfa_resnet_hidden_forward_ctx_f32`): K14's forward pass with the outputs of the context Linears as
+    [B, 128] planes, one per block.  TRAIN_CTX_GLU: x = [inputs | context], h += t_k sigmoid(planes[k]); TRAIN_CTX_ADD:
+    a_k += planes[k], h_0 += initial_plane.  Returns (hidden, saved, params or None, pre [num_blocks, B, 128] or None --
+    t_k, GLU only)."""
+    N.require_device_f32("inputs", x, 2)
+    x = x.detach().contiguous()
+    B, di = x.shape
+    dev = x.device
+    if len(planes) != num_blocks:
+        raise ValueError("nflows_amd: one context plane per block")
+    planes = _train_planes(planes, B, dev)
+    initial = _train_planes([initial_plane], B, dev)[0] if initial_plane is not None else None
+    hidden = torch.empty(B, 128, dtype=torch.float32, device=dev)
+    count = 2 * num_blocks * B * 128
+    saved_all = torch.empty(count + _train_mask_words(num_blocks, B), dtype=torch.float32, device=dev)
+    saved = saved_all[:count].view(2 * num_blocks, B, 128)
+    pre = torch.empty(num_blocks, B, 128, dtype=torch.float32, device=dev) if mode == TRAIN_CTX_GLU else None
+    params = torch.empty(B, out_features, dtype=torch.float32, device=dev) if final_bias is not None else None
+    ptrs = (ctypes.c_void_p * max(1, num_blocks))(*[p.data_ptr() for p in planes])
+    with torch.cuda.device(dev):
+        rc = N.load().nfa_resnet_hidden_forward_ctx_f32(
+            mode, N.ptr(x), ptrs, N.ptr(initial), N.ptr(fwd_stages), N.ptr(fwd_bias),
+            N.ptr(saved_all) if num_blocks else None, N.ptr(pre) if pre is not None and num_blocks else None, N.ptr(hidden),
+            N.ptr(final_bias), N.ptr(params), out_features if final_bias is not None else 0, B, di, 128, num_blocks,
+            N.stream_handle(dev))
+    N.check(rc)
+    return hidden, saved, params, pre
+
+
+def resnet_backward_ctx(mode, grad, bwd_stages, saved, num_identity, planes=(), pre=None, from_params=False):
+    """K27 backward (`nfa_resnet_backward_ctx_f32`): from d loss / d hidden [B, 128] or, `from_params`, from d loss /
+    d params [B, out] (a width the kernel takes: out % 4 == 0).  Returns (grad of the identity features, grads
+    [2 nb, B, 128], d loss / d hidden [B, 128] -- `grad` itself unless from_params --, plane_grads [nb, B, 128] or None,
+    gated_grads [nb, B, 128] or None).  GLU: plane_grads[k] is the gradient of planes[k], gated_grads[k] the
+    grad_outputs of block k's second Linear.  ADD: both None -- the planes' gradients are grads[2 k + 1] and grads[0]."""
+    N.require_device_f32("grad", grad, 2)
+    g = grad.detach().contiguous()
+    B = g.shape[0]
+    dev = g.device
+    nb = saved.shape[0] // 2
+    out = g.shape[1] if from_params else 0
+    if from_params and (out % 4 or out < 4):
+        raise ValueError("nflows_amd: the backward kernel takes output widths in multiples of 4")
+    if nb:
+        _saved_with_masks(saved, nb, B)
+    grads = torch.empty(2 * nb, B, 128, dtype=torch.float32, device=dev)
+    g_hidden = torch.empty(B, 128, dtype=torch.float32, device=dev) if from_params else g
+    gx = torch.empty(B, num_identity, dtype=torch.float32, device=dev)
+    plane_grads = gated = None
+    pptrs = gptrs = None
+    if mode == TRAIN_CTX_GLU and nb:
+        if len(planes) != nb or pre is None or pre.shape != (nb, B, 128):
+            raise ValueError("nflows_amd: the GLU backward pass wants the forward pass's planes and `pre`")
+        planes = _train_planes(planes, B, dev)
+        plane_grads = torch.empty(nb, B, 128, dtype=torch.float32, device=dev)
+        gated = torch.empty(nb, B, 128, dtype=torch.float32, device=dev)
+        pptrs = (ctypes.c_void_p * nb)(*[p.data_ptr() for p in planes])
+        gptrs = (ctypes.c_void_p * nb)(*[plane_grads[k].data_ptr() for k in range(nb)])
+    with torch.cuda.device(dev):
+        rc = N.load().nfa_resnet_backward_ctx_f32(
+            mode, None if from_params else N.ptr(g), N.ptr(g) if from_params else None, out, pptrs,
+            N.ptr(pre) if gated is not None else None, N.ptr(bwd_stages), N.ptr(saved) if nb else None,
+            N.ptr(grads) if nb else None, gptrs, N.ptr(gated), N.ptr(g_hidden) if from_params else None, N.ptr(gx), B,
+            num_identity, 128, nb, N.stream_handle(dev))
+    N.check(rc)
+    return gx, grads, g_hidden, plane_grads, gated
+
+
 def _affine_row_order(num_transform, additive):
     """For every row of the packed output layer of K11: which conditioner output it is (-1 = zero
     padding).  Row i of tile t sits in accumulator register q = 4 (i // 8) + i % 4 of lane-half

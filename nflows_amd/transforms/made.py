@@ -211,14 +211,14 @@ class MADE(nn.Module):
     # layers, so it steps aside by itself under autocast or when an inner module carries a hook.
     fuse_training = os.environ.get("NFA_K25", "1") != "0"
 
-    def _fusable(self, batch, features, context=None):
+    def _fusable(self, batch, features, context=None, _context_layers=False):
         """The net and the shape are K25's (whatever device the tensors are on): the switch is on, a plain MADE with
         residual blocks, ReLU throughout, no context / batch norm / active dropout, no autocast, no hook on an inner
         module, and a shape K14 takes (`ops.resnet_hidden_train_supported`: hidden width 4 .. 128 in multiples of 4, at
         most 64 features and 3 blocks, rows in multiples of 128)."""
         if not (self.fuse_training and type(self) is MADE and self.use_residual_blocks and context is None):
             return False
-        if self.activation is not F.relu or getattr(self, "context_layer", None) is not None:
+        if self.activation is not F.relu or (getattr(self, "context_layer", None) is not None and not _context_layers):
             return False
         if torch.is_autocast_enabled() or torch.is_autocast_enabled("cpu") or _has_inner_hooks(self):
             return False
@@ -230,14 +230,39 @@ class MADE(nn.Module):
             return False
         for b in self.blocks:
             if (type(b) is not MaskedResidualBlock or b.activation is not F.relu or b.use_batch_norm
-                    or (b.training and b.dropout.p != 0.0) or getattr(b, "context_layer", None) is not None):
+                    or (b.training and b.dropout.p != 0.0)
+                    or (getattr(b, "context_layer", None) is not None and not _context_layers)):
                 return False
         return True
 
+    def _fusable_with_context(self, batch, features, context):
+        """K27 -- `_fusable` for a call WITH a context (whatever device the tensors are on): the switch NFA_K27 is on,
+        the context is a float32 [batch, C] tensor with C >= 1, the net and every block carry a `context_layer` that is
+        an nn.Linear with a bias from those C columns to the hidden width, and everything else is as `_fusable` asks of
+        a net without one."""
+        from .. import ops
+        if not (ops.CTX_TRAINING and torch.is_tensor(context) and context.dtype == torch.float32 and context.dim() == 2
+                and context.shape[0] == batch and context.shape[1] >= 1):
+            return False
+        layers = [getattr(self, "context_layer", None)] + [getattr(b, "context_layer", None) for b in self.blocks]
+        for layer in layers:
+            if (type(layer) is not nn.Linear or layer.bias is None or layer.in_features != context.shape[1]
+                    or layer.out_features != self.initial_layer.out_features or layer.weight.dtype != torch.float32
+                    or layer.weight.device != context.device):
+                return False
+        return self._fusable(batch, features, None, _context_layers=True)
+
     def _fused_training(self, inputs, context=None):
-        """K25 applies: `_fusable`, under autograd, float32 inputs, parameters and masks on one HIP device."""
+        """K25 applies: `_fusable`, under autograd, float32 inputs, parameters and masks on one HIP device; with a context
+        (K27) `_fusable_with_context`, the context on that device too."""
         if not (torch.is_grad_enabled() and torch.is_tensor(inputs) and inputs.is_cuda and inputs.dtype == torch.float32
-                and inputs.dim() == 2 and self._fusable(inputs.shape[0], inputs.shape[1], context)):
+                and inputs.dim() == 2):
+            return False
+        if context is None:
+            if not self._fusable(inputs.shape[0], inputs.shape[1]):
+                return False
+        elif not (torch.is_tensor(context) and context.device == inputs.device
+                  and self._fusable_with_context(inputs.shape[0], inputs.shape[1], context)):
             return False
         layers = [self.initial_layer, self.final_layer] + [l for b in self.blocks for l in b.linear_layers]
         for l in layers:
@@ -245,7 +270,8 @@ class MADE(nn.Module):
                     or l.weight.dtype != torch.float32 or l.weight.device != inputs.device
                     or l.mask.dtype != torch.float32 or l.mask.device != inputs.device):
                 return False   # (half-precision or misplaced parameters: the eager modules report it their own way)
-        return any(p.requires_grad for p in self.parameters()) or inputs.requires_grad
+        return (any(p.requires_grad for p in self.parameters()) or inputs.requires_grad
+                or (context is not None and context.requires_grad))
 
     def forward(self, inputs, context=None):
         if self._fused_training(inputs, context):
@@ -256,7 +282,20 @@ class MADE(nn.Module):
                     masks.append(l.mask)
                     params += [l.weight, l.bias]
             masks.append(self.final_layer.mask)
-            return AG.MadeNet.apply(inputs, tuple(masks), *params, self.final_layer.weight, self.final_layer.bias)
+            params += [self.final_layer.weight, self.final_layer.bias]
+            if context is None:
+                return AG.MadeNet.apply(inputs, tuple(masks), *params)
+            # K27: the context Linears stay stock ops under autograd (their own GEMMs, in the eager path's shapes); their
+            # outputs, zero-padded to K14's 128 columns (the net's own through its ReLU, made.py:197-201), enter the
+            # forward kernel as planes
+            pad = 128 - self.initial_layer.out_features
+
+            def plane(layer):
+                out = F.linear(context, layer.weight, layer.bias)
+                return F.pad(out, (0, pad)) if pad else out
+
+            return AG.MadeNetCtx.apply(inputs, tuple(masks), len(self.blocks), F.relu(plane(self.context_layer)),
+                                       *[plane(b.context_layer) for b in self.blocks], *params)
         return self.final_layer(self.hidden(inputs, context))
 
     def is_deterministic(self):
