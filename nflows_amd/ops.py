@@ -42,9 +42,9 @@ def last_redo_blocks():
 
 
 def set_launch_hook(hook):
-    """Measurement aid for bench.py: `hook.begin(name)` / `hook.end(token, algorithmic_bytes)` are
-    called right before / after the K1 kernel is enqueued (on the current stream), so a caller
-    can bracket it with HIP events.  None (default) disables it; nothing else changes."""
+    """Measurement aid for bench.py: the hook's `begin(name)` / `end(token, algorithmic_bytes)` are
+    called right before / after a hooked launcher's kernel is enqueued (on the current stream, by `_launch`), so a
+    caller can bracket it with HIP events.  None (default) disables it; nothing else changes."""
     global _launch_hook
     _launch_hook = hook
 
@@ -147,6 +147,47 @@ def _after_spline(spec, inverse, device):
         check_status(device)
 
 
+def _f32_params(names, tensors, ranks, device, counts):
+    """The parameters of a per-layer launcher, one entry of `names`, `ranks` and `counts` per tensor (surplus entries are
+    ignored): each float32, of its rank, on the inputs' device, with its count of entries in the last dimension.  A
+    tensor that is None (an optional stage) is skipped."""
+    f32, tensor = torch.float32, torch.Tensor
+    for name, t, rank, n in zip(names, tensors, ranks, counts):
+        if t is None:
+            continue
+        # (this runs on every call of a layer: N.require_device_f32's conditions are tested here and it is called to raise)
+        if not isinstance(t, tensor) or not t.is_cuda or t.dtype != f32 or t.dim() != rank:
+            N.require_device_f32(name, t, rank)
+        if t.device != device:
+            raise ValueError("%s is on %s, inputs on %s" % (name, t.device, device))
+        if t.shape[-1] != n:
+            raise ValueError("%s must have %d entries in its last dimension, got shape %s" % (name, n, tuple(t.shape)))
+
+
+def _accumulated(lad, accumulate_into):
+    """`lad`, or the caller's running total with `lad` added to it (the passes whose kernel wrote a fresh tensor)."""
+    if accumulate_into is None:
+        return lad
+    accumulate_into += lad
+    return accumulate_into
+
+
+def _launch(device, entry, args, hook_name=None, nbytes=0, raw=False):
+    """The tail of a per-layer launcher: `entry(*args)` with `device` current, bracketed by the launch hook's
+    `begin(hook_name)` / `end(token, nbytes)` when a hook is set and the launcher has a name (`nbytes`: its algorithmic
+    bytes), then the status check -- after `hook.end` -- unless `raw`.  Returns the entry point's status code.  (Launchers
+    without a hook name that branch on ERR_UNSUPPORTED keep their own three lines: a call here would be no shorter.)"""
+    hook = _launch_hook if hook_name is not None else None
+    with torch.cuda.device(device):
+        token = hook.begin(hook_name) if hook is not None else None
+        rc = entry(*args)
+        if hook is not None:
+            hook.end(token, nbytes)
+    if not raw:
+        N.check(rc)
+    return rc
+
+
 def rqs_coupling(inputs, params, transform_idx, spec, inverse=False, in_perm=None, out_scatter=None,
                  accumulate_into=None, return_bin_idx=False):
     """K1 -- fused rational-quadratic coupling layer.  inputs [B, D], params [B, d_t*P].
@@ -172,10 +213,7 @@ def rqs_coupling(inputs, params, transform_idx, spec, inverse=False, in_perm=Non
     if AG.needs_grad(inputs, params):
         out, lad = AG.RqsCoupling.apply(inputs.contiguous(), params.contiguous(), tidx, spec, bool(inverse),
                                         perm, scat)
-        if accumulate_into is not None:
-            accumulate_into += lad
-            lad = accumulate_into
-        return out, lad
+        return out, _accumulated(lad, accumulate_into)
     return _rqs_coupling_launch(inputs, params, tidx, spec, inverse, perm, scat, accumulate_into)
 
 
@@ -189,23 +227,16 @@ def _rqs_coupling_launch(inputs, params, tidx, spec, inverse, perm, scat, accumu
     out = torch.empty_like(x)
     lad, flags = _lad_buffer(accumulate_into, B, dev, inverse)
     bins = torch.empty(B, dt, dtype=torch.int32, device=dev) if want_bins else None
-    hook = _launch_hook
-    with torch.cuda.device(dev):
-        token = hook.begin("rqs_coupling") if hook is not None else None
-        rc = N.load().nfa_rqs_coupling_f32(N.ptr(x), N.ptr(p), N.ptr(tidx), N.ptr(perm), N.ptr(scat),
-                                           N.ptr(out), N.ptr(lad), N.ptr(bins), N.ptr(_status_word(dev)), B, D, dt,
-                                           ctypes.byref(spec), flags, N.stream_handle(dev))
-        if hook is not None:
-            # algorithmic bytes: inputs + conditioner output + outputs + logabsdet
-            hook.end(token, 4 * (B * D + B * dt * P + B * D + B))
+    # algorithmic bytes: inputs + conditioner output + outputs + logabsdet
+    rc = _launch(dev, N.load().nfa_rqs_coupling_f32,
+                 (N.ptr(x), N.ptr(p), N.ptr(tidx), N.ptr(perm), N.ptr(scat), N.ptr(out), N.ptr(lad), N.ptr(bins),
+                  N.ptr(_status_word(dev)), B, D, dt, ctypes.byref(spec), flags, N.stream_handle(dev)),
+                 "rqs_coupling", 4 * (B * D + B * dt * P + B * D + B), raw=True)
     if rc == N.ERR_UNSUPPORTED:
         if torch.is_grad_enabled() and (inputs.requires_grad or params.requires_grad):
             raise NotImplementedError("nflows_amd: this layer shape has no backward kernel yet")
         res = _rqs_coupling_unfused(x, p, tidx, perm, scat, spec, inverse, want_bins)
-        out, l = res[0], res[1]
-        if accumulate_into is not None:
-            accumulate_into += l
-            l = accumulate_into
+        out, l = res[0], _accumulated(res[1], accumulate_into)
         return (out, l, res[2]) if want_bins else (out, l)
     N.check(rc)
     _after_spline(spec, inverse, dev)
@@ -277,31 +308,16 @@ def _rqs_elementwise_launch(inputs, unnormalized_widths, unnormalized_heights, u
                          % (tuple(shape), K, K, nd_min))
     n = inputs.numel()
     x = inputs.contiguous().view(-1)
-
-    def rows(t, width):
-        """[n, width] view with unit inner stride and a uniform row stride, copying only if needed."""
-        if width == 0:
-            return t.reshape(n, 0), 1
-        try:
-            v = t.view(n, width) if n else t.reshape(n, width)
-        except RuntimeError:
-            v = t.reshape(n, width)
-        if v.stride(1) != 1 or (n > 1 and v.stride(0) < width):
-            v = v.contiguous()
-        return v, (v.stride(0) if n > 1 else width)
-
-    uw, sw = rows(unnormalized_widths, K)
-    uh, sh = rows(unnormalized_heights, K)
-    ud, sd = rows(unnormalized_derivatives, nd)
+    uw, sw = _logit_rows(unnormalized_widths, n, K)
+    uh, sh = _logit_rows(unnormalized_heights, n, K)
+    ud, sd = _logit_rows(unnormalized_derivatives, n, nd)
     y = torch.empty_like(x)
     lad = torch.empty_like(x)
     bins = torch.empty(n, dtype=torch.int32, device=dev) if want_bins else None
-    launch = N.load().nfa_rqs_elementwise_f64 if x.dtype == torch.float64 else N.load().nfa_rqs_elementwise_f32
-    with torch.cuda.device(dev):
-        rc = launch(N.ptr(x), N.ptr(uw), sw, N.ptr(uh), sh, N.ptr(ud) if nd else N.ptr(uw), sd, nd, N.ptr(y),
-                    N.ptr(lad), N.ptr(bins), N.ptr(_status_word(dev)), n, ctypes.byref(spec),
-                    int(bool(inverse)), N.stream_handle(dev))
-    N.check(rc)
+    entry = N.load().nfa_rqs_elementwise_f64 if x.dtype == torch.float64 else N.load().nfa_rqs_elementwise_f32
+    _launch(dev, entry, (N.ptr(x), N.ptr(uw), sw, N.ptr(uh), sh, N.ptr(ud) if nd else N.ptr(uw), sd, nd, N.ptr(y),
+                         N.ptr(lad), N.ptr(bins), N.ptr(_status_word(dev)), n, ctypes.byref(spec),
+                         int(bool(inverse)), N.stream_handle(dev)))
     _after_spline(spec, inverse, dev)
     if want_bins:
         return y.view(shape), lad.view(shape), bins.view(shape)
@@ -310,6 +326,8 @@ def _rqs_elementwise_launch(inputs, unnormalized_widths, unnormalized_heights, u
 
 def _logit_rows(t, n, width):
     """[n, width] view with unit inner stride and a uniform row stride, copying only if needed."""
+    if width == 0:
+        return t.reshape(n, 0), 1
     try:
         v = t.view(n, width) if n else t.reshape(n, width)
     except RuntimeError:
@@ -339,11 +357,9 @@ def _linear_spline_launch(inputs, unnormalized_pdf, spec, inverse):
     x = inputs.detach().contiguous().view(-1)
     pdf, stride = _logit_rows(unnormalized_pdf.detach(), n, K)
     y, lad = torch.empty_like(x), torch.empty_like(x)
-    with torch.cuda.device(dev):
-        rc = N.load().nfa_linear_spline_f32(N.ptr(x), N.ptr(pdf), stride, N.ptr(y), N.ptr(lad),
-                                            N.ptr(_status_word(dev)), n, ctypes.byref(spec),
-                                            int(bool(inverse)), N.stream_handle(dev))
-    N.check(rc)
+    _launch(dev, N.load().nfa_linear_spline_f32,
+            (N.ptr(x), N.ptr(pdf), stride, N.ptr(y), N.ptr(lad), N.ptr(_status_word(dev)), n, ctypes.byref(spec),
+             int(bool(inverse)), N.stream_handle(dev)))
     _after_spline(spec, inverse, dev)
     return y.view(shape), lad.view(shape)
 
@@ -372,11 +388,9 @@ def _quadratic_spline_launch(inputs, unnormalized_widths, unnormalized_heights, 
     uw, sw = _logit_rows(unnormalized_widths.detach(), n, K)
     uh, sh = _logit_rows(unnormalized_heights.detach(), n, nh)
     y, lad = torch.empty_like(x), torch.empty_like(x)
-    with torch.cuda.device(dev):
-        rc = N.load().nfa_quadratic_spline_f32(N.ptr(x), N.ptr(uw), sw, N.ptr(uh), sh, nh, N.ptr(y), N.ptr(lad),
-                                               N.ptr(_status_word(dev)), n, ctypes.byref(spec),
-                                               int(bool(inverse)), N.stream_handle(dev))
-    N.check(rc)
+    _launch(dev, N.load().nfa_quadratic_spline_f32,
+            (N.ptr(x), N.ptr(uw), sw, N.ptr(uh), sh, nh, N.ptr(y), N.ptr(lad), N.ptr(_status_word(dev)), n,
+             ctypes.byref(spec), int(bool(inverse)), N.stream_handle(dev)))
     _after_spline(spec, inverse, dev)
     return y.view(shape), lad.view(shape)
 
@@ -409,11 +423,9 @@ def _cubic_spline_launch(inputs, unnormalized_widths, unnormalized_heights, unno
     dl, sl = _logit_rows(unnorm_derivatives_left.detach(), n, 1)
     dr, sr = _logit_rows(unnorm_derivatives_right.detach(), n, 1)
     y, lad = torch.empty_like(x), torch.empty_like(x)
-    with torch.cuda.device(dev):
-        rc = N.load().nfa_cubic_spline_f32(N.ptr(x), N.ptr(uw), sw, N.ptr(uh), sh, N.ptr(dl), sl, N.ptr(dr), sr,
-                                           N.ptr(y), N.ptr(lad), N.ptr(_status_word(dev)), n, ctypes.byref(spec),
-                                           int(bool(inverse)), N.stream_handle(dev))
-    N.check(rc)
+    _launch(dev, N.load().nfa_cubic_spline_f32,
+            (N.ptr(x), N.ptr(uw), sw, N.ptr(uh), sh, N.ptr(dl), sl, N.ptr(dr), sr, N.ptr(y), N.ptr(lad),
+             N.ptr(_status_word(dev)), n, ctypes.byref(spec), int(bool(inverse)), N.stream_handle(dev)))
     _after_spline(spec, inverse, dev)
     return y.view(shape), lad.view(shape)
 
@@ -441,10 +453,7 @@ def affine_coupling(inputs, params, transform_idx, activation, inverse=False, sc
     if AG.needs_grad(inputs, params, scale):
         out, lad = AG.AffineCoupling.apply(inputs.contiguous(), params.contiguous(), scale, tidx,
                                            int(activation), bool(inverse), perm, scat)
-        if accumulate_into is not None:
-            accumulate_into += lad
-            lad = accumulate_into
-        return out, lad
+        return out, _accumulated(lad, accumulate_into)
     return _affine_coupling_launch(inputs, params, scale, tidx, activation, inverse, perm, scat,
                                    accumulate_into)
 
@@ -458,12 +467,9 @@ def _affine_coupling_launch(inputs, params, scale, tidx, activation, inverse, pe
     scale = None if scale is None else scale.detach().contiguous()
     out = torch.empty_like(x)
     lad, flags = _lad_buffer(accumulate_into, B, dev, inverse)
-    with torch.cuda.device(dev):
-        rc = N.load().nfa_affine_coupling_f32(N.ptr(x), N.ptr(p), N.ptr(scale), N.ptr(tidx), N.ptr(perm),
-                                              N.ptr(scat), N.ptr(out), N.ptr(lad),
-                                              N.ptr(_status_word(dev)), B, D, dt, int(activation),
-                                              flags, N.stream_handle(dev))
-    N.check(rc)
+    _launch(dev, N.load().nfa_affine_coupling_f32,
+            (N.ptr(x), N.ptr(p), N.ptr(scale), N.ptr(tidx), N.ptr(perm), N.ptr(scat), N.ptr(out), N.ptr(lad),
+             N.ptr(_status_word(dev)), B, D, dt, int(activation), flags, N.stream_handle(dev)))
     return out, lad
 
 
@@ -486,10 +492,8 @@ def _affine_autoregressive_launch(inputs, params, inverse):
     p = params.detach().contiguous()
     out = torch.empty_like(x)
     lad = torch.empty(B, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = N.load().nfa_affine_autoregressive_f32(N.ptr(x), N.ptr(p), N.ptr(out), N.ptr(lad), B, D,
-                                                    int(bool(inverse)), N.stream_handle(dev))
-    N.check(rc)
+    _launch(dev, N.load().nfa_affine_autoregressive_f32,
+            (N.ptr(x), N.ptr(p), N.ptr(out), N.ptr(lad), B, D, int(bool(inverse)), N.stream_handle(dev)))
     return out, lad
 
 
@@ -518,11 +522,9 @@ def affine_autoregressive_backward(inputs, params, outputs, grad_outputs, grad_l
         grad_logabsdet = grad_logabsdet.detach().contiguous()
     g_in = torch.empty_like(seen)
     g_p = torch.empty(params.shape, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = N.load().nfa_affine_autoregressive_backward_f32(
-            None if inverse else N.ptr(seen), N.ptr(p), N.ptr(seen) if inverse else None, N.ptr(grad_outputs),
-            N.ptr(grad_logabsdet), N.ptr(g_in), N.ptr(g_p), B, D, int(bool(inverse)), N.stream_handle(dev))
-    N.check(rc)
+    _launch(dev, N.load().nfa_affine_autoregressive_backward_f32,
+            (None if inverse else N.ptr(seen), N.ptr(p), N.ptr(seen) if inverse else None, N.ptr(grad_outputs),
+             N.ptr(grad_logabsdet), N.ptr(g_in), N.ptr(g_p), B, D, int(bool(inverse)), N.stream_handle(dev)))
     return g_in, g_p
 
 
@@ -537,11 +539,12 @@ def permute_cols(inputs, permutation):
     perm = _idx("permutation", permutation, dev, D)
     x = inputs.contiguous()
     out = torch.empty_like(x)
-    with torch.cuda.device(dev):
-        rc = N.load().nfa_permute_cols_b32(N.ptr(x), N.ptr(perm), N.ptr(out), N.ptr(_status_word(dev)),
-                                           B, D, N.stream_handle(dev))
-    N.check(rc)
+    _launch(dev, N.load().nfa_permute_cols_b32,
+            (N.ptr(x), N.ptr(perm), N.ptr(out), N.ptr(_status_word(dev)), B, D, N.stream_handle(dev)))
     return out
+
+
+_LU_PARAMS = ("lower_entries", "upper_entries", "unconstrained_upper_diag", "bias")
 
 
 def lu_linear(inputs, lower_entries, upper_entries, unconstrained_upper_diag, bias, eps=1e-3, inverse=False,
@@ -555,21 +558,13 @@ def lu_linear(inputs, lower_entries, upper_entries, unconstrained_upper_diag, bi
     B, D = inputs.shape
     tri = D * (D - 1) // 2
     params = (lower_entries, upper_entries, unconstrained_upper_diag, bias)
-    for name, t, n in zip(("lower_entries", "upper_entries", "unconstrained_upper_diag", "bias"), params, (tri, tri, D, D)):
-        N.require_device_f32(name, t, 1)
-        if t.device != dev:
-            raise ValueError("%s is on %s, inputs on %s" % (name, t.device, dev))
-        if t.numel() != n:
-            raise ValueError("%s must have %d entries for %d features, got %d" % (name, n, D, t.numel()))
+    _f32_params(_LU_PARAMS, params, (1, 1, 1, 1), dev, (tri, tri, D, D))
     perm = _idx("in_perm", in_perm, dev, D)
     scat = _idx("out_scatter", out_scatter, dev, D)
     if AG.needs_grad(inputs, *params):
         out, lad = AG.LULinear.apply(inputs.contiguous(), lower_entries, upper_entries, unconstrained_upper_diag, bias,
                                      float(eps), bool(inverse), perm, scat)
-        if accumulate_into is not None:
-            accumulate_into += lad
-            lad = accumulate_into
-        return out, lad
+        return out, _accumulated(lad, accumulate_into)
     return _lu_linear_launch(inputs, params, float(eps), inverse, perm, scat, accumulate_into)
 
 
@@ -580,15 +575,11 @@ def _lu_linear_launch(inputs, params, eps, inverse, perm, scat, accumulate_into)
     lower, upper, udiag, bias = (t.detach().contiguous() for t in params)
     out = torch.empty_like(x)
     lad, flags = _lad_buffer(accumulate_into, B, dev, inverse)
-    hook = _launch_hook
-    with torch.cuda.device(dev):
-        token = hook.begin("lu_linear") if hook is not None else None
-        rc = N.load().nfa_lu_linear_f32(N.ptr(x), N.ptr(lower), N.ptr(upper), N.ptr(udiag), N.ptr(bias), N.ptr(perm),
-                                        N.ptr(scat), N.ptr(out), N.ptr(lad), N.ptr(_status_word(dev)), B, D, eps, flags,
-                                        N.stream_handle(dev))
-        if hook is not None:
-            hook.end(token, 4 * (2 * B * D + B))
-    N.check(rc)   # (a shape the kernel does not serve is an error here: there is no second path for float32 rows)
+    # (a shape the kernel does not serve is an error here: there is no second path for float32 rows)
+    _launch(dev, N.load().nfa_lu_linear_f32,
+            (N.ptr(x), N.ptr(lower), N.ptr(upper), N.ptr(udiag), N.ptr(bias), N.ptr(perm), N.ptr(scat), N.ptr(out),
+             N.ptr(lad), N.ptr(_status_word(dev)), B, D, eps, flags, N.stream_handle(dev)),
+            "lu_linear", 4 * (2 * B * D + B))
     return out, lad
 
 
@@ -599,11 +590,9 @@ def _lu_linear_backward_launch(grad_outputs, params, eps, inverse, perm, scat):
     g = grad_outputs.detach().contiguous()
     lower, upper, udiag = (t.detach().contiguous() for t in params[:3])
     g_in = torch.empty_like(g)
-    with torch.cuda.device(dev):
-        rc = N.load().nfa_lu_linear_backward_f32(N.ptr(g), N.ptr(lower), N.ptr(upper), N.ptr(udiag), N.ptr(perm),
-                                                 N.ptr(scat), N.ptr(g_in), N.ptr(_status_word(dev)), B, D, eps,
-                                                 N.FLAG_INVERSE if inverse else 0, N.stream_handle(dev))
-    N.check(rc)
+    _launch(dev, N.load().nfa_lu_linear_backward_f32,
+            (N.ptr(g), N.ptr(lower), N.ptr(upper), N.ptr(udiag), N.ptr(perm), N.ptr(scat), N.ptr(g_in),
+             N.ptr(_status_word(dev)), B, D, eps, N.FLAG_INVERSE if inverse else 0, N.stream_handle(dev)))
     return g_in
 
 
@@ -623,26 +612,14 @@ def householder(inputs, q_first=None, q_second=None, unconstrained_diagonal=None
     dev = inputs.device
     B, D = inputs.shape
     params = (q_first, q_second, unconstrained_diagonal, upper_entries, log_upper_diag, bias)
-    for name, t in zip(HOUSEHOLDER_PARAMS, params):
-        if t is None:
-            continue
-        N.require_device_f32(name, t, 2 if name.startswith("q_") else 1)
-        if t.device != dev:
-            raise ValueError("%s is on %s, inputs on %s" % (name, t.device, dev))
-        want = D * (D - 1) // 2 if name == "upper_entries" else D
-        if t.shape[-1] != want:
-            raise ValueError("%s must have %d entries per row for %d features, got shape %s"
-                             % (name, want, D, tuple(t.shape)))
+    _f32_params(HOUSEHOLDER_PARAMS, params, (2, 2, 1, 1, 1, 1), dev, (D, D, D, D * (D - 1) // 2, D, D))
     if (upper_entries is None) != (log_upper_diag is None):
         raise ValueError("upper_entries and log_upper_diag are given together")
     if upper_entries is not None and unconstrained_diagonal is not None:
         raise ValueError("a program has a triangular or a diagonal stage, not both")
     if AG.needs_grad(inputs, *params):
         out, lad = AG.Householder.apply(inputs.contiguous(), *params, float(eps), bool(inverse))
-        if accumulate_into is not None:
-            accumulate_into += lad
-            lad = accumulate_into
-        return out, lad
+        return out, _accumulated(lad, accumulate_into)
     return _householder_launch(inputs, params, float(eps), inverse, accumulate_into)
 
 
@@ -662,13 +639,10 @@ def _householder_launch(inputs, params, eps, inverse, accumulate_into, want_loga
     held, args = _householder_pointers(params)
     out = torch.empty_like(x)
     lad, flags = _lad_buffer(accumulate_into, B, dev, inverse) if want_logabsdet else (None, N.FLAG_INVERSE if inverse else 0)
-    hook = _launch_hook
-    with torch.cuda.device(dev):
-        token = hook.begin("householder") if hook is not None else None
-        rc = N.load().nfa_householder_f32(N.ptr(x), *args, N.ptr(out), N.ptr(lad), B, D, eps, flags, N.stream_handle(dev))
-        if hook is not None:
-            hook.end(token, 4 * (2 * B * D + B))
-    N.check(rc)   # (a shape the kernel does not serve is an error here: the classes route those to their generic path)
+    # (a shape the kernel does not serve is an error here: the classes route those to their generic path)
+    _launch(dev, N.load().nfa_householder_f32,
+            (N.ptr(x), *args, N.ptr(out), N.ptr(lad), B, D, eps, flags, N.stream_handle(dev)),
+            "householder", 4 * (2 * B * D + B))
     return out, lad
 
 
@@ -707,20 +681,12 @@ def lu_conv1x1(inputs, lower_entries, upper_entries, unconstrained_upper_diag, b
     C = inputs.shape[1]
     tri = C * (C - 1) // 2
     params = (lower_entries, upper_entries, unconstrained_upper_diag, bias)
-    for name, t, n in zip(("lower_entries", "upper_entries", "unconstrained_upper_diag", "bias"), params, (tri, tri, C, C)):
-        N.require_device_f32(name, t, 1)
-        if t.device != dev:
-            raise ValueError("%s is on %s, inputs on %s" % (name, t.device, dev))
-        if t.numel() != n:
-            raise ValueError("%s must have %d entries for %d channels, got %d" % (name, n, C, t.numel()))
+    _f32_params(_LU_PARAMS, params, (1, 1, 1, 1), dev, (tri, tri, C, C))
     perm = _idx("channel_perm", channel_perm, dev, C)
     if AG.needs_grad(inputs, *params):
         out, lad = AG.LUConv1x1.apply(inputs.contiguous(), lower_entries, upper_entries, unconstrained_upper_diag, bias,
                                       float(eps), bool(inverse), perm)
-        if accumulate_into is not None:
-            accumulate_into += lad
-            lad = accumulate_into
-        return out, lad
+        return out, _accumulated(lad, accumulate_into)
     return _lu_conv1x1_launch(inputs, params, float(eps), inverse, perm, accumulate_into)
 
 
@@ -731,15 +697,11 @@ def _lu_conv1x1_launch(inputs, params, eps, inverse, perm, accumulate_into):
     lower, upper, udiag, bias = (t.detach().contiguous() for t in params)
     out = torch.empty_like(x)
     lad, flags = _lad_buffer(accumulate_into, B, dev, inverse)
-    hook = _launch_hook
-    with torch.cuda.device(dev):
-        token = hook.begin("lu_conv1x1") if hook is not None else None
-        rc = N.load().nfa_lu_conv1x1_f32(N.ptr(x), N.ptr(lower), N.ptr(upper), N.ptr(udiag), N.ptr(bias), N.ptr(perm),
-                                         N.ptr(out), N.ptr(lad), N.ptr(_status_word(dev)), B, C, H, W, eps, flags,
-                                         N.stream_handle(dev))
-        if hook is not None:
-            hook.end(token, 4 * (2 * B * C * H * W + B))
-    N.check(rc)   # (a shape the kernel does not serve is an error here, as in lu_linear)
+    # (a shape the kernel does not serve is an error here, as in lu_linear)
+    _launch(dev, N.load().nfa_lu_conv1x1_f32,
+            (N.ptr(x), N.ptr(lower), N.ptr(upper), N.ptr(udiag), N.ptr(bias), N.ptr(perm), N.ptr(out), N.ptr(lad),
+             N.ptr(_status_word(dev)), B, C, H, W, eps, flags, N.stream_handle(dev)),
+            "lu_conv1x1", 4 * (2 * B * C * H * W + B))
     return out, lad
 
 
@@ -750,11 +712,9 @@ def _lu_conv1x1_backward_launch(grad_outputs, params, eps, inverse, perm):
     g = grad_outputs.detach().contiguous()
     lower, upper, udiag = (t.detach().contiguous() for t in params[:3])
     g_in = torch.empty_like(g)
-    with torch.cuda.device(dev):
-        rc = N.load().nfa_lu_conv1x1_backward_f32(N.ptr(g), N.ptr(lower), N.ptr(upper), N.ptr(udiag), N.ptr(perm),
-                                                  N.ptr(g_in), N.ptr(_status_word(dev)), B, C, H, W, eps,
-                                                  N.FLAG_INVERSE if inverse else 0, N.stream_handle(dev))
-    N.check(rc)
+    _launch(dev, N.load().nfa_lu_conv1x1_backward_f32,
+            (N.ptr(g), N.ptr(lower), N.ptr(upper), N.ptr(udiag), N.ptr(perm), N.ptr(g_in), N.ptr(_status_word(dev)),
+             B, C, H, W, eps, N.FLAG_INVERSE if inverse else 0, N.stream_handle(dev)))
     return g_in
 
 
@@ -779,14 +739,9 @@ def column_stats(inputs, return_f64=False):
     var = torch.empty(D, dtype=torch.float32, device=dev)
     wide = torch.empty(2, D, dtype=torch.float64, device=dev) if return_f64 else None
     ws = _norm_workspace(B, D, dev)
-    hook = _launch_hook
-    with torch.cuda.device(dev):
-        token = hook.begin("norm_stats") if hook is not None else None
-        rc = N.load().nfa_norm_column_stats_f32(N.ptr(x), N.ptr(mean), N.ptr(var), N.ptr(wide), N.ptr(ws), B, D,
-                                                N.stream_handle(dev))
-        if hook is not None:
-            hook.end(token, 4 * B * D)
-    N.check(rc)
+    _launch(dev, N.load().nfa_norm_column_stats_f32,
+            (N.ptr(x), N.ptr(mean), N.ptr(var), N.ptr(wide), N.ptr(ws), B, D, N.stream_handle(dev)),
+            "norm_stats", 4 * B * D)
     return (mean, var, wide) if return_f64 else (mean, var)
 
 
@@ -803,10 +758,9 @@ def column_sums(g, u, g_columns=None, u_columns=None):
     g, u = g.detach().contiguous(), u.detach().contiguous()
     sums = torch.empty(2, D, dtype=torch.float64, device=dev)
     ws = _norm_workspace(B, D, dev)
-    with torch.cuda.device(dev):
-        rc = N.load().nfa_norm_column_sums_f32(N.ptr(g), N.ptr(u), N.ptr(gc), N.ptr(uc), N.ptr(sums), N.ptr(ws),
-                                               N.ptr(_status_word(dev)), B, D, N.stream_handle(dev))
-    N.check(rc)
+    _launch(dev, N.load().nfa_norm_column_sums_f32,
+            (N.ptr(g), N.ptr(u), N.ptr(gc), N.ptr(uc), N.ptr(sums), N.ptr(ws), N.ptr(_status_word(dev)), B, D,
+             N.stream_handle(dev)))
     return sums
 
 
@@ -816,12 +770,7 @@ def _norm_params(inputs, kind, params):
     names = ("unconstrained_weight", "bias", "mean", "var") if kind == NORM_BATCH_NORM else ("log_scale", "shift")
     if len(params) != len(names):
         raise ValueError("expected the tensors %s" % (names,))
-    for name, t in zip(names, params):
-        N.require_device_f32(name, t, 1)
-        if t.device != inputs.device:
-            raise ValueError("%s is on %s, inputs on %s" % (name, t.device, inputs.device))
-        if t.numel() != D:
-            raise ValueError("%s must have %d entries, got %d" % (name, D, t.numel()))
+    _f32_params(names, params, (1, 1, 1, 1), inputs.device, (D, D, D, D))   # (ActNorm's two names use the first two)
 
 
 def batch_norm(inputs, unconstrained_weight, bias, mean, var, eps=1e-5, inverse=False, batch_statistics=False,
@@ -855,10 +804,7 @@ def _norm(inputs, kind, params, eps, inverse, batch_statistics, in_perm, out_sca
     scat = _idx("out_scatter", out_scatter, dev, D)
     if AG.needs_grad(inputs, *params[:2]):
         out, lad = AG.NormMap.apply(inputs.contiguous(), kind, eps, inverse, batch_statistics, perm, scat, *params)
-        if accumulate_into is not None:
-            accumulate_into += lad
-            lad = accumulate_into
-        return out, lad
+        return out, _accumulated(lad, accumulate_into)
     return _norm_map_launch(inputs, kind, params, eps, inverse, perm, scat, accumulate_into)
 
 
@@ -869,15 +815,10 @@ def _norm_map_launch(inputs, kind, params, eps, inverse, perm, scat, accumulate_
     p = [t.detach().contiguous() for t in params] + [None] * (4 - len(params))
     out = torch.empty_like(x)
     lad, flags = _lad_buffer(accumulate_into, B, dev, inverse)
-    hook = _launch_hook
-    with torch.cuda.device(dev):
-        token = hook.begin("norm_map") if hook is not None else None
-        rc = N.load().nfa_norm_map_f32(N.ptr(x), N.ptr(p[0]), N.ptr(p[1]), N.ptr(p[2]), N.ptr(p[3]), N.ptr(perm),
-                                       N.ptr(scat), N.ptr(out), N.ptr(lad), N.ptr(_status_word(dev)), B, D, eps, kind,
-                                       flags, N.stream_handle(dev))
-        if hook is not None:
-            hook.end(token, 4 * (2 * B * D + B))
-    N.check(rc)
+    _launch(dev, N.load().nfa_norm_map_f32,
+            (N.ptr(x), N.ptr(p[0]), N.ptr(p[1]), N.ptr(p[2]), N.ptr(p[3]), N.ptr(perm), N.ptr(scat), N.ptr(out),
+             N.ptr(lad), N.ptr(_status_word(dev)), B, D, eps, kind, flags, N.stream_handle(dev)),
+            "norm_map", 4 * (2 * B * D + B))
     return out, lad
 
 
@@ -888,11 +829,9 @@ def _norm_map_backward_launch(grad_outputs, kind, params, eps, inverse, perm, sc
     g = grad_outputs.detach().contiguous()
     p = [t.detach().contiguous() for t in params] + [None] * (4 - len(params))
     g_in = torch.empty_like(g)
-    with torch.cuda.device(dev):
-        rc = N.load().nfa_norm_map_backward_f32(N.ptr(g), N.ptr(p[0]), N.ptr(p[1]), N.ptr(p[2]), N.ptr(p[3]), N.ptr(perm),
-                                                N.ptr(scat), N.ptr(g_in), N.ptr(_status_word(dev)), B, D, eps, kind,
-                                                N.FLAG_INVERSE if inverse else 0, N.stream_handle(dev))
-    N.check(rc)
+    _launch(dev, N.load().nfa_norm_map_backward_f32,
+            (N.ptr(g), N.ptr(p[0]), N.ptr(p[1]), N.ptr(p[2]), N.ptr(p[3]), N.ptr(perm), N.ptr(scat), N.ptr(g_in),
+             N.ptr(_status_word(dev)), B, D, eps, kind, N.FLAG_INVERSE if inverse else 0, N.stream_handle(dev)))
     return g_in
 
 
@@ -902,10 +841,9 @@ def _norm_batch_backward_launch(grad_outputs, inputs, coefficients, perm, scat):
     B, D = grad_outputs.shape
     g, x, c = grad_outputs.detach().contiguous(), inputs.detach().contiguous(), coefficients.contiguous()
     g_in = torch.empty_like(g)
-    with torch.cuda.device(dev):
-        rc = N.load().nfa_norm_batch_backward_f32(N.ptr(g), N.ptr(x), N.ptr(c), N.ptr(perm), N.ptr(scat), N.ptr(g_in),
-                                                  N.ptr(_status_word(dev)), B, D, N.stream_handle(dev))
-    N.check(rc)
+    _launch(dev, N.load().nfa_norm_batch_backward_f32,
+            (N.ptr(g), N.ptr(x), N.ptr(c), N.ptr(perm), N.ptr(scat), N.ptr(g_in), N.ptr(_status_word(dev)), B, D,
+             N.stream_handle(dev)))
     return g_in
 
 
@@ -937,9 +875,7 @@ def nonlinearity(inputs, kind, constants=(), temperature=None, inverse=False, ac
         temperature = None
     if AG.needs_grad(inputs, temperature):
         out, lad = AG.Nonlinearity.apply(inputs.contiguous(), temperature, code, p, bool(inverse))
-        if accumulate_into is not None:
-            accumulate_into += lad
-            lad = accumulate_into
+        lad = _accumulated(lad, accumulate_into)
     else:
         out, lad = _nonlinearity_launch(inputs, temperature, code, p, inverse, accumulate_into)
     if (inverse and code in _NONLIN_BOUNDED_INVERSE) or _error_mode == "immediate":
@@ -958,14 +894,10 @@ def _nonlinearity_launch(inputs, temperature, code, p, inverse, accumulate_into)
     lib = N.load()
     nbytes = lib.nfa_nonlin_workspace_bytes(B, n)
     ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev) if nbytes else None
-    hook = _launch_hook
-    with torch.cuda.device(dev):
-        token = hook.begin("nonlin") if hook is not None else None
-        rc = lib.nfa_nonlin_f32(N.ptr(x), N.ptr(t), N.ptr(out), N.ptr(lad), N.ptr(ws), N.ptr(_status_word(dev)), B, n, code,
-                                p[0], p[1], p[2], flags, N.stream_handle(dev))
-        if hook is not None:
-            hook.end(token, 4 * (2 * B * n + B))
-    N.check(rc)
+    _launch(dev, lib.nfa_nonlin_f32,
+            (N.ptr(x), N.ptr(t), N.ptr(out), N.ptr(lad), N.ptr(ws), N.ptr(_status_word(dev)), B, n, code, p[0], p[1], p[2],
+             flags, N.stream_handle(dev)),
+            "nonlin", 4 * (2 * B * n + B))
     return out, lad
 
 
@@ -983,10 +915,9 @@ def _nonlinearity_backward_launch(inputs, temperature, grad_outputs, grad_logabs
     if want_temperature:
         g_t = torch.zeros(1, dtype=torch.float32, device=dev)
         ws = torch.empty(max(lib.nfa_nonlin_backward_workspace_bytes(B, n) // 8, 1), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.nfa_nonlin_backward_f32(N.ptr(x), N.ptr(t), N.ptr(g), N.ptr(gl), N.ptr(g_in), N.ptr(g_t), N.ptr(ws), B, n,
-                                         code, p[0], p[1], p[2], N.FLAG_INVERSE if inverse else 0, N.stream_handle(dev))
-    N.check(rc)
+    _launch(dev, lib.nfa_nonlin_backward_f32,
+            (N.ptr(x), N.ptr(t), N.ptr(g), N.ptr(gl), N.ptr(g_in), N.ptr(g_t), N.ptr(ws), B, n, code, p[0], p[1], p[2],
+             N.FLAG_INVERSE if inverse else 0, N.stream_handle(dev)))
     return g_in, g_t
 
 
@@ -1060,14 +991,9 @@ def _diag_normal_launch(inputs, means, log_stds, log_z, logabsdet):
     lib = N.load()
     nbytes = lib.nfa_diag_normal_workspace_bytes(B, n)
     ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev) if nbytes else None
-    hook = _launch_hook
-    with torch.cuda.device(dev):
-        token = hook.begin("diag_normal") if hook is not None else None
-        rc = lib.nfa_diag_normal_log_prob_f32(N.ptr(x), N.ptr(m), N.ptr(ls), N.ptr(add), N.ptr(out), N.ptr(ws), B, n, stride,
-                                              log_z, N.stream_handle(dev))
-        if hook is not None:
-            hook.end(token, 4 * (B * n + 2 * n * (B if stride else 1) + B * (2 if add is not None else 1)))
-    N.check(rc)
+    _launch(dev, lib.nfa_diag_normal_log_prob_f32,
+            (N.ptr(x), N.ptr(m), N.ptr(ls), N.ptr(add), N.ptr(out), N.ptr(ws), B, n, stride, log_z, N.stream_handle(dev)),
+            "diag_normal", 4 * (B * n + 2 * n * (B if stride else 1) + B * (2 if add is not None else 1)))
     return out
 
 
@@ -1090,14 +1016,10 @@ def _diag_normal_backward_launch(inputs, means, log_stds, grad_log_prob, want_pa
             g_m = torch.empty(means.shape, dtype=torch.float32, device=dev)
             g_ls = torch.empty(log_stds.shape, dtype=torch.float32, device=dev)
             gstride = n
-    hook = _launch_hook
-    with torch.cuda.device(dev):
-        token = hook.begin("diag_normal_backward") if hook is not None else None
-        rc = N.load().nfa_diag_normal_backward_f32(N.ptr(x), N.ptr(m), N.ptr(ls), N.ptr(g), N.ptr(g_x), N.ptr(g_m), N.ptr(g_ls),
-                                                   B, n, stride, gstride, N.stream_handle(dev))
-        if hook is not None:
-            hook.end(token, 4 * (2 * B * n + (4 * B * n if stride else 2 * n) + B))
-    N.check(rc)
+    _launch(dev, N.load().nfa_diag_normal_backward_f32,
+            (N.ptr(x), N.ptr(m), N.ptr(ls), N.ptr(g), N.ptr(g_x), N.ptr(g_m), N.ptr(g_ls), B, n, stride, gstride,
+             N.stream_handle(dev)),
+            "diag_normal_backward", 4 * (2 * B * n + (4 * B * n if stride else 2 * n) + B))
     if want_params and not stride:
         # the shared row: sum_b grad_means = -sum_b grad_x, sum_b grad_log_stds = -sum_b grad_x (x - m) - sum_b g, from K17's
         # deterministic float64 column reduction (at most NORM_MAX_FEATURES columns a call), rounded once
@@ -1151,14 +1073,9 @@ def _mog_launch(inputs, outputs, K, epsilon, logabsdet):
     lib = N.load()
     nbytes = lib.nfa_mog_workspace_bytes(B, D)
     ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev) if nbytes else None
-    hook = _launch_hook
-    with torch.cuda.device(dev):
-        token = hook.begin("mog") if hook is not None else None
-        rc = lib.nfa_mog_log_prob_f32(N.ptr(x), N.ptr(o), N.ptr(add), N.ptr(out), N.ptr(ws), B, D, K, epsilon,
-                                      N.stream_handle(dev))
-        if hook is not None:
-            hook.end(token, 4 * (B * D * (1 + 3 * K) + B * (2 if add is not None else 1)))
-    N.check(rc)
+    _launch(dev, lib.nfa_mog_log_prob_f32,
+            (N.ptr(x), N.ptr(o), N.ptr(add), N.ptr(out), N.ptr(ws), B, D, K, epsilon, N.stream_handle(dev)),
+            "mog", 4 * (B * D * (1 + 3 * K) + B * (2 if add is not None else 1)))
     return out
 
 
@@ -1168,14 +1085,9 @@ def _mog_backward_launch(inputs, outputs, grad_log_prob, K, epsilon):
     B, D = inputs.shape
     x, o, g = inputs.detach().contiguous(), outputs.detach().contiguous(), grad_log_prob.detach().contiguous()
     g_x, g_o = torch.empty_like(x), torch.empty_like(o)
-    hook = _launch_hook
-    with torch.cuda.device(dev):
-        token = hook.begin("mog_backward") if hook is not None else None
-        rc = N.load().nfa_mog_backward_f32(N.ptr(x), N.ptr(o), N.ptr(g), N.ptr(g_x), N.ptr(g_o), B, D, K, epsilon,
-                                           N.stream_handle(dev))
-        if hook is not None:
-            hook.end(token, 4 * (2 * B * D * (1 + 3 * K) + B))
-    N.check(rc)
+    _launch(dev, N.load().nfa_mog_backward_f32,
+            (N.ptr(x), N.ptr(o), N.ptr(g), N.ptr(g_x), N.ptr(g_o), B, D, K, epsilon, N.stream_handle(dev)),
+            "mog_backward", 4 * (2 * B * D * (1 + 3 * K) + B))
     return g_x, g_o
 
 
@@ -1187,9 +1099,7 @@ def rowsum(x):
     cols = x.numel() // B if B else 0
     v = x.contiguous().view(B, cols)
     out = torch.empty(B, dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = N.load().nfa_rowsum_f32(N.ptr(v), N.ptr(out), B, cols, N.stream_handle(x.device))
-    N.check(rc)
+    _launch(x.device, N.load().nfa_rowsum_f32, (N.ptr(v), N.ptr(out), B, cols, N.stream_handle(x.device)))
     return out
 
 
@@ -1218,10 +1128,8 @@ def searchsorted(bin_locations, inputs, eps=1e-6):
         knots = bin_locations.detach().expand(tuple(shape) + (nk,)).contiguous().view(n, nk)
         stride = nk
     out = torch.empty(n, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        rc = N.load().nfa_searchsorted_f32(N.ptr(knots), stride, nk, N.ptr(x), N.ptr(out), n, float(eps),
-                                           N.stream_handle(dev))
-    N.check(rc)
+    _launch(dev, N.load().nfa_searchsorted_f32,
+            (N.ptr(knots), stride, nk, N.ptr(x), N.ptr(out), n, float(eps), N.stream_handle(dev)))
     return out.view(shape)
 
 
@@ -1248,10 +1156,8 @@ def _standard_normal_log_prob_launch(z, logabsdet):
     if logabsdet is not None:
         logabsdet = logabsdet.detach().contiguous()
     out = torch.empty(B, dtype=torch.float32, device=z.device)
-    with torch.cuda.device(z.device):
-        rc = N.load().nfa_standard_normal_log_prob_f32(N.ptr(v), N.ptr(logabsdet), N.ptr(out), B, cols,
-                                                       N.stream_handle(z.device))
-    N.check(rc)
+    _launch(z.device, N.load().nfa_standard_normal_log_prob_f32,
+            (N.ptr(v), N.ptr(logabsdet), N.ptr(out), B, cols, N.stream_handle(z.device)))
     return out
 
 
@@ -1720,7 +1626,6 @@ def linear_wgrad_batched(problems, need_bias=True):
     """K10 for several Linear layers of ONE shape in one launch pair (`nfa_linear_wgrad_batched_f32`: the four
     128 x 128 layers of a ResidualNet conditioner).  `problems`: [(inputs [B, I], grad_outputs [B, O]), ...], at most 8.
     Returns [(grad_weight, grad_bias or None), ...], or None when the shape has no kernel."""
-    import ctypes
     if not 1 <= len(problems) <= 8:
         raise ValueError("1 .. 8 problems per launch")
     B, I = problems[0][0].shape
@@ -2099,11 +2004,9 @@ def pack_resnet_hidden_train(w_in, b_in, block_params, final=None):
     # (with the final Linear: W_f^T's ceil(out / 16) k-major stages behind W_in^T's -- K14's backward kernel starts with them)
     bwd = torch.empty(16 * nb + 2 * tiles + (out + 15) // 16, 6144, dtype=torch.bfloat16, device=dev)
     ptrs = (ctypes.c_void_p * max(1, 4 * nb))(*[t.data_ptr() for t in flat[2:]])
-    with torch.cuda.device(dev):
-        rc = N.load().nfa_pack_resnet_hidden_train_f32(
-            N.ptr(flat[0]), N.ptr(flat[1]), ptrs, N.ptr(fin[0]) if fin else None, N.ptr(fin[1]) if fin else None, out,
-            di, w_in.shape[0], nb, N.ptr(fwd), N.ptr(bias), N.ptr(fbias), N.ptr(bwd), N.stream_handle(dev))
-    N.check(rc)
+    _launch(dev, N.load().nfa_pack_resnet_hidden_train_f32,
+            (N.ptr(flat[0]), N.ptr(flat[1]), ptrs, N.ptr(fin[0]) if fin else None, N.ptr(fin[1]) if fin else None, out,
+             di, w_in.shape[0], nb, N.ptr(fwd), N.ptr(bias), N.ptr(fbias), N.ptr(bwd), N.stream_handle(dev)))
     return fwd, bias, bwd, fbias
 
 
@@ -2142,11 +2045,9 @@ def pack_made_train(w_in, b_in, block_params, final, masks):
     bwd = torch.empty(16 * nb + 2 * tiles + (out + 15) // 16, 6144, dtype=torch.bfloat16, device=dev)
     ptrs = (ctypes.c_void_p * max(1, 4 * nb))(*[t.data_ptr() for t in flat[2:]])
     mptrs = (ctypes.c_void_p * (2 + 2 * nb))(*[None if m is None else m.data_ptr() for m in masks])
-    with torch.cuda.device(dev):
-        rc = N.load().nfa_pack_made_train_f32(
-            N.ptr(flat[0]), N.ptr(flat[1]), ptrs, N.ptr(fin[0]) if fin else None, N.ptr(fin[1]) if fin else None, mptrs,
-            D, rows, out, di, H, nb, N.ptr(fwd), N.ptr(bias), N.ptr(fbias), N.ptr(bwd), N.stream_handle(dev))
-    N.check(rc)
+    _launch(dev, N.load().nfa_pack_made_train_f32,
+            (N.ptr(flat[0]), N.ptr(flat[1]), ptrs, N.ptr(fin[0]) if fin else None, N.ptr(fin[1]) if fin else None, mptrs,
+             D, rows, out, di, H, nb, N.ptr(fwd), N.ptr(bias), N.ptr(fbias), N.ptr(bwd), N.stream_handle(dev)))
     return fwd, bias, bwd, fbias
 
 
@@ -2238,13 +2139,10 @@ def resnet_hidden_forward(x, fwd_stages, fwd_bias, num_blocks, final_bias=None, 
     saved_all = torch.empty(planes + _train_mask_words(num_blocks, B), dtype=torch.float32, device=dev)
     saved = saved_all[:planes].view(2 * num_blocks, B, 128)
     params = torch.empty(B, out_features, dtype=torch.float32, device=dev) if final_bias is not None else None
-    with torch.cuda.device(dev):
-        rc = N.load().nfa_resnet_hidden_forward_f32(N.ptr(x), N.ptr(fwd_stages), N.ptr(fwd_bias),
-                                                    N.ptr(saved_all) if num_blocks else None, N.ptr(hidden),
-                                                    N.ptr(final_bias), N.ptr(params),
-                                                    out_features if final_bias is not None else 0, B, di, 128,
-                                                    num_blocks, N.stream_handle(dev))
-    N.check(rc)
+    _launch(dev, N.load().nfa_resnet_hidden_forward_f32,
+            (N.ptr(x), N.ptr(fwd_stages), N.ptr(fwd_bias), N.ptr(saved_all) if num_blocks else None, N.ptr(hidden),
+             N.ptr(final_bias), N.ptr(params), out_features if final_bias is not None else 0, B, di, 128, num_blocks,
+             N.stream_handle(dev)))
     return hidden, saved, params
 
 
@@ -2259,11 +2157,9 @@ def resnet_hidden_backward(grad_hidden, bwd_stages, saved, num_identity):
         _saved_with_masks(saved, nb, B)
     grads = torch.empty(2 * nb, B, 128, dtype=torch.float32, device=dev)
     gx = torch.empty(B, num_identity, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = N.load().nfa_resnet_hidden_backward_f32(N.ptr(g), N.ptr(bwd_stages), N.ptr(saved) if nb else None,
-                                                     N.ptr(grads) if nb else None, N.ptr(gx), B, num_identity, 128, nb,
-                                                     N.stream_handle(dev))
-    N.check(rc)
+    _launch(dev, N.load().nfa_resnet_hidden_backward_f32,
+            (N.ptr(g), N.ptr(bwd_stages), N.ptr(saved) if nb else None, N.ptr(grads) if nb else None, N.ptr(gx), B,
+             num_identity, 128, nb, N.stream_handle(dev)))
     return gx, grads
 
 
@@ -2334,13 +2230,11 @@ def resnet_hidden_forward_ctx(mode, x, planes, fwd_stages, fwd_bias, num_blocks,
     pre = torch.empty(num_blocks, B, 128, dtype=torch.float32, device=dev) if mode == TRAIN_CTX_GLU else None
     params = torch.empty(B, out_features, dtype=torch.float32, device=dev) if final_bias is not None else None
     ptrs = (ctypes.c_void_p * max(1, num_blocks))(*[p.data_ptr() for p in planes])
-    with torch.cuda.device(dev):
-        rc = N.load().nfa_resnet_hidden_forward_ctx_f32(
-            mode, N.ptr(x), ptrs, N.ptr(initial), N.ptr(fwd_stages), N.ptr(fwd_bias),
-            N.ptr(saved_all) if num_blocks else None, N.ptr(pre) if pre is not None and num_blocks else None, N.ptr(hidden),
-            N.ptr(final_bias), N.ptr(params), out_features if final_bias is not None else 0, B, di, 128, num_blocks,
-            N.stream_handle(dev))
-    N.check(rc)
+    _launch(dev, N.load().nfa_resnet_hidden_forward_ctx_f32,
+            (mode, N.ptr(x), ptrs, N.ptr(initial), N.ptr(fwd_stages), N.ptr(fwd_bias),
+             N.ptr(saved_all) if num_blocks else None, N.ptr(pre) if pre is not None and num_blocks else None, N.ptr(hidden),
+             N.ptr(final_bias), N.ptr(params), out_features if final_bias is not None else 0, B, di, 128, num_blocks,
+             N.stream_handle(dev)))
     return hidden, saved, params, pre
 
 
@@ -2373,13 +2267,11 @@ def resnet_backward_ctx(mode, grad, bwd_stages, saved, num_identity, planes=(), 
         gated = torch.empty(nb, B, 128, dtype=torch.float32, device=dev)
         pptrs = (ctypes.c_void_p * nb)(*[p.data_ptr() for p in planes])
         gptrs = (ctypes.c_void_p * nb)(*[plane_grads[k].data_ptr() for k in range(nb)])
-    with torch.cuda.device(dev):
-        rc = N.load().nfa_resnet_backward_ctx_f32(
-            mode, None if from_params else N.ptr(g), N.ptr(g) if from_params else None, out, pptrs,
-            N.ptr(pre) if gated is not None else None, N.ptr(bwd_stages), N.ptr(saved) if nb else None,
-            N.ptr(grads) if nb else None, gptrs, N.ptr(gated), N.ptr(g_hidden) if from_params else None, N.ptr(gx), B,
-            num_identity, 128, nb, N.stream_handle(dev))
-    N.check(rc)
+    _launch(dev, N.load().nfa_resnet_backward_ctx_f32,
+            (mode, None if from_params else N.ptr(g), N.ptr(g) if from_params else None, out, pptrs,
+             N.ptr(pre) if gated is not None else None, N.ptr(bwd_stages), N.ptr(saved) if nb else None,
+             N.ptr(grads) if nb else None, gptrs, N.ptr(gated), N.ptr(g_hidden) if from_params else None, N.ptr(gx), B,
+             num_identity, 128, nb, N.stream_handle(dev)))
     return gx, grads, g_hidden, plane_grads, gated
 
 
@@ -2842,10 +2734,7 @@ def _whole_layer_launch(launch, inputs, inverse, accumulate_into, standard_norma
     if spec is not None:
         _after_spline(spec, inverse, dev)
     if pad_rows:
-        out, lad = None if out is None else out[:B], lad[:B]
-        if accumulate_into is not None:
-            accumulate_into += lad
-            lad = accumulate_into
+        out, lad = None if out is None else out[:B], _accumulated(lad[:B], accumulate_into)
     if pad_columns and out is not None:
         out = out[:, :D]
     return out, lad
@@ -3318,11 +3207,9 @@ def pack_resnet_f64(net, num_transform, params_per_feature):
         raise ValueError("final_layer.weight must be [%d, %d], got %s" % (num_transform * params_per_feature, H, tuple(w_f.shape)))
     packed = torch.empty(lay["total"], dtype=torch.float64, device=dev)
     ptrs = (ctypes.c_void_p * max(1, 4 * nb))(*[t.data_ptr() for t in flat[2:-2]])
-    with torch.cuda.device(dev):
-        rc = N.load().nfa_pack_resnet_f64(N.ptr(flat[0]), N.ptr(flat[1]), ptrs, N.ptr(flat[-2]), N.ptr(flat[-1]), di, H, nb,
-                                          num_transform, params_per_feature, N.ptr(packed), lay["total"],
-                                          N.stream_handle(dev))
-    N.check(rc)
+    _launch(dev, N.load().nfa_pack_resnet_f64,
+            (N.ptr(flat[0]), N.ptr(flat[1]), ptrs, N.ptr(flat[-2]), N.ptr(flat[-1]), di, H, nb, num_transform,
+             params_per_feature, N.ptr(packed), lay["total"], N.stream_handle(dev)))
     return packed
 
 
@@ -3350,16 +3237,11 @@ def rqs_resnet_layer_f64(inputs, packed, identity_idx, transform_idx, hidden_fea
         flags |= N.FLAG_ACCUMULATE_LOGABSDET
     if idf.numel() + tf.numel() < D:   # (columns of neither half: the kernel leaves them unwritten)
         out.copy_(x)
-    hook = _launch_hook
-    with torch.cuda.device(dev):
-        token = hook.begin("k26") if hook is not None else None
-        rc = N.load().nfa_rqs_resnet_layer_f64(N.ptr(x), N.ptr(packed), packed.numel(), N.ptr(idf), N.ptr(tf), N.ptr(out),
-                                               N.ptr(lad), N.ptr(_status_word(dev)), B, D, idf.numel(), tf.numel(),
-                                               hidden_features, num_blocks, ctypes.byref(spec), flags,
-                                               N.stream_handle(dev))
-        if hook is not None:
-            hook.end(token, 8 * (2 * B * D + B) + 8 * packed.numel())
-    N.check(rc)
+    _launch(dev, N.load().nfa_rqs_resnet_layer_f64,
+            (N.ptr(x), N.ptr(packed), packed.numel(), N.ptr(idf), N.ptr(tf), N.ptr(out), N.ptr(lad),
+             N.ptr(_status_word(dev)), B, D, idf.numel(), tf.numel(), hidden_features, num_blocks, ctypes.byref(spec),
+             flags, N.stream_handle(dev)),
+            "k26", 8 * (2 * B * D + B) + 8 * packed.numel())
     _after_spline(spec, inverse, dev)
     return out, lad
 
@@ -3367,7 +3249,6 @@ def rqs_resnet_layer_f64(inputs, packed, identity_idx, transform_idx, hidden_fea
 def last_layer_kernel():
     """Name of the layer kernel this thread launched last (`nfa_last_layer_kernel`): the launchers pick the instance
     from the batch, the CU count and the LDS budget."""
-    import ctypes
     buf = ctypes.create_string_buffer(192)
     N.load().nfa_last_layer_kernel(buf, 192)
     return buf.value.decode()
