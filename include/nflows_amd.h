@@ -52,7 +52,9 @@ extern "C" {
                               the behaviour of every caller of 19: an older library rejects a non-zero value as an unknown flag,
                               an older binding never sets one;
                               still 19: nfa_pack_resnet_f64, nfa_rqs_resnet_layer_f64 (K26) are ADDED entry points, for the same
-                              reason */
+                              reason;
+                              still 19: nfa_made_rqs_inverse_ctx_f32 (K28) is an ADDED entry point, for the same reason (it reads
+                              K23's block format) */
 
 /* return codes */
 #define NFA_OK 0
@@ -716,6 +718,33 @@ int nfa_made_affine_inverse_f32(const float *inputs, const float *context_terms,
                                 const float *step_blocks, const int32_t *block_starts, int32_t num_blocks,
                                 const int32_t *layout, int32_t layout_len, float *outputs, float *logabsdet,
                                 int64_t batch, int32_t features, int32_t hidden_features, void *stream);
+
+/*
+ * K28.  The sequential part of AutoregressiveTransform.inverse (autoregressive.py:43-52) of
+ *   MaskedPiecewiseRationalQuadraticAutoregressiveTransform (autoregressive.py:404-495) over a MADE conditioner, context
+ *   included, as one persistent kernel: K12's contract -- steps t = 0 .. sequential_steps - 1, columns < sequential_steps
+ *   of `outputs`, `hidden_out` for the caller's tail (K13, or one GEMM and K1), `status` or-ed -- inside K23's loop:
+ *   context vectors, continuation blocks, units in groups of eight (K23's rule, NFA_K23_GROUP), and `logabsdet` summed
+ *   in float64 per sample and rounded once.
+ *   step_blocks / block_starts / layout: ops.pack_made_schedule(net, sequential_steps, 3K - 1, block_cap=..., context=True):
+ *     K12's blocks with K23's two additions (header word 4, unit word 7; see K23).  block_starts int32 [num_blocks + 2] in
+ *     1 KB grains; num_blocks >= sequential_steps + 1: the block, or run of blocks, behind the last step carries units and
+ *     no output rows and only completes the hidden vector.
+ *   context_terms  [batch, context_vectors, Hp] as for K23; NULL with context_vectors = 0.
+ *   outputs     [batch, features]: columns < sequential_steps are written
+ *   logabsdet   [batch]: sum of those columns' log-derivatives (the inverse's sign)
+ *   hidden_out  [batch, hidden_features]: the output layer's input with every hidden unit final, context terms included
+ * Supported: 2 .. 16 bins with linear tails, softplus beta 1, ReLU, no batch norm; the state of sixteen samples (padded
+ * features + one vector per hidden Linear and per context vector) + two blocks of `layout[7]` floats within the LDS,
+ * otherwise NFA_ERR_UNSUPPORTED (callers keep the column-wise host loop).  Added under ABI 19 (see NFA_ABI_VERSION): no
+ * existing entry point, flag set or packed layout changed.
+ */
+int nfa_made_rqs_inverse_ctx_f32(const float *inputs, const float *context_terms, int32_t context_vectors,
+                                 const float *step_blocks, const int32_t *block_starts, int32_t num_blocks,
+                                 const int32_t *layout, int32_t layout_len, float *outputs, float *logabsdet,
+                                 float *hidden_out, int32_t *status, int64_t batch, int32_t features,
+                                 int32_t hidden_features, int32_t sequential_steps, const nfa_rqs_spec *spec,
+                                 void *stream);
 
 /*
  * K13.  The output layer of a MADE conditioner and the autoregressive spline layer behind it in one kernel:

@@ -38,6 +38,8 @@
 //
 // Supported: 8 or 10 bins with linear tails (P = 23 / 29), ReLU, residual blocks (sequential masks) or
 // feed-forward blocks (any masks), no context, no batch norm; state that fits the LDS.
+// K28 (below, `made_inverse_kernel<KT, 16, true>`, nfa_made_rqs_inverse_ctx_f32): the same with a context, 2 .. 16 bins
+// (P = 5 .. 47; no instance uses scratch, none is left out) and steps cut into continuation blocks -- K23's loop.
 
 #include "fused_common.hpp"
 
@@ -209,10 +211,15 @@ __device__ __forceinline__ void request_block(const MadeInvArgs& a, int t, float
 // LPS = lanes per sample.  16: four waves x four samples (round 3).  32 (round 4): EIGHT waves x two samples -- the same
 // sixteen samples and the same LDS per workgroup, but two waves per SIMD: a batch that gives every CU at most one
 // workgroup (configs[4]: 4 096 samples = 256 workgroups) has nothing else to hide the chain's LDS round trips with.
-template <int KT, int LPS>
+//
+// K28: the RQ element inside K23's loop (FULL_): which element a step inverts (AFFINE) and which loop carries it (FULL:
+// context vectors, continuation blocks, groups of eight, the float64 total) are two questions.  <KT, 16, true> is the
+// sampling kernel of a conditional autoregressive spline layer: T <= D steps, `hidden` written for the caller's tail.
+template <int KT, int LPS, bool FULL_ = false>
 __global__ void __launch_bounds__((LPS / 4) * kWave) made_inverse_kernel(const MadeInvArgs a) {
 #pragma clang fp contract(off)
     constexpr bool AFFINE = KT == 0;
+    constexpr bool FULL = AFFINE || FULL_;                          // K23's loop around the element
     constexpr int P = AFFINE ? 2 : 3 * KT - 1;
     constexpr int RB = AFFINE ? 2 : 8;                              // output rows per pass of dot_rows
     constexpr int NW = LPS / 4;                                     // waves per workgroup (16 samples)
@@ -227,13 +234,13 @@ __global__ void __launch_bounds__((LPS / 4) * kWave) made_inverse_kernel(const M
     const int state_floats = x_floats + a.num_vectors * vec_floats;
     float* xs = lds;                                                // [16][px][4]
     float* vecs = lds + x_floats;                                   // [num_vectors][16][ph][4]
-    const int ctx_floats = AFFINE ? a.num_ctx * vec_floats : 0;
+    const int ctx_floats = FULL ? a.num_ctx * vec_floats : 0;
     float* ctxs = lds + state_floats;                               // [num_ctx][16][ph][4] (K23)
     float* buf0 = lds + state_floats + ctx_floats;                  // two step blocks
     float* buf1 = buf0 + a.max_block;
     request_block<NW>(a, 0, buf0, lane, wave);
     for (int i = threadIdx.x; i < state_floats; i += NW * kWave) lds[i] = 0.0f;
-    if constexpr (AFFINE) {
+    if constexpr (FULL) {
         // this sample's context terms, read by its own sixteen lanes only (a dead sample stages the last row's)
         for (int c = 0; c < a.num_ctx; ++c) {
             const float* from = a.ctx + ((size_t)rrow * a.num_ctx + c) * a.Hp;
@@ -254,13 +261,13 @@ __global__ void __launch_bounds__((LPS / 4) * kWave) made_inverse_kernel(const M
     unsigned long long* tr = (a.trace && blockIdx.x == 0 && threadIdx.x == 0) ? a.trace : nullptr;
     int ti = 0;
 #define NFA_K12_STAMP() if (tr && ti < 250) tr[ti++] = __builtin_readcyclecounter();
-    // (RQ: block b is step b.  Affine: `t` advances on a step's last block, `fresh` = the block opens a step)
-    const int nb = AFFINE ? a.num_blocks : 0;
+    // (K12: block b is step b.  K23 / K28: `t` advances on a step's last block, `fresh` = the block opens a step)
+    const int nb = FULL ? a.num_blocks : 0;
     int t_affine = 0;
     bool fresh = true;
     float z_held = 0.0f;
-    for (int b = 0; AFFINE ? b < nb : b <= a.T; ++b) {
-        const int t = AFFINE ? t_affine : b;
+    for (int b = 0; FULL ? b < nb : b <= a.T; ++b) {
+        const int t = FULL ? t_affine : b;
         float* blk = (b & 1) ? buf1 : buf0;
         NFA_K12_STAMP()
         // block t has landed (every wave's share, requested a whole step ago), every wave is done with the
@@ -268,15 +275,15 @@ __global__ void __launch_bounds__((LPS / 4) * kWave) made_inverse_kernel(const M
         asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
         __syncthreads();
         NFA_K12_STAMP()
-        if constexpr (AFFINE) {
+        if constexpr (FULL) {
             if (b + 1 < nb) request_block<NW>(a, b + 1, (b & 1) ? buf0 : buf1, lane, wave);
             if (fresh) {   // (the z prefetch follows t, not the block index)
                 z_held = z_next;
                 if (t + 1 < a.T) z_next = zrow[t + 1];
             }
         }
-        const float z_t = AFFINE ? z_held : z_next;
-        if constexpr (!AFFINE) {
+        const float z_t = FULL ? z_held : z_next;
+        if constexpr (!FULL) {
             if (t < a.T) {
                 request_block<NW>(a, t + 1, (t & 1) ? buf0 : buf1, lane, wave);
                 if (t + 1 < a.T) z_next = zrow[t + 1];
@@ -298,7 +305,7 @@ __global__ void __launch_bounds__((LPS / 4) * kWave) made_inverse_kernel(const M
         const float* wf = blk + __builtin_amdgcn_readfirstlane(h0.z);
         const float* fbias = blk + __builtin_amdgcn_readfirstlane(h0.w);
         bool continued = false;   // another block of this step follows
-        if constexpr (AFFINE) continued = __builtin_amdgcn_readfirstlane(bv[1].x) != 0;
+        if constexpr (FULL) continued = __builtin_amdgcn_readfirstlane(bv[1].x) != 0;
         // ---- 1. hidden units of degree t in layer order (typically one unit per layer), for this wave's samples
         auto unit = [&](vec4i e0, vec4i e1) {
             const float bias = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(e0.x));
@@ -310,7 +317,7 @@ __global__ void __launch_bounds__((LPS / 4) * kWave) made_inverse_kernel(const M
             const float carried = add_stream ? stream[at] : 0.0f;   // (in flight beside the dot product's reads)
             int ctx_v = 0;
             float ctx_term = 0.0f;
-            if constexpr (AFFINE) {
+            if constexpr (FULL) {
                 ctx_v = __builtin_amdgcn_readfirstlane(e1.w);
                 if (ctx_v) ctx_term = ctxs[(ctx_v - 1) * vec_floats + at];
             }
@@ -319,7 +326,7 @@ __global__ void __launch_bounds__((LPS / 4) * kWave) made_inverse_kernel(const M
             else dot_rows<1, 4, LPS>(acc, rows, kp, src, kp >> 2, q, 1);
             rows += kp;
             float v = acc[0] + bias;
-            if constexpr (AFFINE) {
+            if constexpr (FULL) {
                 if (ctx_v) v = v + ctx_term;                    // h + relu(context_layer(ctx)) / lower(h) + context_layer(ctx)
             }
             if (add_stream) v = carried + v;                    // residual connection (made.py:128)
@@ -332,7 +339,7 @@ __global__ void __launch_bounds__((LPS / 4) * kWave) made_inverse_kernel(const M
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         };
         bool one_by_one = true;
-        if constexpr (AFFINE) {
+        if constexpr (FULL) {
             // K23, NFA_K23_GROUP: a MAF step has many units per Linear -- consecutive in the block, the same source vector and
             // width, independent of each other.  Up to eight of them per pass of dot_rows: the source vector is read once
             // for the eight rows, one fence per group.  Every dot product keeps its summation order (dot_rows<R> sums row
@@ -391,7 +398,7 @@ __global__ void __launch_bounds__((LPS / 4) * kWave) made_inverse_kernel(const M
             for (int u = kMadeUnitsAhead; u < units; ++u) unit(bv[kMadeHeader / 4 + 2 * u], bv[kMadeHeader / 4 + 2 * u + 1]);
         }
         NFA_K12_STAMP()
-        if constexpr (AFFINE) {
+        if constexpr (FULL) {
             fresh = !continued;
             if (continued) continue;
         }
@@ -415,11 +422,11 @@ __global__ void __launch_bounds__((LPS / 4) * kWave) made_inverse_kernel(const M
         float y, l;
         if constexpr (AFFINE) {
             affine_element<true>(z_t, p[1], scale_of(p[0], NFA_SCALE_SOFTPLUS), y, l);   // (K2b: autoregressive.py:96-121)
-            ++t_affine;
         } else {
             my_status |= rqs_eval<KT, true, true, true>(z_t, p, a.sp, y, l);
         }
-        if constexpr (AFFINE) lad_wide += (double)l;
+        if constexpr (FULL) ++t_affine;
+        if constexpr (FULL) lad_wide += (double)l;
         else lad_acc += l;
         // (kept in LDS only: a global store per step would sit in front of the next step's vmcnt(0))
         if (q == 0) xs[state_index(t, s, px)] = y;
@@ -431,7 +438,7 @@ __global__ void __launch_bounds__((LPS / 4) * kWave) made_inverse_kernel(const M
     // input of the output layer for features >= T
     if (live) {
         for (int k = q; k < a.T; k += LPS) a.x[row * a.D + k] = xs[state_index(k, s, px)];
-        if (q == 0) a.lad[row] = AFFINE ? (float)lad_wide : lad_acc;
+        if (q == 0) a.lad[row] = FULL ? (float)lad_wide : lad_acc;
         if constexpr (!AFFINE) {
             const float* fin = vecs + a.final_src * vec_floats;
             for (int k = q; k < a.H; k += LPS) a.hidden[row * a.H + k] = fin[state_index(k, s, ph)];
@@ -574,4 +581,64 @@ extern "C" int nfa_made_affine_inverse_f32(const float* inputs, const float* con
                       context_vectors > 0 ? 1 : 0, num_blocks - (features + 1), a.group);
     return launch_kernel(made_inverse_kernel<0, 16>, dim3((unsigned)blocks), dim3(4 * kWave), lds, (hipStream_t)stream, a,
                          kCuLds - 4096, false);
+}
+
+// K28: the sequential features of MaskedPiecewiseRationalQuadraticAutoregressiveTransform.inverse in K23's loop -- context,
+// continuation blocks, groups, float64 total -- with K12's outputs (columns < T, `hidden_out`, `status`)
+template <int KT>
+static void (*made_rqs_full_kernel(int K))(const MadeInvArgs) {
+    if constexpr (KT > 16) return nullptr;
+    else return K == KT ? made_inverse_kernel<KT, 16, true> : made_rqs_full_kernel<KT + 1>(K);
+}
+
+extern "C" int nfa_made_rqs_inverse_ctx_f32(const float* inputs, const float* context_terms, int32_t context_vectors,
+                                            const float* step_blocks, const int32_t* block_starts, int32_t num_blocks,
+                                            const int32_t* layout, int32_t layout_len, float* outputs, float* logabsdet,
+                                            float* hidden_out, int32_t* status, int64_t batch, int32_t features,
+                                            int32_t hidden_features, int32_t sequential_steps, const nfa_rqs_spec* spec,
+                                            void* stream) {
+    if (batch < 0 || features < 1 || hidden_features < 1 || sequential_steps < 0 || sequential_steps > features ||
+        context_vectors < 0 || !layout || layout_len < 8)
+        return NFA_ERR_INVALID_ARGUMENT;
+    MadeInvArgs a = {};
+    int rc = make_dev_spec(spec, &a.sp);
+    if (rc != NFA_OK) return rc;
+    if (a.sp.beta != 1.0f || !a.sp.linear || a.sp.K < 2 || a.sp.K > 16) return NFA_ERR_UNSUPPORTED;
+    rc = read_made_layout(layout, layout_len, hidden_features, a);
+    if (rc != NFA_OK) return rc;
+    // one block per step at least and one behind the last step; at most one context vector per Linear
+    if (a.Xp < sequential_steps || num_blocks < sequential_steps + 1 || context_vectors > a.num_linears)
+        return NFA_ERR_INVALID_ARGUMENT;
+    const size_t lds = made_lds_bytes(a, context_vectors);
+    if (lds + 4096 > (size_t)kCuLds) return NFA_ERR_UNSUPPORTED;
+    if (batch == 0) return NFA_OK;
+    if (!inputs || !step_blocks || !block_starts || !outputs || !logabsdet || !hidden_out ||
+        (context_vectors > 0 && !context_terms))
+        return NFA_ERR_INVALID_ARGUMENT;
+    const int64_t blocks = (batch + kMadeSamples - 1) / kMadeSamples;
+    if (blocks > 0x7fffffff) return NFA_ERR_UNSUPPORTED;
+    a.z = inputs;
+    a.x = outputs;
+    a.lad = logabsdet;
+    a.hidden = hidden_out;
+    a.blocks = step_blocks;
+    a.block_at = block_starts;
+    a.status = status;
+    a.batch = batch;
+    a.D = features;
+    a.H = hidden_features;
+    a.T = sequential_steps;
+    a.trace = nullptr;
+    a.ctx = context_terms;
+    a.num_ctx = context_vectors;
+    a.num_blocks = num_blocks;
+    // K23's rule for the groups of eight (units per Linear and step: hidden / (features - 1)); NFA_K23_GROUP=0 / 1 forces either
+    const char* group_env = getenv("NFA_K23_GROUP");
+    a.group = group_env && group_env[0] ? (atoi(group_env) != 0 ? 1 : 0)
+                                        : (hidden_features >= 5 * (features > 1 ? features - 1 : 1) ? 1 : 0);
+    void (*kern)(const MadeInvArgs) = made_rqs_full_kernel<2>(a.sp.K);
+    if (!kern) return NFA_ERR_UNSUPPORTED;
+    note_layer_kernel("made_inverse_kernel<element=rqs, K=%d, context=%d, continuation_blocks=%d, group=%d>", a.sp.K,
+                      context_vectors > 0 ? 1 : 0, num_blocks - (sequential_steps + 1), a.group);
+    return launch_kernel(kern, dim3((unsigned)blocks), dim3(4 * kWave), lds, (hipStream_t)stream, a, kCuLds - 4096, false);
 }

@@ -1483,6 +1483,42 @@ def made_affine_inverse(inputs, schedule, hidden_features, context_terms=None):
     return out, lad
 
 
+def made_rqs_inverse_ctx(inputs, schedule, hidden_features, sequential_steps, spec, context_terms=None, out=None):
+    """K28 -- the sequential features of the autoregressive spline inverse in K23's loop: context vectors, continuation
+    blocks, 2 .. 16 bins.  `schedule`: `pack_made_schedule(net, sequential_steps, 3K - 1, block_cap=..., context=True)`.
+    Returns what `made_rqs_inverse` returns -- (outputs [B, D] with columns < sequential_steps filled, their logabsdet [B],
+    hidden [B, H]) -- or None outside the kernel's family (NFA_ERR_UNSUPPORTED)."""
+    N.require_device_f32("inputs", inputs, 2)
+    dev = inputs.device
+    B, D = inputs.shape
+    z = inputs.detach().contiguous()
+    if out is None:
+        out = torch.empty_like(z)
+    elif (out.dtype != torch.float32 or out.device != dev or tuple(out.shape) != (B, D) or not out.is_contiguous()):
+        raise ValueError("out must be a contiguous float32 [batch, features] tensor on the inputs' device")
+    lad = torch.empty(B, dtype=torch.float32, device=dev)
+    hidden = torch.empty(B, hidden_features, dtype=torch.float32, device=dev)
+    floats, ints, layout = schedule
+    vectors = 0
+    if context_terms is not None:
+        N.require_device_f32("context_terms", context_terms, 3)
+        context_terms = context_terms.contiguous()
+        vectors = context_terms.shape[1]
+        if context_terms.shape[0] != B or context_terms.shape[2] != layout[5]:
+            raise ValueError("context_terms is %s, expected [%d, C, %d]" % (tuple(context_terms.shape), B, layout[5]))
+    arr = (ctypes.c_int32 * len(layout))(*layout)
+    with torch.cuda.device(dev):
+        rc = N.load().nfa_made_rqs_inverse_ctx_f32(
+            N.ptr(z), N.ptr(context_terms), vectors, N.ptr(floats), N.ptr(ints), ints.numel() - 2, arr, len(layout),
+            N.ptr(out), N.ptr(lad), N.ptr(hidden), N.ptr(_status_word(dev)), B, D, hidden_features, sequential_steps,
+            ctypes.byref(spec), N.stream_handle(dev))
+    if rc == N.ERR_UNSUPPORTED:
+        return None
+    N.check(rc)
+    _after_spline(spec, True, dev)
+    return out, lad, hidden
+
+
 _sum_workspaces = {}
 
 

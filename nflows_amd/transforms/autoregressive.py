@@ -473,6 +473,14 @@ class MaskedPiecewiseRationalQuadraticAutoregressiveTransform(AutoregressiveTran
     fuse_sequential_inverse = os.environ.get("NFA_K12", "1") != "0"
 
     def _sequential_kernel(self, inputs, context, sequential):
+        if not self.fuse_sequential_inverse or sequential < 1:
+            return None
+        fast = self._sequential_kernel_k12(inputs, context, sequential)
+        if fast is None:   # K12's gate refused, or its entry point answered unsupported (one step block does not fit twice)
+            fast = self._sequential_kernel_ctx(inputs, context, sequential)
+        return fast
+
+    def _sequential_kernel_k12(self, inputs, context, sequential):
         net = self.autoregressive_net
         if not (self.fuse_sequential_inverse and context is None and sequential >= 1
                 and isinstance(net, made_module.MADE) and net.activation is F.relu
@@ -488,6 +496,77 @@ class MaskedPiecewiseRationalQuadraticAutoregressiveTransform(AutoregressiveTran
                                  wh_divisor=float(np.sqrt(net.hidden_features)) if hasattr(net, "hidden_features") else 0.0)
         hidden_features = net.initial_layer.weight.shape[0]
         return ops.made_rqs_inverse(inputs, schedule, hidden_features, sequential, spec)
+
+    # ---- persistent kernel K28 (csrc/made_inverse.hip): the RQ element in K23's loop -- a context, 2 .. 16 bins, steps cut
+    #      into continuation blocks -- for what K12 does not serve.  `fuse_sequential_inverse` (NFA_K12) switches both
+    #      kernels, this one K28 alone.
+    fuse_sequential_inverse_ctx = os.environ.get("NFA_K28", "1") != "0"
+    _SEQUENTIAL_HOOKS = ("inverse", "_elementwise_inverse", "_inverse_column", "_output_dim_multiplier", "_elementwise")
+    # Size rule from profiles/ar_spline_sample_time.json (hidden 128, two blocks): the kernel does one MADE pass per sample
+    # whatever the number of features, sixteen samples per workgroup; the host loop one pass of GEMMs per FEATURE at
+    # full-device rates.  At 65 536 rows the loop is 2.4 x faster with 6 features and 1.6 x with 8 (3.0 x and 1.8 x at
+    # 262 144), with 16 features the kernel is 1.10 x faster at 65 536 rows and 0.97 x at 262 144, with 21-64 features 1.2-2.6 x
+    # faster at both; at 16 384 rows the kernel is 1.5 x faster or better for every shape.  Between 16 384 and 65 536 rows, and
+    # between 8 and 16 features, nothing was measured: such calls keep the loop, which is what they had.
+    _SEQUENTIAL_CTX_ROW_LIMIT = (16, 16384)   # (features <=, rows >): such a call takes the host loop; None: no size rule
+
+    def _sequential_ctx_serves_rows(self, features, rows):
+        limit = self._SEQUENTIAL_CTX_ROW_LIMIT
+        return limit is None or not (features <= limit[0] and rows > limit[1])
+
+    def _sequential_ctx_net(self):
+        """The MADE when K28 can run it -- plain MADE, ReLU, no batch norm, no active dropout, at most 12 Linears --, else
+        None.  The structure is read once per cache epoch; activations and dropouts are plain attributes, read per call."""
+        net = self._modules["autoregressive_net"]
+        if not _cache.keyed(self, "_sequential_ctx_net_held", (_cache.epoch(), net), lambda: (
+                type(net) is made_module.MADE and len(ops._made_linears(net)) <= ops.MADE_MAX_LINEARS
+                and net.initial_layer.weight.dtype == torch.float32
+                and not any(isinstance(m, torch.nn.BatchNorm1d) for m in net.modules()))):
+            return None
+        relu = (F.relu, torch.relu)
+        if net.__dict__.get("activation") not in relu or not all(
+                b.__dict__.get("activation") in relu and (not b.dropout.training or b.dropout.p == 0.0) for b in net.blocks):
+            return None
+        return net
+
+    def _sequential_ctx_plan(self, net, sequential):
+        """(step blocks of `ops.pack_made_schedule` or None where the shape does not fit the LDS, packed context Linears or
+        None), kept until a parameter, a mask or a write through `.data` changes (`_cache.weights_key`)."""
+        def pack():
+            hidden = net.initial_layer.weight.shape[0]
+            linears = len(ops._made_linears(net))
+            vectors = len(ops.made_context_layers(net))
+            cap = ops.made_block_cap(sequential, hidden, linears, vectors)
+            schedule = ops.pack_made_schedule(net, sequential, self._output_dim_multiplier(), block_cap=cap, context=True) \
+                if cap > 0 else None
+            return schedule, ops.pack_made_context(net) if schedule else None
+        return _cache.keyed(self, "_made_schedule_ctx_cache", (_cache.weights_key(self, net), sequential), pack)
+
+    def _sequential_kernel_ctx(self, inputs, context, sequential):
+        cls = type(self)
+        if not (self.fuse_sequential_inverse_ctx and self.tails == "linear" and 2 <= self.num_bins <= 16
+                and torch.is_tensor(inputs) and inputs.dim() == 2 and inputs.dtype == torch.float32 and inputs.is_cuda
+                and inputs.shape[0] >= 1 and self._sequential_ctx_serves_rows(inputs.shape[1], inputs.shape[0])
+                and not any(h in self.__dict__
+                            or getattr(cls, h) is not getattr(MaskedPiecewiseRationalQuadraticAutoregressiveTransform, h)
+                            for h in self._SEQUENTIAL_HOOKS)):
+            return None
+        net = self._sequential_ctx_net()
+        if net is None or net.initial_layer.weight.shape[1] != inputs.shape[1]:
+            return None
+        ce = net.context_layer.weight.shape[1] if hasattr(net, "context_layer") else 0
+        if not ((context is None and ce == 0)
+                or (ce > 0 and torch.is_tensor(context) and context.dim() == 2 and context.dtype == torch.float32
+                    and context.is_cuda and context.shape == (inputs.shape[0], ce))):
+            return None
+        schedule, packed_context = self._sequential_ctx_plan(net, sequential)
+        if schedule is None:
+            return None
+        spec = ops.make_rqs_spec(self.num_bins, self.tails, tail_bound=self.tail_bound,
+                                 min_bin_width=self.min_bin_width, min_bin_height=self.min_bin_height,
+                                 min_derivative=self.min_derivative, wh_divisor=self._wh_divisor())
+        terms = ops.made_context_terms(context, packed_context) if ce else None
+        return ops.made_rqs_inverse_ctx(inputs, schedule, net.initial_layer.weight.shape[0], sequential, spec, terms)
 
     def _inverse_column(self, column, params):
         """One feature: params [B, P]; the spline layer kernel with a single (transformed) feature."""

@@ -167,6 +167,14 @@ with torch.no_grad():
     us = timeit(lambda: t_ar.inverse(za), reps=10, inner=2)
     rows.append("| K12 `made_rqs_inverse_kernel` + tail | autoregressive RQ inverse, D=784 H=256 B=4096 (256 sequential steps) | %.1f | %.2f us per step and 16 samples: latency-bound |"
                 % (us, us / 256))
+    # K28: the same loop with context vectors and continuation blocks (a conditional layer, what K12 does not serve)
+    from nflows_amd.transforms import MaskedPiecewiseRationalQuadraticAutoregressiveTransform as ARQ
+    torch.manual_seed(0)
+    t_ctx = ARQ(features=21, hidden_features=128, context_features=16, num_bins=8, tails="linear", tail_bound=3.0).to(dev).eval()
+    zc, cc = torch.randn(16384, 21, device=dev, generator=g), torch.randn(16384, 16, device=dev, generator=g)
+    us = timeit(lambda: t_ctx.inverse(zc, context=cc), reps=10, inner=2)
+    rows.append("| K28 `made_inverse_kernel<8, 16, true>` + the context GEMM + tail | conditional autoregressive RQ inverse, D=21 H=128 C=16 B=16384 (20 sequential steps) | %.1f | %.2f us per step and 16 samples: latency-bound |"
+                % (us, us / 20))
     # K13: the MADE's output layer inside the spline kernel (the layer's forward pass; the hidden layers are library GEMMs)
     us = timeit(lambda: t_ar(za), reps=10, inner=2)
     rows.append("| K13 `rqs_made_output_kernel` + the MADE's hidden layers | autoregressive RQ forward (density), D=784 H=256 B=4096 | %.1f | %.0f TFLOP/s bf16 over the whole call (6 products x 37.8 GFLOP in the kernel); %.1f M samples/s |"
