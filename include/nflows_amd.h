@@ -54,7 +54,9 @@ extern "C" {
                               still 19: nfa_pack_resnet_f64, nfa_rqs_resnet_layer_f64 (K26) are ADDED entry points, for the same
                               reason;
                               still 19: nfa_made_rqs_inverse_ctx_f32 (K28) is an ADDED entry point, for the same reason (it reads
-                              K23's block format) */
+                              K23's block format);
+                              still 19: nfa_rqs_flow_made_f32 (K29) is an ADDED entry point, for the same reason (its stream is
+                              K22's with another final layer) */
 
 /* return codes */
 #define NFA_OK 0
@@ -654,6 +656,35 @@ int nfa_affine_flow_made_f32(const float *inputs, const float *context, int32_t 
                              int32_t num_layers, float *outputs, float *logabsdet, int32_t *status, int64_t batch,
                              int32_t row_length, int32_t features, int32_t hidden_features, int32_t num_hidden_layers,
                              int32_t flags, void *stream);
+
+/*
+ * K29.  The density pass (forward) of a run of MaskedPiecewiseRationalQuadraticAutoregressiveTransform layers
+ *   (autoregressive.py:404-495) over MADE conditioners (made.py:233-311) in ONE launch: per layer the MADE on the row
+ *   tile's columns as in K22 (nfa_affine_flow_made_f32), then per feature the 3 K - 1 logits of the masked final Linear
+ *   straight from the MFMA accumulators -- they never reach memory -- and the rational-quadratic spline with linear tails
+ *   on them (K1's arithmetic, rqs_math.hpp's register instance); logabsdet is the sum over the features, feature pair
+ *   after feature pair and layer after layer, in an order the shape alone fixes.  Inputs outside +-tail_bound pass through
+ *   bit for bit and add exactly 0; *status gets K1's bits.
+ *   inputs, context, tables, num_layers, outputs, logabsdet, batch, row_length, features, hidden_features,
+ *   num_hidden_layers, flags: as for nfa_affine_flow_made_f32.
+ *   weights_packed  K22's stages (context_layer, initial_layer, the blocks), then the final layer: features padded to pairs,
+ *                   every feature's 3 K - 1 rows (weight * mask, the 2 K width / height rows times
+ *                   1 / sqrt(hidden_features), autoregressive.py:464-466) padded with zero rows to 16 T,
+ *                   T = ceil((3 K - 1) / 16); pair g is T tiles of two stages each whose accumulator values, tile after
+ *                   tile, are the 16 T logits of feature 2 g + (lane >> 5) (row i of a tile: register 4 (i / 8) + i % 4
+ *                   of lane-half (i / 4) % 2).
+ *   bias_packed     as for K22, the final layer's 32 per tile in the same order and with the same factor.
+ *   spec            num_bins 2 .. 16, tails = NFA_TAILS_LINEAR, right = tail_bound, the three minimums; wh_divisor is NOT
+ *                   applied by the kernel (the packed rows carry it).
+ * Supported: hidden_features = 128, features <= 64, context_features <= 64, 2 <= num_bins <= 16, linear tails,
+ * row_length % 4 == 0, batch % 128 == 0, forward only; otherwise NFA_ERR_UNSUPPORTED (callers then run the MADE's GEMMs and
+ * K13 / K1).  Added under ABI 19 (see NFA_ABI_VERSION): no existing entry point, flag set or packed layout changes.
+ */
+int nfa_rqs_flow_made_f32(const float *inputs, const float *context, int32_t context_features,
+                          const void *weights_packed, const float *bias_packed, const int32_t *tables, int32_t num_layers,
+                          float *outputs, float *logabsdet, int32_t *status, int64_t batch, int32_t row_length,
+                          int32_t features, int32_t hidden_features, int32_t num_hidden_layers, const nfa_rqs_spec *spec,
+                          int32_t flags, void *stream);
 
 /*
  * K12.  The sequential part of AutoregressiveTransform.inverse (autoregressive.py:43-52) for

@@ -56,6 +56,7 @@ EXPORTS = (
     "nfa_rqs_resnet_layer_f64",
     "nfa_affine_flow_mlp_f32",
     "nfa_affine_flow_made_f32",
+    "nfa_rqs_flow_made_f32",
     "nfa_made_rqs_inverse_f32",
     "nfa_made_affine_inverse_f32",
     "nfa_made_rqs_inverse_ctx_f32",
@@ -195,6 +196,8 @@ def _declare(lib):
     lib.nfa_affine_flow_mlp_f32.argtypes = [vp] * 4 + [i32] + [vp] * 3 + [i64] + [i32] * 7 + [vp]
     lib.nfa_affine_flow_made_f32.restype = ctypes.c_int
     lib.nfa_affine_flow_made_f32.argtypes = [vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, i64] + [i32] * 5 + [vp]
+    lib.nfa_rqs_flow_made_f32.restype = ctypes.c_int
+    lib.nfa_rqs_flow_made_f32.argtypes = [vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, i64] + [i32] * 4 + [sp, i32, vp]
     lib.nfa_rqs_flow_resnet_context_f32.restype = ctypes.c_int
     lib.nfa_rqs_flow_resnet_context_f32.argtypes = [vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, i64, i32, i32, i32, i32,
                                                     i32, sp, i32, vp]

@@ -2369,13 +2369,15 @@ def _context_linears(net):
     return net.context_layer, blocks
 
 
-def pack_mlp_conditioner(net, num_transform, additive=False, row_order=None, context=None):
+def pack_mlp_conditioner(net, num_transform, additive=False, row_order=None, context=None, final_rows=None):
     """Packs an MLP conditioner (nn/nets/mlp.py: _input_layer, _hidden_layers[*], _output_layer; all
     hidden widths 128) -- or a ResidualNet without a context, or a MADE (`_conditioner_linears`) -- for K11 / K22 (layout
     in include/nflows_amd.h).  `row_order`: which conditioner output every packed output row is (default: K11's
     `_affine_row_order`).  `context` = `_context_linears(net)`: the context stages join the stream where the kernel
     consumes them -- in front of the initial layer's, and behind the first Linear's of every residual block, whose bias takes
-    the block's context bias.  Returns (weights [stages, 768*8] bf16, biases fp32)."""
+    the block's context bias.  `final_rows` = (weight [32 tiles, <= 128], bias [32 tiles]): the output layer's packed rows as
+    they are, in place of the gather through `row_order` (K29: `pack_made_rqs_conditioner`).  Returns (weights [stages,
+    768*8] bf16, biases fp32)."""
     dt = num_transform
     input_layer, hidden_layers, output_layer = _conditioner_linears(net)
     dev = output_layer.weight.device
@@ -2410,14 +2412,17 @@ def pack_mlp_conditioner(net, num_transform, additive=False, row_order=None, con
             stages.append(context_stages(block_context[i // 2]))
             b = b + block_context[i // 2].bias.detach().float()
         biases.append(_bias_accumulator_order(_pad_to(b, rows=128)))
-    order_r = (_affine_row_order(dt, additive) if row_order is None else row_order).to(dev)
-    wo = _pad_to(output_layer.weight.detach().float(), cols=128)
-    bo = output_layer.bias.detach().float()
-    wo = torch.cat((wo, wo.new_zeros(1, 128)), dim=0)     # row -1 = zero padding
-    bo = torch.cat((bo, bo.new_zeros(1)))
-    wf = wo.index_select(0, order_r % wo.shape[0]).index_select(1, order_k)
-    bf = bo.index_select(0, order_r % bo.shape[0])
-    tiles = order_r.numel() // 32
+    if final_rows is not None:
+        wf, bf = _pad_to(final_rows[0], cols=128).index_select(1, order_k), final_rows[1]
+    else:
+        order_r = (_affine_row_order(dt, additive) if row_order is None else row_order).to(dev)
+        wo = _pad_to(output_layer.weight.detach().float(), cols=128)
+        bo = output_layer.bias.detach().float()
+        wo = torch.cat((wo, wo.new_zeros(1, 128)), dim=0)     # row -1 = zero padding
+        bo = torch.cat((bo, bo.new_zeros(1)))
+        wf = wo.index_select(0, order_r % wo.shape[0]).index_select(1, order_k)
+        bf = bo.index_select(0, order_r % bo.shape[0])
+    tiles = bf.numel() // 32
     # (p, tile, i, hs, k4, hf, j) -> (tile, hs, p, k4, hf, i, j): two stages per tile
     stages.append(pieces(wf).view(3, tiles, 32, 2, 4, 2, 8).permute(1, 3, 0, 4, 5, 2, 6).reshape(tiles * 2, -1))
     biases.append(_bias_accumulator_order(bf))
@@ -2431,6 +2436,60 @@ def pack_made_conditioner(net):
     features = net.initial_layer.weight.shape[1]
     return pack_mlp_conditioner(net, features, row_order=_made_row_order(features),
                                 context=_context_linears(net) if hasattr(net, "context_layer") else None)
+
+
+def made_rqs_tiles(num_bins):
+    """T of K29: 32-row tiles per pair of features -- the 3 K - 1 logits of a feature padded to 16 T rows."""
+    return (3 * num_bins - 1 + 15) // 16
+
+
+def pack_made_rqs_conditioner(net, num_bins):
+    """A MADE with 3 K - 1 outputs per feature (the conditioner of MaskedPiecewiseRationalQuadraticAutoregressiveTransform
+    with linear tails) for K29: `pack_mlp_conditioner`'s stages of `weight * mask` for the initial layer, the hidden layers
+    and the context exactly as `pack_made_conditioner` builds them; the final layer's masked rows per feature padded to
+    16 T rows (`made_rqs_tiles`) and the features to pairs (zero rows), in `_k8_row_order_32(tiles_per_group=T)` order, the
+    width / height rows times 1 / sqrt(net.hidden_features) where the net exposes it (autoregressive.py:464-466; a MADE of
+    this package does not: no factor then), three bf16 pieces.  Returns (weights [stages, 768*8] bf16, biases fp32)."""
+    K, P = num_bins, 3 * num_bins - 1
+    final = net.final_layer
+    features = net.initial_layer.weight.shape[1]
+    H = final.weight.shape[1]
+    if final.weight.shape[0] != features * P:
+        raise ValueError("the MADE's final layer must have 3 * num_bins - 1 rows per feature")
+    T = made_rqs_tiles(K)
+    pairs = (features + 1) // 2
+    dev = final.weight.device
+    scale = torch.ones(P, dtype=torch.float64, device=dev)
+    if hasattr(net, "hidden_features"):
+        scale[:2 * K] = 1.0 / math.sqrt(net.hidden_features)
+    wf = ((final.weight.detach() * final.mask).double().view(features, P, H) * scale[None, :, None]).float()
+    bf = (final.bias.detach().double().view(features, P) * scale[None, :]).float()
+    rows = wf.new_zeros(2 * pairs, 16 * T, H)
+    rows[:features, :P] = wf
+    bias = bf.new_zeros(2 * pairs, 16 * T)
+    bias[:features, :P] = bf
+    order = _k8_row_order_32(2 * pairs, T).to(dev)
+    final_rows = (rows.reshape(-1, H).index_select(0, order), bias.reshape(-1).index_select(0, order))
+    return pack_mlp_conditioner(net, features, context=_context_linears(net) if hasattr(net, "context_layer") else None,
+                                final_rows=final_rows)
+
+
+def rqs_flow_made(inputs, weights_packed, bias_packed, tables, features, num_hidden_layers, spec, context=None,
+                  accumulate_into=None, num_layers=1, standard_normal_log_prob=False, pad=None, residual_blocks=True):
+    """K29 -- the density pass of a run of masked autoregressive rational-quadratic spline layers with their MADE
+    conditioners in one launch (blobs of `pack_made_rqs_conditioner` concatenated in execution order, tables from
+    `flow_layer_tables` with every feature in both halves; rows padded to a multiple of four columns by `pad`).
+    `num_hidden_layers`: the hidden Linears (twice the number of residual blocks, or the number of feed-forward blocks);
+    `spec`: `make_rqs_spec` of the layers (2 .. 16 bins, linear tails; its `wh_divisor` is in the packed rows and is not
+    read).  Forward only.  Returns (outputs, logabsdet), or (None, log_prob) with `standard_normal_log_prob`; None when the
+    shape is outside the fast path."""
+    def launch(x, ctx, out, lad, redo, flags, status, stream):
+        return N.load().nfa_rqs_flow_made_f32(
+            N.ptr(x), N.ptr(ctx), 0 if ctx is None else ctx.shape[1], N.ptr(weights_packed), N.ptr(bias_packed),
+            N.ptr(tables), num_layers, N.ptr(out), N.ptr(lad), status, x.shape[0], x.shape[1], features, 128,
+            num_hidden_layers, ctypes.byref(spec), flags, stream)
+    return _whole_layer_launch(launch, inputs, False, accumulate_into, standard_normal_log_prob, pad, context,
+                               flags=N.FLAG_RESIDUAL_BLOCKS if residual_blocks else 0, spec=spec)
 
 
 def affine_flow_mlp(inputs, weights_packed, bias_packed, tables, num_transform, num_identity, num_hidden_layers,

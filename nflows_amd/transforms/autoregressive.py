@@ -34,6 +34,18 @@ class _LazyRows:
         return self._value[index]
 
 
+def _own_run_plan(layer):
+    """(weights, biases, tables) of a layer as a run of one (K22, K29): the run planner's own packing and tables
+    (`CompositeTransform._run_plan`), with the layer standing in for the composite -- the planner keeps its plan cache in
+    the `__dict__` of whatever it is given and reads nothing else of it -- so that a layer called on its own and the same
+    layer inside a composite are served from one code path."""
+    from .base import CompositeTransform, _Run
+    run = layer.__dict__.get("_own_run")
+    if run is None:
+        run = layer.__dict__["_own_run"] = _Run([(layer, None)])
+    return CompositeTransform._run_plan(layer, run, False)[:3]
+
+
 class AutoregressiveTransform(Transform):
     def __init__(self, autoregressive_net):
         super().__init__()
@@ -283,12 +295,7 @@ class MaskedAffineAutoregressiveTransform(AutoregressiveTransform):
         return super().forward(inputs, context)
 
     def _whole_layer(self, inputs, context):
-        from .base import CompositeTransform, _Run
-        run = self.__dict__.get("_own_run")
-        if run is None:
-            run = self.__dict__["_own_run"] = _Run([(self, None)])
-        # (the planner's blob / table cache, kept in this layer's own __dict__: the function reads nothing else of `self`)
-        weights, biases, tables, _, _ = CompositeTransform._run_plan(self, run, False)
+        weights, biases, tables = _own_run_plan(self)
         hidden_linears, residual_blocks = self._conditioner_shape()
         geometry = self._fused_geometry()
         return ops.affine_flow_made(inputs, weights, biases, tables, self.features, hidden_linears, context,
@@ -457,7 +464,133 @@ class MaskedPiecewiseRationalQuadraticAutoregressiveTransform(AutoregressiveTran
         return ops.made_output_spline(inputs, hidden, packed[1], spec, first_column=first_feature, inverse=inverse,
                                       out=out)
 
+    # ---- whole-layer kernel K29 (csrc/made_rqs.hip): the MADE and the spline inside one layer kernel, runs of such
+    #      layers -- their permutations and the base density included -- in one launch.  The density pass only: the inverse
+    #      keeps K12 / K28, K13's tail and the host loop.  What follows is the protocol the run planner reads
+    #      (transforms/base.py), as MaskedAffineAutoregressiveTransform has it for K22.
+    #      The switch (NFA_K29): "0" off; "2" serves 8 bins as well; anything else, unset and empty included, is the default 1:
+    #      every bin count from 2 to 16 except 8, whose calls keep hidden GEMMs + K13 (existing tests pin that path; the 8-bin
+    #      columns of profiles/ar_spline_density_time.json are recorded for a later change of that default).
+    #      No size rule: in all 96 measured cases of that file (log_prob and _transform, 8 and 10 bins, with and without a
+    #      context, 1 024 / 16 384 / 262 144 rows, 5-16 layers on 8-64 features) the one launch is 1.5-4.7 x faster per call
+    #      than the layer-by-layer path, none slower.
+    fuse_conditioner = {"0": 0, "2": 2}.get(os.environ.get("NFA_K29", "1").strip(), 1)
+    unconditional_transform = None
+    _forward_only_run = True
+    _HOOKS = ("forward", "_elementwise", "_elementwise_forward", "_output_dim_multiplier")
+
+    @property
+    def _user_hooks(self):
+        """True when a subclass (or an assignment to the class or the instance) replaced one of the functions the
+        kernel stands for: such a layer runs the sequence below with the user's function."""
+        cls = type(self)
+        return any(h in self.__dict__
+                   or getattr(cls, h) is not getattr(MaskedPiecewiseRationalQuadraticAutoregressiveTransform, h)
+                   for h in self._HOOKS)
+
+    def _conditioner(self):
+        return self._modules["autoregressive_net"]
+
+    @property
+    def features(self):
+        """Width of the rows the layer takes (the planner compares it with the input's)."""
+        return self._conditioner().initial_layer.weight.shape[1]
+
+    def _conditioner_shape(self):
+        """(hidden Linears, residual blocks?) of a MADE that K29 runs inside the layer kernel -- plain MADE in float32, hidden
+        width <= 128, at most 64 features and 64 context features, 3 K - 1 rows per feature, no batch norm --, or None.  Read
+        once per cache epoch; the activations and the dropouts are plain attributes and are read on every call."""
+        net = self._conditioner()
+
+        def read():
+            if type(net) is made_module.MADE and net.initial_layer.weight.dtype == torch.float32:
+                hidden, features = net.initial_layer.weight.shape
+                ce = net.context_layer.weight.shape[1] if hasattr(net, "context_layer") else 0
+                if (hidden <= 128 and 1 <= features <= 64 and ce <= 64
+                        and not any(isinstance(m, torch.nn.BatchNorm1d) for m in net.modules())):
+                    residual = bool(net.use_residual_blocks)
+                    return len(net.blocks) * (2 if residual else 1), residual, net.final_layer.weight.shape[0] // features
+            return None
+        shape = _cache.keyed(self, "_conditioner_shape_held", (_cache.epoch(), net), read)
+        if shape is None or self.tails != "linear" or shape[2] != 3 * self.num_bins - 1:
+            return None
+        relu = (F.relu, torch.relu)
+        if net.__dict__.get("activation") not in relu or not all(
+                b.__dict__.get("activation") in relu and (not b.dropout.training or b.dropout.p == 0.0)
+                for b in net.blocks):
+            return None
+        return shape[:2]
+
+    def _context_features(self):
+        net = self._conditioner()
+        return net.context_layer.weight.shape[1] if hasattr(net, "context_layer") else 0
+
+    def _density_kernel_serves_bins(self):
+        mode = self.fuse_conditioner
+        return bool(mode) and 2 <= self.num_bins <= 16 and (self.num_bins != 8 or int(mode) >= 2)
+
+    def _run_kind(self, context):
+        if (not self._density_kernel_serves_bins() or torch.is_grad_enabled() or self._conditioner_shape() is None):
+            return None
+        ce = self._context_features()
+        if context is None:
+            return "k29" if ce == 0 else None
+        ok = (ce > 0 and torch.is_tensor(context) and context.dim() == 2 and context.dtype == torch.float32
+              and context.is_cuda and context.shape[1] == ce)
+        return "k29" if ok else None
+
+    def _fused_geometry(self, others=()):
+        """(padded features, transformed features, identity features, pad value): the row length in multiples of four,
+        the pad columns pass through; every feature is both read by the conditioner and transformed."""
+        features = self.features
+        return (features + 3) // 4 * 4, features, features, 0.0
+
+    def _spline_constants(self):
+        return (self.num_bins, float(self.tail_bound), float(self.min_bin_width), float(self.min_bin_height),
+                float(self.min_derivative), self._wh_divisor())
+
+    def _run_signature(self):
+        return ("k29", self.features, self._conditioner_shape(), self._context_features(), self._spline_constants())
+
+    def _all_columns(self):
+        dev = self._conditioner().initial_layer.weight.device
+        held = self.__dict__.get("_columns_held")
+        if held is None or held.device != dev or held.numel() != self.features:
+            held = self.__dict__["_columns_held"] = torch.arange(self.features, device=dev)
+        return held
+
+    transform_features = property(_all_columns)   # (what the planner writes into the two halves of the layer's table)
+    identity_features = property(_all_columns)
+
+    def _packed_mlp(self):
+        net = self._conditioner()
+        # (parameters and buffers: the masks are part of the key; the divisor is an attribute of the net)
+        key = (_cache.weights_key(self, net), self.num_bins, self._wh_divisor())
+        return _cache.keyed(self, "_packed_made_rqs_cache", key, lambda: ops.pack_made_rqs_conditioner(net, self.num_bins))
+
+    def _density_spec(self):
+        return ops.make_rqs_spec(self.num_bins, self.tails, tail_bound=self.tail_bound,
+                                 min_bin_width=self.min_bin_width, min_bin_height=self.min_bin_height,
+                                 min_derivative=self.min_derivative, wh_divisor=self._wh_divisor())
+
+    def _whole_layer(self, inputs, context):
+        weights, biases, tables = _own_run_plan(self)
+        hidden_linears, residual_blocks = self._conditioner_shape()
+        geometry = self._fused_geometry()
+        return ops.rqs_flow_made(inputs, weights, biases, tables, self.features, hidden_linears, self._density_spec(),
+                                 context, pad=(geometry[0], geometry[3]), residual_blocks=residual_blocks)
+
     def forward(self, inputs, context=None):
+        if (torch.is_tensor(inputs) and inputs.dim() == 2 and inputs.dtype == torch.float32 and inputs.is_cuda
+                and inputs.shape[0] >= 1 and not self._user_hooks and self._run_kind(context) is not None
+                and inputs.shape[1] == self.features
+                and (context is None or context.shape[0] == inputs.shape[0])):
+            fused = self._whole_layer(inputs, context)   # a run of one
+            if fused is not None:
+                return fused
+        return self._forward_layer_by_layer(inputs, context)
+
+    def _forward_layer_by_layer(self, inputs, context=None):
         net = self.autoregressive_net
         if (self.fuse_output_layer and isinstance(net, made_module.MADE) and inputs.dim() == 2 and inputs.is_cuda
                 and inputs.dtype == torch.float32 and not torch.is_grad_enabled() and self.tails == "linear"
@@ -467,7 +600,7 @@ class MaskedPiecewiseRationalQuadraticAutoregressiveTransform(AutoregressiveTran
             if fused is not None:
                 return fused
             return self._elementwise_forward(inputs, net.final_layer(hidden))
-        return super().forward(inputs, context)
+        return AutoregressiveTransform.forward(self, inputs, context)
 
     # persistent kernel for the sequential features of the inverse (K12, csrc/made_inverse.hip)
     fuse_sequential_inverse = os.environ.get("NFA_K12", "1") != "0"

@@ -58,9 +58,10 @@ def _switch_state():
     from .coupling import (AdditiveCouplingTransform, AffineCouplingTransform,
                            PiecewiseRationalQuadraticCouplingTransform as RQ)
     from .autoregressive import MaskedAffineAutoregressiveTransform as MAF
+    from .autoregressive import MaskedPiecewiseRationalQuadraticAutoregressiveTransform as ARQ
     return (RQ.fuse_conditioner, RQ.fuse_final_linear, RQ.conditioner_engine, RQ.conditioner_act_scale,
             RQ.resnet_log2e, AffineCouplingTransform.fuse_conditioner, AdditiveCouplingTransform.fuse_conditioner,
-            MAF.fuse_conditioner)
+            MAF.fuse_conditioner, ARQ.fuse_conditioner)
 
 
 def _layer_state(units):
@@ -183,7 +184,7 @@ class CompositeTransform(Transform):
                 and inputs.dtype == torch.float32):
             return units, start
 
-        def eligible(t):   # (K22 serves the density pass only: `_forward_only_run`)
+        def eligible(t):   # (K22 and K29 serve the density pass only: `_forward_only_run`)
             return self._joinable(t, inputs.shape[1], context) and not (inverse and getattr(t, "_forward_only_run", False))
         i, signature = start, None
         while i < len(layers):
@@ -207,7 +208,7 @@ class CompositeTransform(Transform):
             signature = sig
             units.append((coupling, perm))
             i += step
-        # (a coupling layer on its own has its whole-layer path in its own forward; a MAF layer is a run of one)
+        # (a coupling layer on its own has its whole-layer path in its own forward; an autoregressive layer is a run of one)
         if len(units) < (1 if units and getattr(units[0][0], "_forward_only_run", False) else 2):
             return [], start
         geometry = _run_geometry(units)
@@ -221,7 +222,8 @@ class CompositeTransform(Transform):
         permutation changes.  (weights, biases, tables, f16 stream or None, K8x's (weights, biases, scales) or None);
         `tile16`: the mode of the f16 stream (ops.use_tile16)."""
         first = units[0][0]
-        mlp = first._run_signature()[0] in ("k11", "k22")
+        kind = first._run_signature()[0]
+        mlp = kind in ("k11", "k22", "k29")
         geometry = _run_geometry(units)   # one padded geometry for the run
         engine = None if mlp else first._whole_layer_engine(geometry)   # "k8x", "k8h" (the two-piece family) or "k8"
         f16, x3 = engine == "k8h", engine == "k8x"
@@ -232,7 +234,9 @@ class CompositeTransform(Transform):
             ids = tuple([id(c) for c, _ in units])
             if isinstance(units, _Run):
                 units.__dict__["_ids"] = ids
-        key = (inverse, engine, tile16, geometry, first._log2e() if not mlp else None, first.conditioner_act_scale if f16 else None,
+        # (K29's blobs depend on the bin count and on the divisor folded into them: part of the key)
+        key = (inverse, engine, tile16, geometry, first._log2e() if not mlp else first._spline_constants() if kind == "k29" else None,
+               first.conditioner_act_scale if f16 else None,
                ids, _run_weights_fingerprint(units),
                tuple([None if p is None else _permutation_key(p) for _, p in units]))
         cache = self.__dict__.setdefault("_run_plans", {})
@@ -280,6 +284,13 @@ class CompositeTransform(Transform):
             head = ops.affine_flow_made(
                 inputs, weights, biases, tables, first.features, hidden_linears, context, total, num_layers=len(units),
                 standard_normal_log_prob=standard_normal_log_prob, pad=(geometry[0], geometry[3]),
+                residual_blocks=residual_blocks)
+        elif first._run_signature()[0] == "k29":
+            weights, biases, tables, _, _ = self._run_plan(units, inverse)
+            hidden_linears, residual_blocks = first._conditioner_shape()
+            head = ops.rqs_flow_made(
+                inputs, weights, biases, tables, first.features, hidden_linears, first._density_spec(), context, total,
+                num_layers=len(units), standard_normal_log_prob=standard_normal_log_prob, pad=(geometry[0], geometry[3]),
                 residual_blocks=residual_blocks)
         elif first._run_signature()[0] == "k11":
             weights, biases, tables, _, _ = self._run_plan(units, inverse)
