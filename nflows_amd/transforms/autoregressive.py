@@ -16,7 +16,7 @@ from .. import _cache
 from .. import _native as N
 from .. import ops
 from . import made as made_module
-from .base import Transform
+from .base import RUN_SWITCHES, RunLayer, Transform, _Run, _run_plan
 from .splines import rational_quadratic
 from . import splines
 from ..utils import torchutils
@@ -34,16 +34,40 @@ class _LazyRows:
         return self._value[index]
 
 
-def _own_run_plan(layer):
-    """(weights, biases, tables) of a layer as a run of one (K22, K29): the run planner's own packing and tables
-    (`CompositeTransform._run_plan`), with the layer standing in for the composite -- the planner keeps its plan cache in
-    the `__dict__` of whatever it is given and reads nothing else of it -- so that a layer called on its own and the same
-    layer inside a composite are served from one code path."""
-    from .base import CompositeTransform, _Run
+def _own_run_plan(layer, tile16=0):
+    """The plan of a layer as a run of one (K22, K29): the run planner's own packing and tables (`base._run_plan`), kept in
+    the layer's own `__dict__`, so that a layer called on its own and the same layer inside a composite are served from one
+    code path."""
     run = layer.__dict__.get("_own_run")
     if run is None:
         run = layer.__dict__["_own_run"] = _Run([(layer, None)])
-    return CompositeTransform._run_plan(layer, run, False)[:3]
+    return _run_plan(layer, run, False, tile16)
+
+
+def _device_rows(inputs):
+    """A 2-D float32 device tensor with at least one row: what every kernel of this module takes."""
+    return (torch.is_tensor(inputs) and inputs.dim() == 2 and inputs.dtype == torch.float32 and inputs.is_cuda
+            and inputs.shape[0] >= 1)
+
+
+def _context_served(context, context_features, rows=None):
+    """None for a net without a context layer, or a 2-D float32 device tensor of the net's width -- and of `rows` rows
+    where the caller gives them."""
+    if context is None:
+        return context_features == 0
+    return (context_features > 0 and torch.is_tensor(context) and context.dim() == 2 and context.dtype == torch.float32
+            and context.is_cuda and context.shape[1] == context_features and (rows is None or context.shape[0] == rows))
+
+
+def _relu_without_active_dropout(net):
+    """The MADE's activations and dropouts are plain attributes: read on every call."""
+    relu = (F.relu, torch.relu)
+    return net.__dict__.get("activation") in relu and all(
+        b.__dict__.get("activation") in relu and (not b.dropout.training or b.dropout.p == 0.0) for b in net.blocks)
+
+
+def _has_batch_norm(net):
+    return any(isinstance(m, torch.nn.BatchNorm1d) for m in net.modules())
 
 
 class AutoregressiveTransform(Transform):
@@ -181,7 +205,125 @@ class AutoregressiveTransform(Transform):
         raise NotImplementedError()
 
 
-class MaskedAffineAutoregressiveTransform(AutoregressiveTransform):
+class _MadeKernelLayer(AutoregressiveTransform, RunLayer):
+    """What MaskedAffineAutoregressiveTransform and MaskedPiecewiseRationalQuadraticAutoregressiveTransform share: the
+    kernels that run the layer's MADE themselves and their gates.  The density pass of a run of such layers is one launch
+    (K22 / K29: the run protocol of transforms/base.py, `RunLayer`; a layer called on its own is a run of one), the steps
+    of the inverse are one persistent kernel (K23 / K28).  Where the two layers' gates differ the subclass says so, in a
+    class attribute or an override beside its kernel."""
+
+    unconditional_transform = None
+    _forward_only_run = True
+    _KIND = None                     # the family of the density kernel
+    _HOOKS = ()                      # the functions the density kernel stands for
+    _FLOAT32_WEIGHTS_ONLY = False    # the structural reads ask for a MADE in float32
+    _COLUMNS_RECOUNTED = False       # `_all_columns` compares the held table's length with `features` on every call
+
+    def _overridden(self, hooks, library):
+        """True when a subclass (or an assignment to the class or the instance) replaced one of `hooks`, the functions a
+        kernel of the class `library` stands for: such a layer runs the host's sequence with the user's function."""
+        cls = type(self)
+        return any(h in self.__dict__ or getattr(cls, h) is not getattr(library, h) for h in hooks)
+
+    def _conditioner(self):
+        return self._modules["autoregressive_net"]
+
+    def _context_features(self):
+        net = self._conditioner()
+        return net.context_layer.weight.shape[1] if hasattr(net, "context_layer") else 0
+
+    def _conditioner_shape(self):
+        """What `_served_shape` makes of a MADE the density kernel runs inside the layer kernel -- plain MADE, hidden width
+        <= 128, at most 64 context features, no batch norm --, or None.  Read once per cache epoch; the activations and the
+        dropouts are plain attributes and are read on every call."""
+        net = self._conditioner()
+
+        def read():
+            if type(net) is made_module.MADE and (not self._FLOAT32_WEIGHTS_ONLY
+                                                  or net.initial_layer.weight.dtype == torch.float32):
+                hidden, features = net.initial_layer.weight.shape
+                if hidden <= 128 and self._context_features() <= 64 and not _has_batch_norm(net):
+                    residual = bool(net.use_residual_blocks)
+                    return self._served_shape(len(net.blocks) * (2 if residual else 1), residual, features,
+                                              net.final_layer.weight.shape[0])
+            return None
+        shape = _cache.keyed(self, "_conditioner_shape_held", (_cache.epoch(), net), read)
+        return shape if shape is not None and _relu_without_active_dropout(net) else None
+
+    def _density_kernel_on(self):
+        return self.fuse_conditioner
+
+    def _run_kind(self, context):
+        if not self._density_kernel_on() or torch.is_grad_enabled() or self._conditioner_shape() is None:
+            return None
+        return self._KIND if _context_served(context, self._context_features()) else None
+
+    def _run_signature(self):
+        return (self._KIND, self.features, self._conditioner_shape(), self._context_features()) + self._run_variant()
+
+    def _fused_geometry(self, others=()):
+        """(padded features, transformed features, identity features, pad value): the row length in multiples of four,
+        the pad columns pass through; every feature is both read by the conditioner and transformed."""
+        features = self.features
+        return (features + 3) // 4 * 4, features, features, 0.0
+
+    def _all_columns(self):
+        dev = self._conditioner().initial_layer.weight.device
+        held = self.__dict__.get("_columns_held")
+        if held is None or held.device != dev or (self._COLUMNS_RECOUNTED and held.numel() != self.features):
+            held = self.__dict__["_columns_held"] = torch.arange(self.features, device=dev)
+        return held
+
+    transform_features = property(_all_columns)   # (what the planner writes into the two halves of the layer's table)
+    identity_features = property(_all_columns)
+
+    def forward(self, inputs, context=None):
+        if (_device_rows(inputs) and not self._user_hooks and self._run_kind(context) is not None
+                and inputs.shape[1] == self.features and self._own_call_served(inputs, context)):
+            fused = self._whole_layer(inputs, context)   # a run of one
+            if fused is not None:
+                return fused
+        return self._forward_layer_by_layer(inputs, context)
+
+    def _own_call_served(self, inputs, context):
+        """What the layer's own `forward` asks of a call beyond the planner's questions."""
+        return True
+
+    def _whole_layer(self, inputs, context):
+        return self._launch_run(lambda tile16=0: _own_run_plan(self, tile16), 1, self._fused_geometry(), inputs, context,
+                                False, None, False)
+
+    def _forward_layer_by_layer(self, inputs, context=None):
+        return AutoregressiveTransform.forward(self, inputs, context)
+
+    # ---- the persistent kernels of the inverse (K23, K28: csrc/made_inverse.hip)
+    def _step_kernel_net(self, slot, served=lambda net: True):
+        """The MADE when a persistent inverse kernel can run it -- plain MADE, ReLU, no batch norm, no active dropout, at most
+        12 Linears, and what `served(net)` adds --, else None.  The structure is read once per cache epoch (kept in `slot`);
+        activations and dropouts are plain attributes, read per call."""
+        net = self._conditioner()
+        if not _cache.keyed(self, slot, (_cache.epoch(), net), lambda: (
+                type(net) is made_module.MADE and len(ops._made_linears(net)) <= ops.MADE_MAX_LINEARS
+                and (not self._FLOAT32_WEIGHTS_ONLY or net.initial_layer.weight.dtype == torch.float32)
+                and not _has_batch_norm(net) and served(net))):
+            return None
+        return net if _relu_without_active_dropout(net) else None
+
+    def _step_kernel_plan(self, slot, key, net, steps, multiplier):
+        """(step blocks of `ops.pack_made_schedule` or None where the shape does not fit the LDS, packed context Linears or
+        None), kept in `slot` under `key` -- made of `_cache.weights_key`: until a parameter, a mask or a write through
+        `.data` changes."""
+        def pack():
+            hidden = net.initial_layer.weight.shape[0]
+            linears = len(ops._made_linears(net))
+            vectors = len(ops.made_context_layers(net))
+            cap = ops.made_block_cap(steps, hidden, linears, vectors)
+            schedule = ops.pack_made_schedule(net, steps, multiplier, block_cap=cap, context=True) if cap > 0 else None
+            return schedule, ops.pack_made_context(net) if schedule else None
+        return _cache.keyed(self, slot, key, pack)
+
+
+class MaskedAffineAutoregressiveTransform(_MadeKernelLayer):
     """MAF layer: y_d = softplus(u_d)+1e-3) * x_d + shift_d with (u, shift) = MADE(x)
     (autoregressive.py:64-128); parameters interleaved [B, D, 2]."""
 
@@ -206,99 +348,25 @@ class MaskedAffineAutoregressiveTransform(AutoregressiveTransform):
 
     # ---- whole-layer kernel K22 (csrc/affine_made.hip): the MADE inside the layer kernel, runs of such layers in one
     #      launch.  The density pass only -- the inverse is sequential in the features and keeps its column-wise loop.
-    #      What follows is the protocol the run planner reads (transforms/base.py), as the coupling layers have it.
     fuse_conditioner = os.environ.get("NFA_K22", "1") != "0"   # class-level switch for A/B measurements
-    unconditional_transform = None
-    _forward_only_run = True
+    _KIND = "k22"
     _HOOKS = ("forward", "_elementwise_forward", "_elementwise_inverse", "_output_dim_multiplier")
+    _user_hooks = property(lambda self: self._overridden(self._HOOKS, MaskedAffineAutoregressiveTransform))
 
-    @property
-    def _user_hooks(self):
-        """True when a subclass (or an assignment to the class or the instance) replaced one of the functions the
-        kernel stands for: such a layer runs the sequence above with the user's function."""
-        cls = type(self)
-        return any(h in self.__dict__ or getattr(cls, h) is not getattr(MaskedAffineAutoregressiveTransform, h)
-                   for h in self._HOOKS)
+    def _served_shape(self, hidden_linears, residual, features, rows):
+        """(hidden Linears, residual blocks?) of a MADE of the layer's width, at most 64 features, two rows per feature"""
+        return (hidden_linears, residual) if features == self.features <= 64 and rows == 2 * features else None
 
-    def _conditioner(self):
-        return self._modules["autoregressive_net"]
-
-    def _conditioner_shape(self):
-        """(hidden Linears, residual blocks?) of a MADE that K22 runs inside the layer kernel -- plain MADE, hidden width
-        <= 128, at most 64 features and 64 context features, no batch norm --, or None.  Read once per cache epoch;
-        the activations and the dropouts are plain attributes and are read on every call."""
-        net = self._conditioner()
-
-        def read():
-            if type(net) is made_module.MADE and self.features <= 64:
-                hidden, features = net.initial_layer.weight.shape
-                ce = net.context_layer.weight.shape[1] if hasattr(net, "context_layer") else 0
-                if (hidden <= 128 and features == self.features and ce <= 64
-                        and net.final_layer.weight.shape[0] == 2 * features
-                        and not any(isinstance(m, torch.nn.BatchNorm1d) for m in net.modules())):
-                    residual = bool(net.use_residual_blocks)
-                    return len(net.blocks) * (2 if residual else 1), residual
-            return None
-        shape = _cache.keyed(self, "_conditioner_shape_held", (_cache.epoch(), net), read)
-        if shape is not None:
-            relu = (F.relu, torch.relu)
-            if net.__dict__.get("activation") not in relu or not all(
-                    b.__dict__.get("activation") in relu and (not b.dropout.training or b.dropout.p == 0.0)
-                    for b in net.blocks):
-                return None
-        return shape
-
-    def _context_features(self):
-        net = self._conditioner()
-        return net.context_layer.weight.shape[1] if hasattr(net, "context_layer") else 0
-
-    def _run_kind(self, context):
-        if not self.fuse_conditioner or torch.is_grad_enabled() or self._conditioner_shape() is None:
-            return None
-        ce = self._context_features()
-        if context is None:
-            return "k22" if ce == 0 else None
-        ok = (ce > 0 and torch.is_tensor(context) and context.dim() == 2 and context.dtype == torch.float32
-              and context.is_cuda and context.shape[1] == ce)
-        return "k22" if ok else None
-
-    def _fused_geometry(self, others=()):
-        """(padded features, transformed features, identity features, pad value): the row length in multiples of four,
-        the pad columns pass through; every feature is both read by the conditioner and transformed."""
-        return (self.features + 3) // 4 * 4, self.features, self.features, 0.0
-
-    def _run_signature(self):
-        return ("k22", self.features, self._conditioner_shape(), self._context_features())
-
-    def _all_columns(self):
-        dev = self._conditioner().initial_layer.weight.device
-        held = self.__dict__.get("_columns_held")
-        if held is None or held.device != dev:
-            held = self.__dict__["_columns_held"] = torch.arange(self.features, device=dev)
-        return held
-
-    transform_features = property(_all_columns)   # (what the planner writes into the two halves of the layer's table)
-    identity_features = property(_all_columns)
-
-    def _packed_mlp(self):
+    def _run_packed(self, geometry=None):
         net = self._conditioner()
         key = _cache.weights_key(self, net)   # (parameters and buffers: the masks are part of the key)
         return _cache.keyed(self, "_packed_made_cache", key, lambda: ops.pack_made_conditioner(net))
 
-    def forward(self, inputs, context=None):
-        if (torch.is_tensor(inputs) and inputs.dim() == 2 and inputs.dtype == torch.float32 and inputs.is_cuda
-                and inputs.shape[0] >= 1 and inputs.shape[1] == self.features and not self._user_hooks
-                and self._run_kind(context) is not None):
-            fused = self._whole_layer(inputs, context)   # a run of one
-            if fused is not None:
-                return fused
-        return super().forward(inputs, context)
-
-    def _whole_layer(self, inputs, context):
-        weights, biases, tables = _own_run_plan(self)
+    def _launch_run(self, plan, num_layers, geometry, inputs, context, inverse, accumulate_into, standard_normal_log_prob):
+        weights, biases, tables = plan()[:3]
         hidden_linears, residual_blocks = self._conditioner_shape()
-        geometry = self._fused_geometry()
-        return ops.affine_flow_made(inputs, weights, biases, tables, self.features, hidden_linears, context,
+        return ops.affine_flow_made(inputs, weights, biases, tables, self.features, hidden_linears, context, accumulate_into,
+                                    num_layers=num_layers, standard_normal_log_prob=standard_normal_log_prob,
                                     pad=(geometry[0], geometry[3]), residual_blocks=residual_blocks)
 
     def _elementwise_inverse(self, inputs, autoregressive_params):
@@ -324,57 +392,33 @@ class MaskedAffineAutoregressiveTransform(AutoregressiveTransform):
         return not (self.features <= few and rows > many)
 
     def _inverse_kernel_net(self):
-        """The MADE when K23 can run it -- plain MADE, ReLU, no batch norm, no active dropout, at most 12 Linears --, else
-        None.  The structure is read once per cache epoch; activations and dropouts are plain attributes, read per call."""
-        net = self._conditioner()
-        if not _cache.keyed(self, "_inverse_net_held", (_cache.epoch(), net), lambda: (
-                type(net) is made_module.MADE and self.features >= 2
-                and net.initial_layer.weight.shape[1] == self.features
-                and net.final_layer.weight.shape[0] == 2 * self.features
-                and len(ops._made_linears(net)) <= ops.MADE_MAX_LINEARS
-                and not any(isinstance(m, torch.nn.BatchNorm1d) for m in net.modules()))):
-            return None
-        relu = (F.relu, torch.relu)
-        if net.__dict__.get("activation") not in relu or not all(
-                b.__dict__.get("activation") in relu and (not b.dropout.training or b.dropout.p == 0.0) for b in net.blocks):
-            return None
-        return net
+        """The MADE when K23 can run it (`_step_kernel_net`): of the layer's width, at least two features, two rows each"""
+        return self._step_kernel_net("_inverse_net_held", lambda net: (
+            self.features >= 2 and net.initial_layer.weight.shape[1] == self.features
+            and net.final_layer.weight.shape[0] == 2 * self.features))
 
     def _inverse_kernel_plan(self, net):
-        """(step blocks of `ops.pack_made_schedule` or None where the shape does not fit the LDS, packed context Linears
-        or None), kept until a parameter, a mask or a write through `.data` changes (`_cache.weights_key`)."""
-        def pack():
-            hidden = net.initial_layer.weight.shape[0]
-            linears = len(ops._made_linears(net))
-            vectors = len(ops.made_context_layers(net))
-            cap = ops.made_block_cap(self.features, hidden, linears, vectors)
-            schedule = ops.pack_made_schedule(net, self.features, 2, block_cap=cap, context=True) if cap > 0 else None
-            return schedule, ops.pack_made_context(net) if schedule else None
-        return _cache.keyed(self, "_made_affine_cache", _cache.weights_key(self, net), pack)
+        return self._step_kernel_plan("_made_affine_cache", _cache.weights_key(self, net), net, self.features, 2)
 
     def inverse(self, inputs, context=None):
-        cls = type(self)
-        if (self.fuse_sequential_inverse and not torch.is_grad_enabled() and torch.is_tensor(inputs) and inputs.dim() == 2
-                and inputs.dtype == torch.float32 and inputs.is_cuda and inputs.shape[0] >= 1
+        if (self.fuse_sequential_inverse and not torch.is_grad_enabled() and _device_rows(inputs)
                 and inputs.shape[1] == self.features and self._inverse_kernel_serves_rows(inputs.shape[0])
-                and not any(h in self.__dict__ or getattr(cls, h) is not getattr(MaskedAffineAutoregressiveTransform, h)
-                            for h in self._INVERSE_HOOKS)):
+                and not self._overridden(self._INVERSE_HOOKS, MaskedAffineAutoregressiveTransform)):
             net = self._inverse_kernel_net()
-            ce = self._context_features() if net is not None else 0
-            if net is not None and (
-                    (context is None and ce == 0)
-                    or (ce > 0 and torch.is_tensor(context) and context.dim() == 2 and context.dtype == torch.float32
-                        and context.is_cuda and context.shape == (inputs.shape[0], ce))):
+            if net is not None and _context_served(context, self._context_features(), inputs.shape[0]):
                 schedule, packed_context = self._inverse_kernel_plan(net)
                 if schedule is not None:
-                    terms = ops.made_context_terms(context, packed_context) if ce else None
+                    terms = ops.made_context_terms(context, packed_context) if context is not None else None
                     fused = ops.made_affine_inverse(inputs, schedule, net.initial_layer.weight.shape[0], terms)
                     if fused is not None:
                         return fused
         return super().inverse(inputs, context)
 
 
-class MaskedPiecewiseRationalQuadraticAutoregressiveTransform(AutoregressiveTransform):
+RUN_SWITCHES.append((MaskedAffineAutoregressiveTransform, ("fuse_conditioner",)))
+
+
+class MaskedPiecewiseRationalQuadraticAutoregressiveTransform(_MadeKernelLayer):
     """Autoregressive neural spline layer (autoregressive.py:404-495): per feature 3K-1 / 3K+1
     logits from MADE, the RQ functional elementwise, logabsdet summed per sample.  Runs as the
     fused coupling kernel with every feature transformed (d_t = D)."""
@@ -407,17 +451,23 @@ class MaskedPiecewiseRationalQuadraticAutoregressiveTransform(AutoregressiveTran
             return self.num_bins * 3 + 1
         raise ValueError
 
+    def _wh_divisor(self):
+        net = self.autoregressive_net
+        return float(np.sqrt(net.hidden_features)) if hasattr(net, "hidden_features") else 0.0
+
+    def _rqs_spec(self):
+        """The spline's constants as every kernel of the layer takes them."""
+        return ops.make_rqs_spec(self.num_bins, self.tails, tail_bound=self.tail_bound,
+                                 min_bin_width=self.min_bin_width, min_bin_height=self.min_bin_height,
+                                 min_derivative=self.min_derivative, wh_divisor=self._wh_divisor())
+
+    _density_spec = _rqs_spec
+
     def _elementwise(self, inputs, autoregressive_params, inverse=False):
         N.require_device_f32("inputs", inputs, 2)
         batch, features = inputs.shape
-        divisor = 0.0
-        if hasattr(self.autoregressive_net, "hidden_features"):
-            divisor = float(np.sqrt(self.autoregressive_net.hidden_features))
         if self.tails not in (None, "linear"):
             raise ValueError
-        spec = ops.make_rqs_spec(self.num_bins, self.tails, tail_bound=self.tail_bound,
-                                 min_bin_width=self.min_bin_width, min_bin_height=self.min_bin_height,
-                                 min_derivative=self.min_derivative, wh_divisor=divisor)
         cache = self._all_features if isinstance(self._all_features, dict) else {}
         cols = cache.get((features, inputs.device))
         if cols is None:
@@ -425,7 +475,7 @@ class MaskedPiecewiseRationalQuadraticAutoregressiveTransform(AutoregressiveTran
             cache[(features, inputs.device)] = cols
             self._all_features = cache
         params = autoregressive_params.reshape(batch, features * self._output_dim_multiplier())
-        return ops.rqs_coupling(inputs, params, cols, spec, inverse=inverse)
+        return ops.rqs_coupling(inputs, params, cols, self._rqs_spec(), inverse=inverse)
 
     def _elementwise_forward(self, inputs, autoregressive_params):
         return self._elementwise(inputs, autoregressive_params)
@@ -437,10 +487,6 @@ class MaskedPiecewiseRationalQuadraticAutoregressiveTransform(AutoregressiveTran
     # last pass of the inverse never form the [batch, features * multiplier] parameter tensor
     fuse_output_layer = os.environ.get("NFA_K13", "1") != "0"
 
-    def _wh_divisor(self):
-        net = self.autoregressive_net
-        return float(np.sqrt(net.hidden_features)) if hasattr(net, "hidden_features") else 0.0
-
     def _output_layer_kernel(self, inputs, hidden, first_feature, inverse, out=None):
         """(outputs with the columns from `first_feature` on written, their logabsdet) from K13, or None."""
         net = self.autoregressive_net
@@ -451,23 +497,15 @@ class MaskedPiecewiseRationalQuadraticAutoregressiveTransform(AutoregressiveTran
             return None
         final = net.final_layer
         key = (_cache.epoch(), first_feature) + tuple((t.data_ptr(), t._version) for t in (final.weight, final.bias, final.mask))
-        cache = self.__dict__.setdefault("_made_output_cache", {})
-        packed = cache.get(first_feature)
-        if packed is None or packed[0] != key:
-            if len(cache) > 4:
-                cache.clear()
-            packed = (key, ops.pack_made_output(net, self._output_dim_multiplier(), first_feature))
-            cache[first_feature] = packed
-        spec = ops.make_rqs_spec(self.num_bins, self.tails, tail_bound=self.tail_bound,
-                                 min_bin_width=self.min_bin_width, min_bin_height=self.min_bin_height,
-                                 min_derivative=self.min_derivative, wh_divisor=self._wh_divisor())
-        return ops.made_output_spline(inputs, hidden, packed[1], spec, first_column=first_feature, inverse=inverse,
+        # (one slot per first feature: 0 for the density pass, the number of sequential steps for the inverse's tail)
+        packed = _cache.keyed(self, "_made_output_cache_%d" % first_feature, key,
+                              lambda: ops.pack_made_output(net, self._output_dim_multiplier(), first_feature))
+        return ops.made_output_spline(inputs, hidden, packed, self._rqs_spec(), first_column=first_feature, inverse=inverse,
                                       out=out)
 
     # ---- whole-layer kernel K29 (csrc/made_rqs.hip): the MADE and the spline inside one layer kernel, runs of such
     #      layers -- their permutations and the base density included -- in one launch.  The density pass only: the inverse
-    #      keeps K12 / K28, K13's tail and the host loop.  What follows is the protocol the run planner reads
-    #      (transforms/base.py), as MaskedAffineAutoregressiveTransform has it for K22.
+    #      keeps K12 / K28, K13's tail and the host loop.
     #      The switch (NFA_K29): "0" off; "2" serves 8 bins as well; anything else, unset and empty included, is the default 1:
     #      every bin count from 2 to 16 except 8, whose calls keep hidden GEMMs + K13 (existing tests pin that path; the 8-bin
     #      columns of profiles/ar_spline_density_time.json are recorded for a later change of that default).
@@ -475,120 +513,55 @@ class MaskedPiecewiseRationalQuadraticAutoregressiveTransform(AutoregressiveTran
     #      context, 1 024 / 16 384 / 262 144 rows, 5-16 layers on 8-64 features) the one launch is 1.5-4.7 x faster per call
     #      than the layer-by-layer path, none slower.
     fuse_conditioner = {"0": 0, "2": 2}.get(os.environ.get("NFA_K29", "1").strip(), 1)
-    unconditional_transform = None
-    _forward_only_run = True
+    _KIND = "k29"
     _HOOKS = ("forward", "_elementwise", "_elementwise_forward", "_output_dim_multiplier")
-
-    @property
-    def _user_hooks(self):
-        """True when a subclass (or an assignment to the class or the instance) replaced one of the functions the
-        kernel stands for: such a layer runs the sequence below with the user's function."""
-        cls = type(self)
-        return any(h in self.__dict__
-                   or getattr(cls, h) is not getattr(MaskedPiecewiseRationalQuadraticAutoregressiveTransform, h)
-                   for h in self._HOOKS)
-
-    def _conditioner(self):
-        return self._modules["autoregressive_net"]
+    _user_hooks = property(lambda self: self._overridden(self._HOOKS, MaskedPiecewiseRationalQuadraticAutoregressiveTransform))
+    _FLOAT32_WEIGHTS_ONLY = True
+    _COLUMNS_RECOUNTED = True    # (`features` is read off the net)
 
     @property
     def features(self):
         """Width of the rows the layer takes (the planner compares it with the input's)."""
         return self._conditioner().initial_layer.weight.shape[1]
 
-    def _conditioner_shape(self):
-        """(hidden Linears, residual blocks?) of a MADE that K29 runs inside the layer kernel -- plain MADE in float32, hidden
-        width <= 128, at most 64 features and 64 context features, 3 K - 1 rows per feature, no batch norm --, or None.  Read
-        once per cache epoch; the activations and the dropouts are plain attributes and are read on every call."""
-        net = self._conditioner()
+    def _served_shape(self, hidden_linears, residual, features, rows):
+        return (hidden_linears, residual, rows // features) if 1 <= features <= 64 else None
 
-        def read():
-            if type(net) is made_module.MADE and net.initial_layer.weight.dtype == torch.float32:
-                hidden, features = net.initial_layer.weight.shape
-                ce = net.context_layer.weight.shape[1] if hasattr(net, "context_layer") else 0
-                if (hidden <= 128 and 1 <= features <= 64 and ce <= 64
-                        and not any(isinstance(m, torch.nn.BatchNorm1d) for m in net.modules())):
-                    residual = bool(net.use_residual_blocks)
-                    return len(net.blocks) * (2 if residual else 1), residual, net.final_layer.weight.shape[0] // features
-            return None
-        shape = _cache.keyed(self, "_conditioner_shape_held", (_cache.epoch(), net), read)
+    def _conditioner_shape(self):
+        """(hidden Linears, residual blocks?) of a MADE that K29 runs inside the layer kernel: in float32, at most 64
+        features, 3 K - 1 rows per feature (read per call, as the tails are)."""
+        shape = super()._conditioner_shape()
         if shape is None or self.tails != "linear" or shape[2] != 3 * self.num_bins - 1:
-            return None
-        relu = (F.relu, torch.relu)
-        if net.__dict__.get("activation") not in relu or not all(
-                b.__dict__.get("activation") in relu and (not b.dropout.training or b.dropout.p == 0.0)
-                for b in net.blocks):
             return None
         return shape[:2]
 
-    def _context_features(self):
-        net = self._conditioner()
-        return net.context_layer.weight.shape[1] if hasattr(net, "context_layer") else 0
-
-    def _density_kernel_serves_bins(self):
+    def _density_kernel_on(self):
         mode = self.fuse_conditioner
         return bool(mode) and 2 <= self.num_bins <= 16 and (self.num_bins != 8 or int(mode) >= 2)
-
-    def _run_kind(self, context):
-        if (not self._density_kernel_serves_bins() or torch.is_grad_enabled() or self._conditioner_shape() is None):
-            return None
-        ce = self._context_features()
-        if context is None:
-            return "k29" if ce == 0 else None
-        ok = (ce > 0 and torch.is_tensor(context) and context.dim() == 2 and context.dtype == torch.float32
-              and context.is_cuda and context.shape[1] == ce)
-        return "k29" if ok else None
-
-    def _fused_geometry(self, others=()):
-        """(padded features, transformed features, identity features, pad value): the row length in multiples of four,
-        the pad columns pass through; every feature is both read by the conditioner and transformed."""
-        features = self.features
-        return (features + 3) // 4 * 4, features, features, 0.0
 
     def _spline_constants(self):
         return (self.num_bins, float(self.tail_bound), float(self.min_bin_width), float(self.min_bin_height),
                 float(self.min_derivative), self._wh_divisor())
 
-    def _run_signature(self):
-        return ("k29", self.features, self._conditioner_shape(), self._context_features(), self._spline_constants())
+    def _run_variant(self, geometry=None, tile16=0):
+        # (K29's blobs depend on the bin count and on the divisor folded into them: part of the plan's key and the signature)
+        return (self._spline_constants(),)
 
-    def _all_columns(self):
-        dev = self._conditioner().initial_layer.weight.device
-        held = self.__dict__.get("_columns_held")
-        if held is None or held.device != dev or held.numel() != self.features:
-            held = self.__dict__["_columns_held"] = torch.arange(self.features, device=dev)
-        return held
-
-    transform_features = property(_all_columns)   # (what the planner writes into the two halves of the layer's table)
-    identity_features = property(_all_columns)
-
-    def _packed_mlp(self):
+    def _run_packed(self, geometry=None):
         net = self._conditioner()
         # (parameters and buffers: the masks are part of the key; the divisor is an attribute of the net)
         key = (_cache.weights_key(self, net), self.num_bins, self._wh_divisor())
         return _cache.keyed(self, "_packed_made_rqs_cache", key, lambda: ops.pack_made_rqs_conditioner(net, self.num_bins))
 
-    def _density_spec(self):
-        return ops.make_rqs_spec(self.num_bins, self.tails, tail_bound=self.tail_bound,
-                                 min_bin_width=self.min_bin_width, min_bin_height=self.min_bin_height,
-                                 min_derivative=self.min_derivative, wh_divisor=self._wh_divisor())
-
-    def _whole_layer(self, inputs, context):
-        weights, biases, tables = _own_run_plan(self)
+    def _launch_run(self, plan, num_layers, geometry, inputs, context, inverse, accumulate_into, standard_normal_log_prob):
+        weights, biases, tables = plan()[:3]
         hidden_linears, residual_blocks = self._conditioner_shape()
-        geometry = self._fused_geometry()
-        return ops.rqs_flow_made(inputs, weights, biases, tables, self.features, hidden_linears, self._density_spec(),
-                                 context, pad=(geometry[0], geometry[3]), residual_blocks=residual_blocks)
+        return ops.rqs_flow_made(inputs, weights, biases, tables, self.features, hidden_linears, self._rqs_spec(), context,
+                                 accumulate_into, num_layers=num_layers, standard_normal_log_prob=standard_normal_log_prob,
+                                 pad=(geometry[0], geometry[3]), residual_blocks=residual_blocks)
 
-    def forward(self, inputs, context=None):
-        if (torch.is_tensor(inputs) and inputs.dim() == 2 and inputs.dtype == torch.float32 and inputs.is_cuda
-                and inputs.shape[0] >= 1 and not self._user_hooks and self._run_kind(context) is not None
-                and inputs.shape[1] == self.features
-                and (context is None or context.shape[0] == inputs.shape[0])):
-            fused = self._whole_layer(inputs, context)   # a run of one
-            if fused is not None:
-                return fused
-        return self._forward_layer_by_layer(inputs, context)
+    def _own_call_served(self, inputs, context):
+        return context is None or context.shape[0] == inputs.shape[0]
 
     def _forward_layer_by_layer(self, inputs, context=None):
         net = self.autoregressive_net
@@ -623,12 +596,8 @@ class MaskedPiecewiseRationalQuadraticAutoregressiveTransform(AutoregressiveTran
         key = (_cache.epoch(), sequential) + tuple((p.data_ptr(), p._version) for p in net.parameters())
         schedule = _cache.keyed(self, "_made_schedule_cache", key,
                                 lambda: ops.pack_made_schedule(net, sequential, self._output_dim_multiplier()))
-        spec = ops.make_rqs_spec(self.num_bins, self.tails, tail_bound=self.tail_bound,
-                                 min_bin_width=self.min_bin_width, min_bin_height=self.min_bin_height,
-                                 min_derivative=self.min_derivative,
-                                 wh_divisor=float(np.sqrt(net.hidden_features)) if hasattr(net, "hidden_features") else 0.0)
         hidden_features = net.initial_layer.weight.shape[0]
-        return ops.made_rqs_inverse(inputs, schedule, hidden_features, sequential, spec)
+        return ops.made_rqs_inverse(inputs, schedule, hidden_features, sequential, self._rqs_spec())
 
     # ---- persistent kernel K28 (csrc/made_inverse.hip): the RQ element in K23's loop -- a context, 2 .. 16 bins, steps cut
     #      into continuation blocks -- for what K12 does not serve.  `fuse_sequential_inverse` (NFA_K12) switches both
@@ -648,63 +617,35 @@ class MaskedPiecewiseRationalQuadraticAutoregressiveTransform(AutoregressiveTran
         return limit is None or not (features <= limit[0] and rows > limit[1])
 
     def _sequential_ctx_net(self):
-        """The MADE when K28 can run it -- plain MADE, ReLU, no batch norm, no active dropout, at most 12 Linears --, else
-        None.  The structure is read once per cache epoch; activations and dropouts are plain attributes, read per call."""
-        net = self._modules["autoregressive_net"]
-        if not _cache.keyed(self, "_sequential_ctx_net_held", (_cache.epoch(), net), lambda: (
-                type(net) is made_module.MADE and len(ops._made_linears(net)) <= ops.MADE_MAX_LINEARS
-                and net.initial_layer.weight.dtype == torch.float32
-                and not any(isinstance(m, torch.nn.BatchNorm1d) for m in net.modules()))):
-            return None
-        relu = (F.relu, torch.relu)
-        if net.__dict__.get("activation") not in relu or not all(
-                b.__dict__.get("activation") in relu and (not b.dropout.training or b.dropout.p == 0.0) for b in net.blocks):
-            return None
-        return net
+        """The MADE when K28 can run it (`_step_kernel_net`: in float32), else None."""
+        return self._step_kernel_net("_sequential_ctx_net_held")
 
     def _sequential_ctx_plan(self, net, sequential):
-        """(step blocks of `ops.pack_made_schedule` or None where the shape does not fit the LDS, packed context Linears or
-        None), kept until a parameter, a mask or a write through `.data` changes (`_cache.weights_key`)."""
-        def pack():
-            hidden = net.initial_layer.weight.shape[0]
-            linears = len(ops._made_linears(net))
-            vectors = len(ops.made_context_layers(net))
-            cap = ops.made_block_cap(sequential, hidden, linears, vectors)
-            schedule = ops.pack_made_schedule(net, sequential, self._output_dim_multiplier(), block_cap=cap, context=True) \
-                if cap > 0 else None
-            return schedule, ops.pack_made_context(net) if schedule else None
-        return _cache.keyed(self, "_made_schedule_ctx_cache", (_cache.weights_key(self, net), sequential), pack)
+        return self._step_kernel_plan("_made_schedule_ctx_cache", (_cache.weights_key(self, net), sequential), net,
+                                      sequential, self._output_dim_multiplier())
 
     def _sequential_kernel_ctx(self, inputs, context, sequential):
-        cls = type(self)
         if not (self.fuse_sequential_inverse_ctx and self.tails == "linear" and 2 <= self.num_bins <= 16
-                and torch.is_tensor(inputs) and inputs.dim() == 2 and inputs.dtype == torch.float32 and inputs.is_cuda
-                and inputs.shape[0] >= 1 and self._sequential_ctx_serves_rows(inputs.shape[1], inputs.shape[0])
-                and not any(h in self.__dict__
-                            or getattr(cls, h) is not getattr(MaskedPiecewiseRationalQuadraticAutoregressiveTransform, h)
-                            for h in self._SEQUENTIAL_HOOKS)):
+                and _device_rows(inputs) and self._sequential_ctx_serves_rows(inputs.shape[1], inputs.shape[0])
+                and not self._overridden(self._SEQUENTIAL_HOOKS, MaskedPiecewiseRationalQuadraticAutoregressiveTransform)):
             return None
         net = self._sequential_ctx_net()
-        if net is None or net.initial_layer.weight.shape[1] != inputs.shape[1]:
-            return None
-        ce = net.context_layer.weight.shape[1] if hasattr(net, "context_layer") else 0
-        if not ((context is None and ce == 0)
-                or (ce > 0 and torch.is_tensor(context) and context.dim() == 2 and context.dtype == torch.float32
-                    and context.is_cuda and context.shape == (inputs.shape[0], ce))):
+        if (net is None or net.initial_layer.weight.shape[1] != inputs.shape[1]
+                or not _context_served(context, self._context_features(), inputs.shape[0])):
             return None
         schedule, packed_context = self._sequential_ctx_plan(net, sequential)
         if schedule is None:
             return None
-        spec = ops.make_rqs_spec(self.num_bins, self.tails, tail_bound=self.tail_bound,
-                                 min_bin_width=self.min_bin_width, min_bin_height=self.min_bin_height,
-                                 min_derivative=self.min_derivative, wh_divisor=self._wh_divisor())
-        terms = ops.made_context_terms(context, packed_context) if ce else None
-        return ops.made_rqs_inverse_ctx(inputs, schedule, net.initial_layer.weight.shape[0], sequential, spec, terms)
+        terms = ops.made_context_terms(context, packed_context) if context is not None else None
+        return ops.made_rqs_inverse_ctx(inputs, schedule, net.initial_layer.weight.shape[0], sequential, self._rqs_spec(), terms)
 
     def _inverse_column(self, column, params):
         """One feature: params [B, P]; the spline layer kernel with a single (transformed) feature."""
         out, lad = self._elementwise(column.reshape(-1, 1), params, inverse=True)
         return out.reshape(-1), lad
+
+
+RUN_SWITCHES.append((MaskedPiecewiseRationalQuadraticAutoregressiveTransform, ("fuse_conditioner",)))
 
 
 class _SiblingSplineAutoregressiveTransform(AutoregressiveTransform):

@@ -53,15 +53,50 @@ def _accepts_fused_permutation(t, inputs):
             and inputs.dtype == torch.float32)   # (float64 flows take the generic device path; a user's hooks: the reference's sequence)
 
 
+class RunLayer:
+    """THE RUN PROTOCOL: what a layer provides so that `CompositeTransform` can hand a run of such layers -- with the
+    column permutations between them -- to one launch of a whole-layer kernel.  The planner compares no kinds and knows no
+    kernel; the first layer of a run answers for the run.  The implementers: `AffineCouplingTransform` (K11) and
+    `PiecewiseRationalQuadraticCouplingTransform` (the K8 family) in coupling.py, and the two MADE-conditioned layers (K22,
+    K29) through `_MadeKernelLayer` in autoregressive.py, which also runs a layer on its own as a run of one.
+
+    Which layers form a run (read on every call, so kept to attribute reads):
+      `_run_kind(context)`     the name of the kernel family the layer can join now (a string the planner only hands on), or None
+      `_run_signature()`       a tuple; consecutive layers with equal signatures form one run
+      `_user_hooks`, `unconditional_transform`, `features`      a layer with a user's hooks, with an unconditional
+                               transform or of another width joins no run
+      `_forward_only_run`      True: the density pass only, and a single layer is a run of one (otherwise two make a run)
+      `_conditioner()`, `fuse_conditioner`, `_fused_geometry(others)`      the conditioner whose weights the plan follows,
+                               the layer's switch (it may be set on an instance), the run's padded geometry
+      `RUN_SWITCHES`           (class, names of its class-level A/B switches) entries, one line below each class
+    The plan of a run (`_run_plan`: cached until a weight, a permutation or one of these answers changes):
+      `_run_variant(geometry, tile16)`     hashable: what of the layer's state, besides weights and geometry, the packed
+                               form depends on -- the engine and its constants; part of the plan's key
+      `_run_packed(geometry)`  the layer's (weights, biases) blobs
+      `_padded_split`          True: the tables take the geometry's padded transform / identity split
+      `transform_features`, `identity_features`      the columns written into the two halves of the layer's table
+      `_run_extras(layers, geometry, variant, tables)`     (f16 stream or None, K8x's blobs or None) of the run
+    The launch:
+      `_launch_run(plan, num_layers, geometry, inputs, context, inverse, accumulate_into, standard_normal_log_prob)`
+                               `plan(tile16=0)` is the run's plan tuple; returns what the `ops` launcher returns
+    The defaults below are those of a kernel with one packed form (K11, K22, K29)."""
+
+    _forward_only_run = False
+    _padded_split = False
+
+    def _run_variant(self, geometry=None, tile16=0):
+        return ()
+
+    def _run_extras(self, layers, geometry, variant, tables):
+        return None, None
+
+
+RUN_SWITCHES = []   # [(class, names)]: appended to where a class that implements the run protocol is defined
+
+
 def _switch_state():
     """The class-level A/B switches a run plan depends on."""
-    from .coupling import (AdditiveCouplingTransform, AffineCouplingTransform,
-                           PiecewiseRationalQuadraticCouplingTransform as RQ)
-    from .autoregressive import MaskedAffineAutoregressiveTransform as MAF
-    from .autoregressive import MaskedPiecewiseRationalQuadraticAutoregressiveTransform as ARQ
-    return (RQ.fuse_conditioner, RQ.fuse_final_linear, RQ.conditioner_engine, RQ.conditioner_act_scale,
-            RQ.resnet_log2e, AffineCouplingTransform.fuse_conditioner, AdditiveCouplingTransform.fuse_conditioner,
-            MAF.fuse_conditioner, ARQ.fuse_conditioner)
+    return tuple([getattr(cls, name) for cls, names in RUN_SWITCHES for name in names])
 
 
 def _layer_state(units):
@@ -111,6 +146,46 @@ def _run_weights_fingerprint(units):
 
 def _run_geometry(units):
     return units.geometry() if isinstance(units, _Run) else units[0][0]._fused_geometry(tuple(c for c, _ in units[1:]))
+
+
+def _run_plan(owner, units, inverse, tile16=0):
+    """Concatenated weight / bias blobs and the composed tables of a run, kept in `owner.__dict__["_run_plans"]` -- the
+    composite's, or the layer's own for a run of one -- until a weight or a permutation changes.  (weights, biases, tables,
+    f16 stream or None, K8x's (weights, biases, scales) or None); `tile16`: the mode of the f16 stream (ops.use_tile16)."""
+    first = units[0][0]
+    geometry = _run_geometry(units)   # one padded geometry for the run
+    # (the key reads version counters only; the layers' packed blobs are looked at on a miss)
+    variant = first._run_variant(geometry, tile16)
+    ids = units.__dict__.get("_ids") if isinstance(units, _Run) else None
+    if ids is None:
+        ids = tuple([id(c) for c, _ in units])
+        if isinstance(units, _Run):
+            units.__dict__["_ids"] = ids
+    key = (inverse, variant, geometry, ids, _run_weights_fingerprint(units),
+           tuple([None if p is None else _permutation_key(p) for _, p in units]))
+    cache = owner.__dict__.setdefault("_run_plans", {})
+    plan = cache.get(key)
+    if plan is None:
+        # (a composite whose layers are runs of one -- MAF layers with a BatchNorm between them -- holds one plan per
+        #  layer: with a fixed bound of 4 every call of an 8-layer flow rebuilt every plan, 0.9 ms each)
+        if len(cache) > 4 + len(getattr(owner, "_transforms", ())):
+            cache.clear()
+        if isinstance(units, _Run):
+            units.verify_before_packing()
+        packed = [c._run_packed(geometry) for c, _ in units]
+        weights = torch.cat([w for w, _ in packed], dim=0).contiguous()
+        biases = torch.cat([b for _, b in packed]).contiguous()
+        spec_layers = []
+        for c, p in units:
+            perm = None if p is None else p._permutation
+            spec_layers.append((c.transform_features, c.identity_features,
+                                None if inverse else perm, perm if inverse else None))
+        Dp, dt4, di_u, _ = geometry
+        split = first._padded_split
+        tables = ops.flow_layer_tables(first.features, spec_layers, padded_features=Dp,
+                                       padded_transform=dt4 if split else None, padded_identity=di_u if split else None)
+        plan = cache[key] = (weights, biases, tables, *first._run_extras([c for c, _ in units], geometry, variant, tables))
+    return plan
 
 
 class CompositeTransform(Transform):
@@ -218,92 +293,16 @@ class CompositeTransform(Transform):
         return units, i
 
     def _run_plan(self, units, inverse, tile16=0):
-        """Concatenated weight / bias blobs and the composed tables of a run, cached until a weight or a
-        permutation changes.  (weights, biases, tables, f16 stream or None, K8x's (weights, biases, scales) or None);
-        `tile16`: the mode of the f16 stream (ops.use_tile16)."""
-        first = units[0][0]
-        kind = first._run_signature()[0]
-        mlp = kind in ("k11", "k22", "k29")
-        geometry = _run_geometry(units)   # one padded geometry for the run
-        engine = None if mlp else first._whole_layer_engine(geometry)   # "k8x", "k8h" (the two-piece family) or "k8"
-        f16, x3 = engine == "k8h", engine == "k8x"
-        # (the key reads version counters only; the layers' packed blobs are looked at on a miss)
-        tile16 = tile16 if f16 else 0
-        ids = units.__dict__.get("_ids") if isinstance(units, _Run) else None
-        if ids is None:
-            ids = tuple([id(c) for c, _ in units])
-            if isinstance(units, _Run):
-                units.__dict__["_ids"] = ids
-        # (K29's blobs depend on the bin count and on the divisor folded into them: part of the key)
-        key = (inverse, engine, tile16, geometry, first._log2e() if not mlp else first._spline_constants() if kind == "k29" else None,
-               first.conditioner_act_scale if f16 else None,
-               ids, _run_weights_fingerprint(units),
-               tuple([None if p is None else _permutation_key(p) for _, p in units]))
-        cache = self.__dict__.setdefault("_run_plans", {})
-        plan = cache.get(key)
-        if plan is None:
-            # (a composite whose layers are runs of one -- MAF layers with a BatchNorm between them -- holds one plan per
-            #  layer: with a fixed bound of 4 every call of an 8-layer flow rebuilt every plan, 0.9 ms each)
-            if len(cache) > 4 + len(getattr(self, "_transforms", ())):
-                cache.clear()
-            if isinstance(units, _Run):
-                units.verify_before_packing()
-            packed = [c._packed_mlp() if mlp else c._packed_resnet(geometry) for c, _ in units]
-            packed_f16 = [c._packed_resnet_f16(geometry, tile16) for c, _ in units] if f16 else None
-            weights = torch.cat([w for w, _ in packed], dim=0).contiguous()
-            biases = torch.cat([b for _, b in packed]).contiguous()
-            spec_layers = []
-            for c, p in units:
-                perm = None if p is None else p._permutation
-                spec_layers.append((c.transform_features, c.identity_features,
-                                    None if inverse else perm, perm if inverse else None))
-            Dp, dt4, di_u, _ = geometry
-            tables = ops.flow_layer_tables(first.features, spec_layers, padded_features=Dp,
-                                           padded_transform=dt4 if not mlp else None,
-                                           padded_identity=di_u if not mlp else None)
-            plan_f16 = ops.build_f16_stream(packed_f16, tables) if f16 else None
-            plan_x3 = None
-            if x3:
-                packed_x3 = [c._packed_resnet_f16x3(geometry) for c, _ in units]
-                plan_x3 = tuple(torch.cat([p[i] for p in packed_x3], dim=0).contiguous() for i in range(3))
-            plan = (weights, biases, tables, plan_f16, plan_x3)
-            cache[key] = plan
-        return plan
+        return _run_plan(self, units, inverse, tile16)
 
     def _run_fused(self, units, inputs, total, context, inverse, standard_normal_log_prob=False):
         """One launch for the run (ragged batches are padded to full 128-row blocks inside `ops`).  Returns
         the outputs (or log_prob with `standard_normal_log_prob`), or None when the kernel declines."""
-        first = units[0][0]
         for _, p in units:
             if p is not None:
                 p._check(inputs)
-        geometry = _run_geometry(units)
-        if first._run_signature()[0] == "k22":
-            weights, biases, tables, _, _ = self._run_plan(units, inverse)
-            hidden_linears, residual_blocks = first._conditioner_shape()
-            head = ops.affine_flow_made(
-                inputs, weights, biases, tables, first.features, hidden_linears, context, total, num_layers=len(units),
-                standard_normal_log_prob=standard_normal_log_prob, pad=(geometry[0], geometry[3]),
-                residual_blocks=residual_blocks)
-        elif first._run_signature()[0] == "k29":
-            weights, biases, tables, _, _ = self._run_plan(units, inverse)
-            hidden_linears, residual_blocks = first._conditioner_shape()
-            head = ops.rqs_flow_made(
-                inputs, weights, biases, tables, first.features, hidden_linears, first._density_spec(), context, total,
-                num_layers=len(units), standard_normal_log_prob=standard_normal_log_prob, pad=(geometry[0], geometry[3]),
-                residual_blocks=residual_blocks)
-        elif first._run_signature()[0] == "k11":
-            weights, biases, tables, _, _ = self._run_plan(units, inverse)
-            hidden_linears, residual_blocks = first._conditioner_shape()
-            head = ops.affine_flow_mlp(
-                inputs, weights, biases, tables, first.num_transform_features, first.num_identity_features,
-                hidden_linears, first._activation_code(), inverse, total,
-                num_layers=len(units), standard_normal_log_prob=standard_normal_log_prob, pad=(geometry[0], geometry[3]),
-                residual_blocks=residual_blocks)
-        else:
-            # (batches that give a CU at most one 128-row block: the 16-sample-tile kernels K8s / K8c and their own stream)
-            head = first._whole_layer_cascade(lambda engine: self._run_plan(units, inverse, ops.TILE16.get(engine, 0)), geometry,
-                                              inputs, context, inverse, total, len(units), standard_normal_log_prob)
+        head = units[0][0]._launch_run(lambda tile16=0: _run_plan(self, units, inverse, tile16), len(units),
+                                       _run_geometry(units), inputs, context, inverse, total, standard_normal_log_prob)
         if head is None:
             return None
         return head[1] if standard_normal_log_prob else head[0]

@@ -28,7 +28,7 @@ from .. import _native as N
 from .. import ops
 from .._cache import StalePackedWeights  # noqa: F401  (re-exported: the path users catch it by)
 from ..utils import torchutils
-from .base import Transform
+from .base import RUN_SWITCHES, RunLayer, Transform
 from . import splines
 from .splines import rational_quadratic
 
@@ -281,7 +281,7 @@ class CouplingTransform(Transform):
         raise NotImplementedError()
 
 
-class AffineCouplingTransform(CouplingTransform):
+class AffineCouplingTransform(CouplingTransform, RunLayer):
     """y = x * scale + shift on the transformed half (RealNVP); coupling.py:212-252.
 
     `scale_activation` may be any callable.  The two predefined ones are evaluated inside the
@@ -345,7 +345,8 @@ class AffineCouplingTransform(CouplingTransform):
             logabsdet = logabsdet_accumulator
         return outputs, logabsdet
 
-    # whole-layer kernel K11 (MLP conditioner inside the layer kernel, runs of layers in one launch)
+    # whole-layer kernel K11 (MLP conditioner inside the layer kernel, runs of layers in one launch): the run protocol of
+    # transforms/base.py (`RunLayer`)
     fuse_conditioner = os.environ.get("NFA_K11", "1") != "0"
 
     def _run_kind(self, context):
@@ -392,11 +393,19 @@ class AffineCouplingTransform(CouplingTransform):
         return ("k11", self.features, self.num_transform_features, self.num_identity_features,
                 self._conditioner_shape(), self._activation_code())
 
-    def _packed_mlp(self):
+    def _run_packed(self, geometry=None):
         net = self.transform_net
         return _cache.keyed(self, "_packed_mlp_cache", _cache.weights_key(self, net),
                             lambda: ops.pack_mlp_conditioner(net, self.num_transform_features,
                                                              additive=self._activation_code() == N.SCALE_ADDITIVE))
+
+    def _launch_run(self, plan, num_layers, geometry, inputs, context, inverse, accumulate_into, standard_normal_log_prob):
+        weights, biases, tables = plan()[:3]
+        hidden_linears, residual_blocks = self._conditioner_shape()
+        return ops.affine_flow_mlp(
+            inputs, weights, biases, tables, self.num_transform_features, self.num_identity_features, hidden_linears,
+            self._activation_code(), inverse, accumulate_into, num_layers=num_layers,
+            standard_normal_log_prob=standard_normal_log_prob, pad=(geometry[0], geometry[3]), residual_blocks=residual_blocks)
 
     def _generic_float64(self, inputs, context, inverse, logabsdet_accumulator):
         """float64 vectors: the reference's expressions (coupling.py:73-130, :228-252) as tensor operations on
@@ -468,6 +477,10 @@ class AdditiveCouplingTransform(AffineCouplingTransform):
                                    out_scatter=out_scatter, accumulate_into=accumulate_into)
 
 
+RUN_SWITCHES.append((AffineCouplingTransform, ("fuse_conditioner",)))
+RUN_SWITCHES.append((AdditiveCouplingTransform, ("fuse_conditioner",)))
+
+
 class PiecewiseCouplingTransform(CouplingTransform):
     """The base of the piecewise (spline) couplings; coupling.py:272-296.  The reference's protocol, for code that
     subclasses it or asks `isinstance(t, PiecewiseCouplingTransform)`: `_coupling_transform_forward / _inverse(inputs,
@@ -509,7 +522,7 @@ class PiecewiseCouplingTransform(CouplingTransform):
 _F16_PACK_SLOTS = ("_packed_resnet_f16_cache", "_packed_resnet_f16s_cache", "_packed_resnet_f16c_cache")   # K8h, K8s, K8c
 
 
-class PiecewiseRationalQuadraticCouplingTransform(PiecewiseCouplingTransform):
+class PiecewiseRationalQuadraticCouplingTransform(PiecewiseCouplingTransform, RunLayer):
     """Neural-spline-flow coupling layer; coupling.py:502-582.
 
     Conditioner output per transformed feature: K width logits, K height logits and K-1
@@ -588,8 +601,33 @@ class PiecewiseRationalQuadraticCouplingTransform(PiecewiseCouplingTransform):
         layers = [(c.num_transform_features, c.num_identity_features) for c in (self,) + tuple(others)]
         return ops.fused_geometry(self.features, layers, self.tail_bound)
 
+    # ---- the run protocol of transforms/base.py (`RunLayer`) for the K8 family: several engines, each with a packed form
+    _padded_split = True
+
     def _run_kind(self, context):
         return "k8" if self._resnet_eligible(context) else None
+
+    def _run_variant(self, geometry=None, tile16=0):
+        """(engine of the run -- "k8x", "k8h" (the two-piece family) or "k8" --, the mode of the f16 stream, the log2(e) fold,
+        the scale of the f16 pieces)"""
+        engine = self._whole_layer_engine(geometry)
+        f16 = engine == "k8h"
+        return engine, tile16 if f16 else 0, self._log2e(), self.conditioner_act_scale if f16 else None
+
+    def _run_extras(self, layers, geometry, variant, tables):
+        engine, tile16 = variant[:2]
+        stream = x3 = None
+        if engine == "k8h":
+            stream = ops.build_f16_stream([c._packed_resnet_f16(geometry, tile16) for c in layers], tables)
+        elif engine == "k8x":
+            packed = [c._packed_resnet_f16x3(geometry) for c in layers]
+            x3 = tuple(torch.cat([p[i] for p in packed], dim=0).contiguous() for i in range(3))
+        return stream, x3
+
+    def _launch_run(self, plan, num_layers, geometry, inputs, context, inverse, accumulate_into, standard_normal_log_prob):
+        # (batches that give a CU at most one 128-row block: the 16-sample-tile kernels K8s / K8c and their own stream)
+        return self._whole_layer_cascade(lambda engine: plan(ops.TILE16.get(engine, 0)), geometry, inputs, context, inverse,
+                                         accumulate_into, num_layers, standard_normal_log_prob)
 
     def _run_signature(self):
         # (layers of one run may differ in their feature split -- odd feature counts under alternating masks --:
@@ -797,6 +835,9 @@ class PiecewiseRationalQuadraticCouplingTransform(PiecewiseCouplingTransform):
                                                                 self._transform_dim_multiplier(), log2e=self._log2e(),
                                                                 pad_transform_to=dt4, pad_identity_to=di_u))
 
+    def _run_packed(self, geometry=None):
+        return self._packed_resnet(geometry)
+
     def _layer_tables(self, in_perm, out_scatter):
         key = tuple(None if t is None else (t.data_ptr(), t._version) for t in
                     (in_perm, out_scatter, self.transform_features, self.identity_features))
@@ -943,6 +984,10 @@ class PiecewiseRationalQuadraticCouplingTransform(PiecewiseCouplingTransform):
         return ops.rqs_coupling(inputs, transform_params, self.transform_features, self._spec(),
                                 inverse=inverse, in_perm=in_perm, out_scatter=out_scatter,
                                 accumulate_into=accumulate_into)
+
+
+RUN_SWITCHES.append((PiecewiseRationalQuadraticCouplingTransform,
+                     ("fuse_conditioner", "fuse_final_linear", "conditioner_engine", "conditioner_act_scale", "resnet_log2e")))
 
 
 class PiecewiseLinearCouplingTransform(PiecewiseCouplingTransform):
