@@ -56,7 +56,9 @@ extern "C" {
                               still 19: nfa_made_rqs_inverse_ctx_f32 (K28) is an ADDED entry point, for the same reason (it reads
                               K23's block format);
                               still 19: nfa_rqs_flow_made_f32 (K29) is an ADDED entry point, for the same reason (its stream is
-                              K22's with another final layer) */
+                              K22's with another final layer);
+                              still 19: nfa_made_mog_sample_f32 (K30) is an ADDED entry point, for the same reason (the bit it
+                              reads in K23's unit entries was zero and unread) */
 
 /* return codes */
 #define NFA_OK 0
@@ -778,7 +780,39 @@ int nfa_made_rqs_inverse_ctx_f32(const float *inputs, const float *context_terms
                                  void *stream);
 
 /*
- * K13.  The output layer of a MADE conditioner and the autoregressive spline layer behind it in one kernel:
+ * K30.  MixtureOfGaussiansMADE.sample (nn/nde/made.py:355-388) -- the sampler behind distributions.MADEMoG -- as one
+ *   persistent kernel: K23's step loop (every feature a step, context vectors, continuation blocks, groups of eight) with
+ *   the mixture element in place of the affine one.  Per sample and step t, on the hidden vector as it stands:
+ *     l_k = logit row k . h + bias (k < K);  m = max_k l_k;  e_k = exp(l_k - m);  S = e_0 + .. + e_{K-1} in index order;
+ *     SELECTION RULE: c = the smallest index whose running sum e_0 + .. + e_c exceeds uniforms[row, t] * S, and K - 1
+ *       where no index does (rounding, or a uniform at the largest float below 1);
+ *     then component c's two rows only: x_t = mean_c + normals[row, t] * (softplus(ustd_c) + epsilon), fp32, softplus
+ *       with F.softplus' threshold of 20 -- K + 2 dot products per step instead of 3 K.
+ *   uniforms, normals  [batch, features]: the caller's draws, U[0, 1) and N(0, 1).
+ *   step_blocks / block_starts / layout: ops.pack_mog_schedule(net, block_cap=...): K23's format with P = 3 K and
+ *     - a feature's output rows (and biases) in the order [K logit rows][K x (mean row, unconstrained-std row)] -- the
+ *       module's own order is [K, 3] interleaved;
+ *     - bit 1 of a unit's set_stream word (unit word 6; bit 0 is set_stream): the unit is stored for the next Linear
+ *       WITHOUT the ReLU -- the density-estimator MADE's initial layer in front of feed-forward blocks (nde/made.py:276-277
+ *       against transforms/made.py:276-279).  Read by this entry point only; zero in every other blob.
+ *   context_terms  [batch, context_vectors, Hp]: vector 0 context_layer(ctx) -- NOT rectified, unlike K23's --, vector
+ *                  1 + i blocks[i].context_layer(ctx) of residual block i; feed-forward blocks take none
+ *                  (ops.made_mog_context_terms).  NULL with context_vectors = 0.
+ *   outputs        [batch, features]: complete.  No logabsdet, no hidden_out.
+ *   components_out int32 [batch, features], may be NULL: the component chosen per element (diagnostic; a global store
+ *                  per step).
+ * Supported: 1 <= num_components <= 16, ReLU, no batch norm; the state of sixteen samples + two blocks of `layout[7]`
+ * floats within the LDS as for K23; otherwise NFA_ERR_UNSUPPORTED (callers keep the host loop).  Added under ABI 19 (see
+ * NFA_ABI_VERSION): no existing entry point, flag set or packed layout changed.
+ */
+int nfa_made_mog_sample_f32(const float *uniforms, const float *normals, const float *context_terms,
+                            int32_t context_vectors, const float *step_blocks, const int32_t *block_starts,
+                            int32_t num_blocks, const int32_t *layout, int32_t layout_len, float *outputs,
+                            int32_t *components_out, int64_t batch, int32_t features, int32_t hidden_features,
+                            int32_t num_components, double epsilon, void *stream);
+
+/*
+ * K13. The output layer of a MADE conditioner and the autoregressive spline layer behind it in one kernel:
  *   params = hidden @ (W * mask)^T + b   (MADE.final_layer, transforms/made.py:261-268, :282; MaskedLinear :71-72)
  *   outputs, logabsdet = the RQ functional per feature, logabsdet summed per sample
  *   (MaskedPiecewiseRationalQuadraticAutoregressiveTransform._elementwise, transforms/autoregressive.py:453-489)

@@ -60,6 +60,7 @@ EXPORTS = (
     "nfa_made_rqs_inverse_f32",
     "nfa_made_affine_inverse_f32",
     "nfa_made_rqs_inverse_ctx_f32",
+    "nfa_made_mog_sample_f32",
     "nfa_rqs_made_output_f32",
     "nfa_pack_resnet_hidden_train_f32",
     "nfa_pack_made_train_f32",
@@ -236,6 +237,9 @@ def _declare(lib):
     lib.nfa_made_rqs_inverse_ctx_f32.restype = ctypes.c_int
     lib.nfa_made_rqs_inverse_ctx_f32.argtypes = [vp, vp, i32, vp, vp, i32, ctypes.POINTER(ctypes.c_int32), i32, vp, vp, vp,
                                                  vp, i64, i32, i32, i32, sp, vp]
+    lib.nfa_made_mog_sample_f32.restype = ctypes.c_int
+    lib.nfa_made_mog_sample_f32.argtypes = [vp, vp, vp, i32, vp, vp, i32, ctypes.POINTER(ctypes.c_int32), i32, vp, vp, i64,
+                                            i32, i32, i32, ctypes.c_double, vp]
     lib.nfa_rqs_made_output_f32.restype = ctypes.c_int
     lib.nfa_rqs_made_output_f32.argtypes = [vp, i64, i32, vp, i32, vp, vp, vp, vp, vp, i64, i32, sp, i32, vp]
     lib.nfa_rqs_flow_resnet_redo_f32.restype = ctypes.c_int

@@ -76,6 +76,12 @@ struct MadeInvArgs {
     // K23 (the affine element): the context terms [B, num_ctx, Hp] and the number of blocks (a step may span several)
     const float* ctx;
     int num_ctx, num_blocks, group;   // group: units of one Linear in groups of eight (NFA_K23_GROUP)
+    // K30 (the mixture element; `z` holds the standard normals): the uniforms [B, D], the components chosen (may be null),
+    // the number of components and what is added to softplus(unconstrained std)
+    const float* uniforms;
+    int32_t* components;
+    int mog_k;
+    float mog_eps;
 };
 
 // sum over the sixteen lanes of a sample (a DPP row), every lane gets it
@@ -215,12 +221,25 @@ __device__ __forceinline__ void request_block(const MadeInvArgs& a, int t, float
 // K28: the RQ element inside K23's loop (FULL_): which element a step inverts (AFFINE) and which loop carries it (FULL:
 // context vectors, continuation blocks, groups of eight, the float64 total) are two questions.  <KT, 16, true> is the
 // sampling kernel of a conditional autoregressive spline layer: T <= D steps, `hidden` written for the caller's tail.
+//
+// K30: the mixture-of-Gaussians element of nn.nde.MixtureOfGaussiansMADE.sample (nde/made.py:355-388) in K23's loop --
+// KT = -1, the number of components K <= 16 at run time (two passes of eight logit rows at most: one instance, no scratch).
+// A feature's 3K output rows arrive as [K logit rows][K x (mean, unconstrained std) rows].  Step t:
+//   logits l_k = row k . h + bias;  m = max_k l_k, e_k = exp(l_k - m), S = sum_k e_k in index order;  u = uniforms[row, t];
+//   THE SELECTION RULE: c = the smallest index whose running sum e_0 + .. + e_c exceeds u * S; K - 1 if none does;
+//   then ONLY component c's two rows (an address per sample: `dot_rows` with a per-lane base) -- K + 2 dot products per step
+//   instead of 3K --, x_t = mean_c + normals[row, t] * (softplus(ustd_c) + epsilon) in fp32 (`softplus1`, affine_math.hpp).
+// All D features are steps; no logabsdet, no `hidden`.  The density-estimator MADE (nde/made.py) differs from the
+// transforms' in two places, both settled by the packer: the initial context term is not rectified (the caller's GEMM), and
+// a feed-forward block takes the initial layer's output as it is -- bit 1 of a unit's set_stream word: store the unit
+// without the ReLU (read by this instance only; the other instances never meet it).
 template <int KT, int LPS, bool FULL_ = false>
 __global__ void __launch_bounds__((LPS / 4) * kWave) made_inverse_kernel(const MadeInvArgs a) {
 #pragma clang fp contract(off)
     constexpr bool AFFINE = KT == 0;
-    constexpr bool FULL = AFFINE || FULL_;                          // K23's loop around the element
-    constexpr int P = AFFINE ? 2 : 3 * KT - 1;
+    constexpr bool MOG = KT < 0;                                    // K30: the mixture element
+    constexpr bool FULL = AFFINE || MOG || FULL_;                   // K23's loop around the element
+    constexpr int P = AFFINE || MOG ? 2 : 3 * KT - 1;
     constexpr int RB = AFFINE ? 2 : 8;                              // output rows per pass of dot_rows
     constexpr int NW = LPS / 4;                                     // waves per workgroup (16 samples)
     constexpr int SPW = kWave / LPS;                                // samples per wave
@@ -258,6 +277,12 @@ __global__ void __launch_bounds__((LPS / 4) * kWave) made_inverse_kernel(const M
     const float* zrow = a.z + rrow * a.D;
     float* stream = a.residual ? vecs + a.stream_vec * vec_floats : nullptr;
     float z_next = zrow[0];
+    const float* urow = nullptr;
+    float u_next = 0.0f, u_held = 0.0f;
+    if constexpr (MOG) {
+        urow = a.uniforms + rrow * a.D;
+        u_next = urow[0];
+    }
     unsigned long long* tr = (a.trace && blockIdx.x == 0 && threadIdx.x == 0) ? a.trace : nullptr;
     int ti = 0;
 #define NFA_K12_STAMP() if (tr && ti < 250) tr[ti++] = __builtin_readcyclecounter();
@@ -280,6 +305,10 @@ __global__ void __launch_bounds__((LPS / 4) * kWave) made_inverse_kernel(const M
             if (fresh) {   // (the z prefetch follows t, not the block index)
                 z_held = z_next;
                 if (t + 1 < a.T) z_next = zrow[t + 1];
+                if constexpr (MOG) {
+                    u_held = u_next;
+                    if (t + 1 < a.T) u_next = urow[t + 1];
+                }
             }
         }
         const float z_t = FULL ? z_held : z_next;
@@ -311,7 +340,10 @@ __global__ void __launch_bounds__((LPS / 4) * kWave) made_inverse_kernel(const M
             const float bias = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(e0.x));
             const int j = __builtin_amdgcn_readfirstlane(e0.y), kp = __builtin_amdgcn_readfirstlane(e0.z);
             const int src_v = __builtin_amdgcn_readfirstlane(e0.w), dst_v = __builtin_amdgcn_readfirstlane(e1.x);
-            const bool add_stream = __builtin_amdgcn_readfirstlane(e1.y) != 0, set_stream = __builtin_amdgcn_readfirstlane(e1.z) != 0;
+            const bool add_stream = __builtin_amdgcn_readfirstlane(e1.y) != 0;
+            const int stream_word = __builtin_amdgcn_readfirstlane(e1.z);
+            const bool set_stream = MOG ? (stream_word & 1) != 0 : stream_word != 0;
+            const bool raw = MOG && (stream_word & 2) != 0;     // K30: the unit enters the next Linear as it is
             const float* src = src_v < 0 ? xs + s * px * 4 : vecs + src_v * vec_floats + s * ph * 4;
             const int at = state_index(j, s, ph);
             const float carried = add_stream ? stream[at] : 0.0f;   // (in flight beside the dot product's reads)
@@ -332,7 +364,7 @@ __global__ void __launch_bounds__((LPS / 4) * kWave) made_inverse_kernel(const M
             if (add_stream) v = carried + v;                    // residual connection (made.py:128)
             if (q == 0) {
                 if (set_stream) stream[at] = v;
-                if (dst_v >= 0) vecs[dst_v * vec_floats + at] = v < 0.0f ? 0.0f : v;   // ReLU'd for the next Linear (NaN stays)
+                if (dst_v >= 0) vecs[dst_v * vec_floats + at] = v < 0.0f && !raw ? 0.0f : v;   // ReLU'd for the next Linear (NaN stays)
             }
             // a unit just written is an input of the next Linear (same wave: LDS is in order)
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -372,7 +404,9 @@ __global__ void __launch_bounds__((LPS / 4) * kWave) made_inverse_kernel(const M
                             const float bias = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(e0.x));
                             const int j = __builtin_amdgcn_readfirstlane(e0.y), dst_v = __builtin_amdgcn_readfirstlane(e1.x);
                             const bool add_stream = __builtin_amdgcn_readfirstlane(e1.y) != 0;
-                            const bool set_stream = __builtin_amdgcn_readfirstlane(e1.z) != 0;
+                            const int stream_word = __builtin_amdgcn_readfirstlane(e1.z);
+                            const bool set_stream = MOG ? (stream_word & 1) != 0 : stream_word != 0;
+                            const bool raw = MOG && (stream_word & 2) != 0;
                             const int ctx_v = __builtin_amdgcn_readfirstlane(e1.w);
                             const int at = state_index(j, s, ph);
                             float v = acc[i] + bias;
@@ -380,7 +414,7 @@ __global__ void __launch_bounds__((LPS / 4) * kWave) made_inverse_kernel(const M
                             if (add_stream) v = stream[at] + v;
                             if (q == 0) {
                                 if (set_stream) stream[at] = v;
-                                if (dst_v >= 0) vecs[dst_v * vec_floats + at] = v < 0.0f ? 0.0f : v;
+                                if (dst_v >= 0) vecs[dst_v * vec_floats + at] = v < 0.0f && !raw ? 0.0f : v;
                             }
                         }
                     }
@@ -405,31 +439,82 @@ __global__ void __launch_bounds__((LPS / 4) * kWave) made_inverse_kernel(const M
         if (t == a.T) break;
         // ---- 2. feature t's P output rows on the hidden vector as it stands: all sums in every lane of the sample
         const float* fin = vecs + a.final_src * vec_floats + s * ph * 4;
-        float p[P];
+        if constexpr (MOG) {
+            // ---- 2. K30: the K logits of feature t (rows 0 .. K - 1 of its output rows), all sums in every lane of the sample
+            const int K = a.mog_k;
+            float lg[16];
 #pragma unroll
-        for (int g = 0; g < (P + RB - 1) / RB; ++g) {
-            float acc[RB];
-            const int left = P - g * RB;
-            if (a.Hp == 256) dot_rows_64<RB, NFA_K12_ROWS_AHEAD, LPS>(acc, wf + g * RB * a.Hp, a.Hp, fin, q, left < RB ? left : RB);
-            else dot_rows<RB, 4, LPS>(acc, wf + g * RB * a.Hp, a.Hp, fin, a.Hp >> 2, q, left < RB ? left : RB);
+            for (int g = 0; g < 2; ++g) {
+                float acc[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+                const int left = K - g * 8;
+                if (left > 0) {
+                    if (a.Hp == 256) dot_rows_64<8, NFA_K12_ROWS_AHEAD, LPS>(acc, wf + g * 8 * a.Hp, a.Hp, fin, q, left < 8 ? left : 8);
+                    else dot_rows<8, 4, LPS>(acc, wf + g * 8 * a.Hp, a.Hp, fin, a.Hp >> 2, q, left < 8 ? left : 8);
+                }
 #pragma unroll
-            for (int i = 0; i < RB; ++i)
-                if (g * RB + i < P) p[g * RB + i] = acc[i] + fbias[g * RB + i];
-        }
-        NFA_K12_STAMP()
-        // ---- 3. invert feature t (rational_quadratic.py:66-181 through the same evaluation as K5); every
-        //      lane of a sample does it, one records the result
-        float y, l;
-        if constexpr (AFFINE) {
-            affine_element<true>(z_t, p[1], scale_of(p[0], NFA_SCALE_SOFTPLUS), y, l);   // (K2b: autoregressive.py:96-121)
+                for (int i = 0; i < 8; ++i) lg[g * 8 + i] = i < left ? acc[i] + fbias[g * 8 + i] : -INFINITY;
+            }
+            // ---- 3. the component: the smallest c with e_0 + .. + e_c > u S, K - 1 if there is none (e_k = 0 behind K - 1)
+            float m = lg[0];
+#pragma unroll
+            for (int k = 1; k < 16; ++k) m = lg[k] > m ? lg[k] : m;
+            float e[16], S = 0.0f;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                e[k] = k < K ? expf(lg[k] - m) : 0.0f;
+                S += e[k];
+            }
+            const float bar = u_held * S;
+            float run = 0.0f;
+            int c = K - 1;
+            bool found = false;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                run += e[k];
+                if (!found && run > bar) {
+                    c = k;
+                    found = true;
+                }
+            }
+            // ---- 4. component c's mean and unconstrained std: two rows at an address of the SAMPLE's own
+            float ms[2];
+            const float* crow = wf + (K + 2 * c) * a.Hp;
+            if (a.Hp == 256) dot_rows_64<2, NFA_K12_ROWS_AHEAD, LPS>(ms, crow, a.Hp, fin, q, 2);
+            else dot_rows<2, 4, LPS>(ms, crow, a.Hp, fin, a.Hp >> 2, q, 2);
+            const float mean = ms[0] + fbias[K + 2 * c], ustd = ms[1] + fbias[K + 2 * c + 1];
+            const float y = mean + z_t * (softplus1(ustd) + a.mog_eps);   // (nde/made.py:376-386)
+            ++t_affine;
+            if (q == 0) {
+                xs[state_index(t, s, px)] = y;
+                if (a.components && live) a.components[row * a.D + t] = c;   // (diagnostic: a global store per step)
+            }
         } else {
-            my_status |= rqs_eval<KT, true, true, true>(z_t, p, a.sp, y, l);
+            float p[P];
+#pragma unroll
+            for (int g = 0; g < (P + RB - 1) / RB; ++g) {
+                float acc[RB];
+                const int left = P - g * RB;
+                if (a.Hp == 256) dot_rows_64<RB, NFA_K12_ROWS_AHEAD, LPS>(acc, wf + g * RB * a.Hp, a.Hp, fin, q, left < RB ? left : RB);
+                else dot_rows<RB, 4, LPS>(acc, wf + g * RB * a.Hp, a.Hp, fin, a.Hp >> 2, q, left < RB ? left : RB);
+#pragma unroll
+                for (int i = 0; i < RB; ++i)
+                    if (g * RB + i < P) p[g * RB + i] = acc[i] + fbias[g * RB + i];
+            }
+            NFA_K12_STAMP()
+            // ---- 3. invert feature t (rational_quadratic.py:66-181 through the same evaluation as K5); every
+            //      lane of a sample does it, one records the result
+            float y, l;
+            if constexpr (AFFINE) {
+                affine_element<true>(z_t, p[1], scale_of(p[0], NFA_SCALE_SOFTPLUS), y, l);   // (K2b: autoregressive.py:96-121)
+            } else {
+                my_status |= rqs_eval<KT, true, true, true>(z_t, p, a.sp, y, l);
+            }
+            if constexpr (FULL) ++t_affine;
+            if constexpr (FULL) lad_wide += (double)l;
+            else lad_acc += l;
+            // (kept in LDS only: a global store per step would sit in front of the next step's vmcnt(0))
+            if (q == 0) xs[state_index(t, s, px)] = y;
         }
-        if constexpr (FULL) ++t_affine;
-        if constexpr (FULL) lad_wide += (double)l;
-        else lad_acc += l;
-        // (kept in LDS only: a global store per step would sit in front of the next step's vmcnt(0))
-        if (q == 0) xs[state_index(t, s, px)] = y;
         NFA_K12_STAMP()
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -438,8 +523,10 @@ __global__ void __launch_bounds__((LPS / 4) * kWave) made_inverse_kernel(const M
     // input of the output layer for features >= T
     if (live) {
         for (int k = q; k < a.T; k += LPS) a.x[row * a.D + k] = xs[state_index(k, s, px)];
-        if (q == 0) a.lad[row] = FULL ? (float)lad_wide : lad_acc;
-        if constexpr (!AFFINE) {
+        if constexpr (!MOG) {
+            if (q == 0) a.lad[row] = FULL ? (float)lad_wide : lad_acc;
+        }
+        if constexpr (!AFFINE && !MOG) {
             const float* fin = vecs + a.final_src * vec_floats;
             for (int k = q; k < a.H; k += LPS) a.hidden[row * a.H + k] = fin[state_index(k, s, ph)];
         }
@@ -641,4 +728,51 @@ extern "C" int nfa_made_rqs_inverse_ctx_f32(const float* inputs, const float* co
     note_layer_kernel("made_inverse_kernel<element=rqs, K=%d, context=%d, continuation_blocks=%d, group=%d>", a.sp.K,
                       context_vectors > 0 ? 1 : 0, num_blocks - (sequential_steps + 1), a.group);
     return launch_kernel(kern, dim3((unsigned)blocks), dim3(4 * kWave), lds, (hipStream_t)stream, a, kCuLds - 4096, false);
+}
+
+// K30: MixtureOfGaussiansMADE.sample (nde/made.py:355-388) -- all features, context included, one launch
+extern "C" int nfa_made_mog_sample_f32(const float* uniforms, const float* normals, const float* context_terms,
+                                       int32_t context_vectors, const float* step_blocks, const int32_t* block_starts,
+                                       int32_t num_blocks, const int32_t* layout, int32_t layout_len, float* outputs,
+                                       int32_t* components_out, int64_t batch, int32_t features, int32_t hidden_features,
+                                       int32_t num_components, double epsilon, void* stream) {
+    if (batch < 0 || features < 1 || hidden_features < 1 || context_vectors < 0 || num_components < 1 || !layout ||
+        layout_len < 8)
+        return NFA_ERR_INVALID_ARGUMENT;
+    if (num_components > 16) return NFA_ERR_UNSUPPORTED;
+    MadeInvArgs a = {};
+    int rc = read_made_layout(layout, layout_len, hidden_features, a);
+    if (rc != NFA_OK) return rc;
+    // one block per step at least, t = 0 .. features (the last one holds nothing); at most one context vector per Linear
+    if (a.Xp < features || num_blocks < features + 1 || context_vectors > a.num_linears) return NFA_ERR_INVALID_ARGUMENT;
+    const size_t lds = made_lds_bytes(a, context_vectors);
+    if (lds + 4096 > (size_t)kCuLds) return NFA_ERR_UNSUPPORTED;
+    if (batch == 0) return NFA_OK;
+    if (!uniforms || !normals || !step_blocks || !block_starts || !outputs || (context_vectors > 0 && !context_terms))
+        return NFA_ERR_INVALID_ARGUMENT;
+    const int64_t blocks = (batch + kMadeSamples - 1) / kMadeSamples;
+    if (blocks > 0x7fffffff) return NFA_ERR_UNSUPPORTED;
+    a.z = normals;
+    a.x = outputs;
+    a.blocks = step_blocks;
+    a.block_at = block_starts;
+    a.batch = batch;
+    a.D = features;
+    a.H = hidden_features;
+    a.T = features;
+    a.ctx = context_terms;
+    a.num_ctx = context_vectors;
+    a.num_blocks = num_blocks;
+    a.uniforms = uniforms;
+    a.components = components_out;
+    a.mog_k = num_components;
+    a.mog_eps = (float)epsilon;
+    // K23's rule for the groups of eight (units per Linear and step: hidden / (features - 1)); NFA_K23_GROUP=0 / 1 forces either
+    const char* group_env = getenv("NFA_K23_GROUP");
+    a.group = group_env && group_env[0] ? (atoi(group_env) != 0 ? 1 : 0)
+                                        : (hidden_features >= 5 * (features > 1 ? features - 1 : 1) ? 1 : 0);
+    note_layer_kernel("made_inverse_kernel<element=mog, K=%d, context=%d, continuation_blocks=%d, group=%d>", num_components,
+                      context_vectors > 0 ? 1 : 0, num_blocks - (features + 1), a.group);
+    return launch_kernel(made_inverse_kernel<-1, 16>, dim3((unsigned)blocks), dim3(4 * kWave), lds, (hipStream_t)stream, a,
+                         kCuLds - 4096, false);
 }

@@ -1,5 +1,8 @@
 """`MADEMoG` (reference: nflows/distributions/mixture.py): a mixture-of-Gaussians MADE as a `Distribution`.  The density is
-`nn.nde.MixtureOfGaussiansMADE.log_prob`: the MADE's forward pass, then one launch of K20 "mog" on a HIP device."""
+`nn.nde.MixtureOfGaussiansMADE.log_prob`: the MADE's forward pass, then one launch of K20 "mog" on a HIP device.
+`sample` (and `sample_and_log_prob`, and every Flow with this base) is `MixtureOfGaussiansMADE.sample`: on a HIP device one
+launch of K30 on `torch.rand(B, D)` and then `torch.randn(B, D)` from the default generator -- other draws than the host
+loop's for a given seed, the same distribution; `NFA_K30=0` gives the host loop (see nn/nde/made.py)."""
 from torch.nn import functional as F
 
 from ..nn.nde import MixtureOfGaussiansMADE

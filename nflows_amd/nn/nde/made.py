@@ -11,16 +11,29 @@ and never uses it; this one does not.
 
 `MixtureOfGaussiansMADE.log_prob` is the MADE's forward pass on stock ops followed by ONE launch of K20 "mog"
 (csrc/density.hip), which reads the final layer's [B, D * K * 3] output in place: on a HIP device, float32, contiguous,
-K <= 64.  Everything else runs the reference's sequence on stock ops.  `sample` is the reference's loop of D forward
-passes; its tensors are created on the context's device (the reference creates them on the CPU).
+K <= 64.  Everything else runs the reference's sequence on stock ops.
+
+`MixtureOfGaussiansMADE.sample` is ONE launch of K30 (csrc/made_inverse.hip, the mixture element in the step loop of the
+sequential samplers) on a HIP device with float32 parameters, K <= 16, residual or feed-forward blocks with ReLU, no
+batch norm, no active dropout: the context rows are repeated, `torch.rand(B, D)` and THEN `torch.randn(B, D)` are drawn
+on the device from the default generator (in that order, once each), the context terms are one GEMM, the kernel runs once.
+Per feature t it chooses the component c as the smallest index whose running sum of exp(l_k - max l) exceeds
+u[row, t] * (the sum over all k, in index order) -- K - 1 if none does -- and sets x_t = mean_c + normal[row, t] *
+(softplus(ustd_c) + epsilon).  The draws differ from the host loop's for a given seed (that loop draws a Categorical and a
+randn per feature); the distribution is the same.  `NFA_K30=0` or `_use_sample_kernel = False` give the host loop: the
+reference's loop of D forward passes, which is also what runs on the CPU (with the reference's random stream) and
+everywhere else outside the kernel's family or its size rule; its tensors are created on the context's device (the
+reference creates them on the CPU).
 """
+import os
+
 import numpy as np
 import torch
 from torch import distributions, nn
 from torch.nn import functional as F
 from torch.nn import init
 
-from ... import ops
+from ... import _cache, ops
 from ...utils import torchutils
 
 
@@ -170,9 +183,78 @@ class MixtureOfGaussiansMADE(MADE):
             return ops.mog_log_prob(inputs, outputs, self.num_mixture_components, self.epsilon)
         return mog_log_prob_generic(inputs, outputs, self.num_mixture_components, self.epsilon)
 
+    # ---- K30: the sampler in one persistent kernel.  Its own switch, independent of K20's.
+    _use_sample_kernel = os.environ.get("NFA_K30", "1") != "0"
+    # Size rule (features <=, rows >) from profiles/mog_sample_time.json: the kernel does one MADE pass per sample whatever
+    # the number of features, sixteen samples per workgroup; the host loop does one pass of GEMMs per FEATURE at full-device
+    # rates.  At 262 144 rows the kernel is 1.7-5.1 x faster with 21-64 features but 0.68-0.70 x with 8 (1.08-1.09 x at
+    # 65 536 rows); between 8 and 21 features nothing was measured there, and K23's bound of 16 is taken: such calls keep
+    # the host loop they had.
+    _SAMPLE_KERNEL_LOSES = ((16, 65536),)
+
+    def _sample_kernel_net(self):
+        """True where K30 serves this network: float32, residual or feed-forward blocks, ReLU, no batch norm, no active
+        dropout, at most MADE_MAX_LINEARS Linears, 1 <= K <= 16.  The structure is read once per cache epoch."""
+        def read():
+            blocks = list(self.blocks)
+            kinds = {type(b) for b in blocks}
+            return (kinds <= {MaskedResidualBlock} or kinds <= {MaskedFeedforwardBlock}) and \
+                len(ops._made_linears(self)) <= ops.MADE_MAX_LINEARS and \
+                not any(isinstance(m, nn.BatchNorm1d) for m in self.modules()) and \
+                all(p.dtype == torch.float32 for p in self.parameters()) and \
+                self.final_layer.weight.shape[0] == 3 * self.num_mixture_components * self.features
+        if not (1 <= self.num_mixture_components <= 16) or not _cache.keyed(self, "_sample_net_held", (_cache.epoch(),), read):
+            return False
+        for block in self.blocks:
+            if block.activation is not F.relu or (self.training and block.dropout.p > 0.0):
+                return False
+        return True
+
+    def _sample_kernel_plan(self):
+        """(step blocks or None where the shape does not fit the LDS, packed context Linears) until a weight or mask changes"""
+        def pack():
+            linears = len(ops._made_linears(self))
+            vectors = len(ops.made_context_layers(self))
+            cap = ops.made_mog_block_cap(self.features, self.hidden_features, linears, vectors)
+            schedule = ops.pack_mog_schedule(self, block_cap=cap) if cap > 0 else None
+            return schedule, ops.pack_made_context(self) if schedule else None
+        return _cache.keyed(self, "_mog_sample_cache", _cache.weights_key(self, self), pack)
+
+    def _sample_kernel_serves(self, context):
+        if not (self._use_sample_kernel and torch.is_tensor(context) and context.is_cuda and context.dim() == 2
+                and context.dtype == torch.float32 and context.shape[0] > 0 and hasattr(self, "context_layer")
+                and context.shape[1] == self.context_layer.weight.shape[1]
+                and self.final_layer.weight.device == context.device):
+            return False
+        rows = context.shape[0]
+        if any(self.features <= f and rows > r for f, r in self._SAMPLE_KERNEL_LOSES):
+            return False
+        return self._sample_kernel_net()
+
+    def _sample_kernel(self, context, draws=None):
+        """The samples [B, D] of K30 for the repeated context rows, or None where the kernel does not take the shape.
+        `draws`: (uniforms, normals) in place of the generator's (tests)."""
+        schedule, packed_context = self._sample_kernel_plan()
+        if schedule is None:
+            return None
+        shape = (context.shape[0], self.features)
+        if draws is None:
+            uniforms = torch.rand(shape, device=context.device)      # (this order: documented above)
+            normals = torch.randn(shape, device=context.device)
+        else:
+            uniforms, normals = draws
+        terms = ops.made_mog_context_terms(context, packed_context)
+        return ops.made_mog_sample(uniforms, normals, schedule, self.hidden_features, self.num_mixture_components,
+                                   self.epsilon, terms)
+
     def sample(self, num_samples, context=None):
         if context is not None:
             context = torchutils.repeat_rows(context, num_samples)
+        if self._sample_kernel_serves(context):
+            with torch.no_grad():
+                samples = self._sample_kernel(context)
+            if samples is not None:
+                return samples.reshape(-1, num_samples, self.features)
         with torch.no_grad():
             device = context.device
             samples = torch.zeros(context.shape[0], self.features, device=device)

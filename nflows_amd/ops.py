@@ -1292,10 +1292,18 @@ MADE_LDS_BYTES = 160 * 1024 - 4096     # what K12 / K23 may use of a CU's LDS (c
 MADE_MAX_LINEARS = 12                  # kMadeMaxLinears
 
 
+def _made_residual(net):
+    """Residual blocks?  The transforms' MADE says so; the density-estimator MADE (nn/nde/made.py) keeps no such attribute:
+    there the blocks' type tells."""
+    flag = getattr(net, "use_residual_blocks", None)
+    return any(hasattr(block, "linear_layers") for block in net.blocks) if flag is None else bool(flag)
+
+
 def _made_linears(net):
     linears = [net.initial_layer]
+    residual = _made_residual(net)
     for block in net.blocks:
-        linears += list(block.linear_layers) if net.use_residual_blocks else [block.linear]
+        linears += list(block.linear_layers) if residual else [block.linear]
     return linears
 
 
@@ -1305,7 +1313,7 @@ def made_context_layers(net):
     if not hasattr(net, "context_layer"):
         return []
     layers = [net.context_layer]
-    if net.use_residual_blocks:
+    if _made_residual(net):
         layers += [block.context_layer for block in net.blocks]
     return layers
 
@@ -1326,16 +1334,19 @@ def made_block_cap(features, hidden_features, num_linears, context_vectors=0):
     return (left // 2 // 1024) * 256 if left > 0 else 0
 
 
-def _pack_made_blocks(net, T, P, block_cap, context):
+def _pack_made_blocks(net, T, P, block_cap, context, mog=False):
     """`pack_made_schedule` with a block cap and context vectors, whole slices of units at a time (the units of one degree
     are consecutive once a Linear's rows are sorted by degree).  Block header: [units, offset of the unit rows, of the
     output rows, of the output biases, 1 = another block of this step follows]; a continuation block carries units
-    only, in layer order, and the step's last block the output rows."""
+    only, in layer order, and the step's last block the output rows.
+    `mog` (K30, `pack_mog_schedule`): `net` is the density-estimator MADE with P = 3K -- a feature's output rows go from
+    [K, 3] interleaved to [K logits][K x (mean, unconstrained std)], and in front of feed-forward blocks the initial layer's
+    units carry the raw-store bit (2 in the set_stream word)."""
     dev = net.final_layer.weight.device
     H = net.initial_layer.weight.shape[0]
     Hp = (H + 15) // 16 * 16
     Xp = max(16, (T + 15) // 16 * 16)
-    residual = bool(net.use_residual_blocks)
+    residual = _made_residual(net)
     linears = _made_linears(net)
     n = len(linears)
     with_context = context and hasattr(net, "context_layer")
@@ -1366,6 +1377,8 @@ def _pack_made_blocks(net, T, P, block_cap, context):
         table[:, 0] = np.ascontiguousarray(bias[order]).view(np.int32)
         table[:, 1] = order
         table[:, 2:7] = entry
+        if mog and not residual and l == 0:
+            table[:, 6] |= 2                                  # nde/made.py: no activation behind the initial layer
         table[:, 7] = ctx_v
         tables.append(table)
     final = net.final_layer
@@ -1373,6 +1386,9 @@ def _pack_made_blocks(net, T, P, block_cap, context):
     wf = np.zeros((T, P, Hp), dtype=np.float32)
     wf[:, :, :H] = (final.weight.detach() * final.mask).float().cpu().numpy().reshape(D, P, H)[:T]
     bf = final.bias.detach().float().cpu().numpy().reshape(D, P)[:T]
+    if mog:
+        order = np.concatenate((np.arange(0, P, 3), np.delete(np.arange(P), np.arange(0, P, 3))))
+        wf, bf = np.ascontiguousarray(wf[:, order]), np.ascontiguousarray(bf[:, order])
     tail = P * Hp + P
     blocks, block_at, at = [], [], 0
 
@@ -1453,6 +1469,63 @@ def made_context_terms(context, packed):
     terms = torch.addmm(b, context.detach(), w.t()).view(context.shape[0], vectors, Hp)
     terms[:, 0].relu_()
     return terms
+
+
+def made_mog_context_terms(context, packed):
+    """`made_context_terms` for the density-estimator MADE (K30): its initial term is context_layer(ctx) as it is
+    (nn/nde/made.py: `temps + context_layer(context)`, no activation) -- one GEMM, no ReLU."""
+    w, b, vectors, Hp = packed
+    return torch.addmm(b, context.detach(), w.t()).view(context.shape[0], vectors, Hp)
+
+
+def made_mog_block_cap(features, hidden_features, num_linears, context_vectors=0):
+    """`made_block_cap` for K30: the same LDS budget (the state of all D features, one vector per Linear and context
+    vector, two blocks).  A feature's 3K output rows must fit one block: `pack_mog_schedule` returns None where not."""
+    return made_block_cap(features, hidden_features, num_linears, context_vectors)
+
+
+def pack_mog_schedule(net, block_cap=None):
+    """The step blocks of K30 for a `nn.nde.MixtureOfGaussiansMADE`: `pack_made_schedule`'s K23 format with every feature
+    a step and P = 3K output rows per feature in the order [K logit rows][K x (mean row, unconstrained-std row)]; the
+    raw-store bit on the initial layer's units in front of feed-forward blocks.  None where a unit or a feature's output
+    rows do not fit a block of `block_cap` floats."""
+    return _pack_made_blocks(net, int(net.features), 3 * int(net.num_mixture_components), block_cap, True, mog=True)
+
+
+def made_mog_sample(uniforms, normals, schedule, hidden_features, num_components, epsilon, context_terms=None,
+                    want_components=False):
+    """K30 -- MixtureOfGaussiansMADE.sample in one persistent kernel from the caller's draws `uniforms` (U[0, 1)) and
+    `normals`, both [B, D].  Per step: the K logits, the component c = the smallest index whose running sum of
+    exp(l_k - max l) exceeds u * (their sum in index order), K - 1 if none does; then x_t = mean_c + normal *
+    (softplus(ustd_c) + epsilon) from component c's two rows only.  Returns the samples [B, D] -- (samples, components
+    int32 [B, D]) with `want_components` --, or None outside the kernel's family (NFA_ERR_UNSUPPORTED)."""
+    N.require_device_f32("uniforms", uniforms, 2)
+    N.require_device_f32("normals", normals, 2)
+    if uniforms.shape != normals.shape or uniforms.device != normals.device:
+        raise ValueError("uniforms %s and normals %s must agree" % (tuple(uniforms.shape), tuple(normals.shape)))
+    dev = uniforms.device
+    B, D = uniforms.shape
+    u, z = uniforms.detach().contiguous(), normals.detach().contiguous()
+    out = torch.empty_like(z)
+    components = torch.empty(B, D, dtype=torch.int32, device=dev) if want_components else None
+    floats, ints, layout = schedule
+    vectors = 0
+    if context_terms is not None:
+        N.require_device_f32("context_terms", context_terms, 3)
+        context_terms = context_terms.contiguous()
+        vectors = context_terms.shape[1]
+        if context_terms.shape[0] != B or context_terms.shape[2] != layout[5]:
+            raise ValueError("context_terms is %s, expected [%d, C, %d]" % (tuple(context_terms.shape), B, layout[5]))
+    arr = (ctypes.c_int32 * len(layout))(*layout)
+    nbytes = 4 * (3 * B * D + (B * D if want_components else 0) + B * vectors * layout[5] + floats.numel())
+    rc = _launch(dev, N.load().nfa_made_mog_sample_f32,
+                 (N.ptr(u), N.ptr(z), N.ptr(context_terms), vectors, N.ptr(floats), N.ptr(ints), ints.numel() - 2, arr,
+                  len(layout), N.ptr(out), N.ptr(components), B, D, hidden_features, int(num_components), float(epsilon),
+                  N.stream_handle(dev)), "made_mog_sample", nbytes, raw=True)
+    if rc == N.ERR_UNSUPPORTED:
+        return None
+    N.check(rc)
+    return (out, components) if want_components else out
 
 
 def made_affine_inverse(inputs, schedule, hidden_features, context_terms=None):
