@@ -58,7 +58,9 @@ extern "C" {
                               still 19: nfa_rqs_flow_made_f32 (K29) is an ADDED entry point, for the same reason (its stream is
                               K22's with another final layer);
                               still 19: nfa_made_mog_sample_f32 (K30) is an ADDED entry point, for the same reason (the bit it
-                              reads in K23's unit entries was zero and unread) */
+                              reads in K23's unit entries was zero and unread);
+                              still 19: nfa_made_mog_log_prob_f32 (K31) is an ADDED entry point, for the same reason (its stream
+                              is K22's with another final layer) */
 
 /* return codes */
 #define NFA_OK 0
@@ -810,6 +812,38 @@ int nfa_made_mog_sample_f32(const float *uniforms, const float *normals, const f
                             int32_t num_blocks, const int32_t *layout, int32_t layout_len, float *outputs,
                             int32_t *components_out, int64_t batch, int32_t features, int32_t hidden_features,
                             int32_t num_components, double epsilon, void *stream);
+
+/*
+ * K31.  MixtureOfGaussiansMADE.log_prob (nn/nde/made.py:328-353 of the reference) in ONE launch: the density-estimator MADE
+ *   (made.py:206-281: h = W_0 x + b_0 + context_layer(ctx) with NO activation on the context term; residual blocks as in
+ *   K29; feed-forward blocks h = relu(W h + b) starting from the RAW initial layer and taking no context of their own; the
+ *   final Linear on the blocks' result as it is), then per feature the 3 K values of the masked final Linear straight from
+ *   the MFMA accumulators -- they never reach memory -- and on them K20's element in float64 (density_math.hpp):
+ *     logsumexp_k(log_softmax(logits)_k - 0.5 (log 2 pi + 2 log std_k + ((x - m_k) / std_k)^2)),
+ *     std_k = softplus(u_k) + epsilon (threshold 20).
+ *   A row's terms are added in float64, pair of features after pair of features, then across the lane pair; `add[row]`
+ *   joins that sum; ONE rounding gives log_prob[row].  The order is fixed by the shape alone: no atomics, the same bits
+ *   from call to call.
+ *   inputs          [batch, features], read once; any row length of 1 .. 64.
+ *   context         [batch, context_features], NULL with context_features = 0.
+ *   weights_packed  K22's stages (context_layer, initial_layer, the blocks; every matrix weight * mask), then the final
+ *                   layer: features padded to pairs, every feature's 3 K rows in the module's own order
+ *                   (logit, mean, unconstrained std) x K padded with zero rows to 16 T, T = ceil(3 K / 16); pair g is T
+ *                   tiles of two stages each whose accumulator values, tile after tile, are the 16 T values of feature
+ *                   2 g + (lane >> 5) (row i of a tile: register 4 (i / 8) + i % 4 of lane-half (i / 4) % 2).
+ *   bias_packed     as for K22 (initial_layer 128, context_layer 128 with a context, 128 per hidden Linear with a residual
+ *                   block's context bias added to its first Linear's), then the final layer's 32 per tile in the same order.
+ *   add             [batch] or NULL.
+ *   num_hidden_layers  the hidden Linears: twice the residual blocks, or the feed-forward blocks.
+ *   flags           NFA_FLAG_RESIDUAL_BLOCKS or 0.
+ * Supported: hidden_features = 128, 1 <= features <= 64, context_features <= 64, 1 <= num_components <= 16,
+ * num_hidden_layers <= 64, batch % 128 == 0; otherwise NFA_ERR_UNSUPPORTED (callers keep the MADE's stock ops and K20).
+ * Added under ABI 19 (see NFA_ABI_VERSION): no existing entry point, flag set or packed layout changes.
+ */
+int nfa_made_mog_log_prob_f32(const float *inputs, const float *context, int32_t context_features,
+                              const void *weights_packed, const float *bias_packed, const float *add, float *log_prob,
+                              int64_t batch, int32_t features, int32_t hidden_features, int32_t num_hidden_layers,
+                              int32_t num_components, double epsilon, int32_t flags, void *stream);
 
 /*
  * K13. The output layer of a MADE conditioner and the autoregressive spline layer behind it in one kernel:

@@ -75,6 +75,48 @@ __device__ __forceinline__ double mog_term(float x, const float* o, int K, doubl
     return mog_lse((double)x, o, K, mog_logit_lse(o, K), epsilon);
 }
 
+// ---- the same three for an element whose 3K floats are REGISTERS (K31, made_mog_kernel.hpp: the accumulators of the
+// final layer's tiles): `o` holds room for KMAX components, the loops over k are unrolled to KMAX so that every index is
+// static (N >= 3 KMAX floats), and the components beyond the run-time K are skipped under a test every lane answers
+// alike.  Operation for operation the functions above -- `mog_component` itself is shared.
+template <int KMAX, int N>
+__device__ __forceinline__ double mog_logit_lse(const float (&o)[N], int K) {
+    double top = (double)o[0];
+#pragma unroll
+    for (int k = 1; k < KMAX; ++k)
+        if (k < K) top = fmax(top, (double)o[3 * k]);
+    double sum = 0.0;
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k)
+        if (k < K) sum += exp((double)o[3 * k] - top);
+    return top + log(sum);
+}
+
+template <int KMAX, int N>
+__device__ __forceinline__ double mog_lse(double x, const float (&o)[N], int K, double lse_logits, double epsilon) {
+    static_assert(3 * KMAX <= N, "the element's registers hold KMAX components");
+    double std, z;
+    double top = mog_component(x, o, 0, lse_logits, epsilon, std, z);
+    double sum = 1.0;
+#pragma unroll
+    for (int k = 1; k < KMAX; ++k) {
+        if (k < K) {
+            const double t = mog_component(x, o, k, lse_logits, epsilon, std, z);
+            // (the two sides of mog_lse's `if` as selects: one exp per component whichever side a lane takes)
+            const bool above = t > top;
+            const double e = exp(above ? top - t : t - top);
+            sum = above ? sum * e + 1.0 : sum + e;
+            top = above ? t : top;
+        }
+    }
+    return top + log(sum);
+}
+
+template <int KMAX, int N>
+__device__ __forceinline__ double mog_term(float x, const float (&o)[N], int K, double epsilon) {
+    return mog_lse<KMAX>((double)x, o, K, mog_logit_lse<KMAX>(o, K), epsilon);
+}
+
 // gradients of g * term: `go` (3K floats; may be `o` itself -- component k is written after its last read) and the return
 // value, the gradient of x.  r_k = exp(t_k - lse):
 //   d/dlogit_k = g (r_k - softmax_k)   d/dm_k = g r_k (x - m_k) / std_k^2

@@ -9,9 +9,14 @@ reference's (`weight`, `bias`, `mask`, `degrees`).  Module names are the referen
 `blocks.{i}.linear` / `blocks.{i}.batch_norm` (feed-forward), `final_layer`.  The reference's module imports matplotlib
 and never uses it; this one does not.
 
-`MixtureOfGaussiansMADE.log_prob` is the MADE's forward pass on stock ops followed by ONE launch of K20 "mog"
-(csrc/density.hip), which reads the final layer's [B, D * K * 3] output in place: on a HIP device, float32, contiguous,
-K <= 64.  Everything else runs the reference's sequence on stock ops.
+`MixtureOfGaussiansMADE.log_prob` without gradients is ONE launch of K31 (csrc/made_mog.hip: the MADE, its final Linear
+and the mixture log-density in the layer kernel; only [B] floats leave the chip) on a HIP device with float32 parameters,
+hidden width <= 128, 1 .. 64 features, no context or 1 .. 64 context features, K <= 16, residual or feed-forward blocks
+(random masks included) with ReLU, no batch norm, no active dropout, at least 128 rows, outside the size rule
+`_DENSITY_KERNEL_LOSES`.  `NFA_K31=0` or `_use_density_kernel = False` give what every other call runs: the MADE's forward
+pass on stock ops followed by ONE launch of K20 "mog" (csrc/density.hip), which reads the final layer's [B, D * K * 3]
+output in place: on a HIP device, float32, contiguous, K <= 64 (differentiable).  Everything else -- and everything with
+`_use_kernel = False` -- runs the reference's sequence on stock ops.
 
 `MixtureOfGaussiansMADE.sample` is ONE launch of K30 (csrc/made_inverse.hip, the mixture element in the step loop of the
 sequential samplers) on a HIP device with float32 parameters, K <= 16, residual or feed-forward blocks with ReLU, no
@@ -177,7 +182,79 @@ class MixtureOfGaussiansMADE(MADE):
                 and inputs.dtype == outputs.dtype == torch.float32 and inputs.is_contiguous() and outputs.is_contiguous()
                 and 1 <= self.num_mixture_components <= ops.MOG_MAX_COMPONENTS)
 
+    # ---- K31: the MADE, its final Linear and the mixture log-density in one launch.  Its own switch; K20's `_use_kernel =
+    #      False` (the generic path) wins over it.
+    _use_density_kernel = os.environ.get("NFA_K31", "1") != "0"
+    # Size rule (features >, components >, rows <) from profiles/mog_density_time.json: the kernel runs a row block's final
+    # layer as ceil(D / 2) x T x 2 weight stages behind one another in ONE workgroup, and below one block per CU nothing
+    # hides that chain.  With 64 features and K = 10 it is 0.86-0.90 x (0.76-0.78 x back to back) of the stock ops + K20
+    # at 64 and 1 024 rows and 1.20 x at 16 384; with 43 features, or with K = 5, it wins at every size.  Between 43 and 64
+    # features and between 5 and 10 components nothing was measured: such calls keep the path they had.
+    _DENSITY_KERNEL_LOSES = ((43, 5, 16384),)
+    # K31 works on whole 128-row blocks: a call with fewer rows than one block would be padded to one by copies of its
+    # operands, and keeps the stock ops + K20 it had (whose launches tests/test_gpu_density.py pins for a 64-row call).
+    # NOT a measured loss: at 64 rows the padded kernel was 1.1-2.6 x faster for all shapes but the one above.
+    _DENSITY_KERNEL_MIN_ROWS = 128
+
+    def _density_kernel_net(self):
+        """True where K31 serves this network: float32, hidden width <= 128, 1 .. 64 features, no context or 1 .. 64 context
+        features, 1 <= K <= 16, residual or feed-forward blocks with ReLU, at most 64 hidden Linears, no batch norm, no
+        active dropout.  The structure is read once per cache epoch."""
+        def read():
+            kinds = {type(b) for b in self.blocks}
+            linears = ops._made_linears(self)
+            hidden, features = self.initial_layer.weight.shape
+            context = getattr(self, "context_layer", None)
+            return (kinds <= {MaskedResidualBlock} or kinds <= {MaskedFeedforwardBlock}) and \
+                len(linears) - 1 <= 64 and hidden <= 128 and 1 <= features <= 64 and \
+                all(lin.weight.shape[0] == hidden for lin in linears) and \
+                (context is None or 1 <= context.weight.shape[1] <= 64) and \
+                not any(isinstance(m, nn.BatchNorm1d) for m in self.modules()) and \
+                all(p.dtype == torch.float32 for p in self.parameters()) and \
+                self.final_layer.weight.shape[0] == 3 * self.num_mixture_components * features
+        if not (1 <= self.num_mixture_components <= ops.MADE_MOG_MAX_COMPONENTS) or \
+                not _cache.keyed(self, "_density_net_held", (_cache.epoch(),), read):
+            return False
+        for block in self.blocks:
+            if block.activation is not F.relu or (self.training and block.dropout.p > 0.0):
+                return False
+        return True
+
+    def _density_kernel_serves(self, inputs, context):
+        if not (self._use_kernel and self._use_density_kernel and torch.is_tensor(inputs) and inputs.is_cuda
+                and inputs.dim() == 2 and inputs.dtype == torch.float32 and inputs.shape[0] > 0
+                and inputs.shape[1] == self.features and self.final_layer.weight.device == inputs.device
+                and inputs.shape[0] >= self._DENSITY_KERNEL_MIN_ROWS
+                # (the kernel stands for THIS class's forward pass: not for one replaced on the instance or in a subclass)
+                and "forward" not in self.__dict__ and type(self).forward is MixtureOfGaussiansMADE.forward):
+            return False
+        if hasattr(self, "context_layer"):
+            if not (torch.is_tensor(context) and context.dim() == 2 and context.dtype == torch.float32
+                    and context.device == inputs.device and context.shape[0] == inputs.shape[0]
+                    and context.shape[1] == self.context_layer.weight.shape[1]):
+                return False
+        elif context is not None:
+            return False
+        rows, K = inputs.shape[0], self.num_mixture_components
+        if any(self.features > f and K > k and rows < r for f, k, r in self._DENSITY_KERNEL_LOSES):
+            return False
+        if torch.is_grad_enabled() and (inputs.requires_grad or (context is not None and context.requires_grad)
+                                        or any(p.requires_grad for p in self.parameters())):
+            return False
+        return self._density_kernel_net()
+
+    def _density_kernel(self, inputs, context=None, logabsdet=None):
+        """log_prob [B] of K31 (`logabsdet` [B] inside the row's float64 sum), or None where the entry point declines."""
+        packed = _cache.keyed(self, "_mog_density_cache", _cache.weights_key(self, self),
+                              lambda: ops.pack_made_mog_conditioner(self))
+        return ops.made_mog_log_prob(inputs, packed, len(ops._made_linears(self)) - 1, self.num_mixture_components,
+                                     residual_blocks=ops._made_residual(self), context=context, logabsdet=logabsdet)
+
     def log_prob(self, inputs, context=None):
+        if self._density_kernel_serves(inputs, context):
+            log_prob = self._density_kernel(inputs, context)
+            if log_prob is not None:
+                return log_prob
         outputs = self.forward(inputs, context=context)
         if self._kernel_serves(inputs, outputs):
             return ops.mog_log_prob(inputs, outputs, self.num_mixture_components, self.epsilon)

@@ -17,6 +17,7 @@ conditions in a per-device status word instead:
 import ctypes
 import math
 import os
+import types
 
 import numpy as np
 import torch
@@ -2563,6 +2564,94 @@ def rqs_flow_made(inputs, weights_packed, bias_packed, tables, features, num_hid
             num_hidden_layers, ctypes.byref(spec), flags, stream)
     return _whole_layer_launch(launch, inputs, False, accumulate_into, standard_normal_log_prob, pad, context,
                                flags=N.FLAG_RESIDUAL_BLOCKS if residual_blocks else 0, spec=spec)
+
+
+MADE_MOG_MAX_COMPONENTS = 16   # K31's three instances: T = ceil(3 K / 16) <= 3
+
+
+def made_mog_tiles(num_components):
+    """T of K31: 32-row tiles per pair of features -- the 3 K rows of a feature padded to 16 T rows."""
+    return (3 * num_components + 15) // 16
+
+
+def pack_made_mog_conditioner(net):
+    """A MixtureOfGaussiansMADE (nn/nde/made.py: the density-estimator MADE with 3 K outputs per feature) for K31:
+    `pack_mlp_conditioner`'s stages of `weight * mask` for the context Linear, the initial layer and the blocks' Linears (a
+    residual block's context Linear behind its first Linear, that bias folded in; feed-forward blocks have none); the final
+    layer's masked rows per feature, in the module's own (logit, mean, unconstrained std) x K order, padded to 16 T rows
+    (`made_mog_tiles`) and the features to pairs (zero rows), in `_k8_row_order_32(tiles_per_group=T)` order, three bf16
+    pieces.  Returns (weights [stages, 768*8] bf16, biases fp32, epsilon)."""
+    K = int(net.num_mixture_components)
+    final = net.final_layer
+    features = net.initial_layer.weight.shape[1]
+    H = final.weight.shape[1]
+    if final.weight.shape[0] != features * 3 * K:
+        raise ValueError("the MADE's final layer must have 3 * num_mixture_components rows per feature")
+    T = made_mog_tiles(K)
+    pairs = (features + 1) // 2
+    dev = final.weight.device
+
+    def masked(lin):
+        return _MaskedLinear((lin.weight.detach() * lin.mask, lin.bias.detach()))
+    rows = final.weight.new_zeros(2 * pairs, 16 * T, H)
+    rows[:features, :3 * K] = (final.weight.detach() * final.mask).view(features, 3 * K, H)
+    bias = final.bias.new_zeros(2 * pairs, 16 * T)
+    bias[:features, :3 * K] = final.bias.detach().view(features, 3 * K)
+    order = _k8_row_order_32(2 * pairs, T).to(dev)
+    final_rows = (rows.reshape(-1, H).index_select(0, order), bias.reshape(-1).index_select(0, order))
+    linears = _made_linears(net)
+    # (the places `_conditioner_linears` reads an MLP's layers from: this MADE keeps no `use_residual_blocks`)
+    layers = types.SimpleNamespace(_input_layer=masked(linears[0]), _hidden_layers=[masked(lin) for lin in linears[1:]],
+                                   _output_layer=final)
+    context = made_context_layers(net)
+    weights, biases = pack_mlp_conditioner(layers, features, context=(context[0], context[1:]) if context else None,
+                                           final_rows=final_rows)
+    return weights, biases, float(net.epsilon)
+
+
+def made_mog_log_prob(inputs, packed, num_hidden_layers, num_components, residual_blocks=True, context=None,
+                      logabsdet=None):
+    """K31 -- MixtureOfGaussiansMADE.log_prob in one launch: the MADE, its final Linear and the mixture log-density
+    (`packed` = `pack_made_mog_conditioner(net)`; `num_hidden_layers`: the hidden Linears, twice the number of residual
+    blocks or the number of feed-forward blocks).  float32 `inputs` [B, 1 .. 64], `context` [B, 1 .. 64] or None,
+    `logabsdet` [B] or None: added inside the row's float64 sum, which is rounded once.  A ragged batch is padded to whole
+    128-row blocks with zero rows whose results are dropped.  Forward only.  Returns log_prob [B], or None where the entry
+    point declines the shape."""
+    weights, biases, epsilon = packed
+    N.require_device_f32("inputs", inputs, 2)
+    B, D = inputs.shape
+    dev = inputs.device
+    x = inputs.detach().contiguous()
+    ctx = add = None
+    if context is not None:
+        N.require_device_f32("context", context, 2)
+        if context.shape[0] != B or context.device != dev:
+            raise ValueError("context must have one row per input row, on the inputs' device")
+        ctx = context.detach().contiguous()
+    if logabsdet is not None:
+        N.require_device_f32("logabsdet", logabsdet, 1)
+        if logabsdet.shape[0] != B or logabsdet.device != dev:
+            raise ValueError("logabsdet must have one entry per input row, on the inputs' device")
+        add = logabsdet.detach().contiguous()
+    if B == 0:
+        return torch.empty(0, dtype=torch.float32, device=dev)
+    pad_rows = (-B) % 128
+    if pad_rows:
+        x = torch.cat((x, x.new_zeros(pad_rows, D)), dim=0)
+        ctx = None if ctx is None else torch.cat((ctx, ctx.new_zeros(pad_rows, ctx.shape[1])), dim=0)
+        add = None if add is None else torch.cat((add, add.new_zeros(pad_rows)), dim=0)
+    rows = x.shape[0]
+    ce = 0 if ctx is None else ctx.shape[1]
+    out = torch.empty(rows, dtype=torch.float32, device=dev)
+    rc = _launch(dev, N.load().nfa_made_mog_log_prob_f32,
+                 (N.ptr(x), N.ptr(ctx), ce, N.ptr(weights), N.ptr(biases), N.ptr(add), N.ptr(out), rows, D, 128,
+                  num_hidden_layers, int(num_components), epsilon, N.FLAG_RESIDUAL_BLOCKS if residual_blocks else 0,
+                  N.stream_handle(dev)),
+                 "made_mog_log_prob", 4 * rows * (D + ce + (2 if add is not None else 1)), raw=True)
+    if rc == N.ERR_UNSUPPORTED:
+        return None
+    N.check(rc)
+    return out[:B] if pad_rows else out
 
 
 def affine_flow_mlp(inputs, weights_packed, bias_packed, tables, num_transform, num_identity, num_hidden_layers,
