@@ -60,7 +60,9 @@ extern "C" {
                               still 19: nfa_made_mog_sample_f32 (K30) is an ADDED entry point, for the same reason (the bit it
                               reads in K23's unit entries was zero and unread);
                               still 19: nfa_made_mog_log_prob_f32 (K31) is an ADDED entry point, for the same reason (its stream
-                              is K22's with another final layer) */
+                              is K22's with another final layer);
+                              still 19: nfa_rqs_layer_resnet_wide_f32 (K32) is an ADDED entry point, for the same reason (its
+                              blobs are its own) */
 
 /* return codes */
 #define NFA_OK 0
@@ -305,6 +307,34 @@ int nfa_rqs_coupling_resnet_f32(const float *inputs, const void *weights_packed,
                                 int32_t features, int32_t num_transform, int32_t num_identity,
                                 int32_t hidden_features, int32_t num_blocks,
                                 const nfa_rqs_spec *spec, int32_t flags, void *stream);
+
+/*
+ * K32: ONE spline coupling layer whose ResidualNet conditioner is wider than K8's 128 hidden units, in one launch, both
+ * directions (csrc/rqs_resnet_wide_kernel.hpp).  Same arithmetic as nfa_rqs_coupling_resnet_f32 (three bf16 pieces per
+ * operand, six products per k-step: the full fp32 range, so there is no redo pass and no redo_blocks); one workgroup of
+ * eight waves per CU takes 64 rows through the layer, the hidden GEMMs split by columns over the waves.
+ *   hidden_features  1 .. 256 (the conditioner's own width, the divisor of the width / height logits); the blobs are
+ *                    packed for Hp = hidden_features rounded up to a multiple of 32, the extra units zero.
+ *   weights_packed   bf16 fragments of 64 lanes x 8 values (1 KB): lane (half, i) holds W[32 tile + i][16 ks + 8 half + j],
+ *                    ordered [GEMM][32-row tile][k-step][piece hi, mid, lo]: the initial layer (Hp / 32 tiles,
+ *                    ceil(num_identity / 16) k-steps), the 2 num_blocks hidden Linears (Hp / 32 tiles, Hp / 16 k-steps,
+ *                    input columns in accumulator order: k-step ks, lane-half hf, element j = hidden unit 32 (ks / 2) +
+ *                    16 (ks % 2) + 8 (j / 4) + 4 hf + j % 4), the final Linear (num_transform / 2 x T tiles, T = ceil((3 K - 1)
+ *                    / 16): the T tiles of pair g give lane-half h the zero-padded logits of feature 2 g + h; width and
+ *                    height rows scaled by 1 / sqrt(hidden_features)).
+ *   bias_packed      fp32 in accumulator order ([tile][lane-half][16]) in the same GEMM order.
+ *   layer_tables     int32 [256] as for nfa_rqs_coupling_resnet_f32.
+ * Supported: 2 .. 16 bins, linear tails, ReLU blocks, no context, num_identity <= 64, num_transform % 4 == 0 and <= 64,
+ * features % 4 == 0 and <= 128, batch % 128 == 0, flags NFA_FLAG_INVERSE | NFA_FLAG_ACCUMULATE_LOGABSDET, the exchange buffer
+ * (Hp / 16 x 6 KB) and the row tile (features x 260 B) within the CU's LDS; otherwise NFA_ERR_UNSUPPORTED, after the argument
+ * errors (callers then run the conditioner's GEMMs and K1 / K7).  batch == 0 returns NFA_OK.  Added under ABI 19 (see
+ * NFA_ABI_VERSION): no existing entry point, flag set or packed layout changes.
+ */
+int nfa_rqs_layer_resnet_wide_f32(const float *inputs, const void *weights_packed, const float *bias_packed,
+                                  const int32_t *layer_tables, float *outputs, float *logabsdet, int32_t *status,
+                                  int64_t batch, int32_t features, int32_t num_transform, int32_t num_identity,
+                                  int32_t hidden_features, int32_t num_blocks, const nfa_rqs_spec *spec, int32_t flags,
+                                  void *stream);
 
 /*
  * K8 over a run of layers.  Rows of a flow are independent, so num_layers coupling layers of the

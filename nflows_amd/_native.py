@@ -47,6 +47,7 @@ EXPORTS = (
     "nfa_rqs_coupling_backward_f32",
     "nfa_rqs_coupling_fused_linear_f32",
     "nfa_rqs_coupling_resnet_f32",
+    "nfa_rqs_layer_resnet_wide_f32",
     "nfa_rqs_flow_resnet_f32",
     "nfa_rqs_flow_resnet_redo_f32",
     "nfa_rqs_flow_resnet_context_f32",
@@ -273,6 +274,8 @@ def _declare(lib):
                                                          i32, i32, i32, sp, i32, vp]
     lib.nfa_rqs_coupling_resnet_f32.restype = ctypes.c_int
     lib.nfa_rqs_coupling_resnet_f32.argtypes = [vp] * 7 + [i64, i32, i32, i32, i32, i32, sp, i32, vp]
+    lib.nfa_rqs_layer_resnet_wide_f32.restype = ctypes.c_int
+    lib.nfa_rqs_layer_resnet_wide_f32.argtypes = lib.nfa_rqs_coupling_resnet_f32.argtypes
     lib.nfa_rqs_elementwise_f32.restype = ctypes.c_int
     lib.nfa_rqs_elementwise_f32.argtypes = [vp, vp, i64, vp, i64, vp, i64, i32, vp, vp, vp, vp, i64, sp, i32, vp]
     lib.nfa_searchsorted_f32.restype = ctypes.c_int

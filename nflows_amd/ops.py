@@ -3037,6 +3037,72 @@ def rqs_coupling_resnet(inputs, weights_packed, bias_packed, tables, num_transfo
                                flags=flags, spec=spec)
 
 
+def _wide_column_order(hidden_padded):
+    """`_k8_column_order` over `hidden_padded` (a multiple of 32) hidden units: the unit consumed at (k-step ks, lane-half
+    hf, element j) of a GEMM whose input is the previous layer's accumulator tiles."""
+    ks = torch.arange(hidden_padded // 16)[:, None, None]
+    hf = torch.arange(2)[None, :, None]
+    j = torch.arange(8)[None, None, :]
+    return (32 * (ks // 2) + 16 * (ks % 2) + 8 * (j // 4) + 4 * hf + j % 4).reshape(-1)  # [ks][hf][j]
+
+
+def _wide_fragments(w):
+    """[32 tiles, 16 nks] fp32 -> bf16 [tiles, nks, 3 pieces, 64 lanes, 8]: lane (hf, i) of fragment (tile, ks) holds
+    W[32 tile + i][16 ks + 8 hf + j], j = 0 .. 7."""
+    tiles, nks = w.shape[0] // 32, w.shape[1] // 16
+    # (p, tile, i, ks, hf, j) -> (tile, ks, p, hf, i, j)
+    return torch.stack(split_bf16x3(w)).view(3, tiles, 32, nks, 2, 8).permute(1, 3, 0, 4, 2, 5).reshape(-1)
+
+
+def pack_resnet_conditioner_wide(net, num_transform, params_per_feature, pad_transform_to=None, pad_identity_to=None):
+    """Packs a ResidualNet without context (or its batch-norm fold, `fold_batch_norm`) for K32 (layout in
+    include/nflows_amd.h, nfa_rqs_layer_resnet_wide_f32): the hidden width zero-padded to Hp, a multiple of 32; every weight
+    as split-bf16 fragments per (GEMM, 32-row tile, k-step, piece), all biases in accumulator order, the
+    1 / sqrt(hidden_features) scale of the width / height logits (coupling.py:554-556) folded into the final layer's rows.
+    Returns (weights bf16, biases fp32)."""
+    dt, P = num_transform, params_per_feature
+    K = (P + 1) // 3
+    T = (P + 15) // 16
+    dev = net.final_layer.weight.device
+    H = net.initial_layer.weight.shape[0]
+    Hp = (H + 31) // 32 * 32
+    order_k = _wide_column_order(Hp).to(dev)
+    wi = _pad_to(net.initial_layer.weight.detach().float(), rows=Hp)
+    di = wi.shape[1] if pad_identity_to is None else max(wi.shape[1], pad_identity_to)
+    blobs = [_wide_fragments(_pad_to(wi, cols=16 * ((di + 15) // 16)))]
+    biases = [_bias_accumulator_order(_pad_to(net.initial_layer.bias.detach().float(), rows=Hp))]
+    for block in net.blocks:
+        for lin in block.linear_layers:
+            blobs.append(_wide_fragments(_pad_to(lin.weight.detach().float(), rows=Hp, cols=Hp).index_select(1, order_k)))
+            biases.append(_bias_accumulator_order(_pad_to(lin.bias.detach().float(), rows=Hp)))
+    scale = torch.ones(P, dtype=torch.float64, device=dev)
+    scale[:2 * K] = 1.0 / math.sqrt(net.hidden_features)
+    wf = (net.final_layer.weight.detach().double().view(dt, P, H) * scale[None, :, None]).float()
+    bf = (net.final_layer.bias.detach().double().view(dt, P) * scale[None, :]).float()
+    dtp = dt if pad_transform_to is None else max(dt, pad_transform_to)   # surplus features: zero rows (fused_geometry)
+    wfull = wf.new_zeros(dtp, 16 * T, Hp)
+    wfull[:dt, :P, :H] = wf
+    bfull = bf.new_zeros(dtp, 16 * T)
+    bfull[:dt, :P] = bf
+    order_r = _k8_row_order_32(dtp, T).to(dev)
+    blobs.append(_wide_fragments(wfull.reshape(dtp * 16 * T, Hp).index_select(0, order_r).index_select(1, order_k)))
+    biases.append(_bias_accumulator_order(bfull.reshape(-1).index_select(0, order_r)))
+    return torch.cat(blobs).contiguous(), torch.cat(biases).contiguous()
+
+
+def rqs_coupling_resnet_wide(inputs, weights_packed, bias_packed, tables, num_transform, num_identity, hidden_features,
+                             num_blocks, spec, inverse=False, accumulate_into=None, pad=None):
+    """K32 -- one spline coupling layer with a ResidualNet conditioner of 129 .. 256 hidden units in one kernel
+    (`pack_resnet_conditioner_wide`, `coupling_layer_tables`).  `pad`: see `_whole_layer_launch`.  Returns (outputs,
+    logabsdet), or None when the shape is outside the kernel's family."""
+    def launch(x, ctx, out, lad, redo, flags, status, stream):
+        B, D = x.shape
+        return N.load().nfa_rqs_layer_resnet_wide_f32(
+            N.ptr(x), N.ptr(weights_packed), N.ptr(bias_packed), N.ptr(tables), N.ptr(out), N.ptr(lad), status, B, D,
+            num_transform, num_identity, hidden_features, num_blocks, ctypes.byref(spec), flags, stream)
+    return _whole_layer_launch(launch, inputs, inverse, accumulate_into, False, pad, spec=spec, redo=None)
+
+
 _ACTIVATION_CODES = {id(torch.nn.functional.relu): N.ACTIVATION_RELU, id(torch.relu): N.ACTIVATION_RELU,
                      id(torch.nn.functional.leaky_relu): N.ACTIVATION_LEAKY_RELU, id(torch.nn.functional.elu): N.ACTIVATION_ELU,
                      id(torch.tanh): N.ACTIVATION_TANH, id(torch.nn.functional.tanh): N.ACTIVATION_TANH}

@@ -853,7 +853,49 @@ class PiecewiseRationalQuadraticCouplingTransform(PiecewiseCouplingTransform, Ru
             cache[key] = hit
         return hit
 
+    # K32: conditioners of 129 .. 256 hidden units, the whole layer in one launch (csrc/rqs_resnet_wide_kernel.hpp); class-level
+    # switch, NFA_K32=0 = off: such layers then take stock GEMMs + K1 / K7 as before
+    fuse_wide_conditioner = os.environ.get("NFA_K32", "1") != "0"
+    # K32's size rule (DESIGN.md section 4 "K32"): measured faster at every size from 1 024 rows up (1.7-4.0 x); fewer rows
+    # were not measured and keep the old path
+    fuse_wide_min_rows = int(os.environ.get("NFA_K32_MIN_ROWS", "1024"))
+
+    def _wide_layer_eligible(self, context):
+        """What K32 asks of the layer: no grad, a plain ResidualNet without context, ReLU blocks, 128 < width <= 256, linear
+        tails, 2 .. 16 bins, the whole-layer geometry (identity <= 64, transformed <= 64 in fours, padded features <= 128),
+        no active dropout or training-mode batch norm, no user hooks, no unconditional transform."""
+        net = self._modules["transform_net"]
+        from ..nn.nets.resnet import ResidualNet
+        return (self.fuse_wide_conditioner and not torch.is_grad_enabled() and context is None
+                and type(net) is ResidualNet and net.context_features is None
+                and 128 < net.hidden_features <= 256
+                and self.tails == "linear" and 2 <= self.num_bins <= 16
+                and self.unconditional_transform is None and not self._user_hooks
+                and 1 <= self.num_identity_features <= 64 and 1 <= self.num_transform_features
+                and self._fused_geometry()[1] <= 64 and self._fused_geometry()[0] <= 128
+                and self._block_activation() == N.ACTIVATION_RELU
+                and all(not b.training or (b.dropout.p == 0.0 and not b.use_batch_norm) for b in net.blocks)
+                and (not any(b.use_batch_norm for b in net.blocks) or self._folded_net() is not None))
+
+    def _packed_resnet_wide(self):
+        """(weights, biases) for K32 (ops.pack_resnet_conditioner_wide), per weight key"""
+        _, dt4, di_u, _ = self._fused_geometry()
+        key = (dt4, di_u) + _cache.weights_key(self, self.transform_net)
+        return _cache.keyed(self, "_packed_resnet_wide_cache", key,
+                            lambda: ops.pack_resnet_conditioner_wide(self._folded_net(), self.num_transform_features,
+                                                                     self._transform_dim_multiplier(),
+                                                                     pad_transform_to=dt4, pad_identity_to=di_u))
+
     def _whole_layer(self, inputs, context, inverse, in_perm, out_scatter, accumulate_into):
+        if (self._wide_layer_eligible(context) and inputs.is_cuda and inputs.dtype == torch.float32
+                and inputs.shape[0] >= self.fuse_wide_min_rows and self.identity_features.device == inputs.device):
+            Dp, dt4, di_u, pad_value = self._fused_geometry()
+            net = self.transform_net
+            res = ops.rqs_coupling_resnet_wide(inputs, *self._packed_resnet_wide(), self._layer_tables(in_perm, out_scatter),
+                                               dt4, di_u, net.hidden_features, len(net.blocks), self._spec(), inverse,
+                                               accumulate_into, pad=(Dp, pad_value))
+            if res is not None:
+                return res
         if not self._resnet_eligible(context):
             return None
         tables = self._layer_tables(in_perm, out_scatter)
