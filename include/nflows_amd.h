@@ -62,7 +62,9 @@ extern "C" {
                               still 19: nfa_made_mog_log_prob_f32 (K31) is an ADDED entry point, for the same reason (its stream
                               is K22's with another final layer);
                               still 19: nfa_rqs_layer_resnet_wide_f32 (K32) is an ADDED entry point, for the same reason (its
-                              blobs are its own) */
+                              blobs are its own);
+                              still 19: nfa_pack_resnet_wide_train_f32, nfa_resnet_wide_forward_f32, nfa_resnet_wide_backward_f32
+                              (K33) are ADDED entry points, for the same reason (their streams are their own) */
 
 /* return codes */
 #define NFA_OK 0
@@ -1114,6 +1116,48 @@ int nfa_resnet_backward_ctx_f32(int32_t mode, const float *grad_hidden, const fl
                                 const float *saved, float *grads, float *const *plane_grads, float *gated_grads,
                                 float *grad_hidden_out, float *grad_identity_inputs, int64_t batch,
                                 int32_t num_identity, int32_t hidden_features, int32_t num_blocks, void *stream);
+
+/*
+ * K33.  K14's pair of kernels for a ResidualNet conditioner of 129 <= hidden_features <= 256 (csrc/resnet_train_wide.hip),
+ * on K32's work split: one workgroup of eight waves per CU on 64 rows, wave w owning hidden columns 32 w .. 32 w + 31.
+ * Hp = hidden_features padded to a multiple of 32; every [.., Hp] array holds exact zeros in its pad columns.
+ *   forward:  identity_inputs [batch, num_identity] -> hidden [batch, Hp], saved [2 num_blocks][batch][Hp] (saved[2k] =
+ *             relu(h_k), saved[2k+1] = relu(a_k): K10's `inputs` and the backward pass's masks, re-derived as saved > 0; no
+ *             packed mask words) and, with out_features > 0, params [batch, out_features] = W_f hidden + b_f.
+ *   backward: exactly one of grad_params [batch, out_features] (out_features > 0; the final Linear's input gradient is the
+ *             kernel's first GEMM, walked in chunks of 256 columns, and is written to grad_hidden_out [batch, Hp]) and
+ *             grad_hidden [batch, Hp] (out_features = 0) -> grads [2 num_blocks][batch][Hp] (grads[2k+1] = d loss / d a_k,
+ *             grads[2k] = d loss / d h_k) and grad_identity_inputs [batch, num_identity].
+ * Fragments: split-bf16 triples, per GEMM [column tile of 32][k-step of 16][piece][lane] x 16 bytes, lane (hf, i) of
+ * fragment (tile, ks) holding A[32 tile + i][k(ks, hf, j)], j = 0 .. 7, zeros past the matrix.
+ *   forward_fragments:  W_in ([Hp / 32][num_identity > 32 ? 4 : 2], k = 16 ks + 8 hf + j), W_0, W_1 per block
+ *                       ([Hp / 32][Hp / 16]) and, with a final Linear, W_f ([ceil(out_features / 32)][Hp / 16]); the last
+ *                       three kinds with k in accumulator order, k = 32 (ks / 2) + 16 (ks % 2) + 8 (j / 4) + 4 hf + j % 4.
+ *   backward_fragments: with a final Linear W_f^T ([Hp / 32][2 ceil(out_features / 32)]), then W_1^T, W_0^T per block from
+ *                       the LAST to the first ([Hp / 32][Hp / 16]), then W_in^T ([ceil(num_identity / 32)][Hp / 16]); all
+ *                       in accumulator order.
+ *   bias_packed: accumulator order ([tile][half][q] = b[32 tile + 8 (q / 4) + 4 half + q % 4]): b_in, (b_0, b_1) per block
+ *                (Hp each), then b_f (32 per tile).
+ * The packer is one launch (the weights change with every optimiser step); block_params: HOST array of 4 num_blocks
+ * device pointers W_0, b_0, W_1, b_1; initial_weight is [hidden_features, src_identity] with src_identity <= num_identity
+ * (the streams hold zeros past it, so odd feature counts need no padded copy of the weight).
+ * fp32-accurate products on the bf16 matrix pipe (three pieces per operand, six products), full fp32 range;
+ * deterministic (no atomics).  NFA_ERR_UNSUPPORTED (the caller keeps the eager modules) outside 129 <= hidden_features <=
+ * 256, num_blocks <= 3, num_identity <= 64 and % 4 == 0, batch % 64 == 0, out_features % 4 == 0 and <= 32768.  Added
+ * under ABI 19 (see NFA_ABI_VERSION): no existing entry point, flag set or packed layout changes.
+ */
+int nfa_pack_resnet_wide_train_f32(const float *initial_weight, const float *initial_bias,
+                                   const float *const *block_params, const float *final_weight, const float *final_bias,
+                                   int32_t out_features, int32_t src_identity, int32_t num_identity,
+                                   int32_t hidden_features, int32_t num_blocks, void *forward_fragments,
+                                   float *bias_packed, void *backward_fragments, void *stream);
+int nfa_resnet_wide_forward_f32(const float *identity_inputs, const void *fragments, const float *bias_packed,
+                                float *saved, float *hidden, float *params, int32_t out_features, int64_t batch,
+                                int32_t num_identity, int32_t hidden_features, int32_t num_blocks, void *stream);
+int nfa_resnet_wide_backward_f32(const float *grad_hidden, const float *grad_params, int32_t out_features,
+                                 const void *fragments, const float *saved, float *grads, float *grad_hidden_out,
+                                 float *grad_identity_inputs, int64_t batch, int32_t num_identity,
+                                 int32_t hidden_features, int32_t num_blocks, void *stream);
 
 /*
  * K9.  The spline's siblings as elementwise functionals (no row-sum), same calling convention as

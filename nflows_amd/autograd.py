@@ -721,6 +721,22 @@ class ResidualNetHidden(torch.autograd.Function):
         return _resnet_hidden_backward(ctx, g_out, ctx.saved_tensors)
 
 
+def _linear_wgrad(inputs, grad_outputs, need_w, need_b, rows=None, cols=None):
+    """(grad_weight, grad_bias) of a Linear through K10; rows / cols: the net's own width inside the padded arrays"""
+    from . import ops
+    if not (need_w or need_b):
+        return None, None
+    got = ops.linear_wgrad(inputs, grad_outputs, need_bias=need_b)
+    if got is None:   # widths K10 does not take
+        got = (grad_outputs.t() @ inputs if need_w else None), (grad_outputs.sum(0) if need_b else None)
+    g_w, g_b = (got[0] if need_w else None), got[1]
+    if g_w is not None and (rows is not None or cols is not None):
+        g_w = g_w[:rows, :cols].contiguous()
+    if g_b is not None and rows is not None:
+        g_b = g_b[:rows].contiguous()
+    return g_w, g_b
+
+
 def _resnet_hidden_backward(ctx, g_out, saved_tensors, context=None):
     """K14's backward pass for ResidualNetHidden and MadeNet: (grad of x, None, then one gradient per parameter).
     `saved_tensors`: (x, saved, bwd_w) or, with the final Linear, (x, saved, bwd_w, hidden, W_f -- or a function
@@ -733,20 +749,7 @@ def _resnet_hidden_backward(ctx, g_out, saved_tensors, context=None):
     need = ctx.needs_input_grad[context["first_param"] if context else 2:]   # per parameter
     g_out = g_out.contiguous()
 
-    def wgrad(inputs, grad_outputs, need_w, need_b, rows=None, cols=None):
-        """(grad_weight, grad_bias) of a Linear; rows / cols: the net's own width inside the 128-wide arrays"""
-        if not (need_w or need_b):
-            return None, None
-        got = ops.linear_wgrad(inputs, grad_outputs, need_bias=need_b)
-        if got is None:   # widths K10 does not take
-            got = (grad_outputs.t() @ inputs if need_w else None), (grad_outputs.sum(0) if need_b else None)
-        g_w, g_b = (got[0] if need_w else None), got[1]
-        if g_w is not None and (rows is not None or cols is not None):
-            g_w = g_w[:rows, :cols].contiguous()
-        if g_b is not None and rows is not None:
-            g_b = g_b[:rows].contiguous()
-        return g_w, g_b
-
+    wgrad = _linear_wgrad
     narrow = H if H != 128 else None
     tail = ()
     fused = gated = None
@@ -803,6 +806,62 @@ def _resnet_hidden_backward(ctx, g_out, saved_tensors, context=None):
         for q, (inp, g_o) in enumerate(hidden_problems):
             out += wgrad(inp, g_o, need[2 + 2 * q], need[3 + 2 * q], rows=narrow, cols=narrow)
     return tuple(out) + tuple(tail)
+
+
+class ResidualNetWide(torch.autograd.Function):
+    """K33: `ResidualNetHidden` for a ResidualNet of 129 .. 256 hidden units -- `nfa_resnet_wide_forward_f32` forward,
+    `nfa_resnet_wide_backward_f32` for the whole chain of input gradients (the final Linear's included), K10 for every
+    weight / bias gradient on the [B, Hp] arrays the two leave behind (Hp: the width padded to a multiple of 32, the pad
+    columns exact zeros).  Arguments as ResidualNetHidden's.  Deterministic."""
+
+    @staticmethod
+    def forward(ctx, x, with_final, *params):
+        from . import ops
+        hidden_params = params[:-2] if with_final else params
+        nb = (len(hidden_params) - 2) // 4
+        blocks = [hidden_params[2 + 4 * k: 6 + 4 * k] for k in range(nb)]
+        final = params[-2:] if with_final else None
+        ctx.di, ctx.nb, ctx.with_final, ctx.H = x.shape[1], nb, with_final, params[0].shape[0]
+        x = x.detach()
+        if ctx.di % 4:   # identity features in multiples of four (the packer pads W_in inside the streams)
+            x = torch.nn.functional.pad(x, (0, 4 - ctx.di % 4))
+        fwd_w, bias, bwd_w = ops.pack_resnet_wide_train(params[0], params[1], blocks, final)
+        hidden, saved, out = ops.resnet_wide_forward(x, fwd_w, bias, ctx.H, nb, final[0].shape[0] if with_final else 0)
+        ctx.save_for_backward(x.contiguous(), saved, bwd_w, hidden)
+        return out if with_final else hidden[:, :ctx.H]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out):
+        from . import ops
+        x, saved, bwd_w, hidden = ctx.saved_tensors
+        nb, H, Hp = ctx.nb, ctx.H, hidden.shape[1]
+        need = ctx.needs_input_grad[2:]
+        g_out = g_out.contiguous()
+        narrow = H if H != Hp else None
+        tail = ()
+        if ctx.with_final:
+            tail = _linear_wgrad(hidden, g_out, need[-2], need[-1], cols=narrow)
+        elif narrow is not None:
+            g_out = torch.nn.functional.pad(g_out, (0, Hp - H))
+        g_x, grads, g_hidden = ops.resnet_wide_backward(g_out, bwd_w, saved, x.shape[1], H, from_params=ctx.with_final)
+        di = ctx.di if ctx.di != x.shape[1] else None      # (x was saved with its pad columns)
+        out = [(g_x if di is None else g_x[:, :di]) if ctx.needs_input_grad[0] else None, None]
+        out += _linear_wgrad(x, grads[0] if nb else g_hidden, need[0], need[1], rows=narrow, cols=di)
+        # the 2 nb hidden Linears on the [B, Hp] planes: one launch pair of K10 when every gradient is wanted
+        problems = []
+        for k in range(nb):
+            problems += [(saved[2 * k], grads[2 * k + 1]), (saved[2 * k + 1], grads[2 * k + 2] if k + 1 < nb else g_hidden)]
+        batched = None
+        if nb and all(need[2:2 + 4 * nb]) and BATCHED_WGRAD:
+            batched = ops.linear_wgrad_batched(problems, need_bias=True)
+        if batched is not None:
+            for g_w, g_b in batched:
+                out += (g_w[:H, :H].contiguous(), g_b[:H].contiguous()) if narrow is not None else (g_w, g_b)
+        else:
+            for q, (inp, g_o) in enumerate(problems):
+                out += _linear_wgrad(inp, g_o, need[2 + 2 * q], need[3 + 2 * q], rows=narrow, cols=narrow)
+        return tuple(out) + tuple(tail)
 
 
 class MadeNet(torch.autograd.Function):

@@ -158,6 +158,12 @@ class _Net(nn.Module):
     # create_graph=True need it OFF), computes in fp32 whatever torch.autocast says, and does not run forward hooks of
     # the inner layers -- so it steps aside by itself while autocast is active or any inner module carries a hook.
     fuse_training = os.environ.get("NFA_K14", "1") != "0"
+    # K33, the same for hidden widths 129 .. 256 without a context: class-level default from NFA_K33 (0 = off; `fuse_training
+    # = False` switches it off as well), for batches of `fuse_wide_training_min_rows` .. `fuse_wide_training_max_rows` rows --
+    # the range tools/wide_train_time.py measured it faster than the eager modules in (DESIGN.md section 4 "K33").
+    fuse_wide_training = os.environ.get("NFA_K33", "1") != "0"
+    fuse_wide_training_min_rows = 1024
+    fuse_wide_training_max_rows = 262144
 
     def _build(self, n_in, n_out, width, context_width, num_blocks, activation, dropout_probability,
                use_batch_norm):
@@ -187,7 +193,15 @@ class _Net(nn.Module):
                 return False
         return True
 
-    def _fused_training(self, inputs, context):
+    def _fused_wide_training(self, inputs, context):
+        """K33 applies: what `_fused_training` asks of the net and the call, for the shapes
+        `ops.resnet_wide_train_supported` lists, no context, and a batch inside the measured range."""
+        return (getattr(self, "hidden_features", 0) > 128 and self.fuse_wide_training and context is None
+                and inputs.dim() == 2
+                and self.fuse_wide_training_min_rows <= inputs.shape[0] <= self.fuse_wide_training_max_rows
+                and self._fused_training(inputs, None, wide=True))
+
+    def _fused_training(self, inputs, context, wide=False):
         """K14 (one kernel for the hidden part's forward pass, one for its input gradients) applies: plain
         ResidualNet under autograd on the device, ReLU, no batch norm / active dropout, the shapes
         `ops.resnet_hidden_train_supported` lists; with a context (K27) what `_fusable_with_context` asks on top.  A net
@@ -201,7 +215,8 @@ class _Net(nn.Module):
             return False
         from ... import ops
         width = inputs.shape[1] + (context.shape[1] if context is not None else 0)
-        if not ops.resnet_hidden_train_supported(inputs.shape[0], width, self.hidden_features, len(self.blocks)):
+        supported = ops.resnet_wide_train_supported if wide else ops.resnet_hidden_train_supported
+        if not supported(inputs.shape[0], width, self.hidden_features, len(self.blocks)):
             return False
         w = self.initial_layer.weight
         if width != self.initial_layer.in_features or w.dtype != torch.float32 or w.device != inputs.device:
@@ -220,8 +235,10 @@ class _Net(nn.Module):
         planes = [F.linear(context, b.context_layer.weight, b.context_layer.bias) for b in self.blocks]
         return [F.pad(p, (0, pad)) for p in planes] if pad else planes
 
-    def _fused_apply(self, inputs, context, with_final, *tail):
+    def _fused_apply(self, inputs, context, with_final, *tail, wide=False):
         from ... import autograd as AG
+        if wide:
+            return AG.ResidualNetWide.apply(inputs, with_final, *self._hidden_parameters(), *tail)
         if context is None:
             return AG.ResidualNetHidden.apply(inputs, with_final, *self._hidden_parameters(), *tail)
         return AG.ResidualNetHiddenCtx.apply(torch.cat((inputs, context), dim=1), with_final, len(self.blocks),
@@ -230,6 +247,8 @@ class _Net(nn.Module):
     def hidden(self, inputs, context=None):
         """Activations in front of `final_layer` (the fused spline kernels K7 / K7b consume these
         and apply `final_layer` themselves)."""
+        if self._fused_wide_training(inputs, context):
+            return self._fused_apply(inputs, None, False, wide=True)
         if self._fused_training(inputs, context):
             return self._fused_apply(inputs, context, False)
         h = inputs if context is None else torch.cat((inputs, context), dim=1)
@@ -247,11 +266,12 @@ class _Net(nn.Module):
 
     def forward(self, inputs, context=None):
         final = self.final_layer
-        if (self._fused_training(inputs, context) and type(final) is nn.Linear and final.bias is not None
+        wide = self._fused_wide_training(inputs, context)
+        if ((wide or self._fused_training(inputs, context)) and type(final) is nn.Linear and final.bias is not None
                 and final.out_features % 4 == 0 and final.out_features <= 32768   # (the packer's / kernel's limit)
                 and final.in_features == self.hidden_features):
             # the whole conditioner's forward pass in one kernel (K14 with the final Linear appended)
-            return self._fused_apply(inputs, context, True, final.weight, final.bias)
+            return self._fused_apply(inputs, context, True, final.weight, final.bias, wide=wide)
         return apply_layer(final, self.hidden(inputs, context))
 
 

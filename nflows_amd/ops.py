@@ -2303,6 +2303,90 @@ def resnet_backward(grad_params, bwd_stages, saved, num_identity):
     return gx, grads, g_hidden
 
 
+# K33: K14's kernels for ResidualNet conditioners of 129 .. 256 hidden units (the switch NFA_K33 lives in nn/nets/resnet.py)
+def resnet_wide_train_supported(batch, num_identity, hidden_features, num_blocks):
+    """The shapes K33 takes (everything else keeps the eager path); the width is zero-padded to a multiple of 32."""
+    return (129 <= hidden_features <= 256 and 1 <= num_identity <= 64 and 0 <= num_blocks <= 3
+            and batch > 0 and batch % 64 == 0)   # (identity features: padded to a multiple of 4)
+
+
+def _wide_padded(hidden_features):
+    return (hidden_features + 31) // 32 * 32
+
+
+def pack_resnet_wide_train(w_in, b_in, block_params, final=None):
+    """K33's packer as one launch (nfa_pack_resnet_wide_train_f32; layout in include/nflows_amd.h): w_in [H, D] (D is
+    padded to a multiple of 4 inside the streams), b_in [H], block_params = [(W_0, b_0, W_1, b_1), ...], final = (W_f
+    [out, H], b_f [out]) or None.  Returns (forward fragments, biases, backward fragments)."""
+    dev = w_in.device
+    H, D, nb = w_in.shape[0], w_in.shape[1], len(block_params)
+    di = (D + 3) // 4 * 4
+    flat = [w_in.detach().contiguous(), b_in.detach().contiguous()]
+    for group in block_params:
+        flat += [t.detach().contiguous() for t in group]
+    fin = [t.detach().contiguous() for t in final] if final is not None else []
+    for t in flat + fin:
+        if t.dtype != torch.float32 or not t.is_cuda or t.device != dev:
+            raise TypeError("nflows_amd: the conditioner's parameters must be float32 tensors on one device")
+    out = fin[0].shape[0] if fin else 0
+    tiles, nks, init_ks, ft = _wide_padded(H) // 32, _wide_padded(H) // 16, 4 if di > 32 else 2, (out + 31) // 32
+    frag = 3 * 64 * 8   # bf16 values of one (column tile, k-step)
+    fwd = torch.empty((tiles * init_ks + 2 * nb * tiles * nks + ft * nks) * frag, dtype=torch.bfloat16, device=dev)
+    bwd = torch.empty((tiles * 2 * ft + 2 * nb * tiles * nks + (di + 31) // 32 * nks) * frag, dtype=torch.bfloat16, device=dev)
+    bias = torch.empty(32 * tiles * (1 + 2 * nb) + 32 * ft, dtype=torch.float32, device=dev)
+    ptrs = (ctypes.c_void_p * max(1, 4 * nb))(*[t.data_ptr() for t in flat[2:]])
+    _launch(dev, N.load().nfa_pack_resnet_wide_train_f32,
+            (N.ptr(flat[0]), N.ptr(flat[1]), ptrs, N.ptr(fin[0]) if fin else None, N.ptr(fin[1]) if fin else None, out, D,
+             di, H, nb, N.ptr(fwd), N.ptr(bias), N.ptr(bwd), N.stream_handle(dev)))
+    return fwd, bias, bwd
+
+
+def _aligned16(t):
+    t = t.detach().contiguous()
+    return t.clone() if t.data_ptr() % 16 else t
+
+
+def resnet_wide_forward(x, fwd_fragments, bias, hidden_features, num_blocks, out_features=0):
+    """K33 forward: identity features [B, d_i] (d_i % 4 == 0) -> (hidden [B, Hp], saved [2 num_blocks, B, Hp], params
+    [B, out_features] or None -- the conditioner's output when the final Linear was packed)."""
+    N.require_device_f32("inputs", x, 2)
+    x = _aligned16(x)
+    B, di = x.shape
+    dev = x.device
+    Hp = _wide_padded(hidden_features)
+    hidden = torch.empty(B, Hp, dtype=torch.float32, device=dev)
+    saved = torch.empty(2 * num_blocks, B, Hp, dtype=torch.float32, device=dev)
+    params = torch.empty(B, out_features, dtype=torch.float32, device=dev) if out_features else None
+    _launch(dev, N.load().nfa_resnet_wide_forward_f32,
+            (N.ptr(x), N.ptr(fwd_fragments), N.ptr(bias), N.ptr(saved) if num_blocks else None, N.ptr(hidden), N.ptr(params),
+             out_features, B, di, hidden_features, num_blocks, N.stream_handle(dev)))
+    return hidden, saved, params
+
+
+def resnet_wide_backward(grad, bwd_fragments, saved, num_identity, hidden_features, from_params=False):
+    """K33 backward from d loss / d hidden [B, Hp] or, `from_params`, d loss / d params [B, out] (`bwd_fragments` packed
+    with the final Linear): -> (d loss / d identity features [B, d_i], grads [2 nb, B, Hp], d loss / d hidden [B, Hp])."""
+    N.require_device_f32("grad", grad, 2)
+    g = _aligned16(grad)
+    B = g.shape[0]
+    dev = g.device
+    nb = saved.shape[0] // 2
+    Hp = _wide_padded(hidden_features)
+    if not from_params and g.shape[1] != Hp:
+        raise ValueError("grad_hidden must be [batch, %d], got %s" % (Hp, tuple(g.shape)))
+    if nb and (not saved.is_contiguous() or tuple(saved.shape) != (2 * nb, B, Hp)):
+        raise ValueError("`saved` must be the [2 num_blocks, batch, %d] tensor of resnet_wide_forward" % Hp)
+    grads = torch.empty(2 * nb, B, Hp, dtype=torch.float32, device=dev)
+    g_hidden = torch.empty(B, Hp, dtype=torch.float32, device=dev) if from_params else g
+    gx = torch.empty(B, num_identity, dtype=torch.float32, device=dev)
+    _launch(dev, N.load().nfa_resnet_wide_backward_f32,
+            (None if from_params else N.ptr(g), N.ptr(g) if from_params else None, g.shape[1] if from_params else 0,
+             N.ptr(bwd_fragments), N.ptr(saved) if nb else None, N.ptr(grads) if nb else None,
+             N.ptr(g_hidden) if from_params else None, N.ptr(gx), B, num_identity, hidden_features, nb,
+             N.stream_handle(dev)))
+    return gx, grads, g_hidden
+
+
 # K27: K14 / K10 for conditioners with a context (A/B switch: NFA_K27=0 keeps the eager modules whenever one is passed)
 CTX_TRAINING = os.environ.get("NFA_K27", "1") != "0"
 TRAIN_CTX_GLU, TRAIN_CTX_ADD = 1, 2     # include/nflows_amd.h: NFA_TRAIN_CTX_GLU / _ADD
