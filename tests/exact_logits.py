@@ -2,9 +2,12 @@
 
 A ResidualNet whose weights, biases and inputs are sparse dyadic numbers computes every intermediate exactly in fp32 --
 in any summation order and on every operand split of the whole-layer engines (two or three f16 pieces, three bf16
-pieces, fp32 FMA chains) -- as long as two conditions hold, which `exact_logits` checks on the actual data:
+pieces, fp32 FMA chains) -- as long as these conditions hold, which `exact_logits` checks on the actual data:
 
   * every GEMM operand (input, weight, activation) has at most 22 significant bits (two f16 pieces hold 22);
+  * the two factors of every product need at most four bf16 pieces together, at 8 significant bits a piece (the
+    three-piece bf16 engines keep the six products of pieces i + j <= 4).  A sufficient condition: round-to-nearest
+    splitting holds a bit more per piece;
   * every output of every Linear -- with q the common quantum of its terms (products, bias and, for the residual add,
     the block's input) -- has  sum |terms| + |bias| (+ |residual|) < 2^24 q:  every partial sum, in any order, is then a
     multiple of q below 2^24 q, i.e. representable in fp32.
@@ -27,6 +30,11 @@ The recipe (`dyadic_conditioner`):
 `spline_inputs` places the transformed features of every row on that row's own knots (the oracle's fp32 knots and one
 ulp on either side), at +-B and one ulp inside / outside, at +-1e30 and +-0.0, or uniformly inside the box; in the
 inverse direction on the height knots; with tails=None on the box's edges and the knots only.
+
+For K32 / K33 (conditioners 129 .. 256 wide, tests/wide_exact_cases.py): `dyadic_conditioner(fold_scale=True)` and
+`scaled_final` for widths whose 1 / sqrt(H) the packer folds into the final layer; `long_mantissa_conditioner`, a second
+recipe in which one factor of every product uses all three bf16 pieces; `exact_forward` (every intermediate) and
+`exact_backward` (the backward chain and every parameter gradient), each product under the same checks.
 """
 import math
 
@@ -55,10 +63,44 @@ def regime_of(feature):
     return REGIMES[feature % len(REGIMES)]
 
 
-def dyadic_conditioner(net, K, tails, seed=0, regimes=True, zero_initial=False):
+def pack_scaled(stored, hidden):
+    """ops.pack_resnet_conditioner_wide's expression for a width / height row of the final layer, on fp32 values `stored`:
+    (w.double() * (1.0 / math.sqrt(H))).float() -- the value K32 holds, as float64"""
+    s = np.asarray(stored, dtype=np.float32).astype(np.float64) * (1.0 / math.sqrt(hidden))
+    return s.astype(np.float32).astype(np.float64)
+
+
+def fold_store(v, hidden):
+    """float32(v sqrt(H)) for dyadic targets v, and whether the pack's own expression returns v exactly from it"""
+    stored = (np.asarray(v, dtype=np.float64) * math.sqrt(hidden)).astype(np.float32)
+    return stored.astype(np.float64), pack_scaled(stored, hidden) == np.asarray(v, dtype=np.float64)
+
+
+def _fold_draw(rng, shape, pool, hidden):
+    """dyadic targets drawn from `pool` (signed), restricted to the values that survive the round trip of `fold_store`"""
+    signed = np.concatenate([-np.asarray(pool, dtype=np.float64), np.asarray(pool, dtype=np.float64)])
+    good = signed[fold_store(signed, hidden)[1]]
+    assert good.size >= signed.size // 2, "folded scale: the pool of round-trip targets at width %d is too small" % hidden
+    return rng.choice(good, size=shape)
+
+
+def _fold_fixed(v, hidden):
+    """the dyadic target nearest `v` (steps of 1 / 8 away from zero) that survives the round trip"""
+    for step in range(64):
+        t = v + math.copysign(step / 8.0, v)
+        if fold_store(t, hidden)[1]:
+            return t
+    raise AssertionError("folded scale: no round-trip target near %r at width %d" % (v, hidden))
+
+
+def dyadic_conditioner(net, K, tails, seed=0, regimes=True, zero_initial=False, fold_scale=False):
     """Overwrites `net` (a ResidualNet [identity (+ context) -> dt * P]) with the recipe above; per transformed feature f
     the regime `regime_of(f)` (regimes=False: every feature "random").  `zero_initial`: the initial layer's weights are
-    zero (its output is its bias: the pass-through first layer of the two-layer run).  Returns `net`."""
+    zero (its output is its bias: the pass-through first layer of the two-layer run).  `fold_scale` (K32 at widths whose
+    square root is no power of two: the packer folds 1 / sqrt(H) into the final layer's width / height rows): those rows
+    are drawn as dyadic TARGETS v -- weights +-{1 .. 8} / 64, biases k / 16, the regimes' 1.5 and +-90 -- and stored as
+    float32(v sqrt(H)), only targets the packer's own expression maps back to v exactly (`fold_store`); the derivative
+    rows are not scaled and stay as they are.  `scaled_final` is then the final layer K32 holds.  Returns `net`."""
     import torch
     rng = np.random.RandomState(seed)
     P = params_per_feature(K, tails)
@@ -95,8 +137,122 @@ def dyadic_conditioner(net, K, tails, seed=0, regimes=True, zero_initial=False):
             elif r.startswith("d"):
                 wv[f, 2 * K:] = 0.0
                 bv[f, 2 * K:] = float(r[1:])
+        if fold_scale:
+            # (the plain recipe's width / height rows after their division by 8, as targets: k / 64 and k / 16)
+            nz = wv[:, :2 * K] != 0
+            wv[:, :2 * K][nz] = _fold_draw(rng, int(nz.sum()), np.arange(1, 9) / 64.0, H)
+            plain = np.ones((dt, 2 * K), bool)
+            for f in range(dt if regimes else 0):
+                r = regime_of(f)
+                if r == "equal":
+                    plain[f] = False
+                    bv[f, :2 * K] = _fold_fixed(1.5, H)
+                elif r in ("width_saturated", "height_saturated"):
+                    sat = np.abs(bv[f, :2 * K]) == SAT
+                    plain[f, sat] = False
+                    bv[f, :2 * K][sat] = [_fold_fixed(math.copysign(SAT / 8, t), H) for t in bv[f, :2 * K][sat]]
+            bv[:, :2 * K][plain] = _fold_draw(rng, int(plain.sum()), np.arange(0, 5) / 16.0, H)
+            for part in (wv, bv):       # targets -> what the net stores; every stored entry makes the round trip
+                stored, ok = fold_store(part[:, :2 * K], H)
+                assert ok.all(), "folded scale: %d entries do not survive the pack's expression" % int((~ok).sum())
+                part[:, :2 * K] = stored
         net.final_layer.weight.copy_(torch.from_numpy(w))
         net.final_layer.bias.copy_(torch.from_numpy(b))
+    return net
+
+
+def scaled_final(net, K, tails):
+    """(weight, bias) of the final layer as K32 holds them (float64 copies of the fp32 values): the width / height rows
+    through `pack_scaled`, the derivative rows as stored.  Logits computed with these are the kernel's own: the oracle is
+    then called with hidden = 1 (a divisor of 1)."""
+    P = params_per_feature(K, tails)
+    H = net.hidden_features
+    w = net.final_layer.weight.detach().cpu().numpy().astype(np.float64).reshape(-1, P, H).copy()
+    b = net.final_layer.bias.detach().cpu().numpy().astype(np.float64).reshape(-1, P).copy()
+    w[:, :2 * K] = pack_scaled(w[:, :2 * K], H)
+    b[:, :2 * K] = pack_scaled(b[:, :2 * K], H)
+    return w.reshape(-1, H), b.reshape(-1)
+
+
+# ---- the long-mantissa recipe ---------------------------------------------------------------------------------------
+# The recipe above has few significant bits per value: the middle and low bf16 pieces of every operand are zero, and a
+# kernel that dropped or misplaced a low piece would still be exact on it.  Here every GEMM product has ONE factor of 20 ..
+# 22 significant bits -- all three bf16 pieces nonzero -- and a signed power of two as the other, one nonzero per weight
+# row, so that every output is a single product (+ bias + residual).  All long values lie on one grid, U = 2^-20 (U / 8
+# inside a block), below 2^20 U in the first layer: each residual add may gain one bit, two blocks end below 2^22 U.
+#   inputs: column j holds +-2^e_j (`long_identity_rows`);
+#   stream units of class A (long) and B (i % 4 == 3: a power of two 2^c_i, the same through all blocks);
+#   initial layer: A rows n U 2^-e_j (n odd, 2^19 < n < 2^20 - 2^12: the WEIGHT is the long side), bias k U; B rows a power
+#     of two, bias 0;
+#   block, first Linear (onto the grid U / 8): rows r % 4 == 0 read a B unit with a long weight n U 2^-3 2^-c (weight long);
+#     r % 4 in (1, 2) read an A unit with +-2^-3 (ACTIVATION long); r % 4 == 3 read a B unit with a negative power of two:
+#     never positive, zero behind the ReLU; biases k U / 8 (0 for the last kind);
+#   block, second Linear: A rows read a unit of the first two kinds with +-2^3 (activation long), bias k U; B rows read a
+#     unit of the last kind: their branch is 0 and the unit stays a power of two;
+#   final layer: one A unit per row with +-2^e (width / height rows +-{2, 4, 8}: at most 2 after the division by 16 at 256
+#     hidden units; derivative rows +-{1, 2}), bias k / 2.
+LONG_UNIT = 2.0 ** -20
+
+
+def long_identity_rows(rows, features, seed):
+    """identity features of the long-mantissa recipe: column j holds +-2^(j % 5 - 2), the sign drawn per element"""
+    rng = np.random.RandomState(seed)
+    return rng.choice((-1.0, 1.0), size=(rows, features)) * np.exp2(np.arange(features) % 5 - 2.0)[None, :]
+
+
+def long_mantissa_conditioner(net, K, tails, seed=0):
+    """Overwrites `net` (a ResidualNet without context, at most two blocks) with the long-mantissa recipe; Returns `net`."""
+    import torch
+    rng = np.random.RandomState(seed)
+    P = params_per_feature(K, tails)
+    H, di = net.hidden_features, net.initial_layer.in_features
+    U = LONG_UNIT
+    unit_b = np.arange(H) % 4 == 3                          # class B stream units
+    c = rng.randint(-1, 2, H).astype(np.float64)            # their exponents
+    a_units, b_units = np.flatnonzero(~unit_b), np.flatnonzero(unit_b)
+    sign = lambda n: rng.choice((-1.0, 1.0), size=n)
+
+    def long(n):    # odd integers of exactly 20 bits, below 2^20 - 2^12
+        return (rng.randint(2 ** 18, 2 ** 19 - 2 ** 11, n) * 2 + 1).astype(np.float64)
+    with torch.no_grad():
+        w, b = np.zeros((H, di)), np.zeros(H)
+        j = rng.randint(0, di, H)
+        e = np.arange(di) % 5 - 2.0
+        w[a_units, j[a_units]] = sign(a_units.size) * long(a_units.size) * U * np.exp2(-e[j[a_units]])
+        b[a_units] = rng.randint(-8, 9, a_units.size) * U
+        w[b_units, j[b_units]] = sign(b_units.size) * np.exp2(c[b_units] - e[j[b_units]])
+        net.initial_layer.weight.copy_(torch.from_numpy(w))
+        net.initial_layer.bias.copy_(torch.from_numpy(b))
+        kind = np.arange(H) % 4                             # of the first Linear's rows
+        live = np.flatnonzero(kind != 3)
+        dead = np.flatnonzero(kind == 3)
+        for block in net.blocks:
+            w, b = np.zeros((H, H)), np.zeros(H)
+            for r in range(H):
+                if kind[r] == 0:
+                    u = rng.choice(b_units)
+                    w[r, u] = sign(1)[0] * long(1)[0] * U / 8 * np.exp2(-c[u])
+                elif kind[r] == 3:
+                    u = rng.choice(b_units)
+                    w[r, u] = -np.exp2(-3.0 - c[u])
+                else:
+                    w[r, rng.choice(a_units)] = sign(1)[0] / 8
+            b[kind != 3] = rng.randint(-8, 9, live.size) * U / 8
+            block.linear_layers[0].weight.copy_(torch.from_numpy(w))
+            block.linear_layers[0].bias.copy_(torch.from_numpy(b))
+            w, b = np.zeros((H, H)), np.zeros(H)
+            for i in range(H):
+                w[i, rng.choice(dead if unit_b[i] else live)] = sign(1)[0] * 8
+            b[a_units] = rng.randint(-8, 9, a_units.size) * U
+            block.linear_layers[1].weight.copy_(torch.from_numpy(w))
+            block.linear_layers[1].bias.copy_(torch.from_numpy(b))
+        out = net.final_layer.out_features
+        w = np.zeros((out, H))
+        wide = (np.arange(out) % P) < 2 * K                 # width / height rows
+        mag = np.where(wide, np.exp2(rng.randint(1, 4, out)), np.exp2(rng.randint(0, 2, out)))
+        w[np.arange(out), rng.choice(a_units, size=out)] = sign(out) * mag
+        net.final_layer.weight.copy_(torch.from_numpy(w))
+        net.final_layer.bias.copy_(torch.from_numpy(rng.randint(-4, 5, out) / 2.0))
     return net
 
 
@@ -141,11 +297,19 @@ def _exact_linear(a, w, b, what, residual=None, chunk=256):
     width = max(1, max(len(j) for j in nz))
     cols = np.zeros((w.shape[0], width), dtype=np.int64)
     lq_w = np.full((w.shape[0], width), np.inf)
+    pieces_w = np.zeros((w.shape[0], width))
     for i, j in enumerate(nz):
         cols[i, :len(j)] = j
         lq_w[i, :len(j)] = _log2_quantum(w[i, j])
+        pieces_w[i, :len(j)] = np.ceil(significant_bits(w[i, j]) / 8.0)
     for s in range(0, a.shape[0], chunk):
         aa = a[s:s + chunk]
+        # the six-product engines (three bf16 pieces per operand, the products (i, j) with i + j <= 4 kept: K8, K32, K33,
+        # K10) hold a product exactly iff the pieces its two factors need (8 significant bits each) are at most 4 together
+        pieces = np.ceil(significant_bits(aa) / 8.0)[:, cols]
+        both = (pieces > 0) & (pieces_w[None] > 0)
+        assert not both.any() or float((pieces + pieces_w[None])[both].max()) <= 4, (
+            "%s: a product whose factors need more than four bf16 pieces together" % what)
         total = np.abs(aa) @ np.abs(w).T + np.abs(b)
         # (the quantum of a product of dyadics is the product of their quanta)
         lq = np.minimum((_log2_quantum(aa)[:, cols] + lq_w[None]).min(axis=2), lq_b[None, :])
@@ -160,23 +324,87 @@ def _exact_linear(a, w, b, what, residual=None, chunk=256):
     return out
 
 
-def exact_logits(net, identity, context=None):
-    """The conditioner's output for `identity` rows ([rows, identity features], dyadic) -- checked to be exact in fp32
-    in any evaluation order -- as float64 [rows, out_features] (raw: the width / height entries NOT divided)."""
+def exact_forward(net, identity, context=None, final=None, with_final=True):
+    """Every intermediate of the conditioner for `identity` rows ([rows, identity features], dyadic), each checked to be
+    exact in fp32 in any evaluation order: {"x", "hidden" (the input of the final layer), "saved" (relu(h_k), relu(a_k)
+    per block: the planes K33 leaves behind), "params" (the final layer's output, raw)}, float64.  `final`: (weight,
+    bias) in place of the net's final layer (`scaled_final`)."""
     sd = {k: v.detach().double().cpu().numpy() for k, v in net.state_dict().items()}
     a = np.asarray(identity, dtype=np.float64)
     if context is not None:
         a = np.concatenate([a, np.asarray(context, dtype=np.float64)], axis=1)
     h = _exact_linear(a, sd["initial_layer.weight"], sd["initial_layer.bias"], "initial layer")
+    saved = []
     for i, block in enumerate(net.blocks):
         p = "blocks.%d." % i
-        t = _exact_linear(np.maximum(h, 0.0), sd[p + "linear_layers.0.weight"], sd[p + "linear_layers.0.bias"], p + "0")
+        s0 = np.maximum(h, 0.0)
+        t = _exact_linear(s0, sd[p + "linear_layers.0.weight"], sd[p + "linear_layers.0.bias"], p + "0")
         t = np.maximum(t, 0.0)
+        saved += [s0, t]
         if getattr(block, "context_layer", None) is not None:
             gate = np.asarray(context, dtype=np.float64) @ sd[p + "context_layer.weight"].T + sd[p + "context_layer.bias"]
             assert gate.min() >= 40.0, "the GLU gate must be exactly 1 in fp32 (sigmoid of >= 40)"
         h = _exact_linear(t, sd[p + "linear_layers.1.weight"], sd[p + "linear_layers.1.bias"], p + "1", residual=h)
-    return _exact_linear(h, sd["final_layer.weight"], sd["final_layer.bias"], "final layer")
+    wf, bf = final if final is not None else (sd["final_layer.weight"], sd["final_layer.bias"])
+    params = _exact_linear(h, wf, bf, "final layer") if with_final else None
+    return {"x": a, "hidden": h, "saved": saved, "params": params}
+
+
+def exact_logits(net, identity, context=None, final=None):
+    """The conditioner's output for `identity` rows ([rows, identity features], dyadic) -- checked to be exact in fp32
+    in any evaluation order -- as float64 [rows, out_features] (raw: the width / height entries NOT divided; with
+    `final` = `scaled_final(net, K, tails)` the logits K32 holds, already scaled)."""
+    return exact_forward(net, identity, context, final)["params"]
+
+
+def _exact_sum(a, b, what):
+    """a + b, ONE addition (how the backward chain joins a block's branch with the stream): exact iff representable"""
+    out = a + b
+    _check_operand(out, what)
+    assert np.array_equal(out.astype(np.float32).astype(np.float64), out), what
+    return out
+
+
+def exact_backward(net, forward, g, weight_grads=True, with_final=True):
+    """The backward chain of the conditioner (no context) on the exact forward intermediates `forward` (`exact_forward`)
+    and a dyadic `g` (d loss / d params [rows, out]; with_final=False: d loss / d hidden [rows, H]), as K33 writes it
+    (tests/test_gpu_wide_train.py `chain`): {"g_hidden", "grads" (grads[2 k + 1] = (g_h W_1) . [a_k > 0], grads[2 k] =
+    g_h += (grads[2 k + 1] W_0) . [h_k > 0]), "g_x", and with `weight_grads` "param_grads": {state_dict name: gradient}
+    of every weight (g_out^T input, the [H, B] x [B, H] product over the rows) and bias (column sums)}.  Every product is
+    checked by `_exact_linear` (transposed weights; dense operands for the weight gradients); the ReLU masks are the
+    exact forward values'."""
+    sd = {k: v.detach().double().cpu().numpy() for k, v in net.state_dict().items()}
+    g = np.asarray(g, dtype=np.float64)
+    nb = len(net.blocks)
+    saved = forward["saved"]
+
+    def through(grad, w, what):     # grad [rows, out] @ w [out, in]
+        return _exact_linear(grad, np.ascontiguousarray(w.T), np.zeros(w.shape[1]), what)
+    g_hidden = through(g, sd["final_layer.weight"], "final layer backward") if with_final else g
+    g_h, grads = g_hidden, [None] * (2 * nb)
+    for k in reversed(range(nb)):
+        p = "blocks.%d.linear_layers." % k
+        grads[2 * k + 1] = through(g_h, sd[p + "1.weight"], p + "1 backward") * (saved[2 * k + 1] > 0)
+        g_h = _exact_sum(g_h, through(grads[2 * k + 1], sd[p + "0.weight"], p + "0 backward") * (saved[2 * k] > 0),
+                         "blocks.%d stream gradient" % k)
+        grads[2 * k] = g_h
+    out = {"g_hidden": g_hidden, "grads": grads, "g_x": through(g_h, sd["initial_layer.weight"], "initial layer backward")}
+    if weight_grads:
+        def wgrad(name, g_out, inp):
+            ones = np.ones((1, g_out.shape[0]))
+            out["param_grads"][name + ".weight"] = _exact_linear(
+                np.ascontiguousarray(g_out.T), np.ascontiguousarray(inp.T), np.zeros(inp.shape[1]), name + " weight gradient",
+                chunk=16)
+            out["param_grads"][name + ".bias"] = _exact_linear(
+                np.ascontiguousarray(g_out.T), ones, np.zeros(1), name + " bias gradient")[:, 0]
+        out["param_grads"] = {}
+        wgrad("initial_layer", grads[0] if nb else g_hidden, forward["x"])
+        for k in range(nb):
+            wgrad("blocks.%d.linear_layers.0" % k, grads[2 * k + 1], saved[2 * k])
+            wgrad("blocks.%d.linear_layers.1" % k, grads[2 * k + 2] if k + 1 < nb else g_hidden, saved[2 * k + 1])
+        if with_final:
+            wgrad("final_layer", g, forward["hidden"])
+    return out
 
 
 def divided(logits, K, tails, hidden=HIDDEN):

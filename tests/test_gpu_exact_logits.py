@@ -62,26 +62,28 @@ def _engine(name, K):
     return _nsf_engines(K)[name]
 
 
-def _case(K, tails="linear", context=False, hidden=X.HIDDEN, variant=""):
-    """flow (CPU) with the dyadic conditioner, its exact logits, inputs and the oracle, per direction.  `variant`: "" (one
-    layer, D = 64), "odd" (one layer, D = 62: 31 transformed features, a padded group), "two_layer" (D = 64: a
-    pass-through layer, a permutation, the layer under test).  Inputs and results in the coordinates of the layer under
-    test (`perm`: its input column j is the flow's column perm[j])."""
-    key = (K, tails, context, hidden, variant)
-    if key in _cases:
-        return _cases[key]
+def _flow(K, tails="linear", context=False, hidden=X.HIDDEN, variant="", num_blocks=2, features=None, recipe="dyadic",
+          regimes=True):
+    """(flow on the CPU, the layer under test, perm, D, fold) of a case: see `_case`"""
     from nflows_amd.distributions import StandardNormal
     from nflows_amd.flows import Flow
     from nflows_amd.nn.nets import ResidualNet
     from nflows_amd.transforms import CompositeTransform, Permutation
     from nflows_amd.transforms import PiecewiseRationalQuadraticCouplingTransform as RQ
-    D = 62 if variant == "odd" else 64
+    D = features or (62 if variant == "odd" else 64)
     C = CONTEXT if context else None
+    # K32 folds 1 / sqrt(hidden) into the final layer at pack time: a power of two at 256 (and the kernels that divide do
+    # so at run time: 64, 128 as before); the other widths take the recipe whose SCALED rows are dyadic
+    fold = hidden > 128 and hidden != 256
 
     def make(mask, seed, zero_initial=False):
-        layer = RQ(mask, lambda i, o: ResidualNet(i, o, hidden_features=hidden, context_features=C, num_blocks=2), num_bins=K,
-                   tails=tails, tail_bound=X.TAIL_BOUND)
-        X.dyadic_conditioner(layer.transform_net, K, tails, seed=seed, zero_initial=zero_initial)
+        layer = RQ(mask, lambda i, o: ResidualNet(i, o, hidden_features=hidden, context_features=C, num_blocks=num_blocks),
+                   num_bins=K, tails=tails, tail_bound=X.TAIL_BOUND)
+        if recipe == "long":
+            X.long_mantissa_conditioner(layer.transform_net, K, tails, seed=seed)
+        else:
+            X.dyadic_conditioner(layer.transform_net, K, tails, seed=seed, zero_initial=zero_initial, regimes=regimes,
+                                 fold_scale=fold)
         return layer
     mask = torch.ones(D)
     mask[::2] = -1
@@ -96,19 +98,43 @@ def _case(K, tails="linear", context=False, hidden=X.HIDDEN, variant=""):
     else:
         layer = make(mask, seed=100 + K)
         transform = CompositeTransform([layer])
-    flow = Flow(transform, StandardNormal([D])).eval()
+    return Flow(transform, StandardNormal([D])).eval(), layer, perm, D, fold
+
+
+def _identity(K, variant, recipe, count, inverse):
+    """the identity features [ROWS, count] of a case's direction"""
+    if recipe == "long":
+        return X.long_identity_rows(ROWS, count, seed=K + 3 * inverse)
+    if variant == "two_layer":      # dyadic values in (B, B + 1]
+        return X.TAIL_BOUND + X.identity_rows(ROWS, count, seed=K + 3 * inverse, low=1, high=4)
+    return X.identity_rows(ROWS, count, seed=K + 3 * inverse)
+
+
+def _case(K, tails="linear", context=False, hidden=X.HIDDEN, variant="", **more):
+    """flow (CPU) with the dyadic conditioner, its exact logits, inputs and the oracle, per direction.  `variant`: "" (one
+    layer, D = 64), "odd" (one layer, D = 62: 31 transformed features, a padded group), "two_layer" (D = 64: a
+    pass-through layer, a permutation, the layer under test).  Inputs and results in the coordinates of the layer under
+    test (`perm`: its input column j is the flow's column perm[j]).  `more` (K32's cases, tests/test_gpu_wide_exact.py):
+    num_blocks, features (D), recipe ("dyadic" / "long": exact_logits' long-mantissa recipe), regimes, reseed; widths above 128
+    other than 256 take the folded-scale recipe, their logits are the SCALED ones and the oracle's divisor is 1."""
+    key = (K, tails, context, hidden, variant) + tuple(sorted(more.items()))
+    if key in _cases:
+        return _cases[key]
+    reseed = more.get("reseed", 0)   # (another draw of the inputs: tests/wide_exact_cases.py says when and why)
+    flow, layer, perm, D, fold = _flow(K, tails, context, hidden, variant, **{k: v for k, v in more.items() if k != "reseed"})
+    recipe = more.get("recipe", "dyadic")
+    C = CONTEXT if context else None
     ti, ii = layer.transform_features.numpy(), layer.identity_features.numpy()
     Pn = X.params_per_feature(K, tails)
-    case = {"flow": flow, "ti": ti, "ii": ii, "hidden": hidden, "perm": perm, "D": D}
+    case = {"flow": flow, "ti": ti, "ii": ii, "hidden": hidden, "perm": perm, "D": D, "fold": fold}
+    final = X.scaled_final(layer.transform_net, K, tails) if fold else None
+    hidden = 1 if fold else hidden      # (the oracle's divisor: the folded recipe's logits are already scaled)
     ctx = X.identity_rows(ROWS, C, seed=K + 7) if context else None
     case["context"] = None if ctx is None else torch.from_numpy(ctx.astype(np.float32))
     for inverse in (False, True):
-        if variant == "two_layer":      # dyadic values in (B, B + 1]
-            ident = X.TAIL_BOUND + X.identity_rows(ROWS, len(ii), seed=K + 3 * inverse, low=1, high=4)
-        else:
-            ident = X.identity_rows(ROWS, len(ii), seed=K + 3 * inverse)
-        raw = X.exact_logits(layer.transform_net, ident, ctx).reshape(ROWS, len(ti), Pn)
-        xt = X.spline_inputs(raw, K, tails, inverse, seed=K + 11 * inverse, hidden=hidden,
+        ident = _identity(K, variant, recipe, len(ii), inverse)
+        raw = X.exact_logits(layer.transform_net, ident, ctx, final).reshape(ROWS, len(ti), Pn)
+        xt = X.spline_inputs(raw, K, tails, inverse, seed=K + 11 * inverse + 1000 * reseed, hidden=hidden,
                              outside_rows=OUTSIDE_ROWS if tails == "linear" else (), huge_rows=np.arange(ROWS) < HUGE_ROWS)
         if tails is None and inverse:
             # (tails=None raises the reference's assertion on a discriminant rounded below zero, rational_quadratic.py:142,

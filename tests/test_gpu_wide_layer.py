@@ -1,7 +1,8 @@
 """K32 on the device (csrc/rqs_resnet_wide_kernel.hpp, ops.rqs_coupling_resnet_wide): spline coupling layers whose ResidualNet
 conditioner is 129 .. 256 units wide, in one launch.  Truth: oracle/eager.py's stock-torch expressions on a float64 copy of
 the modules on the CPU; yardstick: the same in float32.  The project's parity rule (tests/test_gpu_steep.py) with no element
-exempt: mean and 99.9 % quantile of the error against the truth at most 2 x the yardstick's, the maximum at most 4 x."""
+exempt: mean and 99.9 % quantile of the error against the truth at most 2 x the yardstick's, the maximum at most 4 x.
+Per element on logits known bit for bit, every instance, knots / +-B / +-1e30 / outside-box inputs: tests/test_gpu_wide_exact.py."""
 import copy
 
 import numpy as np

@@ -1,7 +1,8 @@
 """K33 on the device (csrc/resnet_train_wide.hip, autograd.ResidualNetWide): training ResidualNet conditioners of 129 .. 256
 hidden units.  Truth: the same chain of torch.nn.functional.linear in float64 on the CPU; yardstick: in float32.  The
 project's parity rule (tests/test_gpu_wide_layer.py) with no element exempt: mean and 99.9 % quantile of the error against
-the truth at most 2 x the yardstick's, no element above 4 x its maximum, everything finite, pad columns exactly zero."""
+the truth at most 2 x the yardstick's, no element above 4 x its maximum, everything finite, pad columns exactly zero.
+Bit for bit on dyadic data (chunk edges 256 / 257, d_i = 33, the class path's parameter gradients): tests/test_gpu_wide_train_exact.py."""
 import copy
 
 import numpy as np
