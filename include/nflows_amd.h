@@ -64,7 +64,9 @@ extern "C" {
                               still 19: nfa_rqs_layer_resnet_wide_f32 (K32) is an ADDED entry point, for the same reason (its
                               blobs are its own);
                               still 19: nfa_pack_resnet_wide_train_f32, nfa_resnet_wide_forward_f32, nfa_resnet_wide_backward_f32
-                              (K33) are ADDED entry points, for the same reason (their streams are their own) */
+                              (K33) are ADDED entry points, for the same reason (their streams are their own);
+                              still 19: nfa_rqs_layer_made_wide_f32 (K34) is an ADDED entry point, for the same reason (its blobs
+                              are K32's fragments of a MADE's masked weights) */
 
 /* return codes */
 #define NFA_OK 0
@@ -337,6 +339,37 @@ int nfa_rqs_layer_resnet_wide_f32(const float *inputs, const void *weights_packe
                                   int64_t batch, int32_t features, int32_t num_transform, int32_t num_identity,
                                   int32_t hidden_features, int32_t num_blocks, const nfa_rqs_spec *spec, int32_t flags,
                                   void *stream);
+
+/*
+ * K34: the density pass of ONE masked autoregressive rational-quadratic spline layer (autoregressive.py:404-495) whose MADE
+ * (made.py:233-311) is wider than the 128 hidden units of nfa_rqs_flow_made_f32, in one launch
+ * (csrc/made_rqs_wide_kernel.hpp).  K32's work split and arithmetic (one workgroup of eight waves per CU on 64 rows, the
+ * hidden GEMMs split by columns, three bf16 pieces per operand: the full fp32 range, no redo pass); every feature is read by
+ * the conditioner and transformed, so the arguments are K32's without the identity / transform split.
+ *   row_length         columns of a row: `features` rounded up to a multiple of 4 (the pad columns pass through), <= 64.
+ *   hidden_features    1 .. 256; the blobs are packed for Hp = hidden_features rounded up to a multiple of 32, extra units zero.
+ *   num_hidden_layers  hidden Linears: twice the number of residual blocks (NFA_FLAG_RESIDUAL_BLOCKS:
+ *                      h += W_1 relu(W_0 relu(h) + b_0) + b_1), or the number of feed-forward blocks (h = relu(W h + b) behind
+ *                      h = relu(W_i x + b_i)).
+ *   weights_packed     K32's fragments of `weight * mask` (masked-out weights are exact zeros in all three pieces), ordered
+ *                      [GEMM][32-row tile][k-step][piece]: the initial layer (Hp / 32 tiles, ceil(features / 16) k-steps, input
+ *                      column k = feature k), the hidden Linears (input columns in accumulator order), the final Linear
+ *                      (ceil(features / 2) x T tiles, T = ceil((3 K - 1) / 16): the T tiles of pair g give lane-half h the
+ *                      zero-padded logits of feature 2 g + h -- zero rows for the missing second feature of an odd count; width
+ *                      and height rows scaled by 1 / sqrt(hidden_features) where the layer divides them).
+ *   bias_packed        fp32 in accumulator order ([tile][lane-half][16]) in the same GEMM order.
+ *   layer_tables       int32 [256] as for nfa_rqs_coupling_resnet_f32, every feature in both halves.
+ * Supported: the forward pass, 2 .. 16 bins, linear tails, ReLU, no context, features <= 64, row_length % 4 == 0,
+ * batch % 128 == 0, flags NFA_FLAG_RESIDUAL_BLOCKS | NFA_FLAG_ACCUMULATE_LOGABSDET; otherwise (hidden_features > 256,
+ * NFA_FLAG_INVERSE, the density flags, tails=None, ...) NFA_ERR_UNSUPPORTED, after the argument errors (callers then run the
+ * MADE's GEMMs and K13 / K1).  batch == 0 returns NFA_OK.  A row's logabsdet is summed in an order the shape fixes: the
+ * same bits for any batch and grid.  Added under ABI 19 (see NFA_ABI_VERSION): no existing entry point, flag set or packed
+ * layout changes.
+ */
+int nfa_rqs_layer_made_wide_f32(const float *inputs, const void *weights_packed, const float *bias_packed,
+                                const int32_t *layer_tables, float *outputs, float *logabsdet, int32_t *status,
+                                int64_t batch, int32_t row_length, int32_t features, int32_t hidden_features,
+                                int32_t num_hidden_layers, const nfa_rqs_spec *spec, int32_t flags, void *stream);
 
 /*
  * K8 over a run of layers.  Rows of a flow are independent, so num_layers coupling layers of the

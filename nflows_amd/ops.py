@@ -3187,6 +3187,62 @@ def rqs_coupling_resnet_wide(inputs, weights_packed, bias_packed, tables, num_tr
     return _whole_layer_launch(launch, inputs, inverse, accumulate_into, False, pad, spec=spec, redo=None)
 
 
+def pack_made_rqs_conditioner_wide(net, num_bins):
+    """A MADE without context and with 3 K - 1 outputs per feature, 129 .. 256 hidden units wide (any width up to 256 packs),
+    for K34 (layout in include/nflows_amd.h, nfa_rqs_layer_made_wide_f32): K32's fragments (`_wide_fragments`) of
+    `weight * mask` -- a masked-out weight is an exact zero in all three pieces --, the hidden width zero-padded to Hp, a
+    multiple of 32; the final layer's rows per feature padded to 16 T (`made_rqs_tiles`) and the features to pairs (zero
+    rows), in `_k8_row_order_32(tiles_per_group=T)` order, the width / height rows times 1 / sqrt(net.hidden_features)
+    where the net exposes it (as `pack_made_rqs_conditioner`); all biases in accumulator order.  Returns (weights bf16,
+    biases fp32)."""
+    K, P = num_bins, 3 * num_bins - 1
+    linears, final = _made_linears(net), net.final_layer
+    H, features = linears[0].weight.shape
+    if final.weight.shape[0] != features * P:
+        raise ValueError("the MADE's final layer must have 3 * num_bins - 1 rows per feature")
+    T = made_rqs_tiles(K)
+    pairs = (features + 1) // 2
+    dev = final.weight.device
+    Hp = (H + 31) // 32 * 32
+    order_k = _wide_column_order(Hp).to(dev)
+
+    def masked(lin):
+        return (lin.weight.detach() * lin.mask).float()
+    blobs = [_wide_fragments(_pad_to(masked(linears[0]), rows=Hp, cols=16 * ((features + 15) // 16)))]
+    biases = [_bias_accumulator_order(_pad_to(linears[0].bias.detach().float(), rows=Hp))]
+    for lin in linears[1:]:
+        blobs.append(_wide_fragments(_pad_to(masked(lin), rows=Hp, cols=Hp).index_select(1, order_k)))
+        biases.append(_bias_accumulator_order(_pad_to(lin.bias.detach().float(), rows=Hp)))
+    scale = torch.ones(P, dtype=torch.float64, device=dev)
+    if hasattr(net, "hidden_features"):
+        scale[:2 * K] = 1.0 / math.sqrt(net.hidden_features)
+    wf = (masked(final).double().view(features, P, H) * scale[None, :, None]).float()
+    bf = (final.bias.detach().double().view(features, P) * scale[None, :]).float()
+    wfull = wf.new_zeros(2 * pairs, 16 * T, Hp)
+    wfull[:features, :P, :H] = wf
+    bfull = bf.new_zeros(2 * pairs, 16 * T)
+    bfull[:features, :P] = bf
+    order_r = _k8_row_order_32(2 * pairs, T).to(dev)
+    blobs.append(_wide_fragments(wfull.reshape(-1, Hp).index_select(0, order_r).index_select(1, order_k)))
+    biases.append(_bias_accumulator_order(bfull.reshape(-1).index_select(0, order_r)))
+    return torch.cat(blobs).contiguous(), torch.cat(biases).contiguous()
+
+
+def rqs_flow_made_wide(inputs, weights_packed, bias_packed, tables, features, hidden_features, num_hidden_layers, spec,
+                       accumulate_into=None, pad=None, residual_blocks=True):
+    """K34 -- the density pass of one masked autoregressive rational-quadratic spline layer with a MADE of 129 .. 256
+    hidden units in one kernel (`pack_made_rqs_conditioner_wide`; tables from `coupling_layer_tables` with every feature in
+    both halves; rows padded to a multiple of four columns by `pad`, see `_whole_layer_launch`).  `num_hidden_layers`: the
+    hidden Linears (twice the number of residual blocks, or the number of feed-forward blocks).  Forward only.  Returns
+    (outputs, logabsdet), or None when the shape is outside the kernel's family."""
+    def launch(x, ctx, out, lad, redo, flags, status, stream):
+        return N.load().nfa_rqs_layer_made_wide_f32(
+            N.ptr(x), N.ptr(weights_packed), N.ptr(bias_packed), N.ptr(tables), N.ptr(out), N.ptr(lad), status, x.shape[0],
+            x.shape[1], features, hidden_features, num_hidden_layers, ctypes.byref(spec), flags, stream)
+    return _whole_layer_launch(launch, inputs, False, accumulate_into, False, pad,
+                               flags=N.FLAG_RESIDUAL_BLOCKS if residual_blocks else 0, spec=spec)
+
+
 _ACTIVATION_CODES = {id(torch.nn.functional.relu): N.ACTIVATION_RELU, id(torch.relu): N.ACTIVATION_RELU,
                      id(torch.nn.functional.leaky_relu): N.ACTIVATION_LEAKY_RELU, id(torch.nn.functional.elu): N.ACTIVATION_ELU,
                      id(torch.tanh): N.ACTIVATION_TANH, id(torch.nn.functional.tanh): N.ACTIVATION_TANH}

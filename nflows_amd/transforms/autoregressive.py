@@ -563,6 +563,65 @@ class MaskedPiecewiseRationalQuadraticAutoregressiveTransform(_MadeKernelLayer):
     def _own_call_served(self, inputs, context):
         return context is None or context.shape[0] == inputs.shape[0]
 
+    # ---- whole-layer kernel K34 (csrc/made_rqs_wide_kernel.hpp): the density pass of ONE layer whose MADE is 129 .. 256
+    #      hidden units wide in one launch -- K32's column split with a MADE's dataflow.  The layer is a run of one:
+    #      `_run_kind` stays None at these widths (no runs of layers, no folded base density), and the inverse, a context,
+    #      training and float64 keep the paths they had.  Class-level switch, NFA_K34=0 = off; 8-bin layers obey K29's mode
+    #      rule as well (`fuse_conditioner` >= 2: existing tests pin hidden GEMMs + K13 there).
+    fuse_wide_conditioner = os.environ.get("NFA_K34", "1") != "0"
+    # K34's size rule (DESIGN.md section 4 "K34"): measured faster at every size from 1 024 rows up (1.2-3.0 x); fewer rows
+    # were not measured and keep the old path
+    fuse_wide_min_rows = int(os.environ.get("NFA_K34_MIN_ROWS", "1024"))
+
+    def _wide_conditioner_shape(self):
+        """(hidden width, hidden Linears, residual blocks?) of a MADE that K34 runs inside the layer kernel -- plain MADE in
+        float32 without context layer or batch norm, 128 < hidden width <= 256, 1 .. 64 features --, or None.  The structure
+        is read once per cache epoch; tails, bins, activations and dropouts are plain attributes, read on every call."""
+        net = self._conditioner()
+
+        def read():
+            first = net.initial_layer
+            if (type(net) is made_module.MADE and first.weight.dtype == torch.float32 and not hasattr(net, "context_layer")
+                    and not _has_batch_norm(net)):
+                hidden, features = first.weight.shape
+                if 128 < hidden <= 256 and 1 <= features <= 64:
+                    residual = bool(net.use_residual_blocks)
+                    return hidden, len(net.blocks) * (2 if residual else 1), residual, net.final_layer.weight.shape[0]
+            return None
+        shape = _cache.keyed(self, "_wide_conditioner_shape_held", (_cache.epoch(), net), read)
+        if (shape is None or self.tails != "linear" or not 2 <= self.num_bins <= 16
+                or shape[3] != self.features * (3 * self.num_bins - 1) or not _relu_without_active_dropout(net)):
+            return None
+        return shape[:3]
+
+    def _wide_layer(self, inputs, context):
+        """(outputs, logabsdet) from K34, or None: the gate and the launch."""
+        if not (self.fuse_wide_conditioner and context is None and not torch.is_grad_enabled() and _device_rows(inputs)
+                and inputs.is_contiguous() and inputs.shape[0] >= self.fuse_wide_min_rows and not self._user_hooks
+                and (self.num_bins != 8 or int(self.fuse_conditioner) >= 2)):
+            return None
+        shape = self._wide_conditioner_shape()
+        net = self._conditioner()
+        if shape is None or inputs.shape[1] != self.features or net.initial_layer.weight.device != inputs.device:
+            return None
+        hidden, hidden_linears, residual = shape
+        # (parameters and buffers: the masks are part of the key; the divisor is an attribute of the net)
+        key = (_cache.weights_key(self, net), self.num_bins, self._wh_divisor())
+        weights, biases = _cache.keyed(self, "_packed_made_rqs_wide_cache", key,
+                                       lambda: ops.pack_made_rqs_conditioner_wide(net, self.num_bins))
+        padded = self._fused_geometry()[0]
+        columns = self._all_columns()
+        tables = _cache.keyed(self, "_wide_tables_held", (columns.device, self.features),
+                              lambda: ops.coupling_layer_tables(self.features, columns, columns, padded_features=padded))
+        return ops.rqs_flow_made_wide(inputs, weights, biases, tables, self.features, hidden, hidden_linears,
+                                      self._rqs_spec(), pad=(padded, 0.0), residual_blocks=residual)
+
+    def forward(self, inputs, context=None):
+        fused = self._wide_layer(inputs, context)
+        if fused is not None:
+            return fused
+        return super().forward(inputs, context)   # (K29, or layer by layer)
+
     def _forward_layer_by_layer(self, inputs, context=None):
         net = self.autoregressive_net
         if (self.fuse_output_layer and isinstance(net, made_module.MADE) and inputs.dim() == 2 and inputs.is_cuda
