@@ -66,7 +66,9 @@ extern "C" {
                               still 19: nfa_pack_resnet_wide_train_f32, nfa_resnet_wide_forward_f32, nfa_resnet_wide_backward_f32
                               (K33) are ADDED entry points, for the same reason (their streams are their own);
                               still 19: nfa_rqs_layer_made_wide_f32 (K34) is an ADDED entry point, for the same reason (its blobs
-                              are K32's fragments of a MADE's masked weights) */
+                              are K32's fragments of a MADE's masked weights);
+                              still 19: nfa_affine_layer_made_wide_f32 (K36) is an ADDED entry point, for the same reason (its
+                              blobs are K32's fragments in K22's order of stages) */
 
 /* return codes */
 #define NFA_OK 0
@@ -370,6 +372,51 @@ int nfa_rqs_layer_made_wide_f32(const float *inputs, const void *weights_packed,
                                 const int32_t *layer_tables, float *outputs, float *logabsdet, int32_t *status,
                                 int64_t batch, int32_t row_length, int32_t features, int32_t hidden_features,
                                 int32_t num_hidden_layers, const nfa_rqs_spec *spec, int32_t flags, void *stream);
+
+/*
+ * K36: the density pass of ONE masked autoregressive affine layer (autoregressive.py:64-128) whose MADE (made.py:233-311) is
+ * wider than the 128 hidden units of nfa_affine_flow_made_f32, with or without a context, in one launch
+ * (csrc/affine_made_wide_kernel.hpp).  K34's work split and arithmetic (one workgroup of eight waves per CU on 64 rows, the
+ * hidden GEMMs split by columns, three bf16 pieces per operand on split accumulators: the full fp32 range, no redo pass);
+ * the scale is softplus(u) + 1e-3, per element K2b's arithmetic.
+ *   context            [batch, context_features], or NULL with context_features == 0.
+ *   row_length         columns of a row: `features` rounded up to a multiple of 4 (the pad columns pass through), <= 64.
+ *   hidden_features    129 .. 256; the blobs are packed for Hp = hidden_features rounded up to a multiple of 32, extra units
+ *                      zero.
+ *   num_hidden_layers  hidden Linears: twice the number of residual blocks (NFA_FLAG_RESIDUAL_BLOCKS), or the number of
+ *                      feed-forward blocks, as for nfa_rqs_layer_made_wide_f32.
+ *   weights_packed     K32's fragments (64 lanes x 8 bf16 x 3 pieces: lane (half, i) holds W[32 tile + i][16 ks + 8 half + j])
+ *                      of `weight * mask` (masked-out weights are exact zeros in all three pieces), every GEMM ordered
+ *                      [32-row tile][k-step][piece], the GEMMs in the order consumed:
+ *                        context_layer     (context)  Hp / 32 tiles, ceil(context_features / 16) k-steps, input column k =
+ *                                                     context column k, columns >= context_features zero (the kernel forms
+ *                                                     b_i + relu(Wc ctx + bc) first and adds the initial layer's products)
+ *                        initial_layer                Hp / 32 tiles, ceil(features / 16) k-steps, input column k = feature k
+ *                        per residual block           linear_layers[0] (Hp / 32 tiles, Hp / 16 k-steps, input columns in
+ *                                                     accumulator order as for K32), blocks[i].context_layer (context; as
+ *                                                     context_layer), linear_layers[1]
+ *                        per feed-forward block       linear
+ *                        final_layer                  ceil(features / 16) tiles, Hp / 16 k-steps; the reference's interleaved
+ *                                                     rows (row 2 f: unconstrained scale of feature f, row 2 f + 1: its
+ *                                                     shift) in K11 / K22's order, [8 shifts | 8 unconstrained scales] per
+ *                                                     lane-half: tile t gives lane-half h features 16 t + 8 h .. + 7; rows of
+ *                                                     features >= `features` zero (the kernel skips them).
+ *   bias_packed        fp32 in accumulator order ([tile][lane-half][16]): initial_layer (Hp), context_layer (Hp; context),
+ *                      per hidden Linear Hp (a residual block's context_layer bias is added to its linear_layers[0] bias),
+ *                      final_layer (32 per tile).
+ *   layer_tables       int32 [256] as for nfa_rqs_coupling_resnet_f32, every feature in both halves.
+ * Supported: the forward pass, ReLU, hidden_features 129 .. 256, features <= 64, context_features <= 64, row_length % 4 == 0,
+ * batch % 128 == 0, flags NFA_FLAG_RESIDUAL_BLOCKS | NFA_FLAG_ACCUMULATE_LOGABSDET, the buffers (exchange buffer Hp / 16 x
+ * 6 KB, row and context tiles of 260 B per column, 2 KB of logabsdet shares) within the CU's LDS; otherwise (NFA_FLAG_INVERSE,
+ * the density flags, ...) NFA_ERR_UNSUPPORTED, after the argument errors (callers then run the MADE's GEMMs and K2b).
+ * batch == 0 returns NFA_OK.  A row's logabsdet is summed in an order the shape fixes: the same bits for any batch and grid.
+ * Added under ABI 19 (see NFA_ABI_VERSION): no existing entry point, flag set or packed layout changes.
+ */
+int nfa_affine_layer_made_wide_f32(const float *inputs, const float *context, int32_t context_features,
+                                   const void *weights_packed, const float *bias_packed, const int32_t *layer_tables,
+                                   float *outputs, float *logabsdet, int32_t *status, int64_t batch, int32_t row_length,
+                                   int32_t features, int32_t hidden_features, int32_t num_hidden_layers, int32_t flags,
+                                   void *stream);
 
 /*
  * K8 over a run of layers.  Rows of a flow are independent, so num_layers coupling layers of the

@@ -1,0 +1,67 @@
+// K36: the density pass of ONE masked autoregressive affine layer (MaskedAffineAutoregressiveTransform.forward,
+// autoregressive.py:64-128) whose MADE (made.py:233-311) is 129 .. 256 hidden units wide, with or without a context, in ONE
+// launch (design notes and the kernel: affine_made_wide_kernel.hpp; instances: affine_made_wide_plain.hip,
+// affine_made_wide_ctx.hip).  K22 serves widths up to 128; this is K34's column split with the affine element and K22's
+// context terms.  Three bf16 pieces per operand, six products: the full fp32 range, so there is no redo pass.
+//
+// Restrictions (the caller keeps the MADE's GEMMs + K2b otherwise): forward only, ReLU, hidden width 129 .. 256 (packed to a
+// multiple of 32), features <= 64, context features <= 64, row_length % 4 == 0 and <= 64 (pad columns pass through),
+// batch % 128 == 0, one layer per launch (no folded base density).
+
+#include "affine_made_wide_kernel.hpp"
+
+using namespace nfa;
+using namespace nfa::k36;
+
+extern "C" int nfa_affine_layer_made_wide_f32(const float* inputs, const float* context, int32_t context_features,
+                                              const void* weights_packed, const float* bias_packed,
+                                              const int32_t* layer_tables, float* outputs, float* logabsdet, int32_t* status,
+                                              int64_t batch, int32_t row_length, int32_t features, int32_t hidden_features,
+                                              int32_t num_hidden_layers, int32_t flags, void* stream) {
+    int activation = 0;   // (no activation bits here)
+    int rc = check_layer_flags(flags, NFA_FLAG_RESIDUAL_BLOCKS, &activation);
+    if (rc != NFA_OK) return rc;
+    const bool resnet = (flags & NFA_FLAG_RESIDUAL_BLOCKS) != 0;
+    if (batch < 0 || features < 1 || row_length < features || context_features < 0 || hidden_features < 1 ||
+        num_hidden_layers < 0 || (resnet && (num_hidden_layers & 1)))   // (residual blocks: two Linears each)
+        return NFA_ERR_INVALID_ARGUMENT;
+    // (one layer per launch: the base density is not folded in)
+    if ((flags & (NFA_FLAG_INVERSE | NFA_FLAG_STANDARD_NORMAL_LOG_PROB | NFA_FLAG_SKIP_OUTPUTS)) || hidden_features > 256 ||
+        hidden_features <= 128 || features > 64 || context_features > 64 || row_length > 64 || (row_length & 3) != 0 ||
+        (batch & 127) != 0 || num_hidden_layers > 128)
+        return NFA_ERR_UNSUPPORTED;
+    AffineWideArgs a;
+    a.tiles = (hidden_features + 31) / 32;
+    a.nks = 2 * a.tiles;
+    a.init_ks = (features + 15) / 16;
+    a.final_tiles = (features + 15) / 16;
+    a.ce = context_features;
+    a.ctx_ks = (context_features + 15) / 16;
+    // the exchange buffer, the row tile, the logabsdet shares, the context tile; the kernel's tables are static
+    const size_t lds = (size_t)a.nks * kStepVec4 * 16 + (size_t)row_length * kPad * sizeof(float) +
+                       (size_t)kWaves * kRows * sizeof(float) + (size_t)context_features * kPad * sizeof(float);
+    if (lds > (size_t)kCuLds - 2048) return NFA_ERR_UNSUPPORTED;
+    if (batch == 0) return NFA_OK;
+    const bool ctx = context_features > 0;
+    if (!inputs || !weights_packed || !bias_packed || !layer_tables || !outputs || !logabsdet || (ctx && !context))
+        return NFA_ERR_INVALID_ARGUMENT;
+    a.x = inputs;
+    a.ctx = context;
+    a.w = reinterpret_cast<const vec4f*>(weights_packed);
+    a.bias = bias_packed;
+    a.tables = layer_tables;
+    a.out = outputs;
+    a.lad = logabsdet;
+    a.status = status;
+    a.batch = batch;
+    a.D = row_length;
+    a.dt = features;
+    a.num_hidden = num_hidden_layers;
+    a.resnet = resnet ? 1 : 0;
+    a.accumulate = (flags & NFA_FLAG_ACCUMULATE_LOGABSDET) ? 1 : 0;
+    const AffineWideKernelFn kern = ctx ? affine_wide_context() : affine_wide_plain();
+    int64_t blocks = batch >> 6;
+    if (blocks > device_cu_count()) blocks = device_cu_count();
+    note_layer_kernel("k36::affine_made_wide_kernel<context=%d, tiles=%d, resnet=%d>", ctx ? 1 : 0, a.tiles, resnet ? 1 : 0);
+    return launch_kernel(kern, dim3((unsigned)blocks), dim3(kThreads), lds, (hipStream_t)stream, a, kCuLds - 2048);
+}

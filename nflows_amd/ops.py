@@ -3243,6 +3243,70 @@ def rqs_flow_made_wide(inputs, weights_packed, bias_packed, tables, features, hi
                                flags=N.FLAG_RESIDUAL_BLOCKS if residual_blocks else 0, spec=spec)
 
 
+def pack_made_affine_conditioner_wide(net):
+    """A MADE with two outputs per feature, 129 .. 256 hidden units wide (any width up to 256 packs), with or without a
+    context, for K36 (layout in include/nflows_amd.h, nfa_affine_layer_made_wide_f32): K32's fragments (`_wide_fragments`) of
+    `weight * mask` -- a masked-out weight is an exact zero in all three pieces --, the hidden width zero-padded to Hp, a
+    multiple of 32; the GEMMs in the order the kernel consumes them, K22's (`pack_mlp_conditioner`): the context Linear in
+    front of the initial layer, a residual block's context Linear behind its first Linear, whose bias takes the context
+    Linear's; the final layer's interleaved rows in K11 / K22's order (`_made_row_order`), rows of features past the last
+    zero; all biases in accumulator order.  Returns (weights bf16, biases fp32)."""
+    linears, final = _made_linears(net), net.final_layer
+    H, features = linears[0].weight.shape
+    if final.weight.shape[0] != 2 * features:
+        raise ValueError("the MADE's final layer must have two rows per feature")
+    dev = final.weight.device
+    Hp = (H + 31) // 32 * 32
+    order_k = _wide_column_order(Hp).to(dev)
+    context, block_context = _context_linears(net) if hasattr(net, "context_layer") else (None, [])
+
+    def masked(lin):
+        return (lin.weight.detach() * lin.mask).float()
+
+    def context_fragments(lin):   # laid out as the initial layer's, ceil(ce / 16) k-steps
+        w = lin.weight.detach().float()
+        return _wide_fragments(_pad_to(w, rows=Hp, cols=16 * ((w.shape[1] + 15) // 16)))
+
+    def bias_of(b):
+        return _bias_accumulator_order(_pad_to(b.detach().float(), rows=Hp))
+    blobs = [_wide_fragments(_pad_to(masked(linears[0]), rows=Hp, cols=16 * ((features + 15) // 16)))]
+    biases = [bias_of(linears[0].bias)]
+    if context is not None:
+        blobs.insert(0, context_fragments(context))   # (consumed in front of the initial layer's)
+        biases.append(bias_of(context.bias))
+    for i, lin in enumerate(linears[1:]):
+        blobs.append(_wide_fragments(_pad_to(masked(lin), rows=Hp, cols=Hp).index_select(1, order_k)))
+        b = lin.bias.detach().float()
+        if block_context and i % 2 == 0:
+            blobs.append(context_fragments(block_context[i // 2]))
+            b = b + block_context[i // 2].bias.detach().float()
+        biases.append(bias_of(b))
+    order_r = _made_row_order(features).to(dev)   # -1 = zero padding
+    wo = _pad_to(masked(final), cols=Hp)
+    wo = torch.cat((wo, wo.new_zeros(1, Hp)), dim=0)
+    bo = final.bias.detach().float()
+    bo = torch.cat((bo, bo.new_zeros(1)))
+    blobs.append(_wide_fragments(wo.index_select(0, order_r % wo.shape[0]).index_select(1, order_k)))
+    biases.append(_bias_accumulator_order(bo.index_select(0, order_r % bo.shape[0])))
+    return torch.cat(blobs).contiguous(), torch.cat(biases).contiguous()
+
+
+def affine_flow_made_wide(inputs, weights_packed, bias_packed, tables, features, hidden_features, num_hidden_layers,
+                          context=None, accumulate_into=None, pad=None, residual_blocks=True):
+    """K36 -- the density pass of one masked autoregressive affine layer with a MADE of 129 .. 256 hidden units, with or
+    without a context, in one kernel (`pack_made_affine_conditioner_wide`; tables from `coupling_layer_tables` with every
+    feature in both halves; rows padded to a multiple of four columns by `pad`, see `_whole_layer_launch`).
+    `num_hidden_layers`: the hidden Linears (twice the number of residual blocks, or the number of feed-forward blocks).
+    Forward only.  Returns (outputs, logabsdet), or None when the shape is outside the kernel's family."""
+    def launch(x, ctx, out, lad, redo, flags, status, stream):
+        return N.load().nfa_affine_layer_made_wide_f32(
+            N.ptr(x), N.ptr(ctx), 0 if ctx is None else ctx.shape[1], N.ptr(weights_packed), N.ptr(bias_packed),
+            N.ptr(tables), N.ptr(out), N.ptr(lad), status, x.shape[0], x.shape[1], features, hidden_features,
+            num_hidden_layers, flags, stream)
+    return _whole_layer_launch(launch, inputs, False, accumulate_into, False, pad, context,
+                               flags=N.FLAG_RESIDUAL_BLOCKS if residual_blocks else 0)
+
+
 _ACTIVATION_CODES = {id(torch.nn.functional.relu): N.ACTIVATION_RELU, id(torch.relu): N.ACTIVATION_RELU,
                      id(torch.nn.functional.leaky_relu): N.ACTIVATION_LEAKY_RELU, id(torch.nn.functional.elu): N.ACTIVATION_ELU,
                      id(torch.tanh): N.ACTIVATION_TANH, id(torch.nn.functional.tanh): N.ACTIVATION_TANH}

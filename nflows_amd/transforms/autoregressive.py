@@ -369,6 +369,61 @@ class MaskedAffineAutoregressiveTransform(_MadeKernelLayer):
                                     num_layers=num_layers, standard_normal_log_prob=standard_normal_log_prob,
                                     pad=(geometry[0], geometry[3]), residual_blocks=residual_blocks)
 
+    # ---- whole-layer kernel K36 (csrc/affine_made_wide_kernel.hpp): the density pass of ONE layer whose MADE is 129 .. 256
+    #      hidden units wide, with or without a context, in one launch -- K34's column split with the affine element.  The
+    #      layer is a run of one: `_run_kind` stays None at these widths (no runs of layers, no folded base density), and the
+    #      inverse, training and float64 keep the paths they had.  Class-level switch, NFA_K36=0 = off; independent of NFA_K22.
+    fuse_wide_conditioner = os.environ.get("NFA_K36", "1") != "0"
+    # K36's size rule (DESIGN.md section 4 "K36"): FEWER THAN 1 024 ROWS WERE NOT MEASURED AND KEEP THE OLD PATH
+    fuse_wide_min_rows = int(os.environ.get("NFA_K36_MIN_ROWS", "1024"))
+
+    def _wide_conditioner_shape(self):
+        """(hidden width, hidden Linears, residual blocks?) of a MADE that K36 runs inside the layer kernel -- plain MADE in
+        float32 without batch norm, 128 < hidden width <= 256, 1 .. 64 features of the layer's width with two rows each, at
+        most 64 context features --, or None.  The structure is read once per cache epoch; activations and dropouts are plain
+        attributes, read on every call."""
+        net = self._conditioner()
+
+        def read():
+            first = net.initial_layer
+            if type(net) is made_module.MADE and first.weight.dtype == torch.float32 and not _has_batch_norm(net):
+                hidden, features = first.weight.shape
+                if (128 < hidden <= 256 and 1 <= features == self.features <= 64 and self._context_features() <= 64
+                        and net.final_layer.weight.shape[0] == 2 * features):
+                    residual = bool(net.use_residual_blocks)
+                    return hidden, len(net.blocks) * (2 if residual else 1), residual
+            return None
+        shape = _cache.keyed(self, "_wide_conditioner_shape_held", (_cache.epoch(), net), read)
+        return shape if shape is not None and _relu_without_active_dropout(net) else None
+
+    def _wide_layer(self, inputs, context):
+        """(outputs, logabsdet) from K36, or None: the gate and the launch."""
+        if not (self.fuse_wide_conditioner and not torch.is_grad_enabled() and _device_rows(inputs) and inputs.is_contiguous()
+                and inputs.shape[0] >= self.fuse_wide_min_rows and not self._user_hooks):
+            return None
+        shape = self._wide_conditioner_shape()
+        net = self._conditioner()
+        if (shape is None or inputs.shape[1] != self.features or net.initial_layer.weight.device != inputs.device
+                or not _context_served(context, self._context_features(), inputs.shape[0])
+                or (context is not None and context.device != inputs.device)):
+            return None
+        hidden, hidden_linears, residual = shape
+        key = _cache.weights_key(self, net)   # (parameters and buffers: the masks are part of the key)
+        weights, biases = _cache.keyed(self, "_packed_made_wide_cache", key,
+                                       lambda: ops.pack_made_affine_conditioner_wide(net))
+        padded = self._fused_geometry()[0]
+        columns = self._all_columns()
+        tables = _cache.keyed(self, "_wide_tables_held", (columns.device, self.features),
+                              lambda: ops.coupling_layer_tables(self.features, columns, columns, padded_features=padded))
+        return ops.affine_flow_made_wide(inputs, weights, biases, tables, self.features, hidden, hidden_linears, context,
+                                         pad=(padded, 0.0), residual_blocks=residual)
+
+    def forward(self, inputs, context=None):
+        fused = self._wide_layer(inputs, context)
+        if fused is not None:
+            return fused
+        return super().forward(inputs, context)   # (K22, or layer by layer)
+
     def _elementwise_inverse(self, inputs, autoregressive_params):
         return ops.affine_autoregressive(inputs, autoregressive_params, inverse=True)
 
