@@ -68,7 +68,9 @@ extern "C" {
                               still 19: nfa_rqs_layer_made_wide_f32 (K34) is an ADDED entry point, for the same reason (its blobs
                               are K32's fragments of a MADE's masked weights);
                               still 19: nfa_affine_layer_made_wide_f32 (K36) is an ADDED entry point, for the same reason (its
-                              blobs are K32's fragments in K22's order of stages) */
+                              blobs are K32's fragments in K22's order of stages);
+                              still 19: nfa_affine_layer_resnet_wide_f32 (K37) is an ADDED entry point, for the same reason (its
+                              blobs are K32's fragments with K11's final rows) */
 
 /* return codes */
 #define NFA_OK 0
@@ -417,6 +419,44 @@ int nfa_affine_layer_made_wide_f32(const float *inputs, const float *context, in
                                    float *outputs, float *logabsdet, int32_t *status, int64_t batch, int32_t row_length,
                                    int32_t features, int32_t hidden_features, int32_t num_hidden_layers, int32_t flags,
                                    void *stream);
+
+/*
+ * K37: ONE affine or additive coupling layer (coupling.py:212-269) whose conditioner is wider than the 128 hidden units of
+ * nfa_affine_flow_mlp_f32, in one launch, both directions (csrc/affine_resnet_wide_kernel.hpp).  K32's work split and
+ * arithmetic in the hidden GEMMs (one workgroup of eight waves per CU on 64 rows, the GEMMs split by columns, three bf16
+ * pieces per operand: the full fp32 range, no redo pass); the final Linear runs as up to eight units (final tile, 32-row
+ * tile), one per wave; per element K2's arithmetic.  The arguments are nfa_rqs_layer_resnet_wide_f32's without the spline
+ * spec, with nfa_affine_flow_mlp_f32's scale activation and count of hidden Linears.
+ *   hidden_features    1 .. 256 (callers use it from 129); the blobs are packed for Hp = hidden_features rounded up to a
+ *                      multiple of 32, extra units zero.  An MLP's hidden sizes are all padded to the Hp of the largest.
+ *   num_hidden_layers  hidden Linears: twice the number of residual blocks (NFA_FLAG_RESIDUAL_BLOCKS: a ResidualNet,
+ *                      h += W_1 relu(W_0 relu(h) + b_0) + b_1, the final Linear on h), or the number of hidden layers of an
+ *                      MLP (h = W relu(h) + b behind h = W_i x + b_i, the final Linear on relu(h)).
+ *   scale_activation   NFA_SCALE_DEFAULT, NFA_SCALE_GENERAL or NFA_SCALE_ADDITIVE.
+ *   weights_packed     K32's fragments (64 lanes x 8 bf16 x 3 pieces: lane (half, i) holds W[32 tile + i][16 ks + 8 half + j]),
+ *                      ordered [GEMM][32-row tile][k-step][piece]: the initial layer (Hp / 32 tiles, ceil(num_identity / 16)
+ *                      k-steps, input column k = identity feature k), the hidden Linears (Hp / 32 tiles, Hp / 16 k-steps, input
+ *                      columns in accumulator order as for K32), the final Linear (Hp / 16 k-steps; affine: ceil(num_transform
+ *                      / 16) tiles of the rows [shift block | unconstrained scale block] in K11's order, [8 shifts | 8
+ *                      unconstrained scales] per lane-half: tile t gives lane-half h features 16 t + 8 h .. + 7; additive:
+ *                      ceil(num_transform / 32) tiles, tile t gives lane-half h the shifts of features 32 t + 16 h .. + 15; rows
+ *                      of features >= num_transform zero -- the kernel skips them).
+ *   bias_packed        fp32 in accumulator order ([tile][lane-half][16]): initial layer (Hp), per hidden Linear Hp, final
+ *                      Linear (32 per tile).
+ *   layer_tables       int32 [256] as for nfa_rqs_coupling_resnet_f32 (no spare column: num_transform needs no padding).
+ * Supported: ReLU, no context, num_identity <= 64, num_transform <= 64, features % 4 == 0 and <= 128, batch % 128 == 0, flags
+ * NFA_FLAG_INVERSE | NFA_FLAG_ACCUMULATE_LOGABSDET | NFA_FLAG_RESIDUAL_BLOCKS, the exchange buffer (Hp / 16 x 6 KB), the row
+ * tile (features x 260 B) and 1 KB of logabsdet shares within the CU's LDS; otherwise (NFA_SCALE_GIVEN, NFA_SCALE_SOFTPLUS,
+ * hidden_features > 256, the density flags, ...) NFA_ERR_UNSUPPORTED, after the argument errors (callers then run the
+ * conditioner's GEMMs and K2).  batch == 0 returns NFA_OK.  A row's logabsdet is summed in an order the shape fixes: the same
+ * bits for any batch and grid; the additive layer's is exactly 0.  Added under ABI 19 (see NFA_ABI_VERSION): no existing entry
+ * point, flag set or packed layout changes.
+ */
+int nfa_affine_layer_resnet_wide_f32(const float *inputs, const void *weights_packed, const float *bias_packed,
+                                     const int32_t *layer_tables, float *outputs, float *logabsdet, int32_t *status,
+                                     int64_t batch, int32_t features, int32_t num_transform, int32_t num_identity,
+                                     int32_t hidden_features, int32_t num_hidden_layers, int32_t scale_activation,
+                                     int32_t flags, void *stream);
 
 /*
  * K8 over a run of layers.  Rows of a flow are independent, so num_layers coupling layers of the

@@ -60,6 +60,7 @@ EXPORTS = (
     "nfa_rqs_flow_made_f32",
     "nfa_rqs_layer_made_wide_f32",
     "nfa_affine_layer_made_wide_f32",
+    "nfa_affine_layer_resnet_wide_f32",
     "nfa_made_rqs_inverse_f32",
     "nfa_made_affine_inverse_f32",
     "nfa_made_rqs_inverse_ctx_f32",
@@ -291,6 +292,8 @@ def _declare(lib):
     lib.nfa_rqs_layer_made_wide_f32.argtypes = [vp] * 7 + [i64, i32, i32, i32, i32, sp, i32, vp]
     lib.nfa_affine_layer_made_wide_f32.restype = ctypes.c_int
     lib.nfa_affine_layer_made_wide_f32.argtypes = [vp, vp, i32] + [vp] * 6 + [i64] + [i32] * 5 + [vp]
+    lib.nfa_affine_layer_resnet_wide_f32.restype = ctypes.c_int
+    lib.nfa_affine_layer_resnet_wide_f32.argtypes = [vp] * 7 + [i64] + [i32] * 7 + [vp]
     lib.nfa_rqs_elementwise_f32.restype = ctypes.c_int
     lib.nfa_rqs_elementwise_f32.argtypes = [vp, vp, i64, vp, i64, vp, i64, i32, vp, vp, vp, vp, i64, sp, i32, vp]
     lib.nfa_searchsorted_f32.restype = ctypes.c_int

@@ -3307,6 +3307,56 @@ def affine_flow_made_wide(inputs, weights_packed, bias_packed, tables, features,
                                flags=N.FLAG_RESIDUAL_BLOCKS if residual_blocks else 0)
 
 
+def pack_affine_conditioner_wide(net, num_transform, additive=False):
+    """Packs the conditioner of an affine / additive coupling layer -- a ResidualNet without context, or a ReLU MLP
+    (`_conditioner_linears`) -- with hidden widths up to 256 for K37 (layout in include/nflows_amd.h,
+    nfa_affine_layer_resnet_wide_f32): K32's fragments (`_wide_fragments`), every hidden width zero-padded to one Hp, a
+    multiple of 32 (an MLP's hidden sizes to that of the largest); the final layer's rows [shift block | unconstrained scale
+    block] in K11's order (`_affine_row_order`), rows of features past the last zero; all biases in accumulator order.
+    Returns (weights bf16, biases fp32)."""
+    first, hidden, final = _conditioner_linears(net)
+    dev = final.weight.device
+    H = max(lin.weight.shape[0] for lin in [first] + hidden)
+    Hp = (H + 31) // 32 * 32
+    order_k = _wide_column_order(Hp).to(dev)
+    di = first.weight.shape[1]
+    blobs = [_wide_fragments(_pad_to(first.weight.detach().float(), rows=Hp, cols=16 * ((di + 15) // 16)))]
+    biases = [_bias_accumulator_order(_pad_to(first.bias.detach().float(), rows=Hp))]
+    for lin in hidden:
+        blobs.append(_wide_fragments(_pad_to(lin.weight.detach().float(), rows=Hp, cols=Hp).index_select(1, order_k)))
+        biases.append(_bias_accumulator_order(_pad_to(lin.bias.detach().float(), rows=Hp)))
+    order_r = _affine_row_order(num_transform, additive).to(dev)   # -1 = zero padding
+    wo = _pad_to(final.weight.detach().float(), cols=Hp)
+    wo = torch.cat((wo, wo.new_zeros(1, Hp)), dim=0)
+    bo = final.bias.detach().float()
+    bo = torch.cat((bo, bo.new_zeros(1)))
+    blobs.append(_wide_fragments(wo.index_select(0, order_r % wo.shape[0]).index_select(1, order_k)))
+    biases.append(_bias_accumulator_order(bo.index_select(0, order_r % bo.shape[0])))
+    return torch.cat(blobs).contiguous(), torch.cat(biases).contiguous()
+
+
+def affine_coupling_wide(inputs, weights_packed, bias_packed, tables, num_transform, num_identity, hidden_features,
+                         num_hidden_layers, scale_activation, inverse=False, accumulate_into=None, pad=None,
+                         residual_blocks=True):
+    """K37 -- one affine / additive coupling layer with a conditioner of 129 .. 256 hidden units in one kernel
+    (`pack_affine_conditioner_wide`, `coupling_layer_tables`; rows padded to a multiple of four columns by `pad`, see
+    `_whole_layer_launch`).  `num_hidden_layers`: the hidden Linears (twice the number of residual blocks, or the number of
+    an MLP's hidden layers).  Returns (outputs, logabsdet), or None when the shape is outside the kernel's family."""
+    tiles = (hidden_features + 31) // 32
+    final_tiles = (num_transform + 31) // 32 if scale_activation == N.SCALE_ADDITIVE else (num_transform + 15) // 16
+    fragments = tiles * ((num_identity + 15) // 16) + num_hidden_layers * tiles * 2 * tiles + final_tiles * 2 * tiles
+    if (weights_packed.numel() != fragments * 3 * 64 * 8
+            or bias_packed.numel() != 32 * (tiles * (1 + num_hidden_layers) + final_tiles)):
+        raise ValueError("the packed conditioner does not belong to this layer shape (pack_affine_conditioner_wide)")
+
+    def launch(x, ctx, out, lad, redo, flags, status, stream):
+        return N.load().nfa_affine_layer_resnet_wide_f32(
+            N.ptr(x), N.ptr(weights_packed), N.ptr(bias_packed), N.ptr(tables), N.ptr(out), N.ptr(lad), status, x.shape[0],
+            x.shape[1], num_transform, num_identity, hidden_features, num_hidden_layers, scale_activation, flags, stream)
+    return _whole_layer_launch(launch, inputs, inverse, accumulate_into, False, pad,
+                               flags=N.FLAG_RESIDUAL_BLOCKS if residual_blocks else 0)
+
+
 _ACTIVATION_CODES = {id(torch.nn.functional.relu): N.ACTIVATION_RELU, id(torch.relu): N.ACTIVATION_RELU,
                      id(torch.nn.functional.leaky_relu): N.ACTIVATION_LEAKY_RELU, id(torch.nn.functional.elu): N.ACTIVATION_ELU,
                      id(torch.tanh): N.ACTIVATION_TANH, id(torch.nn.functional.tanh): N.ACTIVATION_TANH}

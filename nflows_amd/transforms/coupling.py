@@ -407,6 +407,83 @@ class AffineCouplingTransform(CouplingTransform, RunLayer):
             self._activation_code(), inverse, accumulate_into, num_layers=num_layers,
             standard_normal_log_prob=standard_normal_log_prob, pad=(geometry[0], geometry[3]), residual_blocks=residual_blocks)
 
+    # K37: conditioners of 129 .. 256 hidden units, the whole layer in one launch (csrc/affine_resnet_wide_kernel.hpp); class-level
+    # switch, NFA_K37=0 = off: such layers then take stock GEMMs + K2 as before.  A wide layer is a run of one (`_run_kind`
+    # stays None at these widths): no multi-layer runs, no folded base density.
+    fuse_wide_conditioner = os.environ.get("NFA_K37", "1") != "0"
+    # K37's size rule (DESIGN.md section 4 "K37"): the smallest measured row count from which K37's slower session is
+    # below the old path's faster one at every measured shape; fewer rows keep the old path
+    fuse_wide_min_rows = int(os.environ.get("NFA_K37_MIN_ROWS", "1024"))
+
+    def _wide_conditioner_shape(self):
+        """(hidden width, hidden Linears, residual blocks?) of a conditioner K37 runs inside the layer kernel -- exactly a
+        ResidualNet without context or batch norm, ReLU blocks, 128 < hidden_features <= 256, or exactly an MLP with ReLU
+        between its layers and none behind the last, every hidden size <= 256 and at least one > 128 --, or None.  The
+        types and sizes are read once per cache epoch, a block's activation and dropout on every call."""
+        def read():
+            from ..nn.nets.mlp import MLP
+            from ..nn.nets.resnet import ResidualNet
+            net = self._modules["transform_net"]
+            # (the width the packer pads from: the Linears' own shapes, not an attribute that only describes them)
+            if type(net) is MLP:
+                width = max(lin.weight.shape[0] for lin in [net._input_layer, *net._hidden_layers])
+                if net._activation is torch.nn.functional.relu and not net._activate_output and 128 < width <= 256:
+                    return width, len(net._hidden_layers), False
+            elif type(net) is ResidualNet:
+                width = net.initial_layer.weight.shape[0]
+                if (net.context_features is None and 128 < width <= 256
+                        and not any(b.use_batch_norm for b in net.blocks)):
+                    return width, 2 * len(net.blocks), True
+            return None
+        shape = _cache.keyed(self, "_wide_conditioner_shape_held", (_cache.epoch(),), read)
+        if shape is not None and shape[2]:
+            relu = (torch.nn.functional.relu, torch.relu)
+            if not all(b.__dict__.get("activation") in relu and (not b.training or b.dropout.p == 0.0)
+                       for b in self.transform_net.blocks):
+                return None
+        return shape
+
+    def _wide_layer_eligible(self, context):
+        """What K37 asks of the layer: no grad, no context, no unconditional transform, no user hooks, a scale activation the
+        kernel evaluates, a conditioner of `_wide_conditioner_shape`, K11's geometry (identity <= 64, transformed <= 64,
+        padded features <= 128)."""
+        return (self.fuse_wide_conditioner and not torch.is_grad_enabled() and context is None
+                and self.unconditional_transform is None and not self._user_hooks
+                and self._activation_code() != N.SCALE_GIVEN
+                and 1 <= self.num_identity_features <= 64 and 1 <= self.num_transform_features <= 64
+                and self._fused_geometry()[0] <= 128 and self._wide_conditioner_shape() is not None)
+
+    def _packed_wide(self):
+        """(weights, biases) for K37 (ops.pack_affine_conditioner_wide), per weight key"""
+        net = self.transform_net
+        return _cache.keyed(self, "_packed_wide_cache", _cache.weights_key(self, net),
+                            lambda: ops.pack_affine_conditioner_wide(net, self.num_transform_features,
+                                                                     additive=self._activation_code() == N.SCALE_ADDITIVE))
+
+    def _wide_layer_tables(self, in_perm, out_scatter):
+        key = tuple(None if t is None else (t.data_ptr(), t._version) for t in
+                    (in_perm, out_scatter, self.transform_features, self.identity_features))
+        cache = self.__dict__.setdefault("_wide_layer_tables_cache", {})
+        hit = cache.get(key)
+        if hit is None:
+            if len(cache) > 8:
+                cache.clear()
+            hit = cache[key] = ops.coupling_layer_tables(self.features, self.transform_features, self.identity_features,
+                                                         in_perm, out_scatter, padded_features=self._fused_geometry()[0])
+        return hit
+
+    def _whole_layer(self, inputs, context, inverse, in_perm, out_scatter, accumulate_into):
+        """K37 ahead of `_condition_and_transform` (conditioner, then K2); None where the layer, the inputs or the entry
+        point decline."""
+        if not (self._wide_layer_eligible(context) and inputs.is_cuda and inputs.dtype == torch.float32
+                and inputs.shape[0] >= self.fuse_wide_min_rows and self.identity_features.device == inputs.device):
+            return None
+        hidden, hidden_linears, residual_blocks = self._wide_conditioner_shape()
+        Dp, dt, di, pad_value = self._fused_geometry()
+        return ops.affine_coupling_wide(inputs, *self._packed_wide(), self._wide_layer_tables(in_perm, out_scatter), dt, di,
+                                        hidden, hidden_linears, self._activation_code(), inverse, accumulate_into,
+                                        pad=(Dp, pad_value), residual_blocks=residual_blocks)
+
     def _generic_float64(self, inputs, context, inverse, logabsdet_accumulator):
         """float64 vectors: the reference's expressions (coupling.py:73-130, :228-252) as tensor operations on
         the device (conditioner outputs [shift block | unconstrained scale block])."""
