@@ -31,37 +31,21 @@ extern "C" int nfa_affine_layer_made_wide_f32(const float* inputs, const float* 
         (batch & 127) != 0 || num_hidden_layers > 128)
         return NFA_ERR_UNSUPPORTED;
     AffineWideArgs a;
-    a.tiles = (hidden_features + 31) / 32;
-    a.nks = 2 * a.tiles;
     a.init_ks = (features + 15) / 16;
     a.final_tiles = (features + 15) / 16;
+    a.ctx = context;
     a.ce = context_features;
     a.ctx_ks = (context_features + 15) / 16;
-    // the exchange buffer, the row tile, the logabsdet shares, the context tile; the kernel's tables are static
-    const size_t lds = (size_t)a.nks * kStepVec4 * 16 + (size_t)row_length * kPad * sizeof(float) +
-                       (size_t)kWaves * kRows * sizeof(float) + (size_t)context_features * kPad * sizeof(float);
-    if (lds > (size_t)kCuLds - 2048) return NFA_ERR_UNSUPPORTED;
-    if (batch == 0) return NFA_OK;
-    const bool ctx = context_features > 0;
-    if (!inputs || !weights_packed || !bias_packed || !layer_tables || !outputs || !logabsdet || (ctx && !context))
-        return NFA_ERR_INVALID_ARGUMENT;
-    a.x = inputs;
-    a.ctx = context;
-    a.w = reinterpret_cast<const vec4f*>(weights_packed);
-    a.bias = bias_packed;
-    a.tables = layer_tables;
-    a.out = outputs;
-    a.lad = logabsdet;
-    a.status = status;
-    a.batch = batch;
-    a.D = row_length;
-    a.dt = features;
     a.num_hidden = num_hidden_layers;
     a.resnet = resnet ? 1 : 0;
-    a.accumulate = (flags & NFA_FLAG_ACCUMULATE_LOGABSDET) ? 1 : 0;
-    const AffineWideKernelFn kern = ctx ? affine_wide_context() : affine_wide_plain();
-    int64_t blocks = batch >> 6;
-    if (blocks > device_cu_count()) blocks = device_cu_count();
-    note_layer_kernel("k36::affine_made_wide_kernel<context=%d, tiles=%d, resnet=%d>", ctx ? 1 : 0, a.tiles, resnet ? 1 : 0);
-    return launch_kernel(kern, dim3((unsigned)blocks), dim3(kThreads), lds, (hipStream_t)stream, a, kCuLds - 2048);
+    const bool ctx = context_features > 0;
+    // (behind the row tile: the logabsdet shares, the context tile)
+    return wide::launch(a, ctx ? affine_wide_context() : affine_wide_plain(),
+                        {inputs, weights_packed, bias_packed, layer_tables, outputs, logabsdet, status, batch, row_length,
+                         features, hidden_features, flags, stream,
+                         (kWaves * kRows + (size_t)context_features * kPad) * sizeof(float), !ctx || context != nullptr},
+                        [&] {
+                            note_layer_kernel("k36::affine_made_wide_kernel<context=%d, tiles=%d, resnet=%d>", ctx ? 1 : 0,
+                                              a.tiles, resnet ? 1 : 0);
+                        });
 }

@@ -5,21 +5,14 @@
 // they are accumulators, the per-row logabsdet.  The [B, 2 D] parameters never reach memory.  K22 (affine_mlp_kernel.hpp)
 // serves widths up to 128.
 //
-// Arithmetic: K8's three bf16 pieces per fp32 operand, six products per k-step on v_mfma_f32_32x32x16_bf16, on K34's split
-// accumulators (`gemm_exchange_split<true>`) in every GEMM that reads the exchange buffer, the final one included: its
-// tile holds 2 x 16 accumulators per wave, so the second set fits.  The 0/1 masks are multiplied into the weights by the
-// packer: a masked-out weight is an exact zero in all three pieces, so a feature's result does not depend on the features
-// behind it, bit for bit.  Per element the instructions are K22's and K2b's: `affine_element<false>` on
+// Arithmetic, work split, exchange buffer and the shared pieces of the layer loop: wide_layer_common.hpp.  K36 runs on the
+// split-accumulator policy (`gemm_exchange_split<true>`) in every GEMM that reads the exchange buffer, the final one
+// included: its tile holds 2 x 16 accumulators per wave, so the second set fits.  The 0/1 masks are multiplied into the
+// weights by the packer: a masked-out weight is an exact zero in all three pieces, so a feature's result does not depend on
+// the features behind it, bit for bit.  Per element the instructions are K22's and K2b's: `affine_element<false>` on
 // `scale_of(u, NFA_SCALE_SOFTPLUS)` under fp contract(off).
 //
-// Work split: K34's (made_rqs_wide_kernel.hpp), whose GEMM loop -- and through it K32's fragment load, exchange store and
-// barrier -- are included, not copied.  One workgroup of eight waves per CU on 64 rows (two 32-row tiles), persistent over
-// the batch's 64-row blocks; wave w owns hidden columns 32 w .. 32 w + 31 of every hidden GEMM; its slice of the stream
-// stays in two fp32 accumulator tiles; weight fragments go from global memory straight into registers, one k-step ahead,
-// the last request of a GEMM being the first fragment of the wave's next one; activations cross the waves as bf16 pieces
-// through the LDS exchange buffer between two NFA_K32_BARRIERs.
-//
-// What the affine layer changes against K34:
+// What the affine layer changes against K34 (made_rqs_wide_kernel.hpp):
 //   * Final Linear: 2 D rows, which the packer puts in K11 / K22's order ([8 shifts | 8 unconstrained scales] per
 //     lane-half, ops._made_row_order): one 32-row tile gives lane-half `half` BOTH parameters of features 16 t + 8 half ..
 //     + 7 for both row tiles -- ceil(D / 16) <= 4 tiles, tile t on wave t.  Waves 4 .. 7 have no final tile.
@@ -36,26 +29,19 @@
 //       - relu(Wc ctx + bc) is computed FIRST; b_i + relu(...) is the initial value of the accumulators the initial
 //         layer's products are added to;
 //       - per residual block Wcb ctx runs as extra k-steps on the first Linear's accumulators, in front of its ReLU (the
-//         packer adds bcb into b_0).  Feed-forward blocks take no context, as the module.
+//         packer adds bcb into b_0): the residual loop's `after_w0` hook.  Feed-forward blocks take no context, as the module.
 //     Context and initial layer use the same gather + split3 + NFA_MFMA6 loop (`gemm_gather`).
 //
 // LDS: exchange buffer Hp / 16 x 6 KB (98 304 B at Hp = 256) + row tile [D][65] (<= 16 640 B) + logabsdet shares 2 048 B +
 // context tile [C][65] (<= 16 640 B) + tables 1 KB: 134 656 B at the largest shape (Hp 256, D 64, C 64) of the CU's 160 KB.
 #pragma once
 
-#include "made_rqs_wide_kernel.hpp"
+#include "wide_layer_common.hpp"
 
 namespace nfa {
 namespace k36 {
 
-using k32::Frag;
-using k32::kFragVec4;
-using k32::kPad;
-using k32::kRows;
-using k32::kStepVec4;
-using k32::kThreads;
-using k32::kWaves;
-using k34::gemm_exchange_split;
+using namespace wide;
 
 struct AffineWideArgs {
     const float* x;          // [B, D]
@@ -76,40 +62,10 @@ struct AffineWideArgs {
     int final_tiles;         // ceil(dt / 16)
 };
 
-// acc[rt] += W_tile[32 x 16 ksteps] x cols^T, the columns gathered from an LDS tile [column][65] and split into pieces at
-// the use (K34's initial layer): k = ks * 16 + half * 8 + j reads column tab[k] (TABLE) or k itself; k >= n is zero.
-// `w`: the wave's fragments of this GEMM (wave-uniform; the lane is added at the load).  ksteps <= 4.
-template <bool TABLE>
-__device__ __forceinline__ void gemm_gather(f32x16 (&acc)[2], const vec4f* w, int ksteps, const float* tile, const int* tab,
-                                            int n, int half, int r, int lane) {
-    for (int ks = 0; ks < ksteps; ++ks) {
-        const Frag f = k32::load_frag(w + (size_t)ks * kFragVec4 + lane);
-        const bf16x8 ah = __builtin_bit_cast(bf16x8, f.h), am = __builtin_bit_cast(bf16x8, f.m), al = __builtin_bit_cast(bf16x8, f.l);
-#pragma unroll
-        for (int rt = 0; rt < 2; ++rt) {
-            float v[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int i = ks * 16 + half * 8 + j;   // (< 64)
-                const int col = TABLE ? tab[i] : (i < n ? i : 0);
-                const float xv = tile[col * kPad + rt * 32 + r];
-                v[j] = i < n ? xv : 0.0f;
-            }
-            bf16x2 hh[4], mm[4], ll[4];
-#pragma unroll
-            for (int j2 = 0; j2 < 4; ++j2) split3(vec2f{v[j2 * 2], v[j2 * 2 + 1]}, hh[j2], mm[j2], ll[j2]);
-            const bf16x8 bh = join4(hh[0], hh[1], hh[2], hh[3]), bm = join4(mm[0], mm[1], mm[2], mm[3]),
-                         bl = join4(ll[0], ll[1], ll[2], ll[3]);
-            NFA_MFMA6(acc[rt], ah, am, al, bh, bm, bl);
-        }
-    }
-}
-
 template <bool CTX>
 __global__ void __launch_bounds__(kThreads, 1) affine_made_wide_kernel(const AffineWideArgs a) {
 #pragma clang fp contract(off)
-    // dynamic LDS: the exchange buffer (nks x 6 KB), the row tile [D][65], the waves' logabsdet shares [8][64], the
-    // context tile [ce][65] (CTX)
+    // dynamic LDS: the common carve-up, then the context tile [ce][65] (CTX)
     extern __shared__ __attribute__((aligned(16))) float lds_dyn[];
     __shared__ int s_tab[kTabLayer];
     __shared__ int s_final[128];
@@ -117,14 +73,8 @@ __global__ void __launch_bounds__(kThreads, 1) affine_made_wide_kernel(const Aff
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int D = a.D, dt = a.dt, nks = a.nks, tiles = a.tiles, nh = a.num_hidden;
     const bool resnet = a.resnet != 0;
-    int my_status = 0;
-    if (tid < kTabLayer) {
-        const bool used = (tid < kTabTr ? tid : tid - kTabTr) < dt;
-        int v = a.tables[tid], f = a.tables[kTabLayer + tid];
-        if ((used && (v < 0 || v >= D)) || (tid < D && (f < 0 || f >= D))) my_status |= NFA_STATUS_BAD_INDEX;
-        s_tab[tid] = v < 0 ? 0 : (v >= D ? D - 1 : v);
-        s_final[tid] = f < 0 ? 0 : (f >= D ? D - 1 : f);
-    }
+    int my_status = load_tables(a.tables, tid, D, s_tab, s_final, [&](int t) { return (t < kTabTr ? t : t - kTabTr) < dt; });
+    // dynamic LDS, as every wide kernel carves it: exchange buffer (nks x 6 KB), row tile [D][65], logabsdet shares
     uvec4* X = reinterpret_cast<uvec4*>(lds_dyn);
     float* s_row = lds_dyn + (size_t)nks * kStepVec4 * 4;
     float* s_lad = s_row + D * kPad;
@@ -155,7 +105,10 @@ __global__ void __launch_bounds__(kThreads, 1) affine_made_wide_kernel(const Aff
     const int nbias = CTX ? 2 : 1;                                  // bias vectors in front of the hidden Linears'
 
     // the first fragment of the wave's first GEMM: every GEMM leaves that of the wave's next one behind
-    Frag f0 = k32::load_frag(w_first + lane);
+    Frag f0 = load_frag(w_first + lane);
+    const auto gemm = [&](f32x16 (&acc)[2], const vec4f* wl, const vec4f* wnext) {
+        gemm_exchange_split<true>(acc, wl, wnext, nks, f0, xl, lane);
+    };
 
     const int64_t num_blocks64 = a.batch >> 6;
     for (int64_t blk = blockIdx.x; blk < num_blocks64; blk += gridDim.x) {
@@ -163,30 +116,7 @@ __global__ void __launch_bounds__(kThreads, 1) affine_made_wide_kernel(const Aff
         int lane_here = lane;
         asm volatile("" : "+v"(lane_here));
         const int half = lane_here >> 5, r = lane_here & 31;
-        // ---- the 64 rows: one coalesced read; slot j of the tile = input column j
-        {
-            const vec4f* xv = reinterpret_cast<const vec4f*>(a.x + row0 * D);
-            const int nvec = D * (kRows / 4);
-            for (int e0 = tid; e0 < nvec; e0 += kThreads * 4) {
-                vec4f v[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int e = e0 + u * kThreads;
-                    v[u] = xv[e < nvec ? e : 0];
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int e = e0 + u * kThreads;
-                    if (e < nvec) {
-                        const int rr = (e * 4) / D, c0 = e * 4 - rr * D;
-                        s_row[(c0 + 0) * kPad + rr] = v[u].x;
-                        s_row[(c0 + 1) * kPad + rr] = v[u].y;
-                        s_row[(c0 + 2) * kPad + rr] = v[u].z;
-                        s_row[(c0 + 3) * kPad + rr] = v[u].w;
-                    }
-                }
-            }
-        }
+        load_row_tile(a.x + row0 * D, D, s_row, tid);
         if constexpr (CTX) {   // ---- the 64 context rows (64 ce floats from a 256 ce-byte boundary): slot c = context column c
             const int ce = a.ce;
             const vec4f* cv = reinterpret_cast<const vec4f*>(a.ctx + row0 * ce);
@@ -219,7 +149,7 @@ __global__ void __launch_bounds__(kThreads, 1) affine_made_wide_kernel(const Aff
             if constexpr (CTX) {
                 load_bias_tile(h[0], bias + Hp);
                 h[1] = h[0];
-                gemm_gather<false>(h, w_ctx, cks, s_ctx, nullptr, a.ce, half, r, lane);
+                gemm_gather<false>(h, w_ctx + lane, cks, s_ctx, nullptr, a.ce, half, r);
                 f32x16 b0;
                 load_bias_tile(b0, bias);
 #pragma unroll
@@ -231,63 +161,22 @@ __global__ void __launch_bounds__(kThreads, 1) affine_made_wide_kernel(const Aff
                 load_bias_tile(h[0], bias);
                 h[1] = h[0];
             }
-            gemm_gather<true>(h, w_init, a.init_ks, s_row, s_tab + kTabId, dt, half, r, lane);
+            gemm_gather<true>(h, w_init + lane, a.init_ks, s_row, s_tab + kTabId, dt, half, r);
         }
 
-        const float* hbias = a.bias + (size_t)nbias * Hp + wave * 32 + half * 16;   // + Hp per hidden Linear
-        if (resnet) {
-            // ---- residual blocks: h += W_1 relu(W_0 relu(h) + b_0 [+ Wcb ctx + bcb]) + b_1 (made.py:129-137)
-            for (int j = 0; j < nh; j += 2) {
-                const float* bias = hbias + (size_t)j * Hp;
-                const vec4f* w0 = w_hidden + (size_t)(j >> 1) * block_vec4;
-                const vec4f* w1 = w0 + hidden_vec4 + ctx_vec4;
-                f32x16 u[2];
-                if (j > 0) NFA_K32_BARRIER();   // (the first block: nobody has read the buffer in this row block)
-                if (active) k32::exchange_store<kActRelu>(h, X, wave, lane);
-                NFA_K32_BARRIER();
-                if (active) {
-                    load_bias_tile(u[0], bias);
-                    u[1] = u[0];
-                    gemm_exchange_split<true>(u, w0, w1, nks, f0, xl, lane);
-                    if constexpr (CTX)   // (the block's context GEMM lies behind W_0: its tile `wt` from W_0's tile `wt`)
-                        gemm_gather<false>(u, w0 + (ptrdiff_t)hidden_vec4 + (ptrdiff_t)wt * (cks - nks) * kFragVec4, cks, s_ctx,
-                                           nullptr, a.ce, half, r, lane);
-                }
-                NFA_K32_BARRIER();
-                if (active) k32::exchange_store<kActRelu>(u, X, wave, lane);
-                NFA_K32_BARRIER();
-                if (active) {
-                    f32x16 b1;
-                    load_bias_tile(b1, bias + Hp);
-#pragma unroll
-                    for (int q = 0; q < 16; ++q) {
-                        h[0][q] += b1[q];
-                        h[1][q] += b1[q];
-                    }
-                    gemm_exchange_split<true>(h, w1, j + 2 < nh ? w0 + block_vec4 : w_behind_hidden, nks, f0, xl, lane);
-                }
-            }
-        } else {
-            // ---- feed-forward blocks: pre = W relu(pre) + b (made.py:96-98 with the ReLU moved in front of the Linear)
-            for (int j = 0; j < nh; ++j) {
-                const vec4f* wj = w_hidden + (size_t)j * hidden_vec4;
-                if (j > 0) NFA_K32_BARRIER();
-                if (active) k32::exchange_store<kActRelu>(h, X, wave, lane);
-                NFA_K32_BARRIER();
-                if (active) {
-                    load_bias_tile(h[0], hbias + (size_t)j * Hp);
-                    h[1] = h[0];
-                    gemm_exchange_split<true>(h, wj, j + 1 < nh ? wj + hidden_vec4 : w_behind_hidden, nks, f0, xl, lane);
-                }
-            }
-        }
-        // ---- the final layer's B operand: the residual stream as it is, the feed-forward activation through its ReLU
-        if (nh > 0) NFA_K32_BARRIER();
-        if (active) {
-            if (resnet) k32::exchange_store<kActNone>(h, X, wave, lane);
-            else k32::exchange_store<kActRelu>(h, X, wave, lane);
-        }
-        NFA_K32_BARRIER();
+        // ---- blocks: residual, h += W_1 relu(W_0 relu(h) + b_0 [+ Wcb ctx + bcb]) + b_1 (made.py:129-137), or feed-forward
+        //      (made.py:96-98); then the final layer's B operand
+        const float* hbias = a.bias + (size_t)nbias * Hp + wave * 32 + half * 16;
+        if (resnet)
+            residual_blocks(h, nh, active, X, wave, lane, hbias, Hp, w_hidden, block_vec4, hidden_vec4 + ctx_vec4,
+                            w_behind_hidden, gemm, [&](f32x16 (&u)[2], const vec4f* w0) {
+                                if constexpr (CTX)   // (the block's context GEMM lies behind W_0: its tile `wt` from W_0's tile `wt`)
+                                    gemm_gather<false>(u, w0 + (ptrdiff_t)hidden_vec4 + (ptrdiff_t)wt * (cks - nks) * kFragVec4 + lane,
+                                                       cks, s_ctx, nullptr, a.ce, half, r);
+                            });
+        else
+            feedforward_blocks(h, nh, active, X, wave, lane, hbias, Hp, w_hidden, hidden_vec4, w_behind_hidden, gemm);
+        handover(h, !resnet, nh > 0, active, X, wave, lane);
 
         // ---- final Linear and affine element: tile `wave` gives lane-half `half` the shifts (registers 0 .. 7) and the
         //      unconstrained scales (8 .. 15) of features 16 wave + 8 half + j for both row tiles; the results replace the
@@ -297,7 +186,7 @@ __global__ void __launch_bounds__(kThreads, 1) affine_made_wide_kernel(const Aff
             f32x16 acc[2];
             load_bias_tile(acc[0], a.bias + (size_t)(nbias + nh) * Hp + wave * 32 + half * 16);
             acc[1] = acc[0];
-            gemm_exchange_split<true>(acc, w_my_final, w_first, nks, f0, xl, lane);
+            gemm(acc, w_my_final, w_first);
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int f = (wave * 2 + half) * 8 + j;
@@ -313,35 +202,8 @@ __global__ void __launch_bounds__(kThreads, 1) affine_made_wide_kernel(const Aff
                 }
             }
         }
-        // ---- a row's logabsdet: the two lane-halves of every wave, then the waves in their order
-#pragma unroll
-        for (int rt = 0; rt < 2; ++rt) {
-            const float s = lad_acc[rt] + __shfl_xor(lad_acc[rt], 32, kWave);
-            if (half == 0) s_lad[wave * kRows + rt * 32 + r] = s;
-        }
-        __syncthreads();
-        if (tid < kRows) {
-            float s = s_lad[tid];
-#pragma unroll
-            for (int w = 1; w < kWaves; ++w) s += s_lad[w * kRows + tid];
-            float* dst = a.lad + row0 + tid;
-            *dst = a.accumulate ? *dst + s : s;
-        }
-        // ---- output rows: position p of a row comes from slot final[p]; 16 bytes per lane per store
-        {
-            vec4f* ov = reinterpret_cast<vec4f*>(a.out + row0 * D);
-            const int nvec = D * (kRows / 4);
-            for (int e = tid; e < nvec; e += kThreads) {
-                const int rr = (e * 4) / D, c0 = e * 4 - rr * D;
-                vec4f v;
-                v.x = s_row[s_final[c0 + 0] * kPad + rr];
-                v.y = s_row[s_final[c0 + 1] * kPad + rr];
-                v.z = s_row[s_final[c0 + 2] * kPad + rr];
-                v.w = s_row[s_final[c0 + 3] * kPad + rr];
-                ov[e] = v;
-            }
-        }
-        __syncthreads();   // the tiles, the exchange buffer and the logabsdet shares are free for the next row block
+        reduce_logabsdet(lad_acc, s_lad, wave, half, r, tid, a.lad + row0, a.accumulate);
+        scatter_rows(a.out + row0 * D, D, s_row, s_final, tid);
     }
     if (my_status && a.status) atomicOr(a.status, my_status);
 }

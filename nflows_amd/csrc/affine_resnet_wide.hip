@@ -42,36 +42,18 @@ extern "C" int nfa_affine_layer_resnet_wide_f32(const float* inputs, const void*
         return NFA_ERR_UNSUPPORTED;
     const bool additive = scale_activation == NFA_SCALE_ADDITIVE;
     AffineWideArgs a;
-    a.tiles = (hidden_features + 31) / 32;
-    a.nks = 2 * a.tiles;
     a.init_ks = (num_identity + 15) / 16;
     a.final_tiles = additive ? (num_transform + 31) / 32 : (num_transform + 15) / 16;
-    // the exchange buffer, the row tile, the units' logabsdet shares; the kernel's tables are static
-    const size_t lds = (size_t)a.nks * kStepVec4 * 16 + (size_t)features * kPad * sizeof(float) +
-                       (size_t)kWaves * 32 * sizeof(float);
-    if (lds > (size_t)kCuLds - 2048) return NFA_ERR_UNSUPPORTED;
-    if (batch == 0) return NFA_OK;
-    if (!inputs || !weights_packed || !bias_packed || !layer_tables || !outputs || !logabsdet)
-        return NFA_ERR_INVALID_ARGUMENT;
-    a.x = inputs;
-    a.w = reinterpret_cast<const vec4f*>(weights_packed);
-    a.bias = bias_packed;
-    a.tables = layer_tables;
-    a.out = outputs;
-    a.lad = logabsdet;
-    a.status = status;
-    a.batch = batch;
-    a.D = features;
-    a.dt = num_transform;
     a.di = num_identity;
     a.num_hidden = num_hidden_layers;
     a.activation = scale_activation;
-    a.accumulate = (flags & NFA_FLAG_ACCUMULATE_LOGABSDET) ? 1 : 0;
     const bool inv = (flags & NFA_FLAG_INVERSE) != 0;
-    const AffineWideKernelFn kern = resnet ? affine_wide_resnet(inv, additive) : affine_wide_mlp(inv, additive);
-    int64_t blocks = batch >> 6;
-    if (blocks > device_cu_count()) blocks = device_cu_count();
-    note_layer_kernel("k37::affine_resnet_wide_kernel<inverse=%d, additive=%d, resnet=%d, tiles=%d>", inv ? 1 : 0,
-                      additive ? 1 : 0, resnet ? 1 : 0, a.tiles);
-    return launch_kernel(kern, dim3((unsigned)blocks), dim3(kThreads), lds, (hipStream_t)stream, a, kCuLds - 2048);
+    // (behind the row tile: the units' logabsdet shares)
+    return wide::launch(a, resnet ? affine_wide_resnet(inv, additive) : affine_wide_mlp(inv, additive),
+                        {inputs, weights_packed, bias_packed, layer_tables, outputs, logabsdet, status, batch, features,
+                         num_transform, hidden_features, flags, stream, kWaves * 32 * sizeof(float)},
+                        [&] {
+                            note_layer_kernel("k37::affine_resnet_wide_kernel<inverse=%d, additive=%d, resnet=%d, tiles=%d>",
+                                              inv ? 1 : 0, additive ? 1 : 0, resnet ? 1 : 0, a.tiles);
+                        });
 }

@@ -5,21 +5,13 @@
 // unconstrained scale) pairs while they are accumulators, per-row logabsdet, scatter.  The [B, 2 d_t] parameters never
 // reach memory.  K11 (affine_mlp_kernel.hpp) serves widths up to 128.
 //
-// Arithmetic: K8's three bf16 pieces per fp32 operand, six products per k-step on v_mfma_f32_32x32x16_bf16: the full fp32
-// range, no redo pass -- on split accumulators (NFA_MFMA6_SPLIT, as K11 and K36 have them) in every GEMM that reads the
-// exchange buffer, the final one included.  An affine layer shows the shift's error in y as it is, where a spline damps its
-// logits': with K32's single accumulator the outputs of a 129-wide layer came out at 1.8 x (mean) and 2.3 x (99.9 %
-// quantile) the float32 yardstick's error against float64, outside the project's 2 x rule.  Per element the instructions
-// are K2's and K11's: `affine_element<INVERSE>` on `scale_of` under fp contract(off); the additive layer is x + shift /
-// x - shift, exact, with a logabsdet of exactly 0.
-//
-// Hidden GEMMs: K32's split (rqs_resnet_wide_kernel.hpp) with K34's GEMM loop on split accumulators
-// (made_rqs_wide_kernel.hpp, `gemm_exchange_split<true>`) -- the fragment load, the loop, the exchange store and the barrier
-// are included, not copied.  One workgroup of eight waves per CU on 64 rows (two 32-row tiles), persistent over the batch's
-// 64-row blocks; wave w owns hidden columns 32 w .. 32 w + 31 of every hidden GEMM for both row tiles; its slice of the
-// stream stays in two fp32 accumulator tiles; weight fragments go from global memory straight into registers, one k-step
-// ahead, the last request of a GEMM being the first fragment of the wave's next one; activations cross the waves as bf16
-// pieces through the LDS exchange buffer between two NFA_K32_BARRIERs.
+// Arithmetic, work split, exchange buffer and the shared pieces of the layer loop: wide_layer_common.hpp.  K37 runs on the
+// split-accumulator policy (NFA_MFMA6_SPLIT, as K11 and K36 have it) in every GEMM that reads the exchange buffer, the
+// final one included.  An affine layer shows the shift's error in y as it is, where a spline damps its logits': with the
+// single accumulator the outputs of a 129-wide layer came out at 1.8 x (mean) and 2.3 x (99.9 % quantile) the float32
+// yardstick's error against float64, outside the project's 2 x rule.  Per element the instructions are K2's and K11's:
+// `affine_element<INVERSE>` on `scale_of` under fp contract(off); the additive layer is x + shift / x - shift, exact, with
+// a logabsdet of exactly 0.
 //
 // What is K37's own: the final Linear and the element step.
 //   * The final Linear has 2 d_t rows [shift block | unconstrained scale block] (d_t for the additive layer).  The packer
@@ -42,19 +34,12 @@
 // tables 1 KB: 133 632 B at the largest shape (Hp 256, D 128) of the CU's 160 KB.
 #pragma once
 
-#include "made_rqs_wide_kernel.hpp"
+#include "wide_layer_common.hpp"
 
 namespace nfa {
 namespace k37 {
 
-using k32::Frag;
-using k32::kFragVec4;
-using k32::kPad;
-using k32::kRows;
-using k32::kStepVec4;
-using k32::kThreads;
-using k32::kWaves;
-using k34::gemm_exchange_split;
+using namespace wide;
 
 struct AffineWideArgs {
     const float* x;          // [B, D]
@@ -80,7 +65,7 @@ __device__ __forceinline__ void gemm_exchange_unit(f32x16& acc, const vec4f* wl,
                                                    const uvec4* xu, int lane) {
     f32x16 small = {0};
     for (int ks = 0; ks < nks; ++ks) {
-        const Frag f1 = k32::load_frag((ks + 1 < nks ? wl + (size_t)(ks + 1) * kFragVec4 : wnext) + lane);
+        const Frag f1 = load_frag((ks + 1 < nks ? wl + (size_t)(ks + 1) * kFragVec4 : wnext) + lane);
         const uvec4* xk = xu + ks * kStepVec4;
         const bf16x8 ah = __builtin_bit_cast(bf16x8, f0.h), am = __builtin_bit_cast(bf16x8, f0.m),
                      al = __builtin_bit_cast(bf16x8, f0.l);
@@ -95,21 +80,15 @@ __device__ __forceinline__ void gemm_exchange_unit(f32x16& acc, const vec4f* wl,
 template <bool INVERSE, bool ADDITIVE, bool RESNET>
 __global__ void __launch_bounds__(kThreads, 1) affine_resnet_wide_kernel(const AffineWideArgs a) {
 #pragma clang fp contract(off)
-    // dynamic LDS: the exchange buffer (nks x 6 KB), the row tile [D][65], the units' logabsdet shares [8][32]
+    // dynamic LDS: the common carve-up with the units' logabsdet shares [8][32] for the waves'
     extern __shared__ __attribute__((aligned(16))) float lds_dyn[];
     __shared__ int s_tab[kTabLayer];
     __shared__ int s_final[128];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int D = a.D, dt = a.dt, nks = a.nks, tiles = a.tiles, nh = a.num_hidden;
-    int my_status = 0;
-    if (tid < kTabLayer) {
-        const bool used = tid < kTabTr ? tid < a.di : tid - kTabTr < dt;
-        int v = a.tables[tid], f = a.tables[kTabLayer + tid];
-        if ((used && (v < 0 || v >= D)) || (tid < D && (f < 0 || f >= D))) my_status |= NFA_STATUS_BAD_INDEX;
-        s_tab[tid] = v < 0 ? 0 : (v >= D ? D - 1 : v);
-        s_final[tid] = f < 0 ? 0 : (f >= D ? D - 1 : f);
-    }
+    int my_status = load_tables(a.tables, tid, D, s_tab, s_final, [&](int t) { return t < kTabTr ? t < a.di : t - kTabTr < dt; });
+    // dynamic LDS, as every wide kernel carves it: exchange buffer (nks x 6 KB), row tile [D][65], logabsdet shares
     uvec4* X = reinterpret_cast<uvec4*>(lds_dyn);
     float* s_row = lds_dyn + (size_t)nks * kStepVec4 * 4;
     float* s_lad = s_row + D * kPad;
@@ -135,7 +114,10 @@ __global__ void __launch_bounds__(kThreads, 1) affine_resnet_wide_kernel(const A
     constexpr int kPerHalf = ADDITIVE ? 16 : 8;   // features of a lane-half per final tile
 
     // the first fragment of the wave's first GEMM: every GEMM leaves that of the wave's next one behind
-    Frag f0 = k32::load_frag(w_first + lane);
+    Frag f0 = load_frag(w_first + lane);
+    const auto gemm = [&](f32x16 (&acc)[2], const vec4f* wl, const vec4f* wnext) {
+        gemm_exchange_split<true>(acc, wl, wnext, nks, f0, xl, lane);
+    };
 
     const int64_t num_blocks64 = a.batch >> 6;
     for (int64_t blk = blockIdx.x; blk < num_blocks64; blk += gridDim.x) {
@@ -143,30 +125,7 @@ __global__ void __launch_bounds__(kThreads, 1) affine_resnet_wide_kernel(const A
         int lane_here = lane;
         asm volatile("" : "+v"(lane_here));
         const int half = lane_here >> 5, r = lane_here & 31;
-        // ---- the 64 rows: one coalesced read; slot j of the tile = input column j
-        {
-            const vec4f* xv = reinterpret_cast<const vec4f*>(a.x + row0 * D);
-            const int nvec = D * (kRows / 4);
-            for (int e0 = tid; e0 < nvec; e0 += kThreads * 4) {
-                vec4f v[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int e = e0 + u * kThreads;
-                    v[u] = xv[e < nvec ? e : 0];
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int e = e0 + u * kThreads;
-                    if (e < nvec) {
-                        const int rr = (e * 4) / D, c0 = e * 4 - rr * D;
-                        s_row[(c0 + 0) * kPad + rr] = v[u].x;
-                        s_row[(c0 + 1) * kPad + rr] = v[u].y;
-                        s_row[(c0 + 2) * kPad + rr] = v[u].z;
-                        s_row[(c0 + 3) * kPad + rr] = v[u].w;
-                    }
-                }
-            }
-        }
+        load_row_tile(a.x + row0 * D, D, s_row, tid);
         __syncthreads();
 
         f32x16 h[2];   // the wave's slice of the stream: columns 32 w .. 32 w + 31 of both row tiles
@@ -174,76 +133,17 @@ __global__ void __launch_bounds__(kThreads, 1) affine_resnet_wide_kernel(const A
         if (active) {
             load_bias_tile(h[0], a.bias + wave * 32 + half * 16);
             h[1] = h[0];
-            for (int ks = 0; ks < a.init_ks; ++ks) {
-                const Frag f = k32::load_frag(w_init + (size_t)ks * kFragVec4 + lane);
-                const bf16x8 ah = __builtin_bit_cast(bf16x8, f.h), am = __builtin_bit_cast(bf16x8, f.m),
-                             al = __builtin_bit_cast(bf16x8, f.l);
-#pragma unroll
-                for (int rt = 0; rt < 2; ++rt) {
-                    float v[8];
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const int i = ks * 16 + half * 8 + j;   // (< 64)
-                        const float xv = s_row[s_tab[kTabId + i] * kPad + rt * 32 + r];
-                        v[j] = i < a.di ? xv : 0.0f;
-                    }
-                    bf16x2 hh[4], mm[4], ll[4];
-#pragma unroll
-                    for (int j2 = 0; j2 < 4; ++j2) split3(vec2f{v[j2 * 2], v[j2 * 2 + 1]}, hh[j2], mm[j2], ll[j2]);
-                    const bf16x8 bh = join4(hh[0], hh[1], hh[2], hh[3]), bm = join4(mm[0], mm[1], mm[2], mm[3]),
-                                 bl = join4(ll[0], ll[1], ll[2], ll[3]);
-                    NFA_MFMA6(h[rt], ah, am, al, bh, bm, bl);
-                }
-            }
+            gemm_gather<true>(h, w_init + lane, a.init_ks, s_row, s_tab + kTabId, a.di, half, r);
         }
-
-        const float* hbias = a.bias + Hp + wave * 32 + half * 16;   // + Hp per hidden Linear
-        if constexpr (RESNET) {
-            // ---- residual blocks: h += W_1 relu(W_0 relu(h) + b_0) + b_1 (resnet.py:36-52, no context)
-            for (int j = 0; j < nh; j += 2) {
-                const float* bias = hbias + (size_t)j * Hp;
-                const vec4f* w0 = w_hidden + (size_t)j * hidden_vec4;
-                f32x16 u[2];
-                if (j > 0) NFA_K32_BARRIER();   // (the first block: nobody has read the buffer in this row block)
-                if (active) k32::exchange_store<kActRelu>(h, X, wave, lane);
-                NFA_K32_BARRIER();
-                if (active) {
-                    load_bias_tile(u[0], bias);
-                    u[1] = u[0];
-                    gemm_exchange_split<true>(u, w0, w0 + hidden_vec4, nks, f0, xl, lane);
-                }
-                NFA_K32_BARRIER();
-                if (active) k32::exchange_store<kActRelu>(u, X, wave, lane);
-                NFA_K32_BARRIER();
-                if (active) {
-                    f32x16 b1;
-                    load_bias_tile(b1, bias + Hp);
-#pragma unroll
-                    for (int q = 0; q < 16; ++q) {
-                        h[0][q] += b1[q];
-                        h[1][q] += b1[q];
-                    }
-                    gemm_exchange_split<true>(h, w0 + hidden_vec4, j + 2 < nh ? w0 + 2 * hidden_vec4 : w_behind_hidden, nks, f0, xl, lane);
-                }
-            }
-        } else {
-            // ---- hidden layers of the MLP: pre = W relu(pre) + b (mlp.py:60-66 with the ReLU moved in front of the Linear)
-            for (int j = 0; j < nh; ++j) {
-                const vec4f* wj = w_hidden + (size_t)j * hidden_vec4;
-                if (j > 0) NFA_K32_BARRIER();
-                if (active) k32::exchange_store<kActRelu>(h, X, wave, lane);
-                NFA_K32_BARRIER();
-                if (active) {
-                    load_bias_tile(h[0], hbias + (size_t)j * Hp);
-                    h[1] = h[0];
-                    gemm_exchange_split<true>(h, wj, j + 1 < nh ? wj + hidden_vec4 : w_behind_hidden, nks, f0, xl, lane);
-                }
-            }
-        }
-        // ---- the final layer's B operand: the residual stream as it is (resnet.py:99), the MLP's through its ReLU
-        if (nh > 0) NFA_K32_BARRIER();
-        if (active) k32::exchange_store<RESNET ? kActNone : kActRelu>(h, X, wave, lane);
-        NFA_K32_BARRIER();
+        // ---- residual blocks (resnet.py:36-52, no context) / hidden layers of the MLP (mlp.py:60-66); then the final
+        //      layer's B operand: the residual stream as it is (resnet.py:99), the MLP's through its ReLU
+        const float* hbias = a.bias + Hp + wave * 32 + half * 16;
+        if constexpr (RESNET)
+            residual_blocks(h, nh, active, X, wave, lane, hbias, Hp, w_hidden, 2 * hidden_vec4, hidden_vec4, w_behind_hidden,
+                            gemm, [](f32x16 (&)[2], const vec4f*) {});
+        else
+            feedforward_blocks(h, nh, active, X, wave, lane, hbias, Hp, w_hidden, hidden_vec4, w_behind_hidden, gemm);
+        handover(h, !RESNET, nh > 0, active, X, wave, lane);
 
         // ---- final Linear and element step of the wave's unit: tile `utile` against row tile `urt`; the results replace
         //      the inputs in their slots
@@ -272,33 +172,19 @@ __global__ void __launch_bounds__(kThreads, 1) affine_resnet_wide_kernel(const A
         }
         // ---- a row's logabsdet: the two lane-halves of every unit, then the units of the row's tile in tile order
         {
-            const float s = lad_acc + __shfl_xor(lad_acc, 32, kWave);
-            if (half == 0) s_lad[wave * 32 + r] = s;
+            const float sum = lad_acc + __shfl_xor(lad_acc, 32, kWave);
+            if (half == 0) s_lad[wave * 32 + r] = sum;
         }
         __syncthreads();
         if (tid < kRows) {
             const int rt = tid >> 5, rr = tid & 31;
-            float s = s_lad[rt * 32 + rr];
+            float sum = s_lad[rt * 32 + rr];
 #pragma unroll
-            for (int t = 1; t < kWaves / 2; ++t) s += s_lad[(2 * t + rt) * 32 + rr];
+            for (int t = 1; t < kWaves / 2; ++t) sum += s_lad[(2 * t + rt) * 32 + rr];
             float* dst = a.lad + row0 + tid;
-            *dst = a.accumulate ? *dst + s : s;
+            *dst = a.accumulate ? *dst + sum : sum;
         }
-        // ---- output rows: position p of a row comes from slot final[p]; 16 bytes per lane per store
-        {
-            vec4f* ov = reinterpret_cast<vec4f*>(a.out + row0 * D);
-            const int nvec = D * (kRows / 4);
-            for (int e = tid; e < nvec; e += kThreads) {
-                const int rr = (e * 4) / D, c0 = e * 4 - rr * D;
-                vec4f v;
-                v.x = s_row[s_final[c0 + 0] * kPad + rr];
-                v.y = s_row[s_final[c0 + 1] * kPad + rr];
-                v.z = s_row[s_final[c0 + 2] * kPad + rr];
-                v.w = s_row[s_final[c0 + 3] * kPad + rr];
-                ov[e] = v;
-            }
-        }
-        __syncthreads();   // the row tile, the exchange buffer and the logabsdet shares are free for the next row block
+        scatter_rows(a.out + row0 * D, D, s_row, s_final, tid);
     }
     if (my_status && a.status) atomicOr(a.status, my_status);
 }

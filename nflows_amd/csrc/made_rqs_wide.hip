@@ -33,33 +33,12 @@ extern "C" int nfa_rqs_layer_made_wide_f32(const float* inputs, const void* weig
         !a.sp.linear || a.sp.beta != 1.0f || hidden_features > 256 || features > 64 || row_length > 64 ||
         (row_length & 3) != 0 || (batch & 127) != 0 || num_hidden_layers > 128)
         return NFA_ERR_UNSUPPORTED;
-    a.tiles = (hidden_features + 31) / 32;
-    a.nks = 2 * a.tiles;
     a.init_ks = (features + 15) / 16;
-    const size_t lds = (size_t)a.nks * kStepVec4 * 16 + (size_t)row_length * kPad * sizeof(float) +
-                       (size_t)kWaves * kRows * sizeof(float);
-    if (lds > (size_t)kCuLds - 2048) return NFA_ERR_UNSUPPORTED;
-    if (batch == 0) return NFA_OK;
-    if (!inputs || !weights_packed || !bias_packed || !layer_tables || !outputs || !logabsdet)
-        return NFA_ERR_INVALID_ARGUMENT;
-    a.x = inputs;
-    a.w = reinterpret_cast<const vec4f*>(weights_packed);
-    a.bias = bias_packed;
-    a.tables = layer_tables;
-    a.out = outputs;
-    a.lad = logabsdet;
-    a.status = status;
-    a.batch = batch;
-    a.D = row_length;
-    a.dt = features;
     a.num_hidden = num_hidden_layers;
     a.resnet = resnet ? 1 : 0;
-    a.accumulate = (flags & NFA_FLAG_ACCUMULATE_LOGABSDET) ? 1 : 0;
     const int T = (3 * K - 1 + 15) / 16;
-    const MadeWideKernelFn kern = T == 2 ? made_wide_bins_mid(K) : made_wide_bins_low(K);
-    if (!kern) return NFA_ERR_UNSUPPORTED;
-    int64_t blocks = batch >> 6;
-    if (blocks > device_cu_count()) blocks = device_cu_count();
-    note_layer_kernel("k34::made_rqs_wide_kernel<K=%d, tiles=%d, resnet=%d>", K, a.tiles, resnet ? 1 : 0);
-    return launch_kernel(kern, dim3((unsigned)blocks), dim3(kThreads), lds, (hipStream_t)stream, a, kCuLds - 2048);
+    return wide::launch(a, T == 2 ? made_wide_bins_mid(K) : made_wide_bins_low(K),
+                        {inputs, weights_packed, bias_packed, layer_tables, outputs, logabsdet, status, batch, row_length,
+                         features, hidden_features, flags, stream, kWaves * kRows * sizeof(float)},
+                        [&] { note_layer_kernel("k34::made_rqs_wide_kernel<K=%d, tiles=%d, resnet=%d>", K, a.tiles, resnet ? 1 : 0); });
 }

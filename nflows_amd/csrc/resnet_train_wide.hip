@@ -1,5 +1,5 @@
 // K33: K14's pair of training kernels (resnet_train.hip) for a ResidualNet conditioner of 129 .. 256 hidden units, on K32's
-// work split (rqs_resnet_wide_kernel.hpp): the hidden part of nn/nets/resnet.py:92-100 -- initial Linear, blocks
+// work split (wide_layer_common.hpp): the hidden part of nn/nets/resnet.py:92-100 -- initial Linear, blocks
 // h += W_1 relu(W_0 relu(h) + b_0) + b_1, optionally the final Linear -- forward in one kernel that also leaves behind what
 // the backward pass and K10 (linear_wgrad.hip) need, and the whole chain of input gradients in a second one.
 //
@@ -30,12 +30,12 @@
 // columns of g_params whatever Hp is) + eight staging images of 4 608 bytes = 36 KB: 132 KB of the CU's 160 KB.
 // Deterministic: no atomics, every sum in a fixed order.
 
-#include "rqs_resnet_wide_kernel.hpp"
+#include "wide_layer_common.hpp"
 
 namespace nfa {
 namespace k33 {
 
-using namespace k32;
+using namespace wide;
 
 constexpr int kPitch = 36;                      // floats per row of a staging image (32 + 4: b128 accesses)
 constexpr int kImageFloats = 32 * kPitch;       // per wave

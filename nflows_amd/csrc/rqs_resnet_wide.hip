@@ -24,37 +24,17 @@ static int launch_wide_layer(const LayerCall& c) {
     if (rc != NFA_OK) return rc;
     const int K = a.sp.K;
     if (K > 16 || c.hidden_features > 256) return NFA_ERR_UNSUPPORTED;
-    a.tiles = (c.hidden_features + 31) / 32;
-    a.nks = 2 * a.tiles;
+    // (one layer per launch: the base density is not folded in; an empty batch is answered before this rule)
+    if (c.batch != 0 && (c.flags & (NFA_FLAG_STANDARD_NORMAL_LOG_PROB | NFA_FLAG_SKIP_OUTPUTS))) return NFA_ERR_UNSUPPORTED;
     a.init_ks = (c.num_identity + 15) / 16;
-    const size_t lds = (size_t)a.nks * kStepVec4 * 16 + (size_t)c.features * kPad * sizeof(float) +
-                       (size_t)kWaves * kRows * sizeof(float);
-    if (lds > (size_t)kCuLds - 2048) return NFA_ERR_UNSUPPORTED;
-    if (c.batch == 0) return NFA_OK;
-    // (one layer per launch: the base density is not folded in)
-    if (c.flags & (NFA_FLAG_STANDARD_NORMAL_LOG_PROB | NFA_FLAG_SKIP_OUTPUTS)) return NFA_ERR_UNSUPPORTED;
-    if (!layer_buffers_given(c) || !c.bias) return NFA_ERR_INVALID_ARGUMENT;
-    a.x = c.inputs;
-    a.w = reinterpret_cast<const vec4f*>(c.weights);
-    a.bias = c.bias;
-    a.tables = c.tables;
-    a.out = c.outputs;
-    a.lad = c.logabsdet;
-    a.status = c.status;
-    a.batch = c.batch;
-    a.D = c.features;
-    a.dt = c.num_transform;
     a.di = c.num_identity;
     a.num_blocks = c.num_blocks;
-    a.accumulate = (c.flags & NFA_FLAG_ACCUMULATE_LOGABSDET) ? 1 : 0;
     const bool inv = (c.flags & NFA_FLAG_INVERSE) != 0;
     const int T = (3 * K - 1 + 15) / 16;
-    const WideKernelFn kern = T == 2 ? wide_bins_mid(K, inv) : wide_bins_low(K, inv);
-    if (!kern) return NFA_ERR_UNSUPPORTED;
-    int64_t blocks = c.batch >> 6;
-    if (blocks > device_cu_count()) blocks = device_cu_count();
-    note_layer_kernel("k32::rqs_resnet_wide_kernel<inverse=%d, K=%d, tiles=%d>", inv ? 1 : 0, K, a.tiles);
-    return launch_kernel(kern, dim3((unsigned)blocks), dim3(kThreads), lds, (hipStream_t)c.stream, a, kCuLds - 2048);
+    return wide::launch(a, T == 2 ? wide_bins_mid(K, inv) : wide_bins_low(K, inv),
+                        {c.inputs, c.weights, c.bias, c.tables, c.outputs, c.logabsdet, c.status, c.batch, c.features,
+                         c.num_transform, c.hidden_features, c.flags, c.stream, kWaves * kRows * sizeof(float)},
+                        [&] { note_layer_kernel("k32::rqs_resnet_wide_kernel<inverse=%d, K=%d, tiles=%d>", inv ? 1 : 0, K, a.tiles); });
 }
 
 extern "C" int nfa_rqs_layer_resnet_wide_f32(const float* inputs, const void* weights_packed, const float* bias_packed,

@@ -3138,39 +3138,74 @@ def _wide_fragments(w):
     return torch.stack(split_bf16x3(w)).view(3, tiles, 32, nks, 2, 8).permute(1, 3, 0, 4, 2, 5).reshape(-1)
 
 
+def _plain_weight(lin):
+    return lin.weight.detach().float()
+
+
+def _masked_weight(lin):
+    return (lin.weight.detach() * lin.mask).float()   # a masked-out weight: an exact zero in all three pieces
+
+
+def _wide_bias(b, hidden_padded):
+    return _bias_accumulator_order(_pad_to(b.detach().float(), rows=hidden_padded))
+
+
+def _pack_wide_stream(first, hidden, weight_of, initial_columns=None):
+    """The front of every wide kernel's stream: the initial Linear as fragments of ceil(columns / 16) k-steps, the hidden
+    Linears with their columns in `_wide_column_order`, every width zero-padded to one Hp (a multiple of 32), the biases in
+    accumulator order.  `weight_of(linear)`: the fp32 weight (`_plain_weight`, `_masked_weight`).  Returns (fragment list,
+    bias list, Hp, column order) for the packer to append its final layer to."""
+    Hp = (max(lin.weight.shape[0] for lin in [first] + list(hidden)) + 31) // 32 * 32
+    order_k = _wide_column_order(Hp).to(first.weight.device)
+    columns = first.weight.shape[1] if initial_columns is None else initial_columns
+    blobs = [_wide_fragments(_pad_to(weight_of(first), rows=Hp, cols=16 * ((columns + 15) // 16)))]
+    biases = [_wide_bias(first.bias, Hp)]
+    for lin in hidden:
+        blobs.append(_wide_fragments(_pad_to(weight_of(lin), rows=Hp, cols=Hp).index_select(1, order_k)))
+        biases.append(_wide_bias(lin.bias, Hp))
+    return blobs, biases, Hp, order_k
+
+
+def _wide_spline_final(blobs, biases, weight, bias, features, padded_features, params_per_feature, scale, Hp, order_k):
+    """Appends a spline layer's final Linear: the width / height rows times `scale`, a feature's P rows zero-padded to 16 T
+    and the features to `padded_features` (zero rows), in `_k8_row_order_32(tiles_per_group=T)` order."""
+    P, H = params_per_feature, weight.shape[1]
+    K, T = (P + 1) // 3, (P + 15) // 16
+    s = torch.ones(P, dtype=torch.float64, device=weight.device)
+    s[:2 * K] = scale
+    wfull = weight.new_zeros(padded_features, 16 * T, Hp)
+    wfull[:features, :P, :H] = (weight.double().view(features, P, H) * s[None, :, None]).float()
+    bfull = weight.new_zeros(padded_features, 16 * T)
+    bfull[:features, :P] = (bias.detach().double().view(features, P) * s[None, :]).float()
+    order_r = _k8_row_order_32(padded_features, T).to(weight.device)
+    blobs.append(_wide_fragments(wfull.reshape(-1, Hp).index_select(0, order_r).index_select(1, order_k)))
+    biases.append(_bias_accumulator_order(bfull.reshape(-1).index_select(0, order_r)))
+
+
+def _wide_affine_final(blobs, biases, weight, bias, order_r, Hp, order_k):
+    """Appends an affine layer's final Linear with its rows in `order_r` (K11's orders; -1 = a zero row)."""
+    wo = _pad_to(weight, cols=Hp)
+    wo = torch.cat((wo, wo.new_zeros(1, Hp)), dim=0)
+    bo = bias.detach().float()
+    bo = torch.cat((bo, bo.new_zeros(1)))
+    order_r = order_r.to(weight.device)
+    blobs.append(_wide_fragments(wo.index_select(0, order_r % wo.shape[0]).index_select(1, order_k)))
+    biases.append(_bias_accumulator_order(bo.index_select(0, order_r % bo.shape[0])))
+
+
 def pack_resnet_conditioner_wide(net, num_transform, params_per_feature, pad_transform_to=None, pad_identity_to=None):
     """Packs a ResidualNet without context (or its batch-norm fold, `fold_batch_norm`) for K32 (layout in
     include/nflows_amd.h, nfa_rqs_layer_resnet_wide_f32): the hidden width zero-padded to Hp, a multiple of 32; every weight
     as split-bf16 fragments per (GEMM, 32-row tile, k-step, piece), all biases in accumulator order, the
     1 / sqrt(hidden_features) scale of the width / height logits (coupling.py:554-556) folded into the final layer's rows.
     Returns (weights bf16, biases fp32)."""
-    dt, P = num_transform, params_per_feature
-    K = (P + 1) // 3
-    T = (P + 15) // 16
-    dev = net.final_layer.weight.device
-    H = net.initial_layer.weight.shape[0]
-    Hp = (H + 31) // 32 * 32
-    order_k = _wide_column_order(Hp).to(dev)
-    wi = _pad_to(net.initial_layer.weight.detach().float(), rows=Hp)
-    di = wi.shape[1] if pad_identity_to is None else max(wi.shape[1], pad_identity_to)
-    blobs = [_wide_fragments(_pad_to(wi, cols=16 * ((di + 15) // 16)))]
-    biases = [_bias_accumulator_order(_pad_to(net.initial_layer.bias.detach().float(), rows=Hp))]
-    for block in net.blocks:
-        for lin in block.linear_layers:
-            blobs.append(_wide_fragments(_pad_to(lin.weight.detach().float(), rows=Hp, cols=Hp).index_select(1, order_k)))
-            biases.append(_bias_accumulator_order(_pad_to(lin.bias.detach().float(), rows=Hp)))
-    scale = torch.ones(P, dtype=torch.float64, device=dev)
-    scale[:2 * K] = 1.0 / math.sqrt(net.hidden_features)
-    wf = (net.final_layer.weight.detach().double().view(dt, P, H) * scale[None, :, None]).float()
-    bf = (net.final_layer.bias.detach().double().view(dt, P) * scale[None, :]).float()
+    dt = num_transform
+    hidden = [lin for block in net.blocks for lin in block.linear_layers]
+    di = net.initial_layer.weight.shape[1] if pad_identity_to is None else max(net.initial_layer.weight.shape[1], pad_identity_to)
+    blobs, biases, Hp, order_k = _pack_wide_stream(net.initial_layer, hidden, _plain_weight, initial_columns=di)
     dtp = dt if pad_transform_to is None else max(dt, pad_transform_to)   # surplus features: zero rows (fused_geometry)
-    wfull = wf.new_zeros(dtp, 16 * T, Hp)
-    wfull[:dt, :P, :H] = wf
-    bfull = bf.new_zeros(dtp, 16 * T)
-    bfull[:dt, :P] = bf
-    order_r = _k8_row_order_32(dtp, T).to(dev)
-    blobs.append(_wide_fragments(wfull.reshape(dtp * 16 * T, Hp).index_select(0, order_r).index_select(1, order_k)))
-    biases.append(_bias_accumulator_order(bfull.reshape(-1).index_select(0, order_r)))
+    _wide_spline_final(blobs, biases, _plain_weight(net.final_layer), net.final_layer.bias, dt, dtp, params_per_feature,
+                       1.0 / math.sqrt(net.hidden_features), Hp, order_k)
     return torch.cat(blobs).contiguous(), torch.cat(biases).contiguous()
 
 
@@ -3195,36 +3230,15 @@ def pack_made_rqs_conditioner_wide(net, num_bins):
     rows), in `_k8_row_order_32(tiles_per_group=T)` order, the width / height rows times 1 / sqrt(net.hidden_features)
     where the net exposes it (as `pack_made_rqs_conditioner`); all biases in accumulator order.  Returns (weights bf16,
     biases fp32)."""
-    K, P = num_bins, 3 * num_bins - 1
+    P = 3 * num_bins - 1
     linears, final = _made_linears(net), net.final_layer
-    H, features = linears[0].weight.shape
+    features = linears[0].weight.shape[1]
     if final.weight.shape[0] != features * P:
         raise ValueError("the MADE's final layer must have 3 * num_bins - 1 rows per feature")
-    T = made_rqs_tiles(K)
-    pairs = (features + 1) // 2
-    dev = final.weight.device
-    Hp = (H + 31) // 32 * 32
-    order_k = _wide_column_order(Hp).to(dev)
-
-    def masked(lin):
-        return (lin.weight.detach() * lin.mask).float()
-    blobs = [_wide_fragments(_pad_to(masked(linears[0]), rows=Hp, cols=16 * ((features + 15) // 16)))]
-    biases = [_bias_accumulator_order(_pad_to(linears[0].bias.detach().float(), rows=Hp))]
-    for lin in linears[1:]:
-        blobs.append(_wide_fragments(_pad_to(masked(lin), rows=Hp, cols=Hp).index_select(1, order_k)))
-        biases.append(_bias_accumulator_order(_pad_to(lin.bias.detach().float(), rows=Hp)))
-    scale = torch.ones(P, dtype=torch.float64, device=dev)
-    if hasattr(net, "hidden_features"):
-        scale[:2 * K] = 1.0 / math.sqrt(net.hidden_features)
-    wf = (masked(final).double().view(features, P, H) * scale[None, :, None]).float()
-    bf = (final.bias.detach().double().view(features, P) * scale[None, :]).float()
-    wfull = wf.new_zeros(2 * pairs, 16 * T, Hp)
-    wfull[:features, :P, :H] = wf
-    bfull = bf.new_zeros(2 * pairs, 16 * T)
-    bfull[:features, :P] = bf
-    order_r = _k8_row_order_32(2 * pairs, T).to(dev)
-    blobs.append(_wide_fragments(wfull.reshape(-1, Hp).index_select(0, order_r).index_select(1, order_k)))
-    biases.append(_bias_accumulator_order(bfull.reshape(-1).index_select(0, order_r)))
+    blobs, biases, Hp, order_k = _pack_wide_stream(linears[0], linears[1:], _masked_weight)
+    scale = 1.0 / math.sqrt(net.hidden_features) if hasattr(net, "hidden_features") else 1.0
+    _wide_spline_final(blobs, biases, _masked_weight(final), final.bias, features, (features + 1) // 2 * 2, P, scale, Hp,
+                       order_k)
     return torch.cat(blobs).contiguous(), torch.cat(biases).contiguous()
 
 
@@ -3252,42 +3266,23 @@ def pack_made_affine_conditioner_wide(net):
     Linear's; the final layer's interleaved rows in K11 / K22's order (`_made_row_order`), rows of features past the last
     zero; all biases in accumulator order.  Returns (weights bf16, biases fp32)."""
     linears, final = _made_linears(net), net.final_layer
-    H, features = linears[0].weight.shape
+    features = linears[0].weight.shape[1]
     if final.weight.shape[0] != 2 * features:
         raise ValueError("the MADE's final layer must have two rows per feature")
-    dev = final.weight.device
-    Hp = (H + 31) // 32 * 32
-    order_k = _wide_column_order(Hp).to(dev)
     context, block_context = _context_linears(net) if hasattr(net, "context_layer") else (None, [])
-
-    def masked(lin):
-        return (lin.weight.detach() * lin.mask).float()
+    blobs, biases, Hp, order_k = _pack_wide_stream(linears[0], linears[1:], _masked_weight)
 
     def context_fragments(lin):   # laid out as the initial layer's, ceil(ce / 16) k-steps
         w = lin.weight.detach().float()
         return _wide_fragments(_pad_to(w, rows=Hp, cols=16 * ((w.shape[1] + 15) // 16)))
-
-    def bias_of(b):
-        return _bias_accumulator_order(_pad_to(b.detach().float(), rows=Hp))
-    blobs = [_wide_fragments(_pad_to(masked(linears[0]), rows=Hp, cols=16 * ((features + 15) // 16)))]
-    biases = [bias_of(linears[0].bias)]
+    # a residual block's context Linear behind its first Linear (hidden Linear 2 k), its bias added into that one's
+    for k in reversed(range(len(block_context))):
+        blobs.insert(2 + 2 * k, context_fragments(block_context[k]))
+        biases[1 + 2 * k] = _wide_bias(linears[1 + 2 * k].bias.detach().float() + block_context[k].bias.detach().float(), Hp)
     if context is not None:
         blobs.insert(0, context_fragments(context))   # (consumed in front of the initial layer's)
-        biases.append(bias_of(context.bias))
-    for i, lin in enumerate(linears[1:]):
-        blobs.append(_wide_fragments(_pad_to(masked(lin), rows=Hp, cols=Hp).index_select(1, order_k)))
-        b = lin.bias.detach().float()
-        if block_context and i % 2 == 0:
-            blobs.append(context_fragments(block_context[i // 2]))
-            b = b + block_context[i // 2].bias.detach().float()
-        biases.append(bias_of(b))
-    order_r = _made_row_order(features).to(dev)   # -1 = zero padding
-    wo = _pad_to(masked(final), cols=Hp)
-    wo = torch.cat((wo, wo.new_zeros(1, Hp)), dim=0)
-    bo = final.bias.detach().float()
-    bo = torch.cat((bo, bo.new_zeros(1)))
-    blobs.append(_wide_fragments(wo.index_select(0, order_r % wo.shape[0]).index_select(1, order_k)))
-    biases.append(_bias_accumulator_order(bo.index_select(0, order_r % bo.shape[0])))
+        biases.insert(1, _wide_bias(context.bias, Hp))
+    _wide_affine_final(blobs, biases, _masked_weight(final), final.bias, _made_row_order(features), Hp, order_k)
     return torch.cat(blobs).contiguous(), torch.cat(biases).contiguous()
 
 
@@ -3315,23 +3310,9 @@ def pack_affine_conditioner_wide(net, num_transform, additive=False):
     block] in K11's order (`_affine_row_order`), rows of features past the last zero; all biases in accumulator order.
     Returns (weights bf16, biases fp32)."""
     first, hidden, final = _conditioner_linears(net)
-    dev = final.weight.device
-    H = max(lin.weight.shape[0] for lin in [first] + hidden)
-    Hp = (H + 31) // 32 * 32
-    order_k = _wide_column_order(Hp).to(dev)
-    di = first.weight.shape[1]
-    blobs = [_wide_fragments(_pad_to(first.weight.detach().float(), rows=Hp, cols=16 * ((di + 15) // 16)))]
-    biases = [_bias_accumulator_order(_pad_to(first.bias.detach().float(), rows=Hp))]
-    for lin in hidden:
-        blobs.append(_wide_fragments(_pad_to(lin.weight.detach().float(), rows=Hp, cols=Hp).index_select(1, order_k)))
-        biases.append(_bias_accumulator_order(_pad_to(lin.bias.detach().float(), rows=Hp)))
-    order_r = _affine_row_order(num_transform, additive).to(dev)   # -1 = zero padding
-    wo = _pad_to(final.weight.detach().float(), cols=Hp)
-    wo = torch.cat((wo, wo.new_zeros(1, Hp)), dim=0)
-    bo = final.bias.detach().float()
-    bo = torch.cat((bo, bo.new_zeros(1)))
-    blobs.append(_wide_fragments(wo.index_select(0, order_r % wo.shape[0]).index_select(1, order_k)))
-    biases.append(_bias_accumulator_order(bo.index_select(0, order_r % bo.shape[0])))
+    blobs, biases, Hp, order_k = _pack_wide_stream(first, hidden, _plain_weight)
+    _wide_affine_final(blobs, biases, _plain_weight(final), final.bias, _affine_row_order(num_transform, additive), Hp,
+                       order_k)
     return torch.cat(blobs).contiguous(), torch.cat(biases).contiguous()
 
 
